@@ -10,16 +10,23 @@ epochs x frames steps (timed as a second region), so `bits_per_point` and `value
 training:
     value = (full overfit wall / frames) + codec_time_per_frame     [s/frame, whole job: divided by the number of GPUs]
 The codec leg (model compression, one inference forward + D2H + range coding + stream files per frame) is timed
-separately, frames are decoded and checked bit-exact.  Warm-up runs the exact timed-loop body (live kernel timing and
-loss accumulation included) and the state is reset in place, so nothing idles the GPU between warm-up and t0; every
-timed step also gets a HIP event so the log shows the per-step spread.
+separately.  Warm-up runs the exact timed-loop body (live kernel timing and loss accumulation included) and the state is
+reset in place, so nothing idles the GPU between warm-up and t0; every timed step also gets a HIP event so the log shows
+the per-step spread.  A plain run does only this (set-up, ramp, warm-up, the K steps, the rest of the overfit, the codec
+leg) and prints the line; the legs it skips are null in it.
 
-After the headline the BASELINE config[2] flow (300 frames, GOP 32, GOP 0 as serial prefix, GOPs sharded over the GPUs
-with no collective) runs once for real and is reported as `sequence` (whole-sequence wall, phase-B efficiency, ideal
-bound); `--sequence` makes that run the headline (strong scaling).  On one GPU the full-size oracle gradient that the
-CPU baseline computes anyway is compared with the HIP forward/backward tensor by tensor.
+`--full` adds everything reported beside the headline: frames decoded and checked bit-exact, the per-kernel table and
+roofline, the bf16 legs, bits/point over seeds, the rough figure, hidden width 16, the CPU baseline, and the BASELINE
+config[2] flow (300 frames, GOP 32, GOP 0 as serial prefix, GOPs sharded over the GPUs with no collective) run once for
+real and reported as `sequence` (whole-sequence wall, phase-B efficiency, ideal bound), then again from nothing resident.
+On one GPU the full-size oracle gradient that the CPU baseline computes anyway is compared with the HIP forward/backward
+tensor by tensor.  `--sequence` makes the config[2] run the headline (strong scaling).
 
-    python bench.py --gpus 1 --steps 320 --warmup 32
+`--dump-outputs DIR` writes what the last timed step computed - the bits of its frame (float64) and the parameters and
+Adam moments it left behind (float32) - as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output
+for output.
+
+    python bench.py --gpus 1 --steps 320 --warmup 32 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import json
@@ -34,7 +41,7 @@ sys.path.insert(0, ROOT)
 
 # noqa: E402
 from bench.bf16_train import bf16_train_leg, config4_rank_leg
-from bench.common import EPOCHS, TABLE_STEPS, host_threads, log, parse                                            # noqa: E402
+from bench.common import EPOCHS, TABLE_STEPS, dump_outputs, host_threads, log, parse                              # noqa: E402
 from bench.cpu_oracle import cpu_baseline, full_size_parity                                                       # noqa: E402
 from bench.headline import Headline                                                                               # noqa: E402
 from bench.legs import bf16_codec_leg, bpp_seeds_leg, codec_leg, decode_leg, device_report, sequence_leg, wide_leg   # noqa: E402
@@ -94,24 +101,29 @@ def main():
     h = Headline(args, rank, L, _lib)
     h.run(barrier, dist)
     gop = h.gop
-    table_prof = h.kernel_table_leg() if rank == 0 and not os.environ.get('LINR_SKIP_ROOFLINE') else None
-    # ---- codec, decoder, the legs reported beside the headline ------------------------------------------------------------------------
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, h.last_step)
+    full = args.full
+    table_prof = h.kernel_table_leg() if full and rank == 0 and not os.environ.get('LINR_SKIP_ROOFLINE') else None
+    # ---- codec (part of `value`), then with --full the decoder and the legs reported beside the headline ------------------------------
     enc, codec_s, codec_cold_s = codec_leg(h, rank, dist, barrier)
     codec_s_per_frame = codec_s / len(gop)
-    lossless, decode_s, decode_pts, nd = decode_leg(h, enc)
-    wide = wide_leg(h) if rank == 0 and not os.environ.get('LINR_SKIP_WIDE') else None
+    lossless, decode_s, decode_pts, nd = decode_leg(h, enc) if full else (None, None, None, 0)
+    wide = wide_leg(h) if full and rank == 0 and not os.environ.get('LINR_SKIP_WIDE') else None
     bf16_train = None
-    if rank == 0 and not os.environ.get('LINR_SKIP_BF16_TRAIN'):
+    if full and rank == 0 and not os.environ.get('LINR_SKIP_BF16_TRAIN'):
         try:
             bf16_train = bf16_train_leg(gop, L, _lib, EPOCHS)
         except Exception as e:
             bf16_train = {'error': repr(e)}
         log('bf16 training leg: %s' % bf16_train)
-    bf16_leg, bf_lossless = bf16_codec_leg(h, enc, nd, barrier)
-    lossless = lossless and bf_lossless
-    bpp_seeds = bpp_seeds_leg(h, enc) if rank == 0 and not os.environ.get('LINR_SKIP_BPP_SEEDS') else None
+    bf16_leg = None
+    if full:
+        bf16_leg, bf_lossless = bf16_codec_leg(h, enc, nd, barrier)
+        lossless = lossless and bf_lossless
+    bpp_seeds = bpp_seeds_leg(h, enc) if full and rank == 0 and not os.environ.get('LINR_SKIP_BPP_SEEDS') else None
     rough = None
-    if rank == 0 and not os.environ.get('LINR_SKIP_ROUGH'):
+    if full and rank == 0 and not os.environ.get('LINR_SKIP_ROUGH'):
         try:
             mean_rows = sum(f.rows for f in gop.frames) / float(len(gop))
             bf_ms = bf16_train.get('ms_per_step') if isinstance(bf16_train, dict) else None
@@ -124,6 +136,10 @@ def main():
     value = (overfit_s_per_frame + codec_s_per_frame) / world
     out = None
     if rank == 0:
+        decode_components = {} if not full else {'decode_s_per_frame_4_in_flight': round(decode_s, 4),
+                                                 'decode_s_single_frame': round(decode_pts.get(1, 0.0), 4),
+                                                 'decode_s_per_frame_8_in_flight': round(decode_pts.get(8, 0.0), 4),
+                                                 'decode_gop_setup_s': round(decode_pts.get('gop_setup_s', 0.0), 4)}
         out = {'metric': 'encode_sec_per_frame', 'value': round(value, 5), 'unit': 's/frame', 'n_gpus': world,
                'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(h.ms_per_step, 4),
                'higher_is_better': False, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
@@ -150,26 +166,24 @@ def main():
                                 'note': 'value and bits_per_point both come from this complete %d-epoch overfit; ms_per_step is '
                                         'the mean of its first `steps` steps' % EPOCHS},
                'per_step_ms_hip_events': h.step_stats,
-               'components_s_per_frame': {'overfit': round(overfit_s_per_frame, 5),
-                   'codec_modelcomp_fwd_ac_write': round(codec_s_per_frame, 5),
-                                          'codec_first_call': round(codec_cold_s / len(gop), 5),
-                                          'decode_s_per_frame_4_in_flight': round(decode_s, 4),
-                                          'decode_s_single_frame': round(decode_pts.get(1, 0.0), 4),
-                                          'decode_s_per_frame_8_in_flight': round(decode_pts.get(8, 0.0), 4),
-                                          'decode_gop_setup_s': round(decode_pts.get('gop_setup_s', 0.0), 4)},
+               'components_s_per_frame': dict({'overfit': round(overfit_s_per_frame, 5),
+                                               'codec_modelcomp_fwd_ac_write': round(codec_s_per_frame, 5),
+                                               'codec_first_call': round(codec_cold_s / len(gop), 5)}, **decode_components),
                'bf16_codec': bf16_leg,
                'bf16_train': bf16_train,
                'rough': rough,
                'hidden16': wide,
                'epoch_loss_bpp': [round(x, 4) for x in h.losses], 'setup_s': round(h.setup_s, 1),
                'reference_logged': {'train_s_per_frame_epoch': 0.55, 'codec_s_per_frame': 0.43,
-                                    'source': 'loot/info.log, loot/gop_32_62/*/result.json (RTX 3090, real loot)'}}
-        out['roofline'] = None if os.environ.get('LINR_SKIP_ROOFLINE') else kernel_roofline(gop, h.live, table_prof, TABLE_STEPS,
-            h.ms_per_step)
-        log('roofline: %s' % out['roofline'])
+                                    'source': 'loot/info.log, loot/gop_32_62/*/result.json (RTX 3090, real loot)'},
+               'full': full}
+        out['roofline'] = None
+        if full and not os.environ.get('LINR_SKIP_ROOFLINE'):
+            out['roofline'] = kernel_roofline(gop, h.live, table_prof, TABLE_STEPS, h.ms_per_step)
+            log('roofline: %s' % out['roofline'])
     config4_ranks = None
     # every rank its own owlii11 GOP of 64 (bf16): configs [2] and [4] in one N-rank record
-    if world > 1 and not os.environ.get('LINR_SKIP_CONFIG4'):
+    if full and world > 1 and not os.environ.get('LINR_SKIP_CONFIG4'):
         try:
             config4_ranks = config4_rank_leg(rank, world, dist, barrier, EPOCHS, frames=int(os.environ.get('LINR_CONFIG4_FRAMES', 64)))
             log('config[4] per rank: %s' % config4_ranks)
@@ -180,7 +194,7 @@ def main():
         out['config4_per_rank'] = config4_ranks
     parity_ok = True
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             torch.set_num_threads(host_threads())
             log('cpu baseline on %d threads ...' % host_threads())
             out['cpu_baseline'], o_bits, o_grads = cpu_baseline(h.init_sd, gop.infos[0], gop.point_nums[0], args.cpu_sample_rows)
@@ -193,7 +207,7 @@ def main():
     del gop, enc, h
     torch.cuda.empty_cache()
     seq = None
-    if not args.no_sequence:
+    if full and not args.no_sequence:
         try:
             seq = sequence_leg(args, rank, world, dist)
             log('sequence leg: %s' % seq)
@@ -210,7 +224,7 @@ def main():
     # a background thread while the current one trains), overfitted, encoded, spot-decoded.  One GPU only (with N > 1 the headline
     # numbers above already came from N ranks; the cold flow is a per-rank property).
     seq_cold, stage_split = None, None
-    if world == 1 and not args.no_sequence and not os.environ.get('LINR_SKIP_COLD'):
+    if full and world == 1 and not args.no_sequence and not os.environ.get('LINR_SKIP_COLD'):
         try:
             seq_cold = sequence_leg(args, rank, world, dist, stage_all=False)
             log('cold sequence leg: %s' % seq_cold)
@@ -238,7 +252,7 @@ def main():
             out['sequence_wall_s'] = seq['wall_s']
             out['phase_b_efficiency'] = seq['phase_b_efficiency']
             out['ideal_speedup_bound'] = seq['ideal_speedup_bound']
-        assert lossless, 'decoded geometry differs from the input'
+        assert lossless or not full, 'decoded geometry differs from the input'
         print(json.dumps(out))
         assert parity_ok, 'HIP forward/backward differs from the CPU oracle at full size: %s' % out.get('full_size_parity')
 

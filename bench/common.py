@@ -34,7 +34,37 @@ def parse():
     ap.add_argument('--seq-epochs', type=int, default=EPOCHS)
     ap.add_argument('--seq-decode-frames', type=int, default=1, help='frames per GOP decoded and checked in the sequence leg')
     ap.add_argument('--cpu-sample-rows', type=int, default=0, help='0 = whole frame 0')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beside the headline: decode check, roofline / per-kernel table, bf16 legs, bits/point '
+                         'over seeds, rough figure, hidden 16, CPU baseline + full-size parity, config[2] sequence (resident and '
+                         'cold), staging split, config[4] per rank; without it a run times the headline only')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (its frame\'s bits, the parameters and Adam moments after it) '
+                         'as DIR/<name>.npy')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.sequence:
+        ap.error('--dump-outputs describes the overfit headline; it is not available with --sequence')
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> tensor / array; written as out_dir/<name>.npy in float32 (float64 stays float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, 'outputs of %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    log('outputs of the last timed step written to %s: %s' % (out_dir, ', '.join('%s %s %s' % (n, a.dtype, a.shape)
+                                                                                  for n, a in host.items())))
 
 
 def _time_launches(go, iters):

@@ -40,6 +40,7 @@ class Headline:
         _lib.check(L.linr_prof_enable(1), 'linr_prof_enable')     # creates the event pairs ...
         L.linr_prof_enable(0)                                     # ... and stops; sampled steps switch it on (mode 2)
         self.acc = torch.zeros(len(gop), dtype=torch.float64, device='cuda')
+        self.acc_done = torch.zeros_like(self.acc)               # the previous epoch's per-frame bits (swapped with acc at an epoch end)
         self.pns = torch.tensor([float(pn) for pn in gop.point_nums], dtype=torch.float64, device='cuda')
         epoch_end = (self.acc / self.pns).sum()                   # loads the torch kernels the epoch end uses
         del epoch_end
@@ -80,6 +81,7 @@ class Headline:
             self.best_offer(l)                              # before the clamp, as the reference saves (main.py:413-437)
             self.opt.clamp_lr(4e-4)
             self.epoch_loss.append(l)
+            self.acc, self.acc_done = self.acc_done, self.acc
             self.acc.zero_()
 
     def run(self, barrier, dist):
@@ -116,6 +118,14 @@ class Headline:
         elapsed = time.time() - t0
         per_step_ms = [self.step_ev[i].elapsed_time(self.step_ev[i + 1]) for i in range(args.steps)]
         self.live = _read_prof(L, self._lib)
+        self.last_step = None
+        if args.dump_outputs:
+            # what the caller of the last timed step received (between the two timed regions): the bits of its frame and the
+            # parameters / Adam moments it left behind
+            j = (args.steps - 1) % len(self.gop)
+            bits = (self.acc_done if j == len(self.gop) - 1 else self.acc)[j:j + 1]
+            self.last_step = {'bits': bits.clone(), 'parameters': self.flat.detach().clone(),
+                              'adam_exp_avg': self.opt.exp_avg.clone(), 'adam_exp_avg_sq': self.opt.exp_avg_sq.clone()}
         # carry the overfit on to its full length (second timed region) so that bits/point and value describe one training
         rest = max(0, self.total_steps - args.steps)
         barrier()

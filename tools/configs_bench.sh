@@ -3,7 +3,7 @@
 # 10-epoch overfit):  gpurun -- 'bash tools/configs_bench.sh'
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 for cfg in sphere8 loot10 andrew10 owlii11; do
-  LINR_SKIP_ROOFLINE=1 LINR_SKIP_BPP_SEEDS=1 LINR_SKIP_WIDE=1 timeout -k 10 600 python bench.py --no-cpu-baseline --no-sequence --config $cfg --gop 8 --steps 20 --warmup 5 2>/tmp/cfg_err.txt | python3 -c "
+  LINR_SKIP_ROOFLINE=1 LINR_SKIP_BPP_SEEDS=1 LINR_SKIP_WIDE=1 timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-sequence --config $cfg --gop 8 --steps 20 --warmup 5 2>/tmp/cfg_err.txt | python3 -c "
 import json,sys
 t=sys.stdin.read()
 try:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # small / dense frames with and without the fused backward:  gpurun -- 'bash tools/r3_small.sh'
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
-b(){ LINR_SKIP_ROOFLINE=1 LINR_SKIP_BPP_SEEDS=1 timeout -k 10 300 python bench.py --no-cpu-baseline --no-sequence --config $1 --gop 8 --steps 80 2>/tmp/ab_err.txt | python3 -c "
+b(){ LINR_SKIP_ROOFLINE=1 LINR_SKIP_BPP_SEEDS=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-sequence --config $1 --gop 8 --steps 80 2>/tmp/ab_err.txt | python3 -c "
 import json,sys
 t=sys.stdin.read()
 try:
