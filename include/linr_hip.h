@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 11
+#define LINR_ABI_VERSION 12
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -403,6 +403,40 @@ LINR_API size_t linr_net_bf16_arena_bytes(int64_t rows, int32_t block_layers);
 LINR_API int linr_net_forward_bf16(const linr_frame* f, const uint8_t* codes, float min_param, float max_param, void* arena,
                           size_t arena_bytes, int32_t stage_begin, int32_t stage_end, float* probs, double* bits_acc,
                           void* stream);
+
+/* ---- bf16 / uint8-weight inference executor for hidden_channel_conv 16 / 32 (csrc/wide_bf16.hip) -------------------------------
+ * BASELINE config[4]'s numerics (those of linr_net_forward_bf16) on the channel-blocked activations of the wide network: a C-wide matrix
+ * is C / 8 bf16 blocks [1 + rows][8] (zero row in front), `*_bs` elements apart; the pointers passed are those of block 0's FIRST row.
+ * The model is its uint8 codes (w = q / 255 * (max - min) + min in fp32); every 3x3x3 kernel is rounded to bf16 once, products are
+ * accumulated in fp32; biases, conv1_0 / conv1_2, the scale context and head MLPs, sigmoid and the bits are fp32; every stored matrix
+ * is bf16 and its consumers see the stored value; the prune convolution feeds the head MLP unrounded.  The schedule is Python
+ * (WideNet.forward_bf16): the forward of models/model_core.py:38-81 / models/upsample.py:88-97,137-217 / models/resnet.py:12-60.
+ *
+ * linr_wide_bf16_prep (the de-quantisation of encoder.py:101-103's new_model, model_compression/model_size_est.py:72-91, inside the
+ *   executor): pf [n_params] = the de-quantised fp32 parameters; img = the bf16 A-operand images of n_conv 3x3x3 convolutions.
+ *   conv_tab (device, int64 [n_conv][4]): parameter offset of the kernel [27][cin][cout], cin, cout, offset of its image in img
+ *   (8-byte elements, ascending; an image is linr_wide_bf16_image_elems(cin, cout) elements).  n_img: the total.  One launch.
+ * linr_spconv_wide_bf16 (MinkowskiConvolution kernel_size 3, models/upsample.py:88-97, models/resnet.py:25-46): cin in 1..8 or 16 / 32,
+ *   cout 8 / 16 / 32, one gather of every input block per tap.  epi 0: out = [ReLU](conv + bias + res) (then + res2: the extra skip
+ *   rb(out + a) of models/resnet.py:160-161); epi 1 (conv0_0 + conv1_0): out blocks [0, cout / 8) = relu(conv), [cout / 8, cout / 4) =
+ *   relu(in @ pw_w + pw_b) of the row itself (pw_w [cin][cout]); epi 2 (conv1_1 + conv1_2): out = rb(relu(conv)) @ pw_w + pw_b + res
+ *   (pw_w [cout][cout], res = the Inception input's upper half) (then + res2).
+ * linr_head_wide_bf16_fwd (CNP.basic_module, models/upsample.py:137-161): the prune convolution C -> C, then p = sigmoid(w2 . relu(w1 c +
+ *   b1) + b2) (w1 [24][C]) on its fp32 output; with target (fp32 [rows][8], column t_col) the stage's per-256-row nats go to partial
+ *   (linr_bits_finish sums them).
+ * linr_sce_fwd_bf16 (models/model_core.py:48-53): x0 = the scale context, bf16 [1 + rows][8] (the pointer of the zero row, which is
+ *   not written), on the parameters pf. */
+LINR_API int64_t linr_wide_bf16_image_elems(int32_t cin, int32_t cout);
+LINR_API int linr_wide_bf16_prep(const uint8_t* codes, int64_t n_params, float min_param, float max_param, const int64_t* conv_tab,
+                                 int32_t n_conv, int64_t n_img, float* pf, void* img, void* stream);
+LINR_API int linr_spconv_wide_bf16(int32_t epi, const uint16_t* in, int64_t in_bs, int32_t cin, const int32_t* lo, const uint32_t* mask,
+                                   int64_t ld, int64_t n, const void* img, const float* bias, int32_t cout, const uint16_t* res, int64_t res_bs,
+                                   const uint16_t* res2, int64_t res2_bs, const float* pw_w, const float* pw_b, int32_t relu, uint16_t* out,
+                                   int64_t out_bs, void* stream);
+LINR_API int linr_head_wide_bf16_fwd(const uint16_t* in, int64_t in_bs, int32_t C, const int32_t* lo, const uint32_t* mask, int64_t ld,
+                                     int64_t n, const void* img, const float* bias, const float* w1, const float* b1, const float* w2,
+                                     const float* b2, const float* target, int32_t t_col, float* p, double* partial, void* stream);
+LINR_API int linr_sce_fwd_bf16(const float* pf, const linr_frame* f, uint16_t* x0_padded, void* stream);
 
 /* ---- bf16 training executor (BASELINE config[4]: "bf16 SparseConv"; beside the fp32 step above, never instead of it) --
  * The overfit iteration of main.py:305-321 - forward of models/model_core.py:38-81 / models/upsample.py:88-97,137-217 /

@@ -20,44 +20,7 @@
 
 #define TRY(e) do { int rc_ = (e); if (rc_) return rc_; } while (0)
 
-// ---- scale context (model_core.py:48-53) -> x0 bf16; occupancy fp32 -> bf16 copy with the pad row ----------------------------
-struct BSce {
-    int64_t row_off[MAX_SCALES + 1];
-    int64_t emb[MAX_SCALES], w1[MAX_SCALES], b1[MAX_SCALES], w2[MAX_SCALES], b2[MAX_SCALES];
-    int n_scales;
-};
-__global__ __launch_bounds__(LINR_BLOCK) void sce_bf16_k(const float* __restrict__ P, const float* __restrict__ off, BSce a, int64_t n,
-                                                        bf16_t* __restrict__ x0) {
-    const int64_t r = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
-    if (r >= n) return;
-    int s = 0;
-    for (int i = 1; i < a.n_scales; ++i) s += (r >= a.row_off[i]) ? 1 : 0;
-    const float* emb = P + a.emb[s];
-    const float* W1 = P + a.w1[s];
-    const float* b1 = P + a.b1[s];
-    const float* W2 = P + a.w2[s];
-    const float* b2 = P + a.b2[s];
-    float x[15];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = emb[i];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) x[8 + i] = off[r * 7 + i];
-    float h[16];
-#pragma unroll
-    for (int o = 0; o < 16; ++o) h[o] = b1[o];
-#pragma unroll
-    for (int i = 0; i < 15; ++i)
-#pragma unroll
-        for (int o = 0; o < 16; ++o) h[o] = fmaf(x[i], W1[o * 15 + i], h[o]);
-    float y[8];
-#pragma unroll
-    for (int o = 0; o < 8; ++o) y[o] = b2[o];
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-#pragma unroll
-        for (int o = 0; o < 8; ++o) y[o] = fmaf(fmaxf(h[i], 0.0f), W2[o * 16 + i], y[o]);
-    *reinterpret_cast<uint4*>(x0 + r * 8) = pack_row(y);
-}
+// (the scale context sce_bf16_k lives in bf16_common.h: the wide bf16 executor, csrc/wide_bf16.hip, runs it too)
 
 // ---- arena --------------------------------------------------------------------------------------------------------------------
 struct BArena {

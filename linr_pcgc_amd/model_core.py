@@ -246,10 +246,11 @@ class LINR_PCGC_Model(nn.Module):
 
     def _stage_forward(self, frame, k0, k1, probs, bits, precision):
         if self._wide is not None:
-            if precision != 'f32':
-                raise _lib.LinrError('the bf16 / uint8-weight executor exists for hidden_channel_conv=8 only')
             with torch.no_grad():
-                self._wide.forward(frame, k0, k1, probs, bits)
+                if precision == 'bf16':          # csrc/wide_bf16.hip: the uint8 codes as the model, bf16 activations
+                    self._wide.forward_bf16(frame, k0, k1, probs, bits)
+                else:
+                    self._wide.forward(frame, k0, k1, probs, bits)
         elif precision == 'bf16':
             engine.net_forward_bf16(frame, self._qcodes, self._qrange[0], self._qrange[1], k0, k1, probs, bits)
         else:

@@ -475,3 +475,34 @@ def octree_occupancy(child, parent):
     check(L.linr_octree_occupancy(child.data_ptr(), m, parent.data_ptr(), n, occ.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
           'linr_octree_occupancy')
     return occ
+
+
+# ---- bf16 / uint8-weight executor of the wide network (csrc/wide_bf16.hip; WideNet.forward_bf16) ----------------------------------
+def wide_bf16_prep(codes, qrange, conv_tab, n_conv, n_img, pf, img):
+    """linr_wide_bf16_prep: pf = the de-quantised fp32 parameters, img = the bf16 A-operand images of the n_conv convolutions of conv_tab
+    (int64 [n_conv, 4] on the device: kernel offset, cin, cout, image offset)."""
+    check(_lib.lib().linr_wide_bf16_prep(codes.data_ptr(), codes.numel(), float(qrange[0]), float(qrange[1]), conv_tab.data_ptr(), n_conv,
+                                         n_img, pf.data_ptr(), img.data_ptr(), _stream()), 'linr_wide_bf16_prep')
+
+
+def spconv_wide_bf16(epi, x, cin, lo, mask, n, img, bias, cout, out, res=None, res2=None, pw=None, relu=False):
+    """linr_spconv_wide_bf16 on blocked bf16 matrices (x / out / res / res2: (pointer of block 0's first row, block stride) pairs);
+    img: the convolution's image (a device pointer); pw = (W, b) of the fused pointwise layer (epi 1, 2)."""
+    check(_lib.lib().linr_spconv_wide_bf16(epi, x[0], x[1], cin, lo.data_ptr(), mask.data_ptr(), lo.stride(0), n, img, bias.data_ptr(), cout,
+                                           None if res is None else res[0], 0 if res is None else res[1],
+                                           None if res2 is None else res2[0], 0 if res2 is None else res2[1],
+                                           None if pw is None else pw[0].data_ptr(), None if pw is None else pw[1].data_ptr(),
+                                           1 if relu else 0, out[0], out[1], _stream()), 'linr_spconv_wide_bf16')
+
+
+def head_wide_bf16(x, C, lo, mask, n, img, bias, w1, b1, w2, b2, target, t_col, p, partial=None):
+    """linr_head_wide_bf16_fwd: prune convolution + head MLP + sigmoid into p; the stage's per-block nats into partial when given."""
+    check(_lib.lib().linr_head_wide_bf16_fwd(x[0], x[1], C, lo.data_ptr(), mask.data_ptr(), lo.stride(0), n, img, bias.data_ptr(),
+                                             w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                             None if partial is None else target, t_col, p.data_ptr(),
+                                             None if partial is None else partial.data_ptr(), _stream()), 'linr_head_wide_bf16_fwd')
+
+
+def sce_fwd_bf16(pf, frame, x0_padded):
+    """linr_sce_fwd_bf16: the scale context of every row into the bf16 [1 + rows][8] matrix whose zero row is at x0_padded."""
+    check(_lib.lib().linr_sce_fwd_bf16(pf.data_ptr(), frame.cref(), x0_padded, _stream()), 'linr_sce_fwd_bf16')

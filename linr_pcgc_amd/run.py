@@ -47,7 +47,9 @@ def parse(argv=None):
     ap.add_argument('--keep', default='best', choices=['best', 'last'],
                     help="which epoch's model is coded / handed to the next GOPs: the one with the lowest mean loss (the reference: main.py:413-426) or the last")
     ap.add_argument('--precision', default='f32', choices=['f32', 'bf16'],
-                    help='arithmetic of the coding forward: f32, or bf16 features with the uint8 weight codes de-quantised in-kernel (BASELINE config[4]); travels in side_info.json')
+                    help='arithmetic of the coding forward: f32, or bf16 features with the uint8 weight codes de-quantised in-kernel (BASELINE config[4]); '
+                         'every --hidden-channel-conv (8, 16, 32) and --block_layers (1..4); wide and deeper models still train in fp32 '
+                         '(--train-precision); travels in side_info.json')
     ap.add_argument('--train-precision', '--train_precision', dest='train_precision', default=None, choices=['f32', 'bf16'],
                     help='arithmetic of the overfit step: f32 (the headline), or bf16 feature / gradient rows with fp32 master weights and '
                          'accumulation (BASELINE config[4] "bf16 SparseConv"; hidden_channel_conv 8, block_layers 1).  Default: follows --precision')

@@ -16,6 +16,9 @@ so streams decode losslessly.
 The schedule is Python (~190 launches per step; GPU-bound on the BASELINE-sized frames, launch-bound on small ones): 5.9 / 18.1 ms per
 training step at widths 16 / 32 on the loot-like frame (profiles/r04_wide.txt; ~3.7x / ~14x the convolution work of width 8).  The
 8-wide model (every BASELINE config, the reference's default and its shipped checkpoint) never comes here.
+
+forward_bf16 is the inference forward of --precision bf16 (BASELINE config[4]'s numerics) on csrc/wide_bf16.hip: the uint8 weight codes
+as the model, bf16 channel-blocked activations, fp32 accumulation, one launch per layer in the same schedule (profiles/r07_wide_bf16.txt).
 """
 import os
 import threading
@@ -316,6 +319,7 @@ class WideNet:
         self.outter = [_Block(b, C) for b in up.outter_blocks]
         self.prune = [_Conv(p[0].conv) for p in up.prune_blocks]
         self.heads = [(mlp[0][0], mlp[0][2]) for mlp in up.inner_mlps]          # PointwiseMLP([C, 24, 1]) = Linear, ReLU, Linear
+        self._bf = None                    # the bf16 executor's state addresses the parameters by their offsets: rebuilt with them
         self._built = True
 
     # ---- shared pieces ------------------------------------------------------------------------------------------------
@@ -443,3 +447,130 @@ class WideNet:
         slab = _lib.scratch(L.linr_sce_bwd_params_slab_bytes(m.scale_num), dev)
         check(L.linr_sce_bwd_params(m.flat_parameters().data_ptr(), frame.cref(), g_x0.data_ptr(), tape['sce'].data_ptr(), slab.data_ptr(),
                                     slab.numel(), m._flat_grad.data_ptr(), _stream()), 'linr_sce_bwd_params')
+
+    # ---- bf16 / uint8-weight inference forward (csrc/wide_bf16.hip) ----------------------------------------------------------
+    def forward_bf16(self, frame, k0, k1, probs, bits):
+        """_forward's schedule on the bf16 executor: the model is its uint8 codes (model._qcodes / _qrange), de-quantised by one prologue
+        launch per call; bf16 channel-blocked activations from a pool of per-role buffers; no tape.  Stages [k0, k1) as in forward():
+        the decoder's one-stage calls run the same launches as the encoder's [0, 8), so their probabilities are bit-identical."""
+        with self.lock:
+            self._bind(frame)
+            if frame.rows == 0:
+                return
+            m = self.model
+            st = self._bf16_state(frame.device)
+            ops.wide_bf16_prep(m._qcodes, m._qrange, st['tab'], st['n_conv'], st['n_img'], st['pf'], st['img'])
+            n, dev, L = frame.rows, frame.device, _lib.lib()
+            x0 = st['pool'].take('x0', n, 1, dev)
+            ops.sce_fwd_bf16(st['pf'], frame, x0[0] - 16)
+            occ = st['pool'].take('occ', n, 1, dev)         # converted on every call: the decoder fills frame.occ column by column
+            check(L.linr_occ_to_bf16(frame.occ.data_ptr(), n, occ[0] - 16, _stream()), 'linr_occ_to_bf16')
+            xg = self._block_bf16(st, st['blocks'][0], x0, 'bin', None)
+            nb = (n + 255) // 256
+            parts = torch.empty(((k1 - k0) * nb,), dtype=torch.float64, device=dev) if bits is not None else None
+            for k in range(k0, k1):
+                prior = xg if k == 0 else self._block_bf16(st, st['blocks'][k], occ, 'out', xg)
+                p = probs[k] if probs is not None else torch.empty((n,), dtype=torch.float32, device=dev)
+                h = st['heads'][k]
+                ops.head_wide_bf16(prior, self.C, self.lo, self.mask, n, h['img'], h['bias'], h['w1'], h['b1'], h['w2'], h['b2'],
+                                   frame.occ.data_ptr(), k, p, None if parts is None else parts[(k - k0) * nb:(k - k0 + 1) * nb])
+            if parts is not None:
+                ops.bits_finish(parts, (k1 - k0) * nb, bits)
+
+    def _block_bf16(self, st, bd, xin, tag, res):
+        """make_block on bf16 blocks: conv3 -> ReLU -> Inception layers (conv1_0 in conv0_0's epilogue, conv1_2 + the residual in conv1_1's,
+        the extra skip of models/resnet.py:160-161 in the last layer's two launches) -> conv3 (+ res: x_glob)."""
+        n, dev, C = self.n, self.model._flat.device, self.C
+        nbC, nh, h = C // B, C // (2 * B), C // 2
+        pool = st['pool']
+        conv = ops.spconv_wide_bf16
+        a = pool.take(tag + 'a', n, nbC, dev)
+        conv(0, xin, bd['cin'], self.lo, self.mask, n, bd['first'][0], bd['first'][1], C, a, relu=True)
+        x, nl = a, len(bd['layers'])
+        for li, q in enumerate(bd['layers']):
+            skip = a if (nl > 1 and li == nl - 1) else None
+            H = pool.take(tag + 'h%d' % li, n, nbC, dev)
+            I = pool.take(tag + 'i%d' % li, n, nbC, dev)
+            conv(1, x, C, self.lo, self.mask, n, q['c00'][0], q['c00'][1], h, H, pw=q['c10'])
+            conv(0, H, h, self.lo, self.mask, n, q['c01'][0], q['c01'][1], h, I, res=x, res2=skip)
+            conv(2, _sub(H, nh), h, self.lo, self.mask, n, q['c11'][0], q['c11'][1], h, _sub(I, nh), res=_sub(x, nh),
+                 res2=None if skip is None else _sub(skip, nh), pw=q['c12'])
+            x = I
+        o = pool.take(tag + 'o', n, nbC, dev)
+        conv(0, x, C, self.lo, self.mask, n, bd['tail'][0], bd['tail'][1], C, o, res=res)
+        return o
+
+    def _bf16_state(self, dev):
+        """Per model and device: the convolution table of the prologue, the de-quantised fp32 parameters, the bf16 weight images and the
+        activation pool.  Every parameter is addressed in the fp32 copy at its offset in the flat buffer (the codes follow that order)."""
+        if not self._built:
+            self._build()
+        st = getattr(self, '_bf', None)
+        if st is not None and st['dev'] == dev:
+            return st
+        L = _lib.lib()
+        flat = self.model._flat
+        pf = _lib.scratch(4 * flat.numel(), dev).view(torch.float32)
+        convs = []
+
+        def off(t):
+            return (t.data_ptr() - flat.data_ptr()) // 4
+
+        def pfv(t):
+            return pf[off(t):off(t) + t.numel()]
+
+        def cv(mod):
+            convs.append((off(mod.kernel), mod.kernel.shape[1], mod.kernel.shape[2]))
+            return [len(convs) - 1, pfv(mod.bias)]
+
+        def blk(b):
+            return {'cin': b.first.ci, 'first': cv(b.first.mod), 'tail': cv(b.tail.mod),
+                    'layers': [{'c00': cv(q['c00'].mod), 'c01': cv(q['c01'].mod), 'c11': cv(q['c11'].mod),
+                                'c10': (pfv(q['c10'].w), pfv(q['c10'].b)), 'c12': (pfv(q['c12'].w), pfv(q['c12'].b))} for q in b.layers]}
+
+        blocks = [blk(self.block_in)] + [blk(b) for b in self.outter]
+        heads = [{'conv': cv(self.prune[k].mod), 'w1': pfv(l0.weight), 'b1': pfv(l0.bias), 'w2': pfv(l2.weight), 'b2': pfv(l2.bias)}
+                 for k, (l0, l2) in enumerate(self.heads)]
+        starts, tot = [], 0
+        for _, ci, co in convs:
+            starts.append(tot)
+            tot += int(L.linr_wide_bf16_image_elems(ci, co))
+        img = _lib.scratch(8 * tot, dev)
+        tab = torch.tensor([[w, ci, co, s] for (w, ci, co), s in zip(convs, starts)], dtype=torch.int64).to(dev)
+
+        def fix(c):                                         # [conv index, bias] -> (image pointer, bias)
+            return (img.data_ptr() + 8 * starts[c[0]], c[1])
+
+        for b in blocks:
+            b['first'], b['tail'] = fix(b['first']), fix(b['tail'])
+            for q in b['layers']:
+                q['c00'], q['c01'], q['c11'] = fix(q['c00']), fix(q['c01']), fix(q['c11'])
+        for hd in heads:
+            hd['img'], hd['bias'] = fix(hd.pop('conv'))
+        self._bf = {'dev': dev, 'pf': pf, 'img': img, 'tab': tab, 'n_conv': len(convs), 'n_img': tot, 'blocks': blocks, 'heads': heads,
+                    'pool': _Bf16Pool()}
+        return self._bf
+
+
+def _sub(t, j):
+    """Blocks j.. of a blocked bf16 matrix given as (pointer of block 0's first row, block stride in elements)."""
+    return (t[0] + 2 * j * t[1], t[1])
+
+
+class _Bf16Pool:
+    """The bf16 activation buffers of forward_bf16, one per role ('bin' / 'out' block slots, x0, occ), reused from call to call (all
+    launches are on one stream, in order).  A buffer is [nb][cap + 1][8] bf16 whose row 0 is cleared once when it is made; a role is
+    handed out as (pointer of block 0's first row, block stride)."""
+
+    def __init__(self):
+        self.bufs = {}
+
+    def take(self, key, n, nb, dev):
+        b = self.bufs.get(key)
+        if b is None or b.shape[0] != nb or b.shape[1] < n + 1 or b.device != dev:
+            b = torch.empty((nb, n + 1, B), dtype=torch.int16, device=dev)
+            if os.environ.get('LINR_DEBUG_POISON'):
+                b.fill_(-1)
+            b[:, 0].zero_()
+            self.bufs[key] = b
+        return (b[0, 1].data_ptr(), b.stride(0))
