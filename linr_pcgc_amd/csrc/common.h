@@ -21,6 +21,13 @@ static inline int linr_launch_rc() { return linr_hip_rc(hipGetLastError()); }
 #define LINR_TAP(kk) (((kk) / 9) + 3 * (((kk) / 3) % 3) + 9 * ((kk) % 3))
 
 static inline bool linr_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// The gather kernels address rows with 32-bit byte offsets from the zero row in front of a matrix, so the n + 1 rows of row_bytes
+// each (a power of two) must stay below 2^32: n < 2^27 - 1 for the 32-byte rows of an 8-channel fp32 matrix.  The frame of every
+// executor is held to that bound (include/linr_hip.h: linr_frame.rows), the bf16 ones with their 16-byte rows included.
+static inline bool linr_rows_fit32(int64_t n, int64_t row_bytes = 32) { return n < ((int64_t)1 << 32) / row_bytes - 1; }
+// ... and the compressed kernel map: the kernels that have no 64-bit path read lo [9][ld] with 32-bit byte offsets,
+// 9 * ld * 4 B < 2^32; the others pick the 32-bit path by the same test (conv_common.h, bf16_common.h: load_words16).
+static inline bool linr_cmap_fits32(int64_t ld) { return ld < ((int64_t)1 << 26); }
 static inline unsigned linr_grid(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // number of persistent blocks used by the two-pass reductions: enough to fill 256 CUs several times over,

@@ -104,6 +104,7 @@ extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_
     *child_n_h = 0;
     if (n == 0) return 0;
     if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !p_pinned || !s_pinned || !child_xyz) return LINR_EINVAL;
+    // (one row looser than linr_rows_fit32, which the executor's frame check then applies to the frame built below)
     if (child_cap < 0 || n >= ((int64_t)1 << 27)) return LINR_EINVAL;
     if (((uintptr_t)ws) & 255u) return LINR_EALIGN;
     const DecodeWs w = layout(n, block_layers, codes ? 1 : 0);

@@ -334,7 +334,7 @@ extern "C" int linr_spconv_cmap(int32_t bwd, const float* in, int32_t in_ld, con
     if (in_ld < gin || out_ld < gout || (gout != 4 && gout != 8)) return LINR_EINVAL;
     if ((flags & LINR_RELU_MASK) && (!act || act_ld < gout)) return LINR_EINVAL;
     if (res && res_ld < gout) return LINR_EINVAL;
-    if ((uint64_t)(n + 1) * (uint64_t)in_ld * 4u >= 0xFFFFFFFFull) return LINR_EINVAL;     // 32-bit byte offsets
+    if (!linr_rows_fit32(n, 4 * in_ld)) return LINR_EINVAL;
     return linr_cconv_launch(bwd != 0, in, in_ld, lo, mask, ld, n, W, bias, cin, cout, res, res_ld, act, act_ld, out, out_ld,
                              flags, (hipStream_t)stream, nullptr, 1);
 }
@@ -353,7 +353,7 @@ extern "C" int linr_spconv_wgrad_cmap(const float* in, int32_t in_ld, const floa
     if (!in || !gout || !nbr || !slab) return LINR_EINVAL;
     if (!linr_aligned16(in)) return LINR_EALIGN;
     if (!((cin == 8 && (cout == 8 || cout == 4)) || (cin < 8 && cin >= 1 && cout == 8))) return LINR_EINVAL;
-    if ((uint64_t)(n + 1) * (uint64_t)in_ld * 4u >= 0xFFFFFFFFull) return LINR_EINVAL;
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     const int64_t elems = (int64_t)(27 * cin + 1) * cout;
     LinrWgradDst d = {slab, elems, 0, (int64_t)27 * cin * cout, cin};
     if (tile8t && !linr_aligned16(tile8t)) return LINR_EALIGN;
@@ -1203,7 +1203,7 @@ extern "C" int linr_head_fwd(const float* prior, const int32_t* lo, const uint32
     if (!cmap_ok(prior, lo, mask, ld, n) || !Wp || !bp || !w1 || !b1 || !w2 || !b2 || !c_out || !p_out) return LINR_EINVAL;
     if (bits_acc && (!target || target_ld < 1 || !ws)) return LINR_EINVAL;
     if (!linr_aligned16(prior) || !linr_aligned16(c_out)) return LINR_EALIGN;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull) return LINR_EINVAL;
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     double* part = nullptr;
     if (bits_acc) {
         if (ws_bytes < linr_head_workspace_bytes(n)) return LINR_ENOSPC;
@@ -1244,7 +1244,7 @@ extern "C" int linr_inception_fwd(const float* x, const int32_t* lo, const uint3
     if (n == 0) return 0;
     if (!cmap_ok(x, lo, mask, ld, n) || !inc_ok(q) || !H || !M || !I) return LINR_EINVAL;
     if (!linr_aligned16(x) || !linr_aligned16(H) || !linr_aligned16(M) || !linr_aligned16(I)) return LINR_EALIGN;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull) return LINR_EINVAL;
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     int rc = linr_conv_pw_fwd_launch(x, lo, mask, ld, n, q->w00, q->b00, q->w10, q->b10, H, (hipStream_t)stream);
     if (rc) return rc;
     return linr_dual44_fwd_launch(H, lo, mask, ld, n, q->w01, q->b01, q->w11, q->b11, x, q->w12, q->b12, M, I, (hipStream_t)stream);
@@ -1260,7 +1260,7 @@ extern "C" int linr_inception_bwd_data(const float* gI, const float* x, const fl
     if (flags & ~(LINR_RELU_MASK | LINR_ACCUM)) return LINR_EINVAL;
     if (!linr_aligned16(gI) || !linr_aligned16(gM) || !linr_aligned16(gH) || !linr_aligned16(gX) || !linr_aligned16(H) ||
         !linr_aligned16(M)) return LINR_EALIGN;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull) return LINR_EINVAL;
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     // I[:,4:8] = M @ W12 + b12 + x[:,4:8], M = relu(.)  =>  gM = (gI[:,4:8] @ W12^T) * (M > 0)
     int rc = linr_linear_launch(gI + 4, 8, n, q->w12, 1, 4, nullptr, 4, 4, nullptr, 0, M, 4, gM, 4, LINR_RELU_MASK, s);
@@ -1279,7 +1279,7 @@ extern "C" int linr_occ_conv7(const float* occ, const int32_t* lo, const uint32_
     if (!linr_aligned16(occ) || !linr_aligned16(out)) return LINR_EALIGN;
     for (int g = 0; g < 7; ++g)
         if (w_off_h[g] < 0 || b_off_h[g] < 0 || (out_off_h[g] & 3)) return LINR_EINVAL;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull) return LINR_EINVAL;
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     return linr_occ_conv7_launch(occ, lo, mask, ld, n, params, w_off_h, b_off_h, out, out_off_h, (hipStream_t)stream);
 }
 
@@ -1289,7 +1289,7 @@ extern "C" int linr_spconv_wgrad_dual44(const float* H, const float* g0, int32_t
     if (n == 0) return 0;
     if (!H || !g0 || !g1 || !nbr || !slab) return LINR_EINVAL;
     if (!linr_aligned16(H)) return LINR_EALIGN;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull) return LINR_EINVAL;
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     // per block: [W01 432 | b01 4 | W11 432 | b11 4]
     return linr_conv3_wgrad_dual44(H, g0, g0_ld, g1, g1_ld, nbr, ld, n, slab, 872, 0, 432, 436, 868, LINR_WG_BLOCKS,
                                    (hipStream_t)stream, nullptr, 1, tile8t);

@@ -654,7 +654,7 @@ extern "C" int linr_spconv_bwd_fused(const float* gout, const float* in, const i
     if (n == 0) return 0;
     if (!gout || !in || !lo || !mask || !W || !gin || !slab) return LINR_EINVAL;
     if (!linr_aligned16(gout) || !linr_aligned16(gin)) return LINR_EALIGN;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull || ld >= ((int64_t)1 << 26)) return LINR_EINVAL;
+    if (!linr_rows_fit32(n) || !linr_cmap_fits32(ld)) return LINR_EINVAL;
     LinrWgradDst d = {slab, 1736, 0, 1728, 8};
     return linr_conv88_bwd_wgrad_launch(gout, in, lo, mask, ld, n, W, gin, nullptr, d, nblocks, (hipStream_t)stream, nullptr, 1, nullptr);
 }
@@ -671,7 +671,7 @@ extern "C" int linr_inception_bwd_fused(const float* gI, const float* gM, const 
     if (flags & ~(LINR_RELU_MASK | LINR_ACCUM)) return LINR_EINVAL;
     if (!linr_aligned16(gI) || !linr_aligned16(gM) || !linr_aligned16(gH) || !linr_aligned16(gX) || !linr_aligned16(H) ||
         !linr_aligned16(x)) return LINR_EALIGN;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull || ld >= ((int64_t)1 << 26)) return LINR_EINVAL;
+    if (!linr_rows_fit32(n) || !linr_cmap_fits32(ld)) return LINR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     int rc = linr_dual44_bwd_wgrad_launch(gI, gM, H, lo, mask, ld, n, q->w01, q->w11, gH, slab, 1776, 868, 1300, 1304, 1736, nblocks, s,
                                           nullptr, 1, nullptr);

@@ -1,7 +1,9 @@
 // Parameter layout of LINR_PCGC_Model in parameters() order (models/model_core.py:31-35, models/upsample.py:43-76),
-// shared by the fp32 executor (net.hip) and the bf16 / uint8-weight inference executor (net_bf16.hip).
+// shared by the fp32 executor (net.hip) and the bf16 / uint8-weight inference executor (net_bf16.hip), and the frame contract
+// every executor entry checks against it.
 #pragma once
 #include <stdint.h>
+#include "../../include/linr_hip.h"
 #define MAX_SCALES 16
 #define MAX_BL 4              // block_layers of block_in (main.py:521 default 1; the outter blocks always have 1, upsample.py:72-76)
 struct IncP {                 // one InceptionResNet layer (models/resnet.py:7-60)
@@ -70,3 +72,28 @@ static inline bool make_layout(Layout& L, int S, int BL = 1) {
     return true;
 }
 
+// The structure of a linr_frame (include/linr_hip.h), checked once for every entry that takes one: 1..MAX_SCALES scales with their
+// host arrays, row_off_h rising from 0 to rows, every scale_idx_h inside the model.  Builds L at block_layers, 0 = the frame's own
+// (0 read as 1).  What an entry needs beyond this - its matrices, the row bound, its arena - it checks itself.  LINR_EINVAL or 0.
+static inline int linr_frame_layout(const linr_frame* f, int block_layers, Layout& L) {
+    if (!f || f->rows < 0 || f->n_scales < 1 || f->n_scales > MAX_SCALES || !f->row_off_h || !f->scale_idx_h) return LINR_EINVAL;
+    if (block_layers == 0) block_layers = f->block_layers < 1 ? 1 : f->block_layers;
+    if (!make_layout(L, f->model_scale_num, block_layers)) return LINR_EINVAL;
+    if (f->row_off_h[0] != 0 || f->row_off_h[f->n_scales] != f->rows) return LINR_EINVAL;
+    for (int s = 0; s < f->n_scales; ++s)
+        if (f->row_off_h[s + 1] < f->row_off_h[s] || f->scale_idx_h[s] < 0 || f->scale_idx_h[s] >= f->model_scale_num) return LINR_EINVAL;
+    return 0;
+}
+
+// The per-scale table of the scale-context kernels (SceArgs of sce.h, BSce of bf16_common.h): every scale's first row and the
+// offsets of its embedding and MLP parameters, for a frame that has passed linr_frame_layout with L.
+template <class T>
+static inline void linr_sce_table(const linr_frame* f, const Layout& L, T& a) {
+    a.n_scales = f->n_scales;
+    for (int s = 0; s < f->n_scales; ++s) {
+        const int si = f->scale_idx_h[s];
+        a.row_off[s] = f->row_off_h[s];
+        a.emb[s] = L.emb + si * 8; a.w1[s] = L.m0_w[si]; a.b1[s] = L.m0_b[si]; a.w2[s] = L.m2_w[si]; a.b2[s] = L.m2_b[si];
+    }
+    a.row_off[f->n_scales] = f->rows;
+}

@@ -615,8 +615,8 @@ static bool join_block_in(const Ctx& c) {
 // two-kernel schedule (same input gradients bit for bit, weight gradients in another summation order)
 static bool fused_bwd(const Ctx& c) {
     static const int v = getenv("LINR_FUSED_BWD") ? atoi(getenv("LINR_FUSED_BWD")) : 1;
-    // (the fused kernels address the compressed map with 32-bit byte offsets: 9 x ld x 4 B < 2^32; larger maps take the two-kernel path)
-    return v != 0 && c.f->nbr_lo && c.f->nbr_mask && c.nbr_ld < ((int64_t)1 << 26);
+    // (the fused kernels have no 64-bit path into the compressed map: larger maps take the two-kernel path)
+    return v != 0 && c.f->nbr_lo && c.f->nbr_mask && linr_cmap_fits32(c.nbr_ld);
 }
 
 static int conv3(Ctx& c, bool bwd, const float* in, int in_ld, const float* W, const float* bias, int cin, int cout,
@@ -758,17 +758,10 @@ static int block_bwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
 }
 
 static int check_frame(const linr_frame* f, const void* params, const void* arena, size_t arena_bytes, Ctx& c) {
-    if (!f || !params || !arena) return LINR_EINVAL;
-    if (f->rows < 0 || f->n_scales < 1 || f->n_scales > MAX_SCALES || !f->row_off_h || !f->scale_idx_h) return LINR_EINVAL;
+    if (!params || !arena) return LINR_EINVAL;
+    TRY(linr_frame_layout(f, 0, c.L));
     if (f->rows > 0 && (!f->nbr || !f->offset_feat || !f->occ)) return LINR_EINVAL;
-    // the conv kernels address gathered rows with 32-bit byte offsets: (rows + 1) * 32 B must stay below 2^32
-    if (f->rows >= ((int64_t)1 << 27) - 1 || f->nbr_ld < f->rows) return LINR_EINVAL;
-    if (!make_layout(c.L, f->model_scale_num, f->block_layers < 1 ? 1 : f->block_layers)) return LINR_EINVAL;
-    if (f->row_off_h[0] != 0 || f->row_off_h[f->n_scales] != f->rows) return LINR_EINVAL;
-    for (int s = 0; s < f->n_scales; ++s) {
-        if (f->row_off_h[s + 1] < f->row_off_h[s]) return LINR_EINVAL;
-        if (f->scale_idx_h[s] < 0 || f->scale_idx_h[s] >= f->model_scale_num) return LINR_EINVAL;
-    }
+    if (!linr_rows_fit32(f->rows) || f->nbr_ld < f->rows) return LINR_EINVAL;
     if (arena_bytes < linr_net_arena_bytes(f->rows, c.L.BL)) return LINR_ENOSPC;
     if (!linr_aligned16(arena)) return LINR_EALIGN;
     c.f = f;
@@ -782,21 +775,6 @@ static int check_frame(const linr_frame* f, const void* params, const void* aren
         c.A.OCC = const_cast<float*>(f->occ);
     }
     return 0;
-}
-
-static SceArgs sce_args(const Ctx& c) {
-    SceArgs a;
-    a.n_scales = c.f->n_scales;
-    for (int s = 0; s < c.f->n_scales; ++s) {
-        const int si = c.f->scale_idx_h[s];
-        a.row_off[s] = c.f->row_off_h[s];
-        a.emb[s] = c.L.emb + si * 8; a.w1[s] = c.L.m0_w[si]; a.b1[s] = c.L.m0_b[si]; a.w2[s] = c.L.m2_w[si]; a.b2[s] = c.L.m2_b[si];
-    }
-    a.row_off[c.f->n_scales] = c.f->rows;
-    a.blk_off[0] = 0;
-    for (int s = 0; s < c.f->n_scales; ++s)
-        a.blk_off[s + 1] = a.blk_off[s] + (int)linr_grid(a.row_off[s + 1] - a.row_off[s], LINR_BLOCK);
-    return a;
 }
 
 static void goffs(int64_t* dst, const float* const* ptrs, int n) {
@@ -908,7 +886,7 @@ extern "C" int linr_net_forward(const linr_frame* f, const float* params, float*
         for (int i = 0; i < a.npad; ++i) { pl.off[i] = a.pad_off[i]; pl.w[i] = a.pad_w[i]; }
         {   // scale context: one small MLP per scale (model_core.py:48-53), all scales in one launch; its spare blocks clear the pad rows
             ProfScope ps(c.s, PK_SCE, 1);
-            const SceArgs sa = sce_args(c);
+            const SceArgs sa = sce_args(c.f, c.L);
             sce_fwd_k<float><<<sa.blk_off[sa.n_scales] + (a.npad + LINR_BLOCK / 32 - 1) / (LINR_BLOCK / 32), LINR_BLOCK, 0, c.s>>>(
                 P, f->offset_feat, sa, c.R, nullptr, nullptr, a.X0, a.base, pl);      // (no hidden layer kept: sce_bwd_all_k recomputes it)
         }
@@ -955,25 +933,13 @@ extern "C" int linr_net_forward(const linr_frame* f, const float* params, float*
 }
 
 // ---- scale context as stand-alone ops (the launches linr_net_forward / _backward make for it) ---------------------------
-static int sce_frame_check(const linr_frame* f, Layout& L) {
-    if (!f || f->rows < 0 || f->n_scales < 1 || f->n_scales > MAX_SCALES || !f->row_off_h || !f->scale_idx_h) return LINR_EINVAL;
-    if (!make_layout(L, f->model_scale_num, f->block_layers < 1 ? 1 : f->block_layers)) return LINR_EINVAL;
-    if (f->row_off_h[0] != 0 || f->row_off_h[f->n_scales] != f->rows) return LINR_EINVAL;
-    for (int s = 0; s < f->n_scales; ++s) {
-        if (f->row_off_h[s + 1] < f->row_off_h[s]) return LINR_EINVAL;
-        if (f->scale_idx_h[s] < 0 || f->scale_idx_h[s] >= f->model_scale_num) return LINR_EINVAL;
-    }
-    return 0;
-}
-
 extern "C" int linr_sce_fwd(const float* params, const linr_frame* f, float* mix, float* hid, float* x0, void* stream) {
-    Ctx c;
-    TRY(sce_frame_check(f, c.L));
+    Layout L;
+    TRY(linr_frame_layout(f, 0, L));
     if (f->rows == 0) return 0;
     if (!params || !f->offset_feat || !hid || !x0) return LINR_EINVAL;
     if ((mix && !linr_aligned16(mix)) || !linr_aligned16(hid) || !linr_aligned16(x0)) return LINR_EALIGN;
-    c.f = f;
-    const SceArgs sa = sce_args(c);
+    const SceArgs sa = sce_args(f, L);
     sce_fwd_k<float><<<sa.blk_off[sa.n_scales], LINR_BLOCK, 0, (hipStream_t)stream>>>(params, f->offset_feat, sa, f->rows, mix, hid, x0, nullptr,
                                                                               PadList{{}, {}, 0});
     return linr_launch_rc();
@@ -981,13 +947,12 @@ extern "C" int linr_sce_fwd(const float* params, const linr_frame* f, float* mix
 
 extern "C" int linr_sce_bwd(const float* params, const linr_frame* f, const float* gx0, const float* hid, float* ghid,
                             void* stream) {
-    Ctx c;
-    TRY(sce_frame_check(f, c.L));
+    Layout L;
+    TRY(linr_frame_layout(f, 0, L));
     if (f->rows == 0) return 0;
     if (!params || !gx0 || !hid || !ghid) return LINR_EINVAL;
     if (!linr_aligned16(gx0) || !linr_aligned16(hid) || !linr_aligned16(ghid)) return LINR_EALIGN;
-    c.f = f;
-    const SceArgs sa = sce_args(c);
+    const SceArgs sa = sce_args(f, L);
     sce_bwd_k<<<sa.blk_off[sa.n_scales], LINR_BLOCK, 0, (hipStream_t)stream>>>(params, sa, f->rows, gx0, hid, ghid);
     return linr_launch_rc();
 }
@@ -1007,20 +972,19 @@ extern "C" size_t linr_sce_bwd_params_slab_bytes(int32_t model_scale_num) {
 }
 extern "C" int linr_sce_bwd_params(const float* params, const linr_frame* f, const float* gx0, const float* hid, float* slab,
                                    size_t slab_bytes, float* grads, void* stream) {
-    Ctx c;
-    TRY(sce_frame_check(f, c.L));
+    Layout L;
+    TRY(linr_frame_layout(f, 0, L));
     if (!params || !gx0 || !hid || !slab || !grads) return LINR_EINVAL;
     if (f->rows > 0 && !f->offset_feat) return LINR_EINVAL;
     if (!linr_aligned16(gx0) || !linr_aligned16(hid)) return LINR_EALIGN;
-    const int64_t total = c.L.block_in.a_w;
+    const int64_t total = L.block_in.a_w;
     if (slab_bytes < (size_t)SCE_SLAB_ROWS * (size_t)total * sizeof(float)) return LINR_ENOSPC;
-    c.f = f;
     hipStream_t s = (hipStream_t)stream;
     const int nb = SCE_SLAB_ROWS;
-    SceArgs sa = sce_args(c);
+    SceArgs sa = sce_args(f, L);
     ZeroRanges zr;
     zr.n = 0; zr.prefix = total;
-    zr.b[zr.n] = c.L.emb; zr.e[zr.n] = c.L.emb + (int64_t)c.L.S * 8; ++zr.n;
+    zr.b[zr.n] = L.emb; zr.e[zr.n] = L.emb + (int64_t)L.S * 8; ++zr.n;
     ShortRanges sr;
     sr.n = 0;
     bool present[MAX_SCALES] = {};
@@ -1036,13 +1000,13 @@ extern "C" int linr_sce_bwd_params(const float* params, const linr_frame* f, con
         const int si = f->scale_idx_h[j];
         if (present[si]) return LINR_EINVAL;                 // two row ranges of one scale would share slab rows
         present[si] = true;
-        if (wg < nb) { sr.b[sr.n] = c.L.m0_w[si]; sr.e[sr.n] = c.L.m2_b[si] + 8; sr.rows[sr.n] = (int)wg; ++sr.n; }
-        ea.gb1[ns] = c.L.m0_b[si]; ea.w1[ns] = c.L.m0_w[si]; ea.gemb[ns] = c.L.emb + si * 8; ++ns;
+        if (wg < nb) { sr.b[sr.n] = L.m0_w[si]; sr.e[sr.n] = L.m2_b[si] + 8; sr.rows[sr.n] = (int)wg; ++sr.n; }
+        ea.gb1[ns] = L.m0_b[si]; ea.w1[ns] = L.m0_w[si]; ea.gemb[ns] = L.emb + si * 8; ++ns;
     }
-    for (int si = 0; si < c.L.S; ++si)
+    for (int si = 0; si < L.S; ++si)
         if (!present[si]) {
-            zr.b[zr.n] = c.L.m0_w[si];
-            zr.e[zr.n] = si + 1 < c.L.S ? c.L.m0_w[si + 1] : total;
+            zr.b[zr.n] = L.m0_w[si];
+            zr.e[zr.n] = si + 1 < L.S ? L.m0_w[si + 1] : total;
             ++zr.n;
         }
     if (ns > 0) sce_bwd_all_k<<<sa.wg_off[f->n_scales], SB_WAVES * 64, 0, s>>>(params, f->offset_feat, sa, gx0, hid, slab, total);
@@ -1289,7 +1253,7 @@ int linr_bwd_tail_launch(const linr_frame* f, const Layout& L, const float* P, c
         if (f->row_off_h[s + 1] > f->row_off_h[s]) sl[ns++] = s;
     if (ns >= 1) {          // ghid and all four parameter gradients of every scale's context MLP in one launch
         ProfScope ps(c.s, PK_SCE, 1);
-        SceArgs sa = sce_args(c);
+        SceArgs sa = sce_args(c.f, c.L);
         // slab rows per scale: one workgroup per 256 rows, at most nb; a scale with fewer leaves a short range for the reduction
         sa.wg_off[0] = 0;
         for (int j = 0; j < f->n_scales; ++j) {

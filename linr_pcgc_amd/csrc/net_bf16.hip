@@ -178,19 +178,13 @@ static int bheads(const BCtx& c, int k0, int k1, float* probs_stage_major, doubl
 extern "C" int linr_net_forward_bf16(const linr_frame* f, const uint8_t* codes, float min_param, float max_param, void* arena,
                                      size_t arena_bytes, int32_t stage_begin, int32_t stage_end, float* probs, double* bits_acc,
                                      void* stream) {
-    if (!f || !codes || !arena || !probs) return LINR_EINVAL;
-    if (f->rows < 0 || f->n_scales < 1 || f->n_scales > MAX_SCALES || !f->row_off_h || !f->scale_idx_h) return LINR_EINVAL;
-    if (stage_begin < 0 || stage_end > 8 || stage_begin >= stage_end) return LINR_EINVAL;
+    if (!codes || !arena || !probs) return LINR_EINVAL;
     BCtx c;
-    if (!make_layout(c.L, f->model_scale_num, f->block_layers < 1 ? 1 : f->block_layers)) return LINR_EINVAL;
-    if (f->row_off_h[0] != 0 || f->row_off_h[f->n_scales] != f->rows) return LINR_EINVAL;
-    for (int s = 0; s < f->n_scales; ++s) {
-        if (f->row_off_h[s + 1] < f->row_off_h[s]) return LINR_EINVAL;
-        if (f->scale_idx_h[s] < 0 || f->scale_idx_h[s] >= f->model_scale_num) return LINR_EINVAL;
-    }
+    TRY(linr_frame_layout(f, 0, c.L));
+    if (stage_begin < 0 || stage_end > 8 || stage_begin >= stage_end) return LINR_EINVAL;
     if (f->rows == 0) return 0;
     if (!f->nbr_lo || !f->nbr_mask || !f->offset_feat || !f->occ || f->nbr_ld < f->rows) return LINR_EINVAL;   // compressed map only
-    if (f->rows >= ((int64_t)1 << 27) - 1) return LINR_EINVAL;                    // 32-bit byte offsets of the 16-byte gathers
+    if (!linr_rows_fit32(f->rows)) return LINR_EINVAL;
     if (arena_bytes < linr_net_bf16_arena_bytes(f->rows, c.L.BL)) return LINR_ENOSPC;
     if (((uintptr_t)arena) & 63u) return LINR_EALIGN;
     c.f = f; c.codes = codes; c.minv = min_param; c.range = max_param - min_param;      // fp32 subtraction, like ten_range
@@ -203,13 +197,7 @@ extern "C" int linr_net_forward_bf16(const linr_frame* f, const uint8_t* codes, 
         dequant_all_k<<<linr_grid(L.total, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(codes, L.total, c.range, c.minv, a.PF);
         zero_pads16_k<<<a.pads.n, 64, 0, c.s>>>(a.mats, a.pads);
         BSce sa;
-        sa.n_scales = f->n_scales;
-        for (int s = 0; s < f->n_scales; ++s) {
-            const int si = f->scale_idx_h[s];
-            sa.row_off[s] = f->row_off_h[s];
-            sa.emb[s] = L.emb + si * 8; sa.w1[s] = L.m0_w[si]; sa.b1[s] = L.m0_b[si]; sa.w2[s] = L.m2_w[si]; sa.b2[s] = L.m2_b[si];
-        }
-        sa.row_off[f->n_scales] = f->rows;
+        linr_sce_table(f, L, sa);
         linr_poison_hook(c.s, 14);
         sce_bf16_k<<<linr_grid(c.R, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(a.PF, f->offset_feat, sa, c.R, a.X0);
         TRY(bblock(c, L.block_in, a.X0, 0, nullptr));                                   // O[0] = x_glob

@@ -261,7 +261,7 @@ extern "C" int linr_occ_wgrad7(const float* occ, const float* const* gout7_h, co
         if (!gout7_h[b]) return LINR_EINVAL;
         if (!linr_aligned16(gout7_h[b])) return LINR_EALIGN;
     }
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull || ld >= ((int64_t)1 << 26)) return LINR_EINVAL;
+    if (!linr_rows_fit32(n) || !linr_cmap_fits32(ld)) return LINR_EINVAL;
     int64_t w_off[7], b_off[7], cur = 0;
     for (int b = 0; b < 7; ++b) { w_off[b] = cur; cur += 27 * (b + 1) * 8; b_off[b] = cur; cur += 8; }
     int rows = 0;

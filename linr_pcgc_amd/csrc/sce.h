@@ -28,6 +28,16 @@ struct SceArgs {
     int n_scales;
 };
 
+// the arguments of a frame's scale context: linr_sce_table plus blk_off, the first workgroup of every scale (wg_off is the backward's)
+static inline SceArgs sce_args(const linr_frame* f, const Layout& L) {
+    SceArgs a;
+    linr_sce_table(f, L, a);
+    a.blk_off[0] = 0;
+    for (int s = 0; s < f->n_scales; ++s)
+        a.blk_off[s + 1] = a.blk_off[s] + (int)linr_grid(a.row_off[s + 1] - a.row_off[s], LINR_BLOCK);
+    return a;
+}
+
 // scale of workgroup b and the row of this thread (-1: none)
 __device__ __forceinline__ int64_t sce_row_of(const SceArgs& a, int b, int& s) {
     s = 0;

@@ -1035,17 +1035,11 @@ struct TCtx {
 };
 
 static int tcheck(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16, TCtx& c) {
-    if (!f || !params || !arena) return LINR_EINVAL;
-    if (f->rows < 0 || f->n_scales < 1 || f->n_scales > MAX_SCALES || !f->row_off_h || !f->scale_idx_h) return LINR_EINVAL;
+    if (!params || !arena) return LINR_EINVAL;
+    TRY(linr_frame_layout(f, 1, c.L));
     if (f->block_layers > 1) return LINR_EINVAL;                // block_layers 1 only
-    if (!make_layout(c.L, f->model_scale_num, 1)) return LINR_EINVAL;
-    if (f->row_off_h[0] != 0 || f->row_off_h[f->n_scales] != f->rows) return LINR_EINVAL;
-    for (int s = 0; s < f->n_scales; ++s) {
-        if (f->row_off_h[s + 1] < f->row_off_h[s]) return LINR_EINVAL;
-        if (f->scale_idx_h[s] < 0 || f->scale_idx_h[s] >= f->model_scale_num) return LINR_EINVAL;
-    }
     if (f->rows > 0 && (!f->nbr_lo || !f->nbr_mask || !f->offset_feat || !f->occ || f->nbr_ld < f->rows)) return LINR_EINVAL;   // compressed map only
-    if (f->rows >= ((int64_t)1 << 27) - 1) return LINR_EINVAL;                    // 32-bit byte offsets of the 16-byte gathers
+    if (!linr_rows_fit32(f->rows)) return LINR_EINVAL;
     if (arena_bytes < linr_net_train_bf16_arena_bytes(f->rows, 1)) return LINR_ENOSPC;
     if (((uintptr_t)arena) & 63u) return LINR_EALIGN;
     if (occ_bf16 && (((uintptr_t)occ_bf16) & 15u)) return LINR_EALIGN;
@@ -1100,17 +1094,7 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
             tp.pr_w[k] = L.pr_w[k]; tp.c00_w[k] = q.c00_w; tp.c01_w[k] = q.c01_w; tp.c11_w[k] = q.c11_w;
         }
         tpack_k<<<TP_IMAGES + a.pads.n, 64, 0, c.s>>>(c.P, tp, a.WIMG, a.mats, a.pads);
-        SceArgs sa;
-        sa.n_scales = f->n_scales;
-        for (int s = 0; s < f->n_scales; ++s) {
-            const int si = f->scale_idx_h[s];
-            sa.row_off[s] = f->row_off_h[s];
-            sa.emb[s] = L.emb + si * 8; sa.w1[s] = L.m0_w[si]; sa.b1[s] = L.m0_b[si]; sa.w2[s] = L.m2_w[si]; sa.b2[s] = L.m2_b[si];
-        }
-        sa.row_off[f->n_scales] = f->rows;
-        sa.blk_off[0] = 0;
-        for (int s = 0; s < f->n_scales; ++s)
-            sa.blk_off[s + 1] = sa.blk_off[s] + (int)linr_grid(sa.row_off[s + 1] - sa.row_off[s], LINR_BLOCK);
+        const SceArgs sa = sce_args(f, L);
         PadList none;
         none.n = 0;
         sce_fwd_k<bf16_t><<<sa.blk_off[sa.n_scales], LINR_BLOCK, 0, c.s>>>(c.P, f->offset_feat, sa, c.R, nullptr, nullptr, a.X0, nullptr, none);
@@ -1350,7 +1334,7 @@ extern "C" int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* 
     if (n == 0) return 0;
     if (!gout || !in || !lo || !mask || !W || !gin || !slab || !rows_written) return LINR_EINVAL;
     if ((((uintptr_t)gout) & 15u) || (((uintptr_t)in) & 15u) || (((uintptr_t)gin) & 15u)) return LINR_EALIGN;
-    if (n >= ((int64_t)1 << 27) - 1) return LINR_EINVAL;
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     BbArgs a = BbArgs();
     a.g = gout; a.xin = in; a.P = W; a.out = gin; a.lo = lo; a.mask = mask; a.ld = ld; a.n = n;
     a.big = slab; a.block_stride = 1736;

@@ -320,7 +320,7 @@ static int spconv_wide_impl(int32_t bwd, const float* const* in_h, const int32_t
     if ((flags & LINR_RELU_MASK) && !act_h) return LINR_EINVAL;
     if (bwd && cin % 8) return LINR_EINVAL;
     if (!bwd && cin > 8 && cin % 8) return LINR_EINVAL;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull || ld >= ((int64_t)1 << 26)) return LINR_EINVAL;
+    if (!linr_rows_fit32(n) || !linr_cmap_fits32(ld)) return LINR_EINVAL;
     const int gch = bwd ? cout : cin, pch = bwd ? cin : cout;
     const int gb = (gch + 7) / 8, npb = pch / 8;
     if (gb == 3 || npb == 3) return LINR_EINVAL;          // widths are 8, 16 or 32
@@ -656,7 +656,7 @@ extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, con
                                       const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, void* stream) {
     if (n < 0 || ld < n || cin < 1 || cin > 32 || cout < 8 || cout > 32 || cout % 8 || (cin > 8 && cin % 8)) return LINR_EINVAL;
     if (!in_h || !g_h || !nbr || !slab) return LINR_EINVAL;
-    if ((uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull) return LINR_EINVAL;
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     linr_poison_hook(s, 16);
     const int nbi = (cin + 7) / 8, nbo = cout / 8, npairs = nbi * nbo;
@@ -714,7 +714,7 @@ extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, con
 extern "C" int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h, const float* const* gB_h,
                                        int32_t h, const int32_t* tile8t, int64_t n, float* slab, void* stream) {
     if (n < 1 || (h != 8 && h != 16) || !inA_h || !gA_h || !inB_h || !gB_h || !tile8t || !slab) return LINR_EINVAL;
-    if (!linr_aligned16(tile8t) || (uint64_t)(n + 1) * 32u >= 0xFFFFFFFFull) return LINR_EINVAL;
+    if (!linr_aligned16(tile8t) || !linr_rows_fit32(n)) return LINR_EINVAL;
     const int nb = h / 8, npairs = nb * nb;
     WwArgs a;
     for (int i = 0; i < WC_MAXB; ++i) {

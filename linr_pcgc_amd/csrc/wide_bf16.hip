@@ -308,7 +308,7 @@ extern "C" int linr_spconv_wide_bf16(int32_t epi, const uint16_t* in, int64_t in
     if (n < 0) return LINR_EINVAL;
     if (n == 0) return 0;
     if (!in || !lo || !mask || !img || !bias || !out || ld < n || cin < 1 || cin > 32) return LINR_EINVAL;
-    if (n >= ((int64_t)1 << 27) - 1) return LINR_EINVAL;                         // 32-bit byte offsets of the 16-byte gathers
+    if (!linr_rows_fit32(n)) return LINR_EINVAL;
     const int nbi = (cin + 7) / 8;
     if ((epi == WE_PW1 || epi == WE_PW2) && (!pw_w || !pw_b)) return LINR_EINVAL;
     if (epi == WE_PW2 && !res) return LINR_EINVAL;
@@ -337,7 +337,7 @@ extern "C" int linr_head_wide_bf16_fwd(const uint16_t* in, int64_t in_bs, int32_
     if (n == 0) return 0;
     if (!in || !lo || !mask || !img || !bias || !w1 || !b1 || !w2 || !b2 || !p || ld < n || (C != 16 && C != 32)) return LINR_EINVAL;
     if (partial && (!target || t_col < 0 || t_col > 7)) return LINR_EINVAL;
-    if (n >= ((int64_t)1 << 27) - 1 || in_bs < 8 * (n + 1)) return LINR_EINVAL;
+    if (!linr_rows_fit32(n) || in_bs < 8 * (n + 1)) return LINR_EINVAL;
     if (!al16(in) || !al16(img) || (in_bs & 7)) return LINR_EALIGN;
     WArgs a = WArgs();
     a.in = reinterpret_cast<const bf16_t*>(in); a.ibs = in_bs;
@@ -350,20 +350,11 @@ extern "C" int linr_head_wide_bf16_fwd(const uint16_t* in, int64_t in_bs, int32_
 
 // ---- scale context: x0 (8 wide at every width) on the width-8 executor's kernel ------------------------------------------------
 extern "C" int linr_sce_fwd_bf16(const float* pf, const linr_frame* f, uint16_t* x0_padded, void* stream) {
-    if (!f || !pf || !x0_padded) return LINR_EINVAL;
-    if (f->rows < 0 || f->n_scales < 1 || f->n_scales > MAX_SCALES || !f->row_off_h || !f->scale_idx_h) return LINR_EINVAL;
+    if (!pf || !x0_padded) return LINR_EINVAL;
     Layout L;
-    if (!make_layout(L, f->model_scale_num, 1)) return LINR_EINVAL;     // the scale context leads the layout at every width
-    if (f->row_off_h[0] != 0 || f->row_off_h[f->n_scales] != f->rows) return LINR_EINVAL;
+    if (const int rc = linr_frame_layout(f, 1, L)) return rc;          // the scale context leads the layout at every width
     BSce sa;
-    sa.n_scales = f->n_scales;
-    for (int s = 0; s < f->n_scales; ++s) {
-        const int si = f->scale_idx_h[s];
-        if (f->row_off_h[s + 1] < f->row_off_h[s] || si < 0 || si >= f->model_scale_num) return LINR_EINVAL;
-        sa.row_off[s] = f->row_off_h[s];
-        sa.emb[s] = L.emb + si * 8; sa.w1[s] = L.m0_w[si]; sa.b1[s] = L.m0_b[si]; sa.w2[s] = L.m2_w[si]; sa.b2[s] = L.m2_b[si];
-    }
-    sa.row_off[f->n_scales] = f->rows;
+    linr_sce_table(f, L, sa);
     if (f->rows == 0) return 0;
     if (!f->offset_feat) return LINR_EINVAL;
     if (!al16(x0_padded)) return LINR_EALIGN;

@@ -154,6 +154,113 @@ def test_c_abi_argument_checks(lib):
     assert lib.linr_sce_bwd_params_slab_bytes(7) == 256 * (7 * 8 + 7 * 392) * 4
     assert lib.linr_sce_bwd_params(p16, None, p16, p16, p16, 1 << 30, p16, None) == -1                           # no frame
 
+    # ---- the frame contract (linr_frame) at every entry that takes a frame: each call below is refused before anything is launched
+    from linr_pcgc_amd._lib import LinrFrame, LinrInceptionParams
+    byref = ctypes.byref
+    p64 = (p + 63) & ~63                             # buf has 4096 bytes: p64 .. p64 + 4031 are inside it
+    bound = (1 << 27) - 1                            # first row count whose gathered-row byte offsets ((rows + 1) * 32 B) reach 2^32
+    keep = []
+
+    def frame(rows=16, n_scales=2, row_off=(0, 8, 16), sidx=(0, 1), msn=7, bl=1, flags=0, nbr=p64, cmap=True, feat=p64, occ=p64):
+        ro, si = (ctypes.c_int64 * 18)(*row_off), (ctypes.c_int32 * 17)(*sidx)
+        f = LinrFrame(rows, n_scales, msn, bl, flags, ctypes.addressof(ro), ctypes.addressof(si), nbr, rows,
+                      p64 if cmap else None, p64 if cmap else None, feat, occ, None)
+        keep.append((ro, si, f))
+        return byref(f)
+
+    faults = [dict(n_scales=0), dict(n_scales=17, rows=17, row_off=range(18), sidx=[0] * 17),      # n_scales outside 1..MAX_SCALES
+              dict(row_off=(1, 8, 16)), dict(n_scales=3, row_off=(0, 12, 8, 16), sidx=(0, 1, 2)),   # row_off_h[0] != 0, decreasing
+              dict(row_off=(0, 8, 15)), dict(sidx=(0, 7)), dict(sidx=(-1, 1)),                      # last != rows, scale_idx range
+              dict(bl=5)]                                                                           # block_layers > MAX_BL
+    at_bound = dict(rows=bound, row_off=(0, 8, bound))
+    below_bound = dict(rows=bound - 1, row_off=(0, 8, bound - 1))
+    fwd = lambda f, a, nb: lib.linr_net_forward(f, p64, a, nb, 0, 8, None, None, None)
+    bwd = lambda f, a, nb: lib.linr_net_backward(f, p64, a, nb, 1.0, p64, None)
+    step = lambda f, a, nb: lib.linr_net_train_step(f, p64, a, nb, 1.0, p64, p64, 0.01, 1, None, 0.9, 0.999, 1e-8, 0.0, p64, None)
+    dec = lambda f, a, nb: lib.linr_net_decode_stages(f, p64, None, 0.0, 1.0, a, nb, p64, p64, p64, p64, p64, p64, None)
+    bfwd = lambda f, a, nb: lib.linr_net_forward_bf16(f, p64, 0.0, 1.0, a, nb, 0, 8, p64, None, None)
+    bdec = lambda f, a, nb: lib.linr_net_decode_stages(f, None, p64, 0.0, 1.0, a, nb, p64, p64, p64, p64, p64, p64, None)
+    tfwd = lambda f, a, nb: lib.linr_net_forward_train_bf16(f, p64, a, nb, None, None, None, None)
+    tbwd = lambda f, a, nb: lib.linr_net_backward_bf16(f, p64, a, nb, None, 1.0, p64, None)
+    tstep = lambda f, a, nb: lib.linr_net_train_step_bf16(f, p64, a, nb, None, 1.0, p64, p64, 0.01, 1, None, 0.9, 0.999, 1e-8, 0.0, p64, None)
+    # (entries, arena bytes of the 16-row frame, arena alignment)
+    for entries, need, align in (((fwd, bwd, step, dec), lib.linr_net_arena_bytes, 16),
+                                 ((bfwd, bdec), lib.linr_net_bf16_arena_bytes, 64),
+                                 ((tfwd, tbwd, tstep), lib.linr_net_train_bf16_arena_bytes, 64)):
+        n16 = need(16, 1)
+        for call in entries:
+            for fault in faults + [at_bound]:
+                assert call(frame(**fault), p64, n16) == -1, (call, fault)
+                assert call(frame(**fault), p64 + 4, 0) == -1, (call, fault)                        # EINVAL before ENOSPC / EALIGN
+            assert call(frame(**below_bound), p64, n16) == -2                                       # one row below the bound: accepted
+            assert call(frame(), p64, n16 - 1) == -2                                                # short arena
+            assert call(frame(), p64 + 4, n16 - 1) == -2                                            # ENOSPC before EALIGN
+            assert call(frame(), p64 + align // 4, n16) == -3                                       # misaligned arena
+            assert call(frame(bl=0), p64, n16 - 1) == -2                                            # block_layers 0 is read as 1
+            assert call(frame(rows=0, row_off=(0, 0, 0), bl=5), p64, n16) == (0 if call in (dec, bdec) else -1)
+    for call in (fwd, bwd, step, dec):                       # fp32: the plain map, offset_feat and occ; any block_layers
+        for fault in (dict(nbr=None), dict(feat=None), dict(occ=None)):
+            assert call(frame(**fault), p64, 1 << 40) == -1, (call, fault)
+        assert call(frame(bl=2), p64, lib.linr_net_arena_bytes(16, 1)) == -2
+        assert call(frame(flags=1, occ=p64 + 4), p64, lib.linr_net_arena_bytes(16, 1)) == -1   # padded occupancy must be 16-byte aligned
+        assert call(frame(flags=1, occ=p64 + 4), p64 + 4, lib.linr_net_arena_bytes(16, 1)) == -3
+    for call in (bfwd, bdec, tfwd, tbwd, tstep):             # bf16: the compressed map, offset_feat and occ
+        for fault in (dict(cmap=False), dict(feat=None), dict(occ=None)):
+            assert call(frame(**fault), p64, 1 << 40) == -1, (call, fault)
+    for call in (bfwd, bdec):
+        assert call(frame(bl=2), p64, lib.linr_net_bf16_arena_bytes(16, 1)) == -2
+    for call in (tfwd, tbwd, tstep):                         # bf16 training: block_layers 1 only
+        assert call(frame(bl=2), p64, 1 << 40) == -1
+    assert lib.linr_net_forward_train_bf16(frame(), p64, p64, lib.linr_net_train_bf16_arena_bytes(16, 1), p64 + 4, None, None, None) == -3
+    # the scale context as stand-alone ops: the frame's structure only (no row bound, no arena)
+    sfwd = lambda f, a: lib.linr_sce_fwd(p64, f, None, a, p64, None)
+    sbwd = lambda f, a: lib.linr_sce_bwd(p64, f, a, p64, p64, None)
+    sprm = lambda f, a: lib.linr_sce_bwd_params(p64, f, a, p64, p64, 1 << 40, p64, None)
+    sbf = lambda f, a: lib.linr_sce_fwd_bf16(p64, f, a, None)
+    for call in (sfwd, sbwd, sprm, sbf):
+        for fault in faults[:-1]:
+            assert call(frame(**fault), p64) == -1, (call, fault)
+            assert call(frame(**fault), p64 + 4) == -1, (call, fault)
+        assert call(frame(), p64 + 4) == -3
+    for call in (sfwd, sbwd, sprm):
+        assert call(frame(bl=5), p64 + 4) == -1
+    assert sbf(frame(bl=5), p64 + 4) == -3                   # the wide models' scale context takes its layout at block_layers 1
+    assert sfwd(frame(rows=0, row_off=(0, 0, 0)), p64 + 4) == 0 and sbf(frame(rows=0, row_off=(0, 0, 0)), p64 + 4) == 0
+    assert sprm(frame(feat=None), p64) == -1 and sbf(frame(feat=None), p64) == -1
+    assert lib.linr_sce_bwd_params(p64, frame(), p64, p64, p64, 16, p64, None) == -2
+
+    # ---- 32-bit byte offsets: gathered rows ((n + 1) * row bytes < 2^32) and compressed maps (9 * ld * 4 B < 2^32).  At the bound
+    # each entry refuses; one below it, where a later check can tell, the bound has passed and that check answers instead.
+    ld_bound = 1 << 26                               # (spconv_wide: ld >= n, so its compressed-map bound is the one that binds)
+    q = LinrInceptionParams(*([p64] * 10))
+    offs7 = (ctypes.c_int64 * 7)()
+    b2a, b2m = (ctypes.c_void_p * 2)(p64, p64), (ctypes.c_void_p * 2)(p64 + 4, p64 + 4)
+    rw = ctypes.c_int32(7)
+    assert lib.linr_spconv_cmap(0, p64, 8, p64, p64, bound, bound, p64, p64, 8, 8, None, 0, None, 0, p64, 8, 0, None) == -1
+    assert lib.linr_spconv_cmap(0, p64, 4, p64, p64, 2 * bound + 1, 2 * bound + 1, p64, p64, 4, 8, None, 0, None, 0, p64, 8, 0, None) == -1
+    for n, rc, rc_ws in ((bound, -1, -1), (bound - 1, -3, -2)):
+        assert lib.linr_spconv_wgrad_cmap(p64, 8, p64, 8, p64, p64 + 4, n, n, 8, 8, p64, None) == rc
+        assert lib.linr_head_fwd(p64, p64, p64, n, n, p64, p64, p64, p64, p64, p64, p64, 8, p64, p64, p64, p64, 0, None) == rc_ws
+        assert lib.linr_spconv_wgrad_wide2(b2m, b2a, b2a, b2a, 8, p64, n, p64, None) == rc
+        assert lib.linr_spconv_wide_bf16(0, p64 + 4, 0, 8, p64, p64, n, n, p64, p64, 8, None, 0, None, 0, None, None, 0, p64, 0, None) == rc
+        assert lib.linr_head_wide_bf16_fwd(p64 + 4, 8 * (n + 1), 16, p64, p64, n, n, p64, p64, p64, p64, p64, p64, None, 0, p64, None,
+                                           None) == rc
+    for ld, rc in ((ld_bound, -1), (ld_bound - 1, -3)):
+        assert lib.linr_spconv_wide(0, b2m, p64, p64, ld, 16, p64, p64, 16, 16, None, None, b2a, 0, None) == rc
+    assert lib.linr_inception_fwd(p64, p64, p64, bound, bound, byref(q), p64, p64, p64, None) == -1
+    assert lib.linr_inception_bwd_data(p64, p64, p64, p64, p64, p64, bound, bound, byref(q), p64, p64, p64, 0, None) == -1
+    assert lib.linr_occ_conv7(p64, p64, p64, bound, bound, p64, offs7, offs7, p64, offs7, None) == -1
+    assert lib.linr_spconv_wgrad_dual44(p64, p64, 4, p64, 4, p64, None, bound, bound, p64, None) == -1
+    assert lib.linr_spconv_wgrad_wide(b2a, 16, b2a, 16, p64, None, bound, bound, p64, p64, p64, None) == -1
+    assert lib.linr_spconv_bwd_fused_bf16(p64, p64, p64, p64, bound, bound, p64, p64, p64, 1, byref(rw), None) == -1
+    g7a = (ctypes.c_void_p * 7)(*([p64] * 7))
+    for n, ld in ((bound, bound), (16, ld_bound)):
+        assert lib.linr_spconv_bwd_fused(p64, p64, p64, p64, ld, n, p64, p64, p64, 32, None) == -1
+        assert lib.linr_inception_bwd_fused(p64, p64, p64, p64, p64, p64, ld, n, byref(q), p64, p64, 0, p64, 32, None) == -1
+        assert lib.linr_occ_wgrad7(p64, g7a, p64, p64, ld, n, p64, 8, byref(rw), None) == -1
+    cn = ctypes.c_int64(5)
+    assert lib.linr_decode_scale(p64, 1 << 27, 0, 7, 1, 10, p64, None, 0.0, 1.0, p64, p64, p64, 0, p64, p64, p64, 0, byref(cn), None) == -1
+
 def test_param_count_matches_reference_checkpoint(lib, golden_dir):
     g = np.load(os.path.join(golden_dir, 'loot_model_kat.npz'))
     assert lib.linr_param_count(7, 1) == len(g['flat']) == 54712
