@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 12
+#define LINR_ABI_VERSION 13
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -355,8 +355,9 @@ typedef struct linr_frame {
     const int32_t* scale_idx_h;   /* HOST [n_scales]  which scale embedding / scale MLP each scale uses     */
     const int32_t* nbr;           /* [27][nbr_ld] kernel map with global row ids                            */
     int64_t nbr_ld;               /* leading dimension of nbr (>= rows; a multiple of 4 enables 16-byte index loads) */
-    const int32_t* nbr_lo;        /* [9][nbr_ld]  compressed kernel map (linr_kmap_compress), or NULL            */
-    const uint32_t* nbr_mask;     /* [nbr_ld]     27-bit presence masks of the compressed map, or NULL           */
+    const int32_t* nbr_lo;        /* [9][nbr_ld]  compressed kernel map (linr_kmap_compress): required by every network
+                                   * entry (linr_net_*, fp32 and bf16), may be NULL for linr_sce_*, which do not read it */
+    const uint32_t* nbr_mask;     /* [nbr_ld]     27-bit presence masks of the compressed map: required like nbr_lo  */
     const float*   offset_feat;   /* [rows][7]  7-neighbour occupancy (qscTensor.set_offset_tensor)         */
     const float*   occ;           /* [rows][8]  child occupancy ground truth (occ_lst concatenated)         */
     const int32_t* nbr8t;         /* linr_kmap_tile8t over nbr (the tiled copy in gather-lane order), or NULL             */

@@ -7,7 +7,6 @@
 #include "common.h"
 #include "conv_common.h"
 #include "head_bwd.h"
-#include <stdlib.h>
 #define WG_WAVES 4          // waves per block of the MFMA weight-gradient kernels (same-box A/B: 2 -> 2.765, 4 -> 2.574, 8 -> 2.596 ms/step)
 
 __global__ __launch_bounds__(LINR_BLOCK) void kmap_compress_k(const int32_t* __restrict__ nbr, int64_t nbr_ld, int64_t n,
@@ -37,79 +36,18 @@ extern "C" int linr_kmap_compress(const int32_t* nbr, int64_t nbr_ld, int64_t n,
     return linr_launch_rc();
 }
 
-// Plain conv3 forward / backward-data on the compressed map.  Same arithmetic order as spconv_gather_k (taps in LINR_TAP order,
-// gathered channel ascending) => bit-identical results.  `in` must have the zero pad row at index -1.
+// ---- plain conv3 forward / backward-data on the compressed map, on the matrix cores --------------------------------------
+// `in` must have the zero pad row at index -1.
 //   BWD == false: acc[o] += x[i] * W[(k*GIN + i)*GOUT + o]
 //   BWD == true : acc[o] += x[i] * W[(k*GOUT + o)*GIN + i]   (gathered rows come from the mirrored offset)
-template <int GIN, int GOUT, bool BWD, int LOADW>
-__global__ __launch_bounds__(LINR_BLOCK) void cconv_k(const float* __restrict__ in, int in_ld,
-                                                      const int32_t* __restrict__ lo, const uint32_t* __restrict__ mask,
-                                                      int64_t ld, int64_t n, const float* __restrict__ W,
-                                                      const float* __restrict__ bias, const float* __restrict__ res,
-                                                      int res_ld, const float* __restrict__ act, int act_ld,
-                                                      float* __restrict__ out, int out_ld, unsigned flags) {
-    const int64_t row = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
-    if (row >= n) return;
-    const char* pad = reinterpret_cast<const char*>(in - in_ld);
-    uint32_t off[27];
-    decode_offsets<BWD>(lo, mask, ld, row, (uint32_t)in_ld * 4u, off);
-    float acc[GOUT];
-#pragma unroll
-    for (int o = 0; o < GOUT; ++o) acc[o] = (bias != nullptr) ? bias[o] : 0.0f;
-#pragma unroll
-    for (int kk = 0; kk < 27; ++kk) {
-        const int k = LINR_TAP(kk);
-        float x[LOADW];
-        RowLoadF<LOADW>::run(pad + off[k], x);
-        const float* __restrict__ wk = W + k * GIN * GOUT;
-#pragma unroll
-        for (int i = 0; i < GIN; ++i) {
-#pragma unroll
-            for (int o = 0; o < GOUT; ++o) {
-                const float w = BWD ? wk[o * GIN + i] : wk[i * GOUT + o];
-                acc[o] = fmaf(x[i], w, acc[o]);
-            }
-        }
-    }
-    // epilogue order: + res, + old (ACCUM), * mask, ReLU
-    if (res != nullptr) {
-        const float* r = res + row * res_ld;
-#pragma unroll
-        for (int o = 0; o < GOUT; ++o) acc[o] += r[o];
-    }
-    float* op = out + row * out_ld;
-    if (flags & LINR_ACCUM) {
-#pragma unroll
-        for (int o = 0; o < GOUT; ++o) acc[o] += op[o];
-    }
-    if (flags & LINR_RELU_MASK) {
-        const float* a = act + row * act_ld;
-#pragma unroll
-        for (int o = 0; o < GOUT; ++o) acc[o] = a[o] > 0.0f ? acc[o] : 0.0f;
-    }
-    if (flags & LINR_RELU) {
-#pragma unroll
-        for (int o = 0; o < GOUT; ++o) acc[o] = fmaxf(acc[o], 0.0f);
-    }
-    if ((GOUT % 4 == 0) && (out_ld % 4 == 0)) {
-#pragma unroll
-        for (int v = 0; v < GOUT / 4; ++v)
-            *reinterpret_cast<float4*>(op + 4 * v) = make_float4(acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
-    } else {
-#pragma unroll
-        for (int o = 0; o < GOUT; ++o) op[o] = acc[o];
-    }
-}
-
-// ---- the same convolution on the matrix cores ----------------------------------------------------------------------------
 // v_mfma_f32_4x4x1_16b_f32 is 16 independent 4x4 outer products (K = 1); with CBSZ = 4 the A operand of block ABID is
 // broadcast to all 16 blocks, so ONE instruction computes, for all 64 lanes at once,
 //        acc[row(lane)][4*ABID + i] += W[ci][4*ABID + i] * x[row(lane)][ci]        i = 0..3
 // i.e. 64 rows x 4 output channels x 1 input channel = 256 FMAs with NO padding (the 16-wide MFMA shapes waste half
-// of their N dimension at Cout = 8).  The lane keeps the thread-per-row layout of the VALU kernel: B = the lane's
+// of their N dimension at Cout = 8).  The lane keeps the thread-per-row layout of spconv_gather_k (csrc/spconv.hip): B = the lane's
 // gathered feature x[ci], D = the lane's 4 accumulators, A = the weight row held by lanes 0..GOUT-1 (read from an LDS
 // copy of the whole [27][Cin][Cout] kernel).  K = 1 makes every instruction a single-rounding fmaf(x, w, acc), issued
-// in the same order as the VALU kernel (taps in LINR_TAP order, ci ascending) => bit-identical results, at the MFMA rate
+// in the same order as spconv_gather_k (taps in LINR_TAP order, ci ascending) => bit-identical results, at the MFMA rate
 // (measured 91-119 TFLOP/s for this stream vs 52-71 TFLOP/s for v_pk_fma_f32; tools/mfma_probe.hip, valu_probe.hip).
 // Measured dead ends for this kernel (kept out of the tree): hand-pinned software pipelines
 // (2-3 offsets ahead, or a whole dz-plane of gathers in flight) and wave-cooperative staging of each (dx,dy) column's
@@ -1149,7 +1087,8 @@ int linr_head_bwd_launch(const float* c, const float* p, const float* target, in
     return linr_launch_rc();
 }
 
-// executor entry: all matrices are arena matrices (16-byte aligned rows, ld in {4, 8}, pad row present)
+// executor entry: all matrices are arena matrices (16-byte aligned rows, ld in {4, 8}, pad row present).  The kernel writes 4 or
+// 8 channels, so the backward-data of an outter block's first conv into 1..3 or 5..7 occupancy channels is refused (nothing needs it).
 int linr_cconv_launch(bool bwd, const float* in, int in_ld, const int32_t* lo, const uint32_t* mask, int64_t ld,
                       int64_t n, const float* W, const float* bias, int cin, int cout, const float* res, int res_ld,
                       const float* act, int act_ld, float* out, int out_ld, unsigned flags, hipStream_t s, const Grp* gp,
@@ -1157,25 +1096,18 @@ int linr_cconv_launch(bool bwd, const float* in, int in_ld, const int32_t* lo, c
     if (n == 0) return 0;
     const Grp g0 = gp ? *gp : Grp();
     const dim3 grid(linr_grid(n, LINR_CONV_BLOCK), ngroups);
-    static const int use_mfma = getenv("LINR_CONV_MFMA") ? atoi(getenv("LINR_CONV_MFMA")) : 1;   // 0: the VALU kernel (bitwise reference)
-#define GO(GI, GO_, B, LW)                                                                                              \
+#define GO(GI, GO_, B)                                                                                                  \
     do {                                                                                                                \
-        if (use_mfma && (GO_ == 4 || GO_ == 8))                                                                    \
-            cconv_mfma_k<GI, (GO_ == 4 || GO_ == 8) ? GO_ : 8, B, LW><<<grid, LINR_CONV_BLOCK, 0, s>>>(                       \
-                in, in_ld, lo, mask, ld, n, W, bias, res, res_ld, act, act_ld, out, out_ld, flags, HeadArgs(), PwArgs(), g0);  \
-        else                                                                                                            \
-            cconv_k<GI, GO_, B, LW><<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(in, in_ld, lo, mask, ld, n, W, bias, res, res_ld, act,   \
-                                                                act_ld, out, out_ld, flags);                            \
+        cconv_mfma_k<GI, GO_, B, ((GI + 3) / 4 * 4)><<<grid, LINR_CONV_BLOCK, 0, s>>>(                                  \
+            in, in_ld, lo, mask, ld, n, W, bias, res, res_ld, act, act_ld, out, out_ld, flags, HeadArgs(), PwArgs(), g0); \
         return linr_launch_rc();                                                                                        \
     } while (0)
-#define CASE(CI, CO)                                                      \
-    if (cin == CI && cout == CO) {                                        \
-        if (!bwd) GO(CI, CO, false, ((CI + 3) / 4 * 4));                  \
-        else GO(CO, CI, true, ((CO + 3) / 4 * 4));                        \
-    }
-    CASE(8, 8) CASE(8, 4) CASE(4, 4)
-    CASE(1, 8) CASE(2, 8) CASE(3, 8) CASE(4, 8) CASE(5, 8) CASE(6, 8) CASE(7, 8)
-#undef CASE
+#define FWD(CI, CO) if (!bwd && cin == CI && cout == CO) GO(CI, CO, false);
+#define BWD(CI, CO) if (bwd && cin == CI && cout == CO) GO(CO, CI, true);
+    FWD(8, 8) FWD(8, 4) FWD(4, 4) FWD(1, 8) FWD(2, 8) FWD(3, 8) FWD(4, 8) FWD(5, 8) FWD(6, 8) FWD(7, 8)
+    BWD(8, 8) BWD(8, 4) BWD(4, 4) BWD(4, 8)
+#undef BWD
+#undef FWD
 #undef GO
     return LINR_EINVAL;
 }

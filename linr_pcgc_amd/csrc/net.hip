@@ -40,14 +40,14 @@ struct Arena {
     float *A[8], *H[8], *M[8], *I[8], *O[8];
     float *Hx[MAX_BL - 1], *Mx[MAX_BL - 1], *Ix[MAX_BL - 1];        // Inception layers 1.. of block_in (block_layers > 1)
     float *gIx[MAX_BL - 1], *gMx[MAX_BL - 1], *gHx[MAX_BL - 1];
-    float *C[8], *HH[8], *Z[8], *P[8];
+    float *C[8], *P[8];
     // backward scratch
-    float *gZ, *gHH, *gXG, *gX0;
+    float *gXG, *gX0;
     float *gC[8], *gO[8], *gI[8], *gA[8], *gH[8], *gM[8];   // one set per stage / block (the grouped launches need them side by side)
     float* BIG;                  // [LINR_WG_BLOCKS][n_params] per-block partial weight gradients
     float* GSUM;                 // [n_params] their fixed-order sum (the gradient of this backward call)
     int64_t n_params;
-    void* slab; size_t slab_bytes;
+    void* slab;
 };
 
 static float* arena_mat(Arena& a, int ld) {
@@ -58,9 +58,8 @@ static float* arena_mat(Arena& a, int ld) {
     return p;
 }
 
-static size_t slab_need(int64_t rows) {
-    const size_t a = linr_bce_workspace_bytes(rows), b = (size_t)8 * linr_grid(rows, LINR_BLOCK) * sizeof(double);
-    return (a > b ? a : b) + 64;
+static size_t slab_need(int64_t rows) {          // the 8 heads' per-block bits partials
+    return (size_t)8 * linr_grid(rows, LINR_BLOCK) * sizeof(double) + 64;
 }
 
 static void make_arena(Arena& a, int64_t rows, float* base, int64_t n_params, int block_layers = 1) {
@@ -71,9 +70,9 @@ static void make_arena(Arena& a, int64_t rows, float* base, int64_t n_params, in
         a.I[b] = arena_mat(a, 8); a.O[b] = arena_mat(a, 8);
     }
     for (int k = 0; k < 8; ++k) {
-        a.C[k] = arena_mat(a, 8); a.HH[k] = arena_mat(a, 24); a.Z[k] = arena_mat(a, 1); a.P[k] = arena_mat(a, 1);
+        a.C[k] = arena_mat(a, 8); a.P[k] = arena_mat(a, 1);
     }
-    a.gZ = arena_mat(a, 1); a.gHH = arena_mat(a, 24); a.gXG = arena_mat(a, 8); a.gX0 = arena_mat(a, 8);
+    a.gXG = arena_mat(a, 8); a.gX0 = arena_mat(a, 8);
     for (int i = 0; i < 8; ++i) {
         a.gC[i] = arena_mat(a, 8); a.gO[i] = arena_mat(a, 8); a.gI[i] = arena_mat(a, 8); a.gA[i] = arena_mat(a, 8);
         a.gH[i] = arena_mat(a, 8); a.gM[i] = arena_mat(a, 4);
@@ -91,8 +90,7 @@ static void make_arena(Arena& a, int64_t rows, float* base, int64_t n_params, in
     a.BIG = base ? base + a.cur : nullptr; a.cur += (int64_t)LINR_WG_BLOCKS * n_params;
     a.cur = (a.cur + 15) & ~(int64_t)15;                     // 64-byte alignment for the slab (doubles inside)
     a.slab = base ? (void*)(base + a.cur) : nullptr;
-    a.slab_bytes = slab_need(rows);
-    a.cur += (int64_t)((a.slab_bytes + 3) / 4);
+    a.cur += (int64_t)((slab_need(rows) + 3) / 4);
 }
 
 extern "C" size_t linr_net_arena_bytes(int64_t rows, int32_t block_layers) {
@@ -347,11 +345,6 @@ __global__ __launch_bounds__(SB_WAVES * 64) void sce_bwd_all_k(const float* __re
     }
 }
 
-__global__ __launch_bounds__(LINR_BLOCK) void sigmoid_k(const float* __restrict__ z, int64_t n, float* __restrict__ p) {
-    const int64_t i = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
-    if (i < n) p[i] = 1.0f / (1.0f + expf(-z[i]));
-}
-
 // dst (+)= src over n floats
 __global__ __launch_bounds__(LINR_BLOCK) void axpy_k(const float* __restrict__ src, int64_t n, float* __restrict__ dst,
                                                      int accumulate) {
@@ -597,37 +590,22 @@ extern "C" int linr_prof_read(int32_t kind, double* total_ms, int64_t* launches,
 static const int32_t* clo(const Ctx& c) { return c.f->nbr_lo; }
 static const uint32_t* cmk(const Ctx& c) { return c.f->nbr_mask; }
 
-// grouped launches need the matrix-core conv kernel (the VALU fallback of LINR_CONV_MFMA=0 is a single-layer kernel)
-static bool grouped_enabled() {
-    static const int batched = getenv("LINR_BATCHED") ? atoi(getenv("LINR_BATCHED")) : 1;
-    static const int conv_mfma = getenv("LINR_CONV_MFMA") ? atoi(getenv("LINR_CONV_MFMA")) : 1;
-    return batched != 0 && conv_mfma != 0;
-}
-
-// block_in joins the grouped launches of the outter blocks when it has their shape (one Inception layer) - LINR_JOIN_BLOCK_IN=0
-// keeps its layers as single launches (the round-1/2 schedule; same kernels, same bits)
-static bool join_block_in(const Ctx& c) {
-    static const int v = getenv("LINR_JOIN_BLOCK_IN") ? atoi(getenv("LINR_JOIN_BLOCK_IN")) : 1;
-    return v != 0 && grouped_enabled() && c.f->nbr_lo && c.f->nbr_mask && c.L.block_in.nl == 1;
-}
+// block_in joins the grouped launches of the outter blocks when it has their shape (one Inception layer)
+static bool join_block_in(const Ctx& c) { return c.L.block_in.nl == 1; }
 
 // backward-data and weight gradient of the 8->8 convolutions from ONE gather (csrc/fused_bwd.hip); LINR_FUSED_BWD=0 restores the
 // two-kernel schedule (same input gradients bit for bit, weight gradients in another summation order)
 static bool fused_bwd(const Ctx& c) {
     static const int v = getenv("LINR_FUSED_BWD") ? atoi(getenv("LINR_FUSED_BWD")) : 1;
     // (the fused kernels have no 64-bit path into the compressed map: larger maps take the two-kernel path)
-    return v != 0 && c.f->nbr_lo && c.f->nbr_mask && linr_cmap_fits32(c.nbr_ld);
+    return v != 0 && linr_cmap_fits32(c.nbr_ld);
 }
 
 static int conv3(Ctx& c, bool bwd, const float* in, int in_ld, const float* W, const float* bias, int cin, int cout,
                  const float* res, int res_ld, const float* act, int act_ld, float* out, int out_ld, unsigned flags) {
-    if (c.f->nbr_lo && c.f->nbr_mask) {
-        ProfScope ps(c.s, bwd ? PK_BWD_DATA : PK_CONV88, 1);
-        return linr_cconv_launch(bwd, in, in_ld, clo(c), cmk(c), c.nbr_ld, c.R, W, bias, cin, cout, res, res_ld,
-                                 act, act_ld, out, out_ld, flags, c.s);
-    }
-    return linr_conv3_launch(bwd, in, in_ld, c.f->nbr, c.nbr_ld, c.R, W, bias, cin, cout, res, res_ld, act, act_ld, out, out_ld,
-                             flags | LINR_PAD_ROW, c.s);
+    ProfScope ps(c.s, bwd ? PK_BWD_DATA : PK_CONV88, 1);
+    return linr_cconv_launch(bwd, in, in_ld, clo(c), cmk(c), c.nbr_ld, c.R, W, bias, cin, cout, res, res_ld,
+                             act, act_ld, out, out_ld, flags, c.s);
 }
 
 // transposed tiled table of the stand-alone weight-gradient kernels (csrc/fused.hip: spconv_wgrad_t_k), or NULL: indices from nbr
@@ -671,23 +649,12 @@ static int block_fwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
     for (int l = 0; l < bp.nl; ++l) {
         const IncP& q = bp.inc[l];
         const LayerBufs t = layer_bufs(a, b, l);
-        if (c.f->nbr_lo && c.f->nbr_mask) {
-            // Inception layer in two launches (csrc/fused.hip): [conv0_0 | conv1_0 centre tap] -> H, then the two 4->4 convs
-            // as one pass with conv1_2 and the residual in the epilogue -> M, I
-            TRY(linr_conv_pw_fwd_launch(X, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c00_w, P + q.c00_b, P + q.c10_w,
-                                        P + q.c10_b, t.H, c.s));
-            TRY(linr_dual44_fwd_launch(t.H, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c01_w, P + q.c01_b, P + q.c11_w,
-                                       P + q.c11_b, X, P + q.c12_w, P + q.c12_b, t.M, t.I, c.s));
-        } else {
-            // path 0: H[:,0:4] = relu(conv3 8->4 (X));  path 1: H[:,4:8] = relu(X @ conv1_0)
-            TRY(conv3(c, false, X, 8, P + q.c00_w, P + q.c00_b, 8, 4, nullptr, 0, nullptr, 0, t.H, 8, LINR_RELU));
-            TRY(linear(c, X, 8, c.R, P + q.c10_w, 4, 1, P + q.c10_b, 8, 4, nullptr, 0, nullptr, 0, t.H + 4, 8, LINR_RELU));
-            // I[:,0:4] = conv3 4->4 (H0) + X[:,0:4]
-            TRY(conv3(c, false, t.H, 8, P + q.c01_w, P + q.c01_b, 4, 4, X, 8, nullptr, 0, t.I, 8, 0));
-            // M = relu(conv3 4->4 (H1)); I[:,4:8] = M @ conv1_2 + X[:,4:8]
-            TRY(conv3(c, false, t.H + 4, 8, P + q.c11_w, P + q.c11_b, 4, 4, nullptr, 0, nullptr, 0, t.M, 4, LINR_RELU));
-            TRY(linear(c, t.M, 4, c.R, P + q.c12_w, 4, 1, P + q.c12_b, 4, 4, X + 4, 8, nullptr, 0, t.I + 4, 8, 0));
-        }
+        // Inception layer in two launches (csrc/fused.hip): [conv0_0 | conv1_0 centre tap] -> H, then the two 4->4 convs
+        // as one pass with conv1_2 and the residual in the epilogue -> M, I
+        TRY(linr_conv_pw_fwd_launch(X, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c00_w, P + q.c00_b, P + q.c10_w,
+                                    P + q.c10_b, t.H, c.s));
+        TRY(linr_dual44_fwd_launch(t.H, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c01_w, P + q.c01_b, P + q.c11_w,
+                                   P + q.c11_b, X, P + q.c12_w, P + q.c12_b, t.M, t.I, c.s));
         X = t.I;
     }
     float* Il = layer_bufs(a, b, bp.nl - 1).I;
@@ -701,7 +668,6 @@ static int block_fwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
 static int block_bwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b, const float* gO, float* gin) {
     Arena& a = c.A;
     const float* P = c.P;
-    const bool cm = c.f->nbr_lo && c.f->nbr_mask;
     const int nl = bp.nl;
     const LayerBufs last = layer_bufs(a, b, nl - 1);
     // O = conv3(I_last; b)
@@ -712,28 +678,16 @@ static int block_bwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
         const float* X = l == 0 ? a.A[b] : layer_bufs(a, b, l - 1).I;         // the layer's input
         float* gX = l == 0 ? a.gA[b] : layer_bufs(a, b, l - 1).gI;           // where its input gradient goes
         // gI of this layer: from the block's tail conv (last layer) or written by layer l+1 as its input gradient
-        if (l == nl - 1) {
-            if (cm) {   // gI = bwd(gO; Wb) with gM = (gI[:,4:8] @ W12^T) * (M > 0) in the epilogue (csrc/fused.hip)
-                TRY(linr_conv_bwd_gm_launch(gO, clo(c), cmk(c), c.nbr_ld, c.R, P + bp.b_w, P + q.c12_w, t.M, t.gI, t.gM, c.s));
-            } else {
-                TRY(conv3(c, true, gO, 8, P + bp.b_w, nullptr, 8, 8, nullptr, 0, nullptr, 0, t.gI, 8, 0));
-            }
-        }
-        if (!(cm && l == nl - 1))   // I[:,4:8] = M @ c12 + b12 + X[:,4:8]  =>  gM = (gI[:,4:8] @ W12^T) * (M > 0)
+        // I[:,4:8] = M @ c12 + b12 + X[:,4:8]  =>  gM = (gI[:,4:8] @ W12^T) * (M > 0)
+        if (l == nl - 1)   // gI = bwd(gO; Wb) with gM in the epilogue (csrc/fused.hip)
+            TRY(linr_conv_bwd_gm_launch(gO, clo(c), cmk(c), c.nbr_ld, c.R, P + bp.b_w, P + q.c12_w, t.M, t.gI, t.gM, c.s));
+        else
             TRY(linear(c, t.gI + 4, 8, c.R, P + q.c12_w, 1, 4, nullptr, 4, 4, nullptr, 0, t.M, 4, t.gM, 4, LINR_RELU_MASK));
         TRY(linear_wgrad(c, t.M, 4, t.gI + 4, 8, c.R, 4, 4, q.c12_w, 4, 1, q.c12_b));
-        if (cm) {
-            TRY(linr_conv3_wgrad_dual44(t.H, t.gI, 8, t.gM, 4, c.f->nbr, c.nbr_ld, c.R, a.BIG, c.L.total, q.c01_w, q.c01_b,
-                                        q.c11_w, q.c11_b, c.nb, c.s, nullptr, 1, wg_t8t(c)));
-            TRY(linr_dual44_bwd_launch(t.gI, t.gM, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c01_w, P + q.c11_w, t.H, t.gH, c.s));
-        } else {
-            // I[:,0:4] = conv3(H0; c01) + X[:,0:4]
-            TRY(conv3_wgrad(c, t.H, 8, t.gI, 8, 4, 4, q.c01_w, q.c01_b));
-            TRY(conv3(c, true, t.gI, 8, P + q.c01_w, nullptr, 4, 4, nullptr, 0, t.H, 8, t.gH, 8, LINR_RELU_MASK));
-            // M = relu(conv3(H1; c11))
-            TRY(conv3_wgrad(c, t.H + 4, 8, t.gM, 4, 4, 4, q.c11_w, q.c11_b));
-            TRY(conv3(c, true, t.gM, 4, P + q.c11_w, nullptr, 4, 4, nullptr, 0, t.H + 4, 8, t.gH + 4, 8, LINR_RELU_MASK));
-        }
+        // I[:,0:4] = conv3(H0; c01) + X[:,0:4], M = relu(conv3(H1; c11))
+        TRY(linr_conv3_wgrad_dual44(t.H, t.gI, 8, t.gM, 4, c.f->nbr, c.nbr_ld, c.R, a.BIG, c.L.total, q.c01_w, q.c01_b,
+                                    q.c11_w, q.c11_b, c.nb, c.s, nullptr, 1, wg_t8t(c)));
+        TRY(linr_dual44_bwd_launch(t.gI, t.gM, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c01_w, P + q.c11_w, t.H, t.gH, c.s));
         // H0 = relu(conv3(X; c00)), H1 = relu(X @ c10)
         TRY(conv3_wgrad(c, X, 8, t.gH, 8, 8, 4, q.c00_w, q.c00_b));
         TRY(linear_wgrad(c, X, 8, t.gH + 4, 8, c.R, 8, 4, q.c10_w, 4, 1, q.c10_b));
@@ -742,14 +696,8 @@ static int block_bwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
         const bool skip = (l == 0 && nl > 1);
         if (skip)
             TRY(linr_hip_rc(hipMemcpyAsync(gX, last.gI, (size_t)c.R * 8 * sizeof(float), hipMemcpyDeviceToDevice, c.s)));
-        if (cm) {
-            TRY(linr_conv_bwd_ga_launch(t.gH, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c00_w, P + q.c10_w, t.gI, l == 0 ? a.A[b] : nullptr,
-                                        gX, (l == 0 ? LINR_RELU_MASK : 0u) | (skip ? LINR_ACCUM : 0u), c.s));
-        } else {
-            TRY(conv3(c, true, t.gH, 8, P + q.c00_w, nullptr, 8, 4, t.gI, 8, nullptr, 0, gX, 8, skip ? LINR_ACCUM : 0u));
-            TRY(linear(c, t.gH + 4, 8, c.R, P + q.c10_w, 1, 4, nullptr, 4, 8, nullptr, 0, l == 0 ? a.A[b] : nullptr, 8, gX, 8,
-                       LINR_ACCUM | (l == 0 ? LINR_RELU_MASK : 0u)));
-        }
+        TRY(linr_conv_bwd_ga_launch(t.gH, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c00_w, P + q.c10_w, t.gI, l == 0 ? a.A[b] : nullptr,
+                                    gX, (l == 0 ? LINR_RELU_MASK : 0u) | (skip ? LINR_ACCUM : 0u), c.s));
     }
     // A = relu(conv3(in; a))
     TRY(conv3_wgrad(c, in, in_ld, a.gA[b], 8, bp.cin, 8, bp.a_w, bp.a_b));
@@ -760,7 +708,7 @@ static int block_bwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
 static int check_frame(const linr_frame* f, const void* params, const void* arena, size_t arena_bytes, Ctx& c) {
     if (!params || !arena) return LINR_EINVAL;
     TRY(linr_frame_layout(f, 0, c.L));
-    if (f->rows > 0 && (!f->nbr || !f->offset_feat || !f->occ)) return LINR_EINVAL;
+    if (f->rows > 0 && (!f->nbr || !f->nbr_lo || !f->nbr_mask || !f->offset_feat || !f->occ)) return LINR_EINVAL;
     if (!linr_rows_fit32(f->rows) || f->nbr_ld < f->rows) return LINR_EINVAL;
     if (arena_bytes < linr_net_arena_bytes(f->rows, c.L.BL)) return LINR_ENOSPC;
     if (!linr_aligned16(arena)) return LINR_EALIGN;
@@ -784,9 +732,7 @@ static void goffs(int64_t* dst, const float* const* ptrs, int n) {
 // Teacher-forced forward of all 8 stages with the 7 outter blocks and the 8 heads as grouped launches (their inputs -
 // the ground-truth occupancy and x_glob - are all known up front).  Same kernels and per-row arithmetic as the staged
 // path below, so the decoder reproduces these probabilities bit for bit.
-// part 1: the occupancy-only layers of the outter blocks (first conv, conv0_0 | conv1_0, both 4->4 convs: they do not need
-// x_glob); part 2: everything that does (tail conv + x_glob, the 8 heads).  3 = both.
-static int forward_batched(Ctx& c, float* probs, double* bits_acc, int part = 3, bool join = false) {
+static int forward_batched(Ctx& c, float* probs, double* bits_acc) {
     Arena& a = c.A;
     const float* P = c.P;
     const Layout& L = c.L;
@@ -797,6 +743,7 @@ static int forward_batched(Ctx& c, float* probs, double* bits_acc, int part = 3,
     // eight blocks have the same structure behind their first conv (models/upsample.py:88-97) and do not depend on each
     // other until prior_k = x_glob + outter_k.  g0 = first slot in the grouped launches, ng = their group count; the
     // occupancy conv and the tail conv (which needs x_glob as residual) always cover slots 1..7 = arrays + o7.
+    const bool join = join_block_in(c);
     const int g0 = join ? 0 : 1, ng = 8 - g0, o7 = 1 - g0;
     const float *pA[8], *pH[8], *pM[8], *pI[8], *pO[8], *p_ab[8], *p_c00w[8], *p_c00b[8], *p_c10w[8], *p_c10b[8], *p_c01w[8],
         *p_c01b[8], *p_c11w[8], *p_c11b[8], *p_c12w[8], *p_c12b[8], *p_bw[8], *p_bb[8];
@@ -808,7 +755,6 @@ static int forward_batched(Ctx& c, float* probs, double* bits_acc, int part = 3,
         p_c01w[g] = P + bp.inc[0].c01_w; p_c01b[g] = P + bp.inc[0].c01_b; p_c11w[g] = P + bp.inc[0].c11_w; p_c11b[g] = P + bp.inc[0].c11_b;
         p_c12w[g] = P + bp.inc[0].c12_w; p_c12b[g] = P + bp.inc[0].c12_b; p_bw[g] = P + bp.b_w; p_bb[g] = P + bp.b_b;
     }
-    if (part & 1) {
     {   // first conv of every outter block: A[b] = relu(conv3(occ[:, :b]; a) + a_b), one shared gather (csrc/fused.hip)
         int64_t w_off[7], b_off[7], o_off[7];
         for (int g = 0; g < 7; ++g) { w_off[g] = L.outter[g].a_w; b_off[g] = L.outter[g].a_b; o_off[g] = a.A[g + 1] - a.A[1]; }
@@ -830,8 +776,6 @@ static int forward_batched(Ctx& c, float* probs, double* bits_acc, int part = 3,
         TRY(linr_dual44_fwd_launch(pH[0], lo, mk, c.nbr_ld, c.R, p_c01w[0], p_c01b[0], p_c11w[0], p_c11b[0], pA[0], p_c12w[0],
                                    p_c12b[0], a.M[g0], a.I[g0], c.s, &gp, ng));
     }
-    }
-    if (!(part & 2)) return linr_launch_rc();
     if (join)   // x_glob = O[0] = conv3(I[0]; b) of block_in: the one tail conv the others wait for
         TRY(conv3(c, false, a.I[0], 8, P + L.block_in.b_w, P + L.block_in.b_b, 8, 8, nullptr, 0, nullptr, 0, a.O[0], 8, 0));
     {   // O[b] = conv3(I; b) + x_glob
@@ -878,8 +822,8 @@ extern "C" int linr_net_forward(const linr_frame* f, const float* params, float*
     // has the zero row in front (check_frame points a.OCC at it), else copied into the padded arena matrix
     if (!(f->flags & LINR_FRAME_OCC_PADDED))
         TRY(linr_hip_rc(hipMemcpyAsync(a.OCC, f->occ, (size_t)c.R * 8 * sizeof(float), hipMemcpyDeviceToDevice, c.s)));
-    const bool batched = grouped_enabled();
-    const bool all_grouped = batched && stage_begin == 0 && stage_end == 8 && f->nbr_lo && f->nbr_mask;
+    // all 8 stages: grouped launches (forward_batched); a stage range (the decoder's single stages): stage by stage
+    const bool all_stages = stage_begin == 0 && stage_end == 8;
     if (stage_begin == 0) {
         PadList pl;
         pl.n = a.npad;
@@ -890,7 +834,7 @@ extern "C" int linr_net_forward(const linr_frame* f, const float* params, float*
             sce_fwd_k<float><<<sa.blk_off[sa.n_scales] + (a.npad + LINR_BLOCK / 32 - 1) / (LINR_BLOCK / 32), LINR_BLOCK, 0, c.s>>>(
                 P, f->offset_feat, sa, c.R, nullptr, nullptr, a.X0, a.base, pl);      // (no hidden layer kept: sce_bwd_all_k recomputes it)
         }
-        if (all_grouped && join_block_in(c)) {
+        if (all_stages && join_block_in(c)) {
             // block_in's first conv only: its Inception layer runs as group 0 of the outter blocks' launches (forward_batched)
             const BlockP& bi = c.L.block_in;
             TRY(conv3(c, false, a.X0, 8, P + bi.a_w, P + bi.a_b, bi.cin, 8, nullptr, 0, nullptr, 0, a.A[0], 8, LINR_RELU));
@@ -898,35 +842,21 @@ extern "C" int linr_net_forward(const linr_frame* f, const float* params, float*
             TRY(block_fwd(c, c.L.block_in, a.X0, 8, 0, nullptr));       // O[0] = x_glob
         }
     }
-    if (all_grouped) return forward_batched(c, probs, bits_acc, 3, join_block_in(c));
+    if (all_stages) return forward_batched(c, probs, bits_acc);
     const int64_t nblk = linr_grid(c.R, LINR_BLOCK);
-    bool fused_bits = false;
     for (int k = stage_begin; k < stage_end; ++k) {
         // prior_k = x_glob + outter_blocks[k-1](occ[:, :k])   (upsample.py:206-214; always the original x_glob)
         if (k > 0) TRY(block_fwd(c, c.L.outter[k - 1], a.OCC, 8, k, a.O[0]));
-        if (c.f->nbr_lo && c.f->nbr_mask) {
-            // prune conv + MLP + sigmoid + BCE partials in one launch (csrc/fused.hip)
-            double* part = bits_acc ? (double*)a.slab + (int64_t)k * nblk : nullptr;
-            TRY(linr_cconv_head_launch(a.O[k], clo(c), cmk(c), c.nbr_ld, c.R, P + c.L.pr_w[k], P + c.L.pr_b[k],
-                                       a.C[k], P + c.L.h0_w[k], P + c.L.h0_b[k], P + c.L.h2_w[k], P + c.L.h2_b[k],
-                                       a.OCC + k, 8, a.P[k], part, c.s));
-            if (bits_acc) fused_bits = true;
-        } else {
-            TRY(conv3(c, false, a.O[k], 8, P + c.L.pr_w[k], P + c.L.pr_b[k], 8, 8, nullptr, 0, nullptr, 0, a.C[k], 8, 0));
-            TRY(linear(c, a.C[k], 8, c.R, P + c.L.h0_w[k], 1, 8, P + c.L.h0_b[k], 8, 24, nullptr, 0, nullptr, 0, a.HH[k], 24,
-                       LINR_RELU));
-            TRY(linear(c, a.HH[k], 24, c.R, P + c.L.h2_w[k], 1, 24, P + c.L.h2_b[k], 24, 1, nullptr, 0, nullptr, 0, a.Z[k], 1, 0));
-            if (bits_acc) {
-                TRY(linr_bce_bits_fwd(a.Z[k], a.OCC + k, 8, c.R, a.P[k], bits_acc, a.slab, a.slab_bytes, c.s));
-            } else {
-                sigmoid_k<<<linr_grid(c.R, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(a.Z[k], c.R, a.P[k]);
-            }
-        }
+        // prune conv + MLP + sigmoid + BCE partials in one launch (csrc/fused.hip)
+        double* part = bits_acc ? (double*)a.slab + (int64_t)k * nblk : nullptr;
+        TRY(linr_cconv_head_launch(a.O[k], clo(c), cmk(c), c.nbr_ld, c.R, P + c.L.pr_w[k], P + c.L.pr_b[k],
+                                   a.C[k], P + c.L.h0_w[k], P + c.L.h0_b[k], P + c.L.h2_w[k], P + c.L.h2_b[k],
+                                   a.OCC + k, 8, a.P[k], part, c.s));
         if (probs)
             TRY(linr_hip_rc(hipMemcpyAsync(probs + (int64_t)k * c.R, a.P[k], (size_t)c.R * sizeof(float),
                                            hipMemcpyDeviceToDevice, c.s)));
     }
-    if (fused_bits)   // all stages' block partials in one fixed-order pass
+    if (bits_acc)   // all stages' block partials in one fixed-order pass
         TRY(linr_bits_finish_launch((const double*)a.slab + (int64_t)stage_begin * nblk, (int)((stage_end - stage_begin) * nblk),
                                     bits_acc, c.s));
     return linr_launch_rc();
@@ -1027,7 +957,7 @@ int linr_slab_reduce_launch(const float* big, int nblocks, int64_t total, float*
 }
 
 struct Ptr8 { const float* p[8]; };
-// dst = ((((((s7 + s6) + s5) + s4) + s3) + s2) + s1) + s0: the accumulation order of the stage-by-stage backward
+// dst = ((((((s7 + s6) + s5) + s4) + s3) + s2) + s1) + s0
 __global__ __launch_bounds__(LINR_BLOCK) void sum8_k(Ptr8 src, int64_t n, float* __restrict__ dst) {
     const int64_t i = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -1041,10 +971,8 @@ static void goffs_i(int64_t* dst, const int64_t* v, int n) {
     for (int i = 0; i < n; ++i) dst[i] = v[i] - v[0];
 }
 
-// Backward of the 8 heads and the 7 outter blocks as grouped launches (one launch per layer, gridDim.y = group); every
-// kernel, its per-row arithmetic and the slab rows it writes are those of the stage-by-stage path, so gradients are
-// bitwise the same.
-static int backward_batched(Ctx& c, float gz_scale, bool join) {
+// Backward of the 8 heads and the 7 outter blocks as grouped launches (one launch per layer, gridDim.y = group).
+static int backward_batched(Ctx& c, float gz_scale) {
     Arena& a = c.A;
     const float* P = c.P;
     const Layout& L = c.L;
@@ -1103,7 +1031,8 @@ static int backward_batched(Ctx& c, float gz_scale, bool join) {
     }
     // outter blocks 1..7 (slot b = block b; gO[b] is the gradient of the block output) and, with `join`, block_in as slot 0
     // (output gradient gXG = the sum above): one group per slot, g0 = first slot, ng = group count
-    const int g0 = join ? 0 : 1, ng = 8 - g0, o7 = 1 - g0;
+    const bool join = join_block_in(c);
+    const int g0 = join ? 0 : 1, ng = 8 - g0;
     const float *pA[8], *pH[8], *pM[8], *pI[8], *p_gO[8], *p_gI[8], *p_gM[8], *p_gH[8], *p_gA[8], *p_bw[8], *p_c12w[8], *p_c01w[8],
         *p_c11w[8], *p_c00w[8], *p_c10w[8], *p_in[8];
     int64_t o_bw[8], o_bb[8], o_c12w[8], o_c12b[8], o_c01w[8], o_c01b[8], o_c11w[8], o_c11b[8], o_c00w[8], o_c00b[8], o_c10w[8],
@@ -1119,7 +1048,6 @@ static int backward_batched(Ctx& c, float gz_scale, bool join) {
         o_c11w[g] = bp.inc[0].c11_w; o_c11b[g] = bp.inc[0].c11_b; o_c00w[g] = bp.inc[0].c00_w; o_c00b[g] = bp.inc[0].c00_b; o_c10w[g] = bp.inc[0].c10_w;
         o_c10b[g] = bp.inc[0].c10_b; o_aw[g] = bp.a_w; o_ab[g] = bp.a_b;
     }
-    (void)o7;
     if (fused_bwd(c)) {   // O = conv3(I; b): gI = bwd(gO; b), gM = (gI[:,4:8] @ W12^T) * (M > 0) and the weight gradient, one gather of gO
         Grp gp = Grp();
         goffs(gp.in, p_gO, ng); goffs(gp.res, pI, ng); goffs(gp.w, p_bw, ng); goffs(gp.out, p_gI, ng);
@@ -1304,42 +1232,18 @@ static int backward_core(Ctx& c, float gscale) {
     Arena& a = c.A;
     const float* P = c.P;
     const float gz_scale = gscale * 1.4426950408889634f;       // d(bits)/d(nats) = 1/ln 2
-    const bool batched = grouped_enabled();
-    const bool grouped = batched && c.f->nbr_lo && c.f->nbr_mask;
-    const bool join = grouped && join_block_in(c);
-    if (grouped) TRY(backward_batched(c, gz_scale, join));
-    for (int k = grouped ? -1 : 7; k >= 0; --k) {
-        if (c.f->nbr_lo && c.f->nbr_mask) {
-            // recompute the hidden layer, gC and the four head-parameter gradients in one launch (csrc/fused.hip)
-            TRY(linr_head_bwd_launch(a.C[k], a.P[k], a.OCC + k, 8, P + c.L.h0_w[k], P + c.L.h0_b[k], P + c.L.h2_w[k], gz_scale,
-                                     a.gC[k], c.R, a.BIG, c.L.total, c.L.h0_w[k], c.L.h0_b[k], c.L.h2_w[k], c.L.h2_b[k], c.s, nullptr, 1, c.nb));
-        } else {
-            TRY(linr_bce_bits_bwd(a.P[k], a.OCC + k, 8, c.R, gz_scale, a.gZ, c.s));
-            // z = HH @ h2 + b ; HH = relu(C @ h0 + b)
-            TRY(linear_wgrad(c, a.HH[k], 24, a.gZ, 1, c.R, 24, 1, c.L.h2_w[k], 1, 24, c.L.h2_b[k]));
-            TRY(linear(c, a.gZ, 1, c.R, P + c.L.h2_w[k], 24, 1, nullptr, 1, 24, nullptr, 0, a.HH[k], 24, a.gHH, 24, LINR_RELU_MASK));
-            TRY(linear_wgrad(c, a.C[k], 8, a.gHH, 24, c.R, 8, 24, c.L.h0_w[k], 1, 8, c.L.h0_b[k]));
-            TRY(linear(c, a.gHH, 24, c.R, P + c.L.h0_w[k], 8, 1, nullptr, 24, 8, nullptr, 0, nullptr, 0, a.gC[k], 8, 0));
-        }
-        // C = conv3(prior_k; prune_k)
-        TRY(conv3_wgrad(c, a.O[k], 8, a.gC[k], 8, 8, 8, c.L.pr_w[k], c.L.pr_b[k]));
-        TRY(conv3(c, true, a.gC[k], 8, P + c.L.pr_w[k], nullptr, 8, 8, nullptr, 0, nullptr, 0, a.gO[k], 8, 0));
-        // prior_k = x_glob (+ outter block k-1): both receive gO
-        axpy_k<<<linr_grid(c.R * 8, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(a.gO[k], c.R * 8, a.gXG, k == 7 ? 0 : 1);
-        if (k > 0) TRY(block_bwd(c, c.L.outter[k - 1], a.OCC, 8, k, a.gO[k], nullptr));
-    }
-    if (join && fused_bwd(c)) {      // first conv of block_in: input gradient and weight gradient from one gather of gA[0]
-        const BlockP& bi = c.L.block_in;
+    TRY(backward_batched(c, gz_scale));
+    const BlockP& bi = c.L.block_in;
+    if (join_block_in(c) && fused_bwd(c)) {      // first conv of block_in: input gradient and weight gradient from one gather of gA[0]
         LinrWgradDst d = {a.BIG, c.L.total, bi.a_w, bi.a_b, 8};
         ProfScope ps(c.s, PK_FUSED88, 1);
         int rows = 0;
         TRY(linr_conv88_bwd_wgrad_launch(a.gA[0], a.X0, clo(c), cmk(c), c.nbr_ld, c.R, P + bi.a_w, a.gX0, nullptr, d, c.nb, c.s, nullptr, 1, &rows));
         c.note_short(bi.a_w, bi.a_b + 8, rows);
-    } else if (join) {      // everything but the input gradient of its first conv was part of the grouped launches
-        const BlockP& bi = c.L.block_in;
+    } else if (join_block_in(c)) {      // everything but the input gradient of its first conv was part of the grouped launches
         TRY(conv3(c, true, a.gA[0], 8, P + bi.a_w, nullptr, bi.cin, 8, nullptr, 0, nullptr, 0, a.gX0, 8, 0));
     } else {
-        TRY(block_bwd(c, c.L.block_in, a.X0, 8, 0, a.gXG, a.gX0));
+        TRY(block_bwd(c, bi, a.X0, 8, 0, a.gXG, a.gX0));
     }
     std::vector<LinrShortRange> sh(c.shortr.size());
     for (size_t i = 0; i < sh.size(); ++i) sh[i] = {c.shortr[i].b, c.shortr[i].e, c.shortr[i].rows};

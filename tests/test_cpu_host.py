@@ -161,10 +161,11 @@ def test_c_abi_argument_checks(lib):
     bound = (1 << 27) - 1                            # first row count whose gathered-row byte offsets ((rows + 1) * 32 B) reach 2^32
     keep = []
 
-    def frame(rows=16, n_scales=2, row_off=(0, 8, 16), sidx=(0, 1), msn=7, bl=1, flags=0, nbr=p64, cmap=True, feat=p64, occ=p64):
+    def frame(rows=16, n_scales=2, row_off=(0, 8, 16), sidx=(0, 1), msn=7, bl=1, flags=0, nbr=p64, cmap=True, mask=True, feat=p64,
+              occ=p64):
         ro, si = (ctypes.c_int64 * 18)(*row_off), (ctypes.c_int32 * 17)(*sidx)
         f = LinrFrame(rows, n_scales, msn, bl, flags, ctypes.addressof(ro), ctypes.addressof(si), nbr, rows,
-                      p64 if cmap else None, p64 if cmap else None, feat, occ, None)
+                      p64 if cmap else None, p64 if cmap and mask else None, feat, occ, None)
         keep.append((ro, si, f))
         return byref(f)
 
@@ -198,14 +199,14 @@ def test_c_abi_argument_checks(lib):
             assert call(frame(), p64 + align // 4, n16) == -3                                       # misaligned arena
             assert call(frame(bl=0), p64, n16 - 1) == -2                                            # block_layers 0 is read as 1
             assert call(frame(rows=0, row_off=(0, 0, 0), bl=5), p64, n16) == (0 if call in (dec, bdec) else -1)
-    for call in (fwd, bwd, step, dec):                       # fp32: the plain map, offset_feat and occ; any block_layers
-        for fault in (dict(nbr=None), dict(feat=None), dict(occ=None)):
+    for call in (fwd, bwd, step, dec):                       # fp32: both maps, offset_feat and occ; any block_layers
+        for fault in (dict(nbr=None), dict(cmap=False), dict(mask=False), dict(feat=None), dict(occ=None)):
             assert call(frame(**fault), p64, 1 << 40) == -1, (call, fault)
         assert call(frame(bl=2), p64, lib.linr_net_arena_bytes(16, 1)) == -2
         assert call(frame(flags=1, occ=p64 + 4), p64, lib.linr_net_arena_bytes(16, 1)) == -1   # padded occupancy must be 16-byte aligned
         assert call(frame(flags=1, occ=p64 + 4), p64 + 4, lib.linr_net_arena_bytes(16, 1)) == -3
     for call in (bfwd, bdec, tfwd, tbwd, tstep):             # bf16: the compressed map, offset_feat and occ
-        for fault in (dict(cmap=False), dict(feat=None), dict(occ=None)):
+        for fault in (dict(cmap=False), dict(mask=False), dict(feat=None), dict(occ=None)):
             assert call(frame(**fault), p64, 1 << 40) == -1, (call, fault)
     for call in (bfwd, bdec):
         assert call(frame(bl=2), p64, lib.linr_net_bf16_arena_bytes(16, 1)) == -2

@@ -159,34 +159,6 @@ def test_more_scales_than_one_grouped_launch(pkg):
     _close(grads, gref, 1e-3, 1e-4 * float(gref.abs().max()), 'gradients with %d scales' % S)
 
 
-def test_executor_without_compressed_map(pkg, shell):
-    """linr_frame.nbr_lo / nbr_mask are optional: without them the executor runs the generic op-level kernels layer by
-    layer (no fused epilogues, no grouped launches).  Same per-row fmaf chains => same probabilities; gradients agree to
-    rounding (different partial-sum tiling)."""
-    import copy
-    from linr_pcgc_amd import engine
-    model, _ = _model_and_oracle(pkg, 5)
-    frame = model.make_frame(shell['scales'])
-    flat = model.flat_parameters()
-    probs, bits = model.frame_probs(frame)
-    grads = torch.zeros_like(flat)
-    engine.net_forward(frame, flat, 0, 8, None, torch.zeros(1, dtype=torch.float64, device='cuda'))
-    engine.net_backward(frame, flat, grads, 1.0 / shell['point_num'])
-    plain = copy.copy(frame)
-    plain._c = type(frame._c)(rows=frame._c.rows, n_scales=frame._c.n_scales, model_scale_num=frame._c.model_scale_num,
-                              row_off_h=frame._c.row_off_h, scale_idx_h=frame._c.scale_idx_h, nbr=frame._c.nbr,
-                              nbr_ld=frame._c.nbr_ld, nbr_lo=None, nbr_mask=None, offset_feat=frame._c.offset_feat,
-                              occ=frame._c.occ)
-    probs2 = torch.empty_like(probs)
-    bits2 = torch.zeros(1, dtype=torch.float64, device='cuda')
-    engine.net_forward(plain, flat, 0, 8, probs2, bits2)
-    assert torch.equal(probs, probs2), float((probs - probs2).abs().max())
-    assert abs(float(bits) - float(bits2)) <= 1e-9 * float(bits)
-    grads2 = torch.zeros_like(flat)
-    engine.net_backward(plain, flat, grads2, 1.0 / shell['point_num'])
-    _close(grads2, grads, 1e-4, 1e-6 * float(grads.abs().max()), 'gradients of the generic executor path')
-
-
 def test_multiscale_batch_equals_per_scale(pkg, shell):
     """Batching all scales into one row space must not change any row's arithmetic (bitwise)."""
     model, _ = _model_and_oracle(pkg, 5)
@@ -289,48 +261,45 @@ def test_staged_probs_bitwise_equal_one_shot(pkg, shell):
     assert torch.equal(one, staged)
 
 
-def _dump_under(env, golden_dir, out):
+def _dump_under(env, golden_dir, out, block_layers=1):
     import subprocess
     import sys
     script = os.path.join(os.path.dirname(__file__), '_dump_net.py')
     golden = os.path.join(golden_dir, 'octree_shell128.npz')
     clean = {k: v for k, v in os.environ.items() if not k.startswith('LINR_') or k == 'LINR_DEBUG_POISON'}
-    subprocess.run([sys.executable, script, golden, out], check=True, env=dict(clean, **env), timeout=600)
+    subprocess.run([sys.executable, script, golden, out, str(block_layers)], check=True, env=dict(clean, **env), timeout=600)
     return np.load(out)
 
 
 @pytest.fixture(scope='module')
 def base_dumps(golden_dir, tmp_path_factory):
-    """Reference dumps per base environment ({} = the default executor), computed once."""
+    """Reference dumps per base environment ({} = the default executor) and block_layers, computed once."""
     cache = {}
 
-    def get(base):
-        key = tuple(sorted(base.items()))
+    def get(base, block_layers=1):
+        key = (tuple(sorted(base.items())), block_layers)
         if key not in cache:
-            cache[key] = _dump_under(base, golden_dir, str(tmp_path_factory.mktemp('dump') / ('base%d.npz' % len(cache))))
+            out = str(tmp_path_factory.mktemp('dump') / ('base%d.npz' % len(cache)))
+            cache[key] = _dump_under(base, golden_dir, out, block_layers)
         return cache[key]
     return get
 
 
-# Every executor switch the library reads from the environment (README.md).  Probabilities and bits must be BIT FOR BIT those of
-# the default executor under every switch - that is what lets the stage-serial decoder reproduce the encoder.  Gradients: the
-# schedules that differ from the default only in how launches are grouped reproduce it bit for bit ONCE the fused backward
-# (one gather for backward-data + weight gradient, csrc/fused_bwd.hip) is switched off on both sides: the fused kernels sum the
-# weight gradients over other row partitions, and the stage-by-stage / single-launch schedules do not use them.  Against the
-# default (fused) executor the same gradients agree to rounding.
+# Executor switches the library reads from the environment (README.md).  Probabilities and bits must be BIT FOR BIT those of the
+# default executor under every switch - that is what lets the stage-serial decoder reproduce the encoder.  Gradients agree with the
+# default executor to rounding: the two-kernel backward (LINR_FUSED_BWD=0) and the fused one-gather kernels (csrc/fused_bwd.hip) sum
+# the weight gradients over other row partitions.
 NOFUSE = {'LINR_FUSED_BWD': '0'}
 
 
-SWITCHES = [({'LINR_JOIN_BLOCK_IN': '0'}, NOFUSE), ({'LINR_BATCHED': '0'}, NOFUSE), ({'LINR_CONV_MFMA': '0'}, NOFUSE),
-            ({'LINR_BATCHED': '0', 'LINR_CONV_MFMA': '0', 'LINR_JOIN_BLOCK_IN': '0'}, NOFUSE), ({'LINR_FUSED_CUS': '64'}, None)]
+SWITCHES = [(NOFUSE, None), ({'LINR_FUSED_CUS': '64'}, None)]
 
 
 @pytest.mark.parametrize('env,base', SWITCHES, ids=lambda e: ','.join('%s=%s' % (k[5:], v) for k, v in (e or {}).items()) or 'default')
 def test_executor_switch_is_bit_identical_to_default(pkg, golden_dir, tmp_path, base_dumps, env, base):
     """The grouped executor (one launch per layer for block_in + the 7 outter blocks / 8 heads / all scales of the scale
-    context) against every alternative path it can be switched to - stage by stage, block_in as single launches, VALU
-    convolutions: same probabilities and bits everywhere; gradients bit for bit against the matching base, to rounding against
-    the default executor with its fused backward."""
+    context) against every alternative path it can be switched to: same probabilities and bits everywhere; gradients bit for bit
+    against the matching base (if any), to rounding against the default executor with its fused backward."""
     default = base_dumps({})
     got = _dump_under(dict(base or {}, **env), golden_dir, str(tmp_path / 'switched.npz'))
     for key in ('probs', 'bits'):
@@ -351,15 +320,16 @@ def test_results_do_not_depend_on_leftover_onchip_state(pkg, golden_dir, tmp_pat
     0 x NaN poisons a gradient that 0 x finite never would (found by two ranks rehearsing on one GPU: a register of the fused
     4->4 backward kernel's first pipeline step fed the matrix cores unloaded, against a zero operand).  With every launch
     preceded by a kernel that fills the LDS and the vector registers of all CUs with 0xFFFFFFFF (linr_debug_poison), results must
-    not move by a bit: (a) forward + backward on the multi-scale golden shell under three executor schedules, in child processes;
-    (b) training steps at full size in this process.  LINR_DEBUG_POISON=1 runs the WHOLE suite that way (tools/README.md)."""
+    not move by a bit: (a) forward + backward on the multi-scale golden shell under three executor schedules (the default, the
+    two-kernel backward, and block_layers 2, whose block_in runs as single launches), in child processes; (b) training steps at full
+    size in this process.  LINR_DEBUG_POISON=1 runs the WHOLE suite that way (tools/README.md)."""
     from linr_pcgc_amd import _lib, overfit, synthetic
     from linr_pcgc_amd.model_core import FlatAdam, train_step
-    for i, base in enumerate(({}, NOFUSE, dict(NOFUSE, LINR_BATCHED='0', LINR_CONV_MFMA='0', LINR_JOIN_BLOCK_IN='0'))):
-        ref = base_dumps(base)
-        got = _dump_under(dict(base, LINR_DEBUG_POISON='1'), golden_dir, str(tmp_path / ('poison%d.npz' % i)))
+    for i, (base, bl) in enumerate((({}, 1), (NOFUSE, 1), ({}, 2))):
+        ref = base_dumps(base, bl)
+        got = _dump_under(dict(base, LINR_DEBUG_POISON='1'), golden_dir, str(tmp_path / ('poison%d.npz' % i)), bl)
         for key in ('probs', 'bits', 'grads'):
-            assert np.array_equal(ref[key], got[key]), (base, key)
+            assert np.array_equal(ref[key], got[key]), (base, bl, key)
     gop = overfit.Gop(None, [synthetic.sequence_frame_device('loot10', 0, 'cuda')], None, 64, 'cuda')
     L = _lib.lib()
 
