@@ -12,7 +12,7 @@ import torch
 from oracle import network as onet          # noqa: E402,F401
 from oracle import octree as ooct           # noqa: E402,F401
 from oracle import ac as oac                # noqa: E402,F401
-from gpu_common import _dev, _close, _model_and_oracle, _grads_close_per_tensor          # noqa: E402,F401
+from gpu_common import _dev, _close, _model_and_oracle, _grads_close_per_tensor, _smallest_relu_input          # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -235,27 +235,6 @@ def test_config4_size_wave_specialised_backward_is_bit_identical(pkg):
             os.environ['LINR_FUSED_SPLIT'] = old
     assert float(a.abs().max()) > 0 and bool(torch.isfinite(a).all())
     assert torch.equal(a, b) and torch.equal(a, c)
-
-
-def _smallest_relu_input(sd, sc):
-    """Smallest |x| any ReLU of the network sees on this scale, from the oracle in float64.  Below ~3e-7 (inputs are O(1)) the sign of x - and with
-    it a whole term of the gradient - is decided by fp32 rounding order, so no two fp32 implementations need agree there."""
-    import types
-    seen = []
-
-    def relu(x):
-        if x.numel():
-            seen.append(float(x.detach().abs().min()))
-        return torch.relu(x)
-    shim = types.SimpleNamespace(relu=relu, linear=torch.nn.functional.linear,
-                                 binary_cross_entropy=torch.nn.functional.binary_cross_entropy)
-    keep, onet.F = onet.F, shim
-    try:
-        with torch.no_grad():
-            onet.forward_scale({k: v.double() for k, v in sd.items()}, onet.to_torch_scales([sc], torch.float64)[0])
-    finally:
-        onet.F = keep
-    return min(seen)
 
 
 @pytest.mark.parametrize('n', [1, 2, 17, 63, 64, 65, 127, 129, 255, 256, 257, 511, 1025])

@@ -11,6 +11,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import network as onet          # noqa: E402
 from oracle import octree as ooct           # noqa: E402
+from gpu_common import _close, _grads_close_per_tensor, _relu_tie_slack, _smallest_relu_input          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -76,30 +77,35 @@ def test_wide_forward_and_backward_match_the_oracle(pkg, shell, hidden, block_la
     assert abs(float(bits) - ref_bits) <= 1e-5 * ref_bits, (float(bits), ref_bits)
     probs2, bits2 = model.frame_probs(frame)
     assert torch.equal(probs, probs2) and torch.equal(bits, bits2), 'forward must be bit-reproducible'
-    # gradients through the executor's own tape against autograd of the oracle, every tensor against its own largest entry
+    # gradients through the executor's own tape against autograd of the oracle, every tensor against its own largest entry: the direct
+    # fp32-vs-fp32 sanity bound (3e-3) and the criterion proper, HIP as close to the float64 oracle as the fp32 oracle is.  The shell
+    # cannot be redrawn: its ReLU ties at fp32 resolution enter the float64 bound as slack (at width 32, block_layers 1: one input of
+    # 1.3e-7 in head 1's hidden layer on scale 2 moves scale_mlp.2.0.weight's gradient by 5.717e-7 - the HIP's whole difference there)
     gscale = 1.0 / shell['point_num']
+    grads = _tape_grads(model, frame, gscale)
+    sdo, sd64 = _oracle_grads(sd, shell['scales'], gscale)
+    _grads_close_per_tensor(grads, sdo, rtol=3e-3, sd64=sd64, slack=_relu_tie_slack(sd, shell['scales'], gscale))
+    assert torch.equal(grads, _tape_grads(model, frame, gscale)), 'backward must be bit-reproducible'
+
+
+def _tape_grads(model, frame, gscale):
+    """d (gscale * bits) / d params through the executor's own tape (forward with keep, backward into the zeroed flat gradient)."""
     model._ensure_grad_views()
-    model._flat_grad.zero_()
     b = torch.zeros(1, dtype=torch.float64, device='cuda')
-    with torch.no_grad():
-        tape = model._wide.forward(frame, 0, 8, None, b, keep=True)
-        model._wide.backward(frame, tape, gscale)
-    grads = model._flat_grad.clone()
-    sdo = {k: v.clone().requires_grad_() for k, v in sd.items()}
-    (onet.frame_bits(sdo, tsc) * gscale).backward()
-    off = 0
-    for name, v in sdo.items():
-        n = v.numel()
-        mine = grads[off:off + n].view(v.shape).double().cpu()
-        ref = torch.zeros_like(v).double() if v.grad is None else v.grad.double()
-        gmax = float(ref.abs().max())
-        assert float((mine - ref).abs().max()) <= 3e-3 * gmax + 1e-9, name
-        off += n
     with torch.no_grad():
         model._flat_grad.zero_()
         tape = model._wide.forward(frame, 0, 8, None, b, keep=True)
         model._wide.backward(frame, tape, gscale)
-    assert torch.equal(grads, model._flat_grad), 'backward must be bit-reproducible'
+    return model._flat_grad.clone()
+
+
+def _oracle_grads(sd, scales, gscale):
+    """Autograd of the oracle's gscale * frame bits with fp32 leaves and with float64 leaves (numpy scales, on the host)."""
+    sdo = {k: v.clone().requires_grad_() for k, v in sd.items()}
+    (onet.frame_bits(sdo, onet.to_torch_scales(scales)) * gscale).backward()
+    sd64 = {k: v.double().clone().requires_grad_() for k, v in sd.items()}
+    (onet.frame_bits(sd64, onet.to_torch_scales(scales, torch.float64)) * gscale).backward()
+    return sdo, sd64
 
 
 def test_wide_model_surface_autograd(pkg, shell):
@@ -115,11 +121,12 @@ def test_wide_model_surface_autograd(pkg, shell):
     ref = onet.forward_scale(sdo, onet.to_torch_scales([s])[0])['bits'] / 1000.0
     assert abs(float(loss) - float(ref)) <= 1e-5 * float(ref)
     ref.backward()
-    for (name, p) in model.named_parameters():
-        g = sdo[name].grad
-        g = torch.zeros_like(sdo[name]) if g is None else g
-        gmax = float(g.abs().max())
-        assert float((p.grad.cpu().double() - g.double()).abs().max()) <= 3e-3 * gmax + 1e-9, name
+    sd64 = {k: v.double().clone().requires_grad_() for k, v in sd.items()}
+    (onet.forward_scale(sd64, onet.to_torch_scales([s], torch.float64)[0])['bits'] / 1000.0).backward()
+    params = dict(model.named_parameters())
+    assert sorted(params) == sorted(sdo)
+    grads = torch.cat([params[name].grad.reshape(-1) for name in sdo])          # the oracle's order
+    _grads_close_per_tensor(grads, sdo, rtol=3e-3, sd64=sd64, slack=_relu_tie_slack(sd, [s], 1.0 / 1000.0))
 
 
 def test_wide_train_steps_track_torch_adam_and_decode_losslessly(pkg, shell):
@@ -434,3 +441,313 @@ def test_wide_fused_pointwise_epilogues_equal_the_separate_launches(pkg, hidden,
     assert bool(torch.isfinite(a[0]).all())
     for x, y in zip(a, b):
         assert torch.equal(x, y)
+
+
+# ---- tiny, ragged and multi-tile frames ------------------------------------------------------------------------------------------------
+def _empty_scale(idx):
+    return {'coord': np.zeros((0, 3), np.int32), 'occ': np.zeros((0, 8), np.float32), 'offset_tensor': np.zeros((0, 7), np.float32),
+            'scale_idx': idx}
+
+
+@pytest.mark.parametrize('n', [1, 2, 7, 8, 9, 63, 64, 65, 255, 256, 257, 1025])
+@pytest.mark.parametrize('hidden,block_layers', [(16, 2), (32, 1)])
+def test_wide_tiny_and_ragged_frames(pkg, hidden, block_layers, n):
+    """tests/test_gpu_configs.py::test_tiny_and_ragged_frames for the channel-blocked executor: one scale of n voxels beside a zero-row
+    scale, n around the 8-row weight-gradient tiles (wwgrad_k), the 64-lane waves and the 256-row convolution / head / pointwise tiles,
+    so most of the 256 persistent weight-gradient blocks and of the pointwise slab rows are empty.  Bits and probabilities against the
+    oracle, every gradient (the tape's) against the float64-anchored criterion - the absent scale's MLP gradients exactly zero - and the
+    staged forward bitwise equal to the one-shot one.  A cloud with a ReLU tie at fp32 resolution is redrawn (the criterion is the
+    oracle's, not the kernels'); where six draws all have one (n = 1025: ~1e6 ReLU inputs) the last one's ties enter as slack."""
+    model, sd = _model(hidden, scale_num=3, block_layers=block_layers)
+    side = max(6, int(round((3 * n) ** (1 / 3))) + 2)          # a box that holds n distinct voxels at ~1/3 occupancy
+    want = n
+    for attempt in range(6):
+        rng = np.random.default_rng(want + 1000 * attempt + hidden)
+        c = ooct.unique_sorted(rng.integers(0, side, size=(4 * want, 3)))[:want]
+        n = len(c)
+        sc = {'coord': c, 'occ': (rng.random((n, 8)) < 0.5).astype(np.float32), 'offset_tensor': ooct.offset_tensor(c), 'scale_idx': 1,
+              'nbr': ooct.neighbour_table(c)}
+        if _smallest_relu_input(sd, sc) >= 3e-7:
+            break
+    assert n == want
+    frame = model.make_frame([{k: v for k, v in sc.items() if k != 'nbr'}, _empty_scale(0)])
+    assert frame.rows == n
+    probs, bits = model.frame_probs(frame)
+    out = onet.forward_scale(sd, onet.to_torch_scales([sc])[0])
+    assert abs(float(bits) - float(out['bits'])) <= 1e-5 * float(out['bits']), (float(bits), float(out['bits']))
+    for k in range(8):
+        _close(probs[k], out['probs'][k].reshape(-1), 1e-4, 1e-4, 'probs of stage %d' % k)
+    staged = torch.empty_like(probs)
+    for k in range(8):
+        model._stage_forward(frame, k, k + 1, staged, None, 'f32')
+    assert torch.equal(probs, staged)
+    grads = _tape_grads(model, frame, 1.0)
+    assert bool(torch.isfinite(grads).all())
+    sdo, sd64 = _oracle_grads(sd, [sc], 1.0)
+    assert sdo['scale_mlp.0.0.weight'].grad is None          # the zero-row scale: no gradient at all, the executor's must be zero
+    _grads_close_per_tensor(grads, sdo, sd64=sd64, slack=_relu_tie_slack(sd, [sc]))
+
+
+@pytest.mark.parametrize('hidden', [16, 32])
+def test_wide_ragged_multi_scale_frame_with_colliding_coordinates(pkg, hidden):
+    """tests/test_gpu_configs.py::test_ragged_multi_scale_frame_with_colliding_coordinates for the channel-blocked executor: three scales
+    of 257, 65 and 3 rows from the SAME 9^3 box batched at offsets that are no multiple of any tile; a voxel of one scale must not become
+    a neighbour of another scale's.  Per-scale probabilities, the summed bits and every gradient (float64-anchored) against the oracle;
+    ties that six draws cannot avoid enter as slack."""
+    model, sd = _model(hidden, scale_num=3)
+    for attempt in range(6):
+        rng = np.random.default_rng(77 + attempt)
+        scales = []
+        for idx, n in ((0, 257), (1, 65), (2, 3)):
+            c = ooct.unique_sorted(rng.integers(0, 9, size=(4 * n, 3)))[:n]
+            scales.append({'coord': c, 'occ': (rng.random((len(c), 8)) < 0.5).astype(np.float32), 'offset_tensor': ooct.offset_tensor(c),
+                           'scale_idx': idx, 'nbr': ooct.neighbour_table(c)})
+        if min(_smallest_relu_input(sd, s) for s in scales) >= 3e-7:
+            break
+    frame = model.make_frame([{k: v for k, v in s.items() if k != 'nbr'} for s in scales])
+    assert frame.rows == 325
+    probs, bits = model.frame_probs(frame)
+    ref = 0.0
+    for i, s in enumerate(onet.to_torch_scales(scales)):
+        out = onet.forward_scale(sd, s)
+        sl = frame.scale_slice(i)
+        for k in range(8):
+            _close(probs[k, sl], out['probs'][k].reshape(-1), 1e-4, 1e-4, 'probs of scale %d, stage %d' % (i, k))
+        ref += float(out['bits'])
+    assert abs(float(bits) - ref) <= 1e-5 * ref, (float(bits), ref)
+    grads = _tape_grads(model, frame, 1.0)
+    sdo, sd64 = _oracle_grads(sd, scales, 1.0)
+    _grads_close_per_tensor(grads, sdo, sd64=sd64, slack=_relu_tie_slack(sd, scales))
+
+
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.fixture(scope='module')
+def sphere9(pkg):
+    """A 9-bit sphere shell (501,702 points; 7 scales, 215,286 rows, the finest 156,985): more rows than 2 workgroups per CU x 256, so
+    the convolutions' workgroups loop over several row tiles and the pointwise weight gradients run their full 512 slab rows."""
+    from linr_pcgc_amd import synthetic
+    from linr_pcgc_amd.module_utils import prepare_frame
+    pts = synthetic.sequence_frame({'bitdepth': 9, 'radius': 200, 'thickness': 0.5}, 0)
+    return prepare_frame(pts, None, 64, device='cuda')
+
+
+class _NoTF32:
+    """fp32 matmuls of the GPU oracle in fp32 proper."""
+
+    def __enter__(self):
+        self.old = torch.backends.cuda.matmul.allow_tf32
+        torch.backends.cuda.matmul.allow_tf32 = False
+
+    def __exit__(self, *exc):
+        torch.backends.cuda.matmul.allow_tf32 = self.old
+
+
+def test_wide_multi_tile_frame_matches_the_oracle(pkg, sphere9):
+    """The whole width-16 network on a frame of more than 2 x CUs x 256 rows (checked here, on any card): every convolution's
+    workgroups walk several 256-row tiles, the weight-gradient blocks many 8-row tiles, the pointwise slabs all 512 rows.  Forward bits
+    and probabilities, and every gradient of the training loss (bits / points) with the float64 anchor; the fp32 and float64 oracles run
+    on the GPU, their backward one scale at a time (the im2col columns of one scale alive at once).  Measured on the MI355X: 119 s,
+    peak 20.5 GB of device memory; worst fp32-vs-fp32 gradient difference 2.8e-4 of its tensor's largest entry."""
+    import time
+    t0 = time.perf_counter()
+    torch.cuda.reset_peak_memory_stats()
+    fr = sphere9
+    model, sd = _model(16, scale_num=fr['scale_num'])
+    frame = model.make_frame(fr['all_input_info'])
+    assert frame.rows > 2 * _cus() * 256, (frame.rows, _cus())
+    probs, bits = model.frame_probs(frame)
+    gscale = 1.0 / fr['point_num']
+    grads = _tape_grads(model, frame, gscale)
+    sdo = {k: v.cuda().requires_grad_() for k, v in sd.items()}
+    sd64 = {k: v.double().cuda().requires_grad_() for k, v in sd.items()}
+    ref = 0.0
+    with _NoTF32():
+        for i, info in enumerate(fr['all_input_info']):
+            nbr = torch.from_numpy(ooct.neighbour_table(info['coord'].cpu().numpy().astype(np.int32))).long().cuda()
+            sl = frame.scale_slice(i)
+            for leaves, dt in ((sdo, torch.float32), (sd64, torch.float64)):
+                s = {'offset_tensor': info['offset_tensor'].to(dt), 'occ': info['occ'].to(dt), 'nbr': nbr, 'scale_idx': info['scale_idx']}
+                out = onet.forward_scale(leaves, s)
+                if dt == torch.float32:
+                    for k in range(8):
+                        _close(probs[k, sl], out['probs'][k].reshape(-1), 1e-4, 1e-4, 'probs of scale %d, stage %d' % (i, k))
+                    ref += float(out['bits'])
+                (out['bits'] * gscale).backward()
+                del out
+    assert abs(float(bits) - ref) <= 1e-5 * ref, (float(bits), ref)
+    worst = _grads_close_per_tensor(grads, sdo, rtol=3e-3, sd64=sd64)
+    print('multi-tile frame: %d rows, worst fp32-vs-fp32 gradient difference %.3e of its tensor\'s largest entry (%s); %.1f s, peak %.1f GB'
+          % (frame.rows, worst[0], worst[1], time.perf_counter() - t0, torch.cuda.max_memory_allocated() / 2 ** 30))
+
+
+# Op level at the multi-tile size: per-entry bounds against float64.  A relative-to-max bound loses its sharpness at 1e5 rows (one lost
+# 256-row tile moves a weight-gradient entry by ~1e-3 of its largest), so every entry gets the rounding bound of its own sum,
+#     |got - exact| <= C_ROUND * 2^-24 * (the same sum over the absolute values of its terms)
+# (forward: |x| (*) |W| + |b| + |res|; backward-data: |g| (*) |W|^T; weight gradients: sum over rows of |x| |g|), computed by the same
+# float64 oracle.  A recursive fp32 sum of m terms errs by at most ~m 2^-24 of that; the kernels' sums are blocked (depth < 200 at 157 k
+# rows) and rounding errors cancel, so C_ROUND = 64 is far above what any summation order gives in practice and far below what a skipped
+# tile or 8-row group costs (16 of a typical term per 256 rows, against 64 2^-24 157 k = 0.6 of one).  Measured on the MI355X: worst
+# entries at 0.12 of the bound (forward), 0.1 (backward-data), 1.4e-3 (weight gradients); a weight-gradient kernel that drops the last
+# 8-row group lands at 17-43 x.  Every output is pre-filled with NaN, so a tile that is never written fails instead of reading stale memory.
+C_ROUND = 64.0
+_U = 2.0 ** -24
+
+
+def _within_rounding(got, exact, absum, what):
+    got = got.double()
+    tol = C_ROUND * _U * absum
+    ratio = (got - exact).abs() / tol.clamp(min=1e-300)
+    assert bool(torch.isfinite(got).all()), '%s: %d entries never written (NaN)' % (what, int((~torch.isfinite(got)).sum()))
+    worst = float(ratio.max())
+    assert bool(((got - exact).abs() <= tol).all()), '%s: worst entry at %.3g x its bound' % (what, worst)
+    return worst
+
+
+def _nan_blocks(n, nb):
+    return [torch.full((n, 8), float('nan'), device='cuda') for _ in range(nb)]
+
+
+def _padded_blocks(t, nb):
+    """[n, c <= 8 nb] -> nb blocks (views buf[i, 1:] of [n + 1, 8] buffers whose row 0 is zero; channels past c zero)."""
+    n = t.shape[0]
+    buf = torch.zeros((nb, n + 1, 8), device=t.device)
+    for i in range(nb):
+        w = min(8, t.shape[1] - 8 * i)
+        buf[i, 1:, :w] = t[:, 8 * i:8 * i + w]
+    return buf, [buf[i, 1:] for i in range(nb)]
+
+
+@pytest.fixture(scope='module')
+def finest9(sphere9):
+    """The finest scale of the 9-bit shell: coordinates, the oracle's [n, 27] map and the library's maps."""
+    from linr_pcgc_amd import ops
+    c = sphere9['all_input_info'][0]['coord']
+    n = c.shape[0]
+    assert n > 2 * _cus() * 256, (n, _cus())
+    ld = (n + 63) // 64 * 64
+    nbr = torch.full((27, ld), -1, dtype=torch.int32, device='cuda')
+    nbr[:, :n] = ops.kmap_build(c.to(torch.int32).contiguous())
+    lo, mask = ops.kmap_compress(nbr, n)
+    return {'n': n, 'nbr_o': torch.from_numpy(ooct.neighbour_table(c.cpu().numpy().astype(np.int32))).long().cuda(), 'nbr': nbr,
+            'lo': lo, 'mask': mask, 'tile8t': ops.kmap_tile8t(nbr, n)}
+
+
+@pytest.mark.parametrize('cin,cout', [(16, 16), (8, 16), (16, 8), (32, 32), (3, 16), (16, 32)])
+def test_wide_conv_entries_multi_tile_against_float64(pkg, finest9, cin, cout):
+    """test_wide_conv_entries_match_the_oracle_conv on the finest scale of the 9-bit shell (> 2 x CUs x 256 rows: the workgroups of
+    linr_spconv_wide walk several tiles): forward with bias / residual / ReLU, backward-data with the ReLU mask, and the tiled one-launch
+    weight gradient (linr_spconv_wgrad_wide: 256 blocks over ~600 rows each) against the float64 oracle.conv3 and its autograd on the
+    GPU, every entry within its own rounding bound."""
+    from linr_pcgc_amd import ops
+    m = finest9
+    n, nbr_o = m['n'], m['nbr_o']
+    torch.manual_seed(cin * 100 + cout)
+    W = torch.randn(27, cin, cout, device='cuda') * 0.1
+    b = torch.randn(cout, device='cuda')
+    x = torch.randn(n, cin, device='cuda')
+    res = torch.randn(n, cout, device='cuda')
+    g = torch.randn(n, cout, device='cuda')
+    nbi, nbo = (cin + 7) // 8, cout // 8
+    xbuf, xs = _padded_blocks(x, nbi)
+    if cin % 8:
+        xbuf[-1, 1:, cin % 8:] = 7.0                                           # channels past cin must be ignored
+    W64, b64, x64 = W.double().requires_grad_(), b.double().reshape(1, -1).requires_grad_(), x.double().requires_grad_()
+    outs = ops.spconv_wide(xs, m['lo'], m['mask'], n, W, b, res=_padded_blocks(res, nbo)[1], relu=True, outs=_nan_blocks(n, nbo))
+    y64 = onet.conv3(x64, nbr_o, W64, b64)
+    with torch.no_grad():
+        exact = torch.relu(y64 + res.double())
+        absum = onet.conv3(x64.abs(), nbr_o, W64.abs(), b64.abs()) + res.double().abs()
+    worst = [_within_rounding(torch.cat(outs, dim=1), exact, absum, 'forward')]
+
+    gx, gw, gb = torch.autograd.grad(y64, [x64, W64, b64], g.double())
+    wabs = W64.detach().abs().requires_grad_()
+    xabs = x64.detach().abs().requires_grad_()
+    gabs = g.double().abs()
+    gx_abs, gw_abs = torch.autograd.grad(onet.conv3(xabs, nbr_o, wabs, torch.zeros_like(b64)), [xabs, wabs], gabs)
+    gws, gbs = torch.full((27, cin, cout), float('nan'), device='cuda'), torch.full((cout,), float('nan'), device='cuda')
+    ops.spconv_wgrad_wide(xs, _to_blocks(g), m['nbr'], m['tile8t'], n, cin, cout, gw=gws, gb=gbs)
+    worst.append(_within_rounding(gws, gw, gw_abs, 'kernel gradient'))
+    worst.append(_within_rounding(gbs, gb.reshape(-1), gabs.sum(0), 'bias gradient'))
+    if cin % 8 == 0:
+        act = torch.randn(n, cin, device='cuda')
+        gi = ops.spconv_wide(_to_blocks(g), m['lo'], m['mask'], n, W, None, bwd=True, act=_to_blocks(act), outs=_nan_blocks(n, nbi))
+        worst.append(_within_rounding(torch.cat(gi, dim=1), gx * (act > 0), gx_abs, 'backward-data'))
+    print('conv %d -> %d at %d rows: worst entry at %s of its bound' % (cin, cout, n, ['%.3g' % w for w in worst]))
+
+
+@pytest.mark.parametrize('h', [8, 16])
+def test_wide_paired_wgrad_multi_tile_against_float64(pkg, finest9, h):
+    """linr_spconv_wgrad_wide2 (conv0_1 and conv1_1 of an Inception layer as one launch) and the deferred reductions of its shared slab
+    (linr_wide_reduce_many, row stride = the pair's) on the finest scale of the 9-bit shell, against float64 autograd of oracle.conv3."""
+    from linr_pcgc_amd import ops
+    m = finest9
+    n, nbr_o = m['n'], m['nbr_o']
+    torch.manual_seed(h)
+    outs, worst = [], []
+    for _ in range(2):
+        x, g = torch.randn(n, h, device='cuda'), torch.randn(n, h, device='cuda')
+        gw, gb = torch.full((27, h, h), float('nan'), device='cuda'), torch.full((h,), float('nan'), device='cuda')
+        outs.append((x, g, gw, gb))
+    deferred = []
+    (xa, ga, gwa, gba), (xb, gb_, gwb, gbb) = outs
+    ops.spconv_wgrad_wide2(_to_blocks(xa), _to_blocks(ga), gwa, gba, _to_blocks(xb), _to_blocks(gb_), gwb, gbb, m['tile8t'], n, deferred)
+    assert len(deferred) == 2
+    ops.wide_reduce_many(deferred)
+    for which, (x, g, gw, gb) in zip('AB', outs):
+        W64 = torch.zeros(27, h, h, dtype=torch.float64, device='cuda', requires_grad=True)
+        b64 = torch.zeros(1, h, dtype=torch.float64, device='cuda', requires_grad=True)
+        gw64, gb64 = torch.autograd.grad(onet.conv3(x.double(), nbr_o, W64, b64), [W64, b64], g.double())
+        gw_abs = torch.autograd.grad(onet.conv3(x.double().abs(), nbr_o, W64, b64), [W64], g.double().abs())[0]
+        worst.append(_within_rounding(gw, gw64, gw_abs, 'kernel gradient ' + which))
+        worst.append(_within_rounding(gb, gb64.reshape(-1), g.double().abs().sum(0), 'bias gradient ' + which))
+    print('paired weight gradients h = %d at %d rows: worst entry at %s of its bound' % (h, n, ['%.3g' % w for w in worst]))
+
+
+@pytest.mark.parametrize('cin,cout,layout', [(16, 8, 'me'), (32, 16, 'me'), (8, 8, 'me'), (16, 16, 'me'), (16, 24, 'torch'), (32, 24, 'torch')])
+def test_wide_pointwise_entries_multi_tile_against_float64(pkg, cin, cout, layout):
+    """test_wide_pointwise_entries_match_torch at n = 196,685 (> 512 x 256: all 512 slab rows of the weight gradient, each over several
+    256-row tiles; no multiple of any tile): linr_linear_wide forward (bias / residual / ReLU) and backward-data (+ old, masked),
+    linr_linear_wgrad_wide with its own reduction and deferred into linr_wide_reduce_many - every entry within its rounding bound of the
+    float64 result."""
+    from linr_pcgc_amd import ops
+    n = 3 * 65536 + 77
+    torch.manual_seed(7 * cin + cout + 1)
+    x = torch.randn(n, cin, device='cuda')
+    W = torch.randn((cin, cout) if layout == 'me' else (cout, cin), device='cuda') * 0.3
+    b = torch.randn(cout, device='cuda')
+    Wm = (W if layout == 'me' else W.t()).double()                             # [cin, cout]
+    ws = (cout, 1) if layout == 'me' else (1, cin)
+    blocked_out = cout % 8 == 0 and layout == 'me'
+    res = torch.randn(n, cout, device='cuda')
+    outs = _nan_blocks(n, cout // 8) if blocked_out else [torch.full((n, cout), float('nan'), device='cuda')]
+    ops.linear_wide(_to_blocks(x), cin, W, ws[0], ws[1], b, cout, outs, out_blocked=blocked_out,
+                    res=_to_blocks(res) if blocked_out else [res], relu=True)
+    x64, r64 = x.double(), res.double()
+    worst = [_within_rounding(torch.cat(outs, dim=1), torch.relu(x64 @ Wm + b.double() + r64),
+                              x64.abs() @ Wm.abs() + b.double().abs() + r64.abs(), 'forward')]
+    g = torch.randn(n, cout, device='cuda')
+    gs = _to_blocks(g) if blocked_out else [g]
+    g64 = g.double()
+    old, act = torch.randn(n, cin, device='cuda'), torch.randn(n, cin, device='cuda')
+    gins = _to_blocks(old)
+    ops.linear_wide(gs, cout, W, ws[1], ws[0], None, cin, gins, in_blocked=blocked_out, act=_to_blocks(act), accumulate=True)
+    worst.append(_within_rounding(torch.cat(gins, dim=1), (g64 @ Wm.t() + old.double()) * (act > 0),
+                                  g64.abs() @ Wm.abs().t() + old.double().abs(), 'backward-data'))
+    gw_exact, gb_exact = x64.t() @ g64, g64.sum(0)
+    gw_abs, gb_abs = x64.abs().t() @ g64.abs(), g64.abs().sum(0)
+    if layout == 'torch':
+        gw_exact, gw_abs = gw_exact.t(), gw_abs.t()
+    deferred = []
+    for defer in (None, deferred):
+        gw, gb = torch.full_like(W, float('nan')), torch.full_like(b, float('nan'))
+        ops.linear_wgrad_wide(_to_blocks(x), cin, gs, cout, gw, ws[0], ws[1], gb, g_blocked=blocked_out, defer=defer)
+        if defer is not None:
+            assert len(deferred) == 1 and bool(torch.isnan(gw).all())
+            ops.wide_reduce_many(deferred)
+        what = 'deferred ' if defer is not None else ''
+        worst.append(_within_rounding(gw, gw_exact, gw_abs, what + 'weight gradient'))
+        worst.append(_within_rounding(gb, gb_exact, gb_abs, what + 'bias gradient'))
+    print('pointwise %d -> %d (%s) at %d rows: worst entry at %s of its bound' % (cin, cout, layout, n, ['%.3g' % w for w in worst]))
