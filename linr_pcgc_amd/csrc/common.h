@@ -87,6 +87,10 @@ int linr_adam_launch(float* params, const float* grads, float* exp_avg, float* e
 // ground-truth occupancy and x_glob during overfitting / encoding) run as ONE launch with gridDim.y = groups.  Group g adds
 // these ELEMENT offsets to the kernel's base pointers; a plain launch passes all zeros.  Per-row arithmetic is identical
 // in grouped and plain launches, so the staged decoder (plain) reproduces the encoder (grouped) bit for bit.
+// Grp is the kernels' side of this and is filled by the launchers alone: a caller describes every group with the launcher's
+// typed struct below (one element per group, a plain launch is an array of one); the launcher takes the kernel's base pointers
+// and slab offsets from element 0 and writes the differences of the others into the slots its kernel reads.  What a slot
+// (e0..e6 above all) means is the business of the kernel and of the launcher next to it, nobody else names one.
 #define LINR_MAXG 8
 struct Grp {
     int64_t in[LINR_MAXG], w[LINR_MAXG], b[LINR_MAXG], res[LINR_MAXG], act[LINR_MAXG], out[LINR_MAXG];
@@ -94,6 +98,67 @@ struct Grp {
     int64_t n[LINR_MAXG];      // > 0: the group's own row count (groups of unequal size: the scales of a frame)
 };
 
+// compressed kernel map of n rows: lo [9][ld], mask [ld]
+struct LinrCmap { const int32_t* lo; const uint32_t* mask; int64_t ld, n; };
+
+// ---- one group's operands, per launcher ---------------------------------------------------------------------------------------
+// Pointers are the group's own matrices and parameter tensors; *_off are offsets into a row of the partial weight-gradient
+// slab.  A pointer the launch does not use is NULL in every group.
+struct ConvGroup {           // linr_cconv_launch: out = conv3(in; W) (+ bias) (+ res), masked by act > 0 with LINR_RELU_MASK
+    const float *in, *W, *bias, *res, *act;
+    float* out;
+};
+struct HeadFwdGroup {        // linr_cconv_head_launch: c_out = conv3(in; W) + bias, p_out = sigmoid(w2 . relu(w1 c + b1) + b2)
+    const float *in, *W, *bias;
+    float* c_out;
+    const float *w1, *b1, *w2, *b2;
+    const float* target;   // the group's occupancy column, or NULL (probabilities only)
+    float* p_out;
+    double* partial;       // [linr_grid(n, 256)] block partials of the bits, or NULL
+};
+struct HeadBwdGroup {        // linr_head_bwd_launch
+    const float *c, *p, *target, *w1, *b1, *w2;
+    float* gc;
+    int64_t w1_off, b1_off, w2_off, b2_off;
+};
+struct ConvPwGroup {         // linr_conv_pw_fwd_launch: H = [relu(conv3(A; w00) + b00) | relu(A @ w10 + b10)]
+    const float *A, *w00, *b00, *w10, *b10;
+    float* H;
+};
+struct Dual44FwdGroup {      // linr_dual44_fwd_launch
+    const float *H, *w01, *b01, *w11, *b11, *A, *w12, *b12;
+    float *M, *I;
+};
+// backward of the two 4->4 convolutions of an Inception layer: linr_dual44_bwd_launch (gH alone; no offsets), linr_conv3_wgrad_dual44
+// (the weight gradients alone; no w01 / w11 / gH), linr_dual44_bwd_wgrad_launch (both)
+struct Dual44BwdGroup {
+    const float *gI, *gM, *H, *w01, *w11;
+    float* gH;
+    int64_t w01_off, b01_off, w11_off, b11_off;
+};
+// backward of a conv 8->8 with input xin: linr_conv88_bwd_wgrad_launch (out = bwd(g; W) and the weight gradient), with w12 != NULL
+// in every group also gM = (out[:, 4:8] @ w12^T) * (M > 0) and conv1_2's weight gradient; linr_conv_bwd_gm_launch (out and gM alone;
+// no xin, no offsets)
+struct Conv88BwdGroup {
+    const float *g, *xin, *W;
+    float* out;
+    int64_t w_off, b_off;
+    const float *w12, *M;
+    float* gM;
+    int64_t w12_off, b12_off;
+};
+// backward of conv0_0 8->4 | conv1_0 1x1 of an Inception layer with input A: linr_conv84_bwd_wgrad_launch (gA and both weight
+// gradients), linr_conv_bwd_ga_launch (gA alone; A only as the ReLU mask, no offsets)
+struct Conv84BwdGroup {
+    const float *gH, *A, *gI, *w00, *w10;
+    float* gA;
+    int64_t w00_off, b00_off, w10_off, b10_off;
+};
+struct WgradGroup {          // linr_conv3_wgrad_mfma, linr_linear_wgrad_partial: the layer's input and its output gradient
+    const float *in, *gout;
+    int64_t w_off, b_off;
+    int cin_live;          // conv3 only, > 0: input channels this group actually has (<= cin)
+};
 
 // ---- internal launchers shared with the network executor (C++ linkage, not exported) ---------------------------
 // epilogue order of both: acc (+ bias) -> + res -> + old (LINR_ACCUM) -> * (act > 0) (LINR_RELU_MASK) -> ReLU
@@ -109,91 +174,69 @@ __attribute__((visibility("hidden")))
 int linr_conv3_wgrad_partial(const float* in, int in_ld, const float* gout, int gout_ld, const int32_t* nbr,
                              int64_t nbr_ld, int64_t n, int cin, int cout, LinrWgradDst d, int nblocks, unsigned flags,
                              hipStream_t s);
+// The grouped launchers: g[0 .. ng) describes the groups, 1 <= ng <= LINR_MAXG (else LINR_EINVAL).  Those that write weight-gradient
+// partials put element e of block b at big[b * block_stride + the group's offset + e].
+// pointwise layers: element (ci, co) at w_off + ci * ws_ci + co * ws_co, bias co at b_off + co
 __attribute__((visibility("hidden")))
-int linr_linear_wgrad_partial(const float* in, int in_ld, const float* gout, int gout_ld, int64_t n, int cin, int cout,
-                              LinrLinDst d, int nblocks, hipStream_t s, const Grp* gp = nullptr, int ngroups = 1);
+int linr_linear_wgrad_partial(const WgradGroup* g, int ng, int in_ld, int gout_ld, int64_t n, int cin, int cout, float* big,
+                              int64_t block_stride, int ws_ci, int ws_co, int nblocks, hipStream_t s);
 __attribute__((visibility("hidden"))) int linr_lin_blocks(int64_t n);
 __attribute__((visibility("hidden")))
 int linr_linear_slab_reduce_launch(const float* slab, int nblocks, int64_t stride, int cin, int cout, float* gW, int ws_ci, int ws_co,
                                    float* gb, unsigned flags, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_cconv_launch(bool bwd, const float* in, int in_ld, const int32_t* lo, const uint32_t* mask, int64_t ld,
-                      int64_t n, const float* W, const float* bias, int cin, int cout, const float* res, int res_ld,
-                      const float* act, int act_ld, float* out, int out_ld, unsigned flags, hipStream_t s,
-                      const Grp* gp = nullptr, int ngroups = 1);
+int linr_cconv_launch(bool bwd, LinrCmap m, const ConvGroup* g, int ng, int in_ld, int cin, int cout, int res_ld, int act_ld,
+                      int out_ld, unsigned flags, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_cconv_head_launch(const float* in, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                           const float* W, const float* bias, float* c_out, const float* w1, const float* b1,
-                           const float* w2, const float* b2, const float* target, int target_ld, float* p_out,
-                           double* partial, hipStream_t s, const Grp* gp = nullptr, int ngroups = 1);
+int linr_cconv_head_launch(LinrCmap m, const HeadFwdGroup* g, int ng, int target_ld, hipStream_t s);
+// rows_written == nullptr: slab rows 0 .. nblocks - 1 are all written; otherwise only the active blocks' rows (see csrc/fused.hip)
 __attribute__((visibility("hidden")))
-int linr_head_bwd_launch(const float* c, const float* p, const float* target, int target_ld, const float* w1,
-                         const float* b1, const float* w2, float gscale, float* gc, int64_t n, float* big,
-                         int64_t block_stride, int64_t off_w1, int64_t off_b1, int64_t off_w2, int64_t off_b2,
-                         hipStream_t s, const Grp* gp = nullptr, int ngroups = 1, int nblocks = LINR_WG_BLOCKS,
-                         int* rows_written = nullptr);
+int linr_head_bwd_launch(const HeadBwdGroup* g, int ng, int target_ld, float gscale, int64_t n, float* big, int64_t block_stride,
+                         int nblocks, int* rows_written, hipStream_t s);
 __attribute__((visibility("hidden")))
 int linr_slab_reduce_launch(const float* big, int nblocks, int64_t total, float* gsum, hipStream_t s);
 __attribute__((visibility("hidden")))
 int linr_bits_finish_launch(const double* partial, int count, double* bits_acc, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_dual44_fwd_launch(const float* H, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* w01,
-                           const float* b01, const float* w11, const float* b11, const float* A, const float* w12,
-                           const float* b12, float* M, float* I, hipStream_t s, const Grp* gp = nullptr, int ngroups = 1);
+int linr_dual44_fwd_launch(LinrCmap m, const Dual44FwdGroup* g, int ng, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_dual44_bwd_launch(const float* gI, const float* gM, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                           const float* w01, const float* w11, const float* H, float* gH, hipStream_t s,
-                           const Grp* gp = nullptr, int ngroups = 1);
+int linr_dual44_bwd_launch(LinrCmap m, const Dual44BwdGroup* g, int ng, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_conv_pw_fwd_launch(const float* A, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* w00,
-                            const float* b00, const float* w10, const float* b10, float* H, hipStream_t s,
-                            const Grp* gp = nullptr, int ngroups = 1);
+int linr_conv_pw_fwd_launch(LinrCmap m, const ConvPwGroup* g, int ng, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_conv_bwd_gm_launch(const float* gO, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* wb,
-                            const float* w12, const float* M, float* gI, float* gM, hipStream_t s,
-                            const Grp* gp = nullptr, int ngroups = 1);
+int linr_conv_bwd_gm_launch(LinrCmap m, const Conv88BwdGroup* g, int ng, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_conv_bwd_ga_launch(const float* gH, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* w00,
-                            const float* w10, const float* gI, const float* A, float* gA, unsigned flags, hipStream_t s,
-                            const Grp* gp = nullptr, int ngroups = 1);
+int linr_conv_bwd_ga_launch(LinrCmap m, const Conv84BwdGroup* g, int ng, unsigned flags, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_occ_conv7_launch(const float* occ, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* P,
-                          const int64_t* w_off, const int64_t* b_off, float* out, const int64_t* out_off, hipStream_t s);
+int linr_occ_conv7_launch(const float* occ, LinrCmap m, const float* P, const int64_t* w_off, const int64_t* b_off, float* out,
+                          const int64_t* out_off, hipStream_t s);
+// cin, cout: the kernel's width (a group with fewer live input channels says so in cin_live); tile8t: the transposed tiled
+// table (csrc/fused.hip: spconv_wgrad_t_k), or NULL: indices from nbr
 __attribute__((visibility("hidden")))
-int linr_conv3_wgrad_mfma(const float* in, int in_ld, const float* gout, int gout_ld, const int32_t* nbr, int64_t nbr_ld,
-                          int64_t n, int cin, int cout, LinrWgradDst d, int nblocks, hipStream_t s, const Grp* gp = nullptr,
-                          int ngroups = 1, const int32_t* tile8t = nullptr);
-struct PwArgs;
+int linr_conv3_wgrad_mfma(const WgradGroup* g, int ng, int in_ld, int gout_ld, const int32_t* nbr, int64_t nbr_ld, int64_t n,
+                          const int32_t* tile8t, int cin, int cout, float* big, int64_t block_stride, int nblocks, hipStream_t s);
 __attribute__((visibility("hidden")))
 int linr_fused_bwd_rows(int64_t n, int nb, int ngroups);
-// backward-data + weight gradient of a conv 8->8 from one gather (csrc/fused_bwd.hip); pw != nullptr: gM epilogue
+// The fused launches (csrc/fused_bwd.hip): backward-data + weight gradient from one gather.  rows_written == nullptr: rows
+// 0 .. nb - 1 of the slab are all written; otherwise only the grid's rows, and *rows_written tells the caller how many.
 __attribute__((visibility("hidden")))
-int linr_conv88_bwd_wgrad_launch(const float* g, const float* xin, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                                 const float* W, float* out, const PwArgs* pw, LinrWgradDst d, int nb, hipStream_t s,
-                                 const Grp* gp = nullptr, int ngroups = 1, int* rows_written = nullptr, int64_t w12_off = 0,
-                                 int64_t b12_off = 0);
-// ... of the two 4->4 convolutions of an Inception layer (gH, masked by H > 0) and of conv0_0 8->4 (gA with cconv_mfma_k's EPI 4)
+int linr_conv88_bwd_wgrad_launch(LinrCmap m, const Conv88BwdGroup* g, int ng, float* big, int64_t block_stride, int nb,
+                                 int* rows_written, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_dual44_bwd_wgrad_launch(const float* gI, const float* gM, const float* H, const int32_t* lo, const uint32_t* mask,
-                                 int64_t ld, int64_t n, const float* w01, const float* w11, float* gH, float* big,
-                                 int64_t block_stride, int64_t w_off0, int64_t b_off0, int64_t w_off1, int64_t b_off1, int nb,
-                                 hipStream_t s, const Grp* gp = nullptr, int ngroups = 1, int* rows_written = nullptr);
+int linr_dual44_bwd_wgrad_launch(LinrCmap m, const Dual44BwdGroup* g, int ng, float* big, int64_t block_stride, int nb,
+                                 int* rows_written, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_conv84_bwd_wgrad_launch(const float* gH, const float* A, const float* gI, const int32_t* lo, const uint32_t* mask,
-                                 int64_t ld, int64_t n, const float* w00, const float* w10, float* gA, unsigned flags,
-                                 LinrWgradDst d, int64_t w10_off, int64_t b10_off, int nb, hipStream_t s, const Grp* gp = nullptr,
-                                 int ngroups = 1, int* rows_written = nullptr);
+int linr_conv84_bwd_wgrad_launch(LinrCmap m, const Conv84BwdGroup* g, int ng, unsigned flags, float* big, int64_t block_stride,
+                                 int nb, int* rows_written, hipStream_t s);
+// the weight gradients of both 4->4 convolutions from H, gI (ld gI_ld) and gM (ld gM_ld)
 __attribute__((visibility("hidden")))
-int linr_conv3_wgrad_dual44(const float* H, const float* g0, int g0_ld, const float* g1, int g1_ld, const int32_t* nbr,
-                            int64_t nbr_ld, int64_t n, float* big, int64_t block_stride, int64_t w_off0, int64_t b_off0,
-                            int64_t w_off1, int64_t b_off1, int nblocks, hipStream_t s, const Grp* gp = nullptr,
-                            int ngroups = 1, const int32_t* tile8t = nullptr);
+int linr_conv3_wgrad_dual44(const Dual44BwdGroup* g, int ng, int gI_ld, int gM_ld, const int32_t* nbr, int64_t nbr_ld, int64_t n,
+                            const int32_t* tile8t, float* big, int64_t block_stride, int nblocks, hipStream_t s);
 
 // test hook (include/linr_hip.h: linr_debug_poison): poisons LDS and vector registers of every CU on `s` when bit `kind` of the
 // mask is set; kinds 0..13 = the linr_prof_* classes of the fp32 executor, 14 = the bf16 executor, 15 = the decoder's own kernels
 __attribute__((visibility("hidden"))) void linr_poison_hook(hipStream_t s, int kind);
 // csrc/occ_wgrad.hip: weight gradients of the first convolutions of the 7 outter blocks from one gather of the occupancy rows
 __attribute__((visibility("hidden")))
-int linr_occ_wgrad7_launch(const float* occ, const float* const* g, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                           float* big, int64_t block_stride, const int64_t* w_off, const int64_t* b_off, int nb, hipStream_t s,
-                           int* rows_written);
+int linr_occ_wgrad7_launch(const float* occ, const float* const* g, LinrCmap m, float* big, int64_t block_stride,
+                           const int64_t* w_off, const int64_t* b_off, int nb, hipStream_t s, int* rows_written);

@@ -273,8 +273,8 @@ extern "C" int linr_spconv_cmap(int32_t bwd, const float* in, int32_t in_ld, con
     if ((flags & LINR_RELU_MASK) && (!act || act_ld < gout)) return LINR_EINVAL;
     if (res && res_ld < gout) return LINR_EINVAL;
     if (!linr_rows_fit32(n, 4 * in_ld)) return LINR_EINVAL;
-    return linr_cconv_launch(bwd != 0, in, in_ld, lo, mask, ld, n, W, bias, cin, cout, res, res_ld, act, act_ld, out, out_ld,
-                             flags, (hipStream_t)stream, nullptr, 1);
+    const ConvGroup g = {in, W, bias, res, act, out};
+    return linr_cconv_launch(bwd != 0, {lo, mask, ld, n}, &g, 1, in_ld, cin, cout, res_ld, act_ld, out_ld, flags, (hipStream_t)stream);
 }
 
 // The executor's backward-weight kernel through its own entry: per-block partial sums of
@@ -293,21 +293,24 @@ extern "C" int linr_spconv_wgrad_cmap(const float* in, int32_t in_ld, const floa
     if (!((cin == 8 && (cout == 8 || cout == 4)) || (cin < 8 && cin >= 1 && cout == 8))) return LINR_EINVAL;
     if (!linr_rows_fit32(n)) return LINR_EINVAL;
     const int64_t elems = (int64_t)(27 * cin + 1) * cout;
-    LinrWgradDst d = {slab, elems, 0, (int64_t)27 * cin * cout, cin};
     if (tile8t && !linr_aligned16(tile8t)) return LINR_EALIGN;
-    return linr_conv3_wgrad_mfma(in, in_ld, gout, gout_ld, nbr, ld, n, cin, cout, d, LINR_WG_BLOCKS, (hipStream_t)stream, nullptr, 1, tile8t);
+    const WgradGroup g = {in, gout, 0, (int64_t)27 * cin * cout, 0};
+    return linr_conv3_wgrad_mfma(&g, 1, in_ld, gout_ld, nbr, ld, n, tile8t, cin, cout, slab, elems, LINR_WG_BLOCKS, (hipStream_t)stream);
 }
 
 // prune conv 8->8 + head of stage k in one launch; partial: [linr_grid(n,256)] doubles or nullptr
-int linr_cconv_head_launch(const float* in, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                           const float* W, const float* bias, float* c_out, const float* w1, const float* b1,
-                           const float* w2, const float* b2, const float* target, int target_ld, float* p_out,
-                           double* partial, hipStream_t s, const Grp* gp, int ngroups) {
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    HeadArgs hd = {w1, b1, w2, b2, target, target_ld, p_out, partial};
-    cconv_mfma_k<8, 8, false, 8, 1><<<dim3(linr_grid(n, LINR_CONV_BLOCK), ngroups), LINR_CONV_BLOCK, 0, s>>>(
-        in, 8, lo, mask, ld, n, W, bias, nullptr, 0, nullptr, 0, c_out, 8, 0, hd, PwArgs(), g0);
+int linr_cconv_head_launch(LinrCmap m, const HeadFwdGroup* g, int ng, int target_ld, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].in - g[0].in; gp.w[i] = g[i].W - g[0].W; gp.b[i] = g[i].bias - g[0].bias; gp.out[i] = g[i].c_out - g[0].c_out;
+        gp.e0[i] = g[i].w1 - g[0].w1; gp.e1[i] = g[i].b1 - g[0].b1; gp.e2[i] = g[i].w2 - g[0].w2; gp.e3[i] = g[i].b2 - g[0].b2;
+        gp.e4[i] = g[i].target - g[0].target; gp.e5[i] = g[i].p_out - g[0].p_out; gp.e6[i] = g[i].partial - g[0].partial;
+    }
+    HeadArgs hd = {g[0].w1, g[0].b1, g[0].w2, g[0].b2, g[0].target, target_ld, g[0].p_out, g[0].partial};
+    cconv_mfma_k<8, 8, false, 8, 1><<<dim3(linr_grid(m.n, LINR_CONV_BLOCK), ng), LINR_CONV_BLOCK, 0, s>>>(
+        g[0].in, 8, m.lo, m.mask, m.ld, m.n, g[0].W, g[0].bias, nullptr, 0, nullptr, 0, g[0].c_out, 8, 0, hd, PwArgs(), gp);
     return linr_launch_rc();
 }
 
@@ -422,60 +425,77 @@ __global__ __launch_bounds__(LINR_BLOCK) void cconv_dual44_k(const float* __rest
     }
 }
 
-int linr_dual44_fwd_launch(const float* H, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* w01,
-                           const float* b01, const float* w11, const float* b11, const float* A, const float* w12,
-                           const float* b12, float* M, float* I, hipStream_t s, const Grp* gp, int ngroups) {
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    DualArgs d = {nullptr, 0, w01, w11, b01, b11, A, w12, b12, M, nullptr};
-    cconv_dual44_k<false><<<dim3(linr_grid(n, LINR_BLOCK), ngroups), LINR_BLOCK, 0, s>>>(H, 8, lo, mask, ld, n, d, I, g0);
+int linr_dual44_fwd_launch(LinrCmap m, const Dual44FwdGroup* g, int ng, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].H - g[0].H; gp.w[i] = g[i].w01 - g[0].w01; gp.b[i] = g[i].b01 - g[0].b01; gp.e1[i] = g[i].w11 - g[0].w11;
+        gp.e2[i] = g[i].b11 - g[0].b11; gp.res[i] = g[i].A - g[0].A; gp.e3[i] = g[i].w12 - g[0].w12; gp.e4[i] = g[i].b12 - g[0].b12;
+        gp.e5[i] = g[i].M - g[0].M; gp.out[i] = g[i].I - g[0].I;
+    }
+    DualArgs d = {nullptr, 0, g[0].w01, g[0].w11, g[0].b01, g[0].b11, g[0].A, g[0].w12, g[0].b12, g[0].M, nullptr};
+    cconv_dual44_k<false><<<dim3(linr_grid(m.n, LINR_BLOCK), ng), LINR_BLOCK, 0, s>>>(g[0].H, 8, m.lo, m.mask, m.ld, m.n, d, g[0].I, gp);
     return linr_launch_rc();
 }
 
-int linr_dual44_bwd_launch(const float* gI, const float* gM, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                           const float* w01, const float* w11, const float* H, float* gH, hipStream_t s, const Grp* gp,
-                           int ngroups) {
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    DualArgs d = {gM, 4, w01, w11, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, H};
-    cconv_dual44_k<true><<<dim3(linr_grid(n, LINR_BLOCK), ngroups), LINR_BLOCK, 0, s>>>(gI, 8, lo, mask, ld, n, d, gH, g0);
+int linr_dual44_bwd_launch(LinrCmap m, const Dual44BwdGroup* g, int ng, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].gI - g[0].gI; gp.e0[i] = g[i].gM - g[0].gM; gp.w[i] = g[i].w01 - g[0].w01; gp.e1[i] = g[i].w11 - g[0].w11;
+        gp.act[i] = g[i].H - g[0].H; gp.out[i] = g[i].gH - g[0].gH;
+    }
+    DualArgs d = {g[0].gM, 4, g[0].w01, g[0].w11, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, g[0].H};
+    cconv_dual44_k<true><<<dim3(linr_grid(m.n, LINR_BLOCK), ng), LINR_BLOCK, 0, s>>>(g[0].gI, 8, m.lo, m.mask, m.ld, m.n, d, g[0].gH, gp);
     return linr_launch_rc();
 }
 
 // conv0_0 (8->4) + conv1_0 (1x1 8->4) forward with both ReLUs: H = [relu(conv3(A)) | relu(A @ W10 + b10)]
-int linr_conv_pw_fwd_launch(const float* A, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* w00,
-                            const float* b00, const float* w10, const float* b10, float* H, hipStream_t s, const Grp* gp,
-                            int ngroups) {
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    PwArgs pw = {w10, b10, nullptr, nullptr};
-    cconv_mfma_k<8, 4, false, 8, 2><<<dim3(linr_grid(n, LINR_CONV_BLOCK), ngroups), LINR_CONV_BLOCK, 0, s>>>(
-        A, 8, lo, mask, ld, n, w00, b00, nullptr, 0, nullptr, 0, H, 8, 0, HeadArgs(), pw, g0);
+int linr_conv_pw_fwd_launch(LinrCmap m, const ConvPwGroup* g, int ng, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].A - g[0].A; gp.w[i] = g[i].w00 - g[0].w00; gp.b[i] = g[i].b00 - g[0].b00; gp.out[i] = g[i].H - g[0].H;
+        gp.e0[i] = g[i].w10 - g[0].w10; gp.e1[i] = g[i].b10 - g[0].b10;
+    }
+    PwArgs pw = {g[0].w10, g[0].b10, nullptr, nullptr};
+    cconv_mfma_k<8, 4, false, 8, 2><<<dim3(linr_grid(m.n, LINR_CONV_BLOCK), ng), LINR_CONV_BLOCK, 0, s>>>(
+        g[0].A, 8, m.lo, m.mask, m.ld, m.n, g[0].w00, g[0].b00, nullptr, 0, nullptr, 0, g[0].H, 8, 0, HeadArgs(), pw, gp);
     return linr_launch_rc();
 }
 
-// backward of the block's tail conv: gI = bwd(gO; Wb) and gM = (gI[:,4:8] @ W12^T) * (M > 0)
-int linr_conv_bwd_gm_launch(const float* gO, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* wb,
-                            const float* w12, const float* M, float* gI, float* gM, hipStream_t s, const Grp* gp,
-                            int ngroups) {
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    PwArgs pw = {w12, nullptr, M, gM};
-    cconv_mfma_k<8, 8, true, 8, 3><<<dim3(linr_grid(n, LINR_CONV_BLOCK), ngroups), LINR_CONV_BLOCK, 0, s>>>(
-        gO, 8, lo, mask, ld, n, wb, nullptr, nullptr, 0, nullptr, 0, gI, 8, 0, HeadArgs(), pw, g0);
+// backward of the block's tail conv: gI = bwd(gO; Wb) and gM = (gI[:,4:8] @ W12^T) * (M > 0)   (Conv88BwdGroup: g = gO, out = gI)
+int linr_conv_bwd_gm_launch(LinrCmap m, const Conv88BwdGroup* g, int ng, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].g - g[0].g; gp.w[i] = g[i].W - g[0].W; gp.out[i] = g[i].out - g[0].out;
+        gp.e0[i] = g[i].w12 - g[0].w12; gp.e1[i] = g[i].M - g[0].M; gp.e2[i] = g[i].gM - g[0].gM;
+    }
+    PwArgs pw = {g[0].w12, nullptr, g[0].M, g[0].gM};
+    cconv_mfma_k<8, 8, true, 8, 3><<<dim3(linr_grid(m.n, LINR_CONV_BLOCK), ng), LINR_CONV_BLOCK, 0, s>>>(
+        g[0].g, 8, m.lo, m.mask, m.ld, m.n, g[0].W, nullptr, nullptr, 0, nullptr, 0, g[0].out, 8, 0, HeadArgs(), pw, gp);
     return linr_launch_rc();
 }
 
 // gA = (bwd(gH[:,0:4]; W00) + gI (+ old gA: LINR_ACCUM) + gH[:,4:8] @ W10^T) (* (A > 0): LINR_RELU_MASK)
-int linr_conv_bwd_ga_launch(const float* gH, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* w00,
-                            const float* w10, const float* gI, const float* A, float* gA, unsigned flags, hipStream_t s,
-                            const Grp* gp, int ngroups) {
-    if (n == 0) return 0;
-    if ((flags & LINR_RELU_MASK) && !A) return LINR_EINVAL;
-    const Grp g0 = gp ? *gp : Grp();
-    PwArgs pw = {w10, nullptr, gH, nullptr};
-    cconv_mfma_k<4, 8, true, 4, 4><<<dim3(linr_grid(n, LINR_CONV_BLOCK), ngroups), LINR_CONV_BLOCK, 0, s>>>(
-        gH, 8, lo, mask, ld, n, w00, nullptr, gI, 8, A, 8, gA, 8, flags & (LINR_RELU_MASK | LINR_ACCUM), HeadArgs(), pw, g0);
+int linr_conv_bwd_ga_launch(LinrCmap m, const Conv84BwdGroup* g, int ng, unsigned flags, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    if ((flags & LINR_RELU_MASK) && !g[0].A) return LINR_EINVAL;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].gH - g[0].gH; gp.w[i] = g[i].w00 - g[0].w00; gp.res[i] = g[i].gI - g[0].gI; gp.act[i] = g[i].A - g[0].A;
+        gp.out[i] = g[i].gA - g[0].gA; gp.e0[i] = g[i].w10 - g[0].w10; gp.e1[i] = g[i].gH - g[0].gH;
+    }
+    PwArgs pw = {g[0].w10, nullptr, g[0].gH, nullptr};
+    cconv_mfma_k<4, 8, true, 4, 4><<<dim3(linr_grid(m.n, LINR_CONV_BLOCK), ng), LINR_CONV_BLOCK, 0, s>>>(
+        g[0].gH, 8, m.lo, m.mask, m.ld, m.n, g[0].w00, nullptr, g[0].gI, 8, g[0].A, 8, g[0].gA, 8, flags & (LINR_RELU_MASK | LINR_ACCUM),
+        HeadArgs(), pw, gp);
     return linr_launch_rc();
 }
 
@@ -576,8 +596,9 @@ __global__ __launch_bounds__(LINR_CONV_BLOCK) void occ_conv7_k(const float* __re
 
 // occ: arena copy of the occupancy [n][8] with the zero pad row in front; w_off / b_off: parameter offsets of the 7 first
 // convolutions (kernel [27][b][8] of block b) ; out + out_off[g]: A matrix of block g + 1
-int linr_occ_conv7_launch(const float* occ, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, const float* P,
-                          const int64_t* w_off, const int64_t* b_off, float* out, const int64_t* out_off, hipStream_t s) {
+int linr_occ_conv7_launch(const float* occ, LinrCmap m, const float* P, const int64_t* w_off, const int64_t* b_off, float* out,
+                          const int64_t* out_off, hipStream_t s) {
+    const int64_t n = m.n;
     if (n == 0) return 0;
     Occ7Args a;
     for (int g = 0; g < 7; ++g) { a.w[g] = w_off[g]; a.b[g] = b_off[g]; a.out[g] = out_off[g]; }
@@ -594,7 +615,7 @@ int linr_occ_conv7_launch(const float* occ, const int32_t* lo, const uint32_t* m
     const int64_t want = (int64_t)cus * per_cu;
     const int64_t per = (tiles + want - 1) / want;                 // tiles per workgroup
     const int64_t grid = (tiles + per - 1) / per;
-    occ_conv7_k<<<(unsigned)grid, LINR_CONV_BLOCK, 0, s>>>(occ, lo, mask, ld, n, P, a, out);
+    occ_conv7_k<<<(unsigned)grid, LINR_CONV_BLOCK, 0, s>>>(occ, m.lo, m.mask, m.ld, n, P, a, out);
     return linr_launch_rc();
 }
 
@@ -977,26 +998,31 @@ extern "C" int linr_kmap_tile8t(const int32_t* nbr, int64_t ld, int64_t n, int32
     return linr_launch_rc();
 }
 
-int linr_conv3_wgrad_mfma(const float* in, int in_ld, const float* gout, int gout_ld, const int32_t* nbr, int64_t nbr_ld,
-                          int64_t n, int cin, int cout, LinrWgradDst d, int nblocks, hipStream_t s, const Grp* gp,
-                          int ngroups, const int32_t* tile8t) {
+int linr_conv3_wgrad_mfma(const WgradGroup* g, int ng, int in_ld, int gout_ld, const int32_t* nbr, int64_t nbr_ld, int64_t n,
+                          const int32_t* tile8t, int cin, int cout, float* big, int64_t block_stride, int nblocks, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
     if (in_ld != 8 && in_ld != 4) return LINR_EINVAL;  // the kernels address gathered rows by a shift: 32- or 16-byte rows
     const int idx = (nbr_ld % 4 == 0 && linr_aligned16(nbr)) ? 1 : 0;
-    const Grp g0 = gp ? *gp : Grp();
-    const dim3 grid(nblocks, ngroups);
-    WgradSrc S = {in, in_ld, gout, gout_ld, nullptr, 0};
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].in - g[0].in; gp.res[i] = g[i].gout - g[0].gout; gp.w[i] = g[i].w_off - g[0].w_off;
+        gp.b[i] = g[i].b_off - g[0].b_off; gp.e2[i] = g[i].cin_live;
+    }
+    const float* in = g[0].in;
+    const dim3 grid(nblocks, ng);
+    WgradSrc S = {in, in_ld, g[0].gout, gout_ld, nullptr, 0};
+    LinrWgradDst d = {big, block_stride, g[0].w_off, g[0].b_off, cin};
     WgradDual dd = {0, 0};
-    d.cin_valid = cin;
     // coalesced gathers + LDS transpose: 32-byte rows, the transposed tiled table
     if (tile8t && in_ld == 8 && cin <= 8 && (cout == 8 || (cout == 4 && cin == 8)) && linr_aligned16(in) && linr_aligned16(tile8t)) {
-        if (cout == 8) spconv_wgrad_t_k<8, false><<<grid, WG_WAVES * 64, 0, s>>>(S, tile8t, n, d, dd, g0);
-        else spconv_wgrad_t_k<4, false><<<grid, WG_WAVES * 64, 0, s>>>(S, tile8t, n, d, dd, g0);
+        if (cout == 8) spconv_wgrad_t_k<8, false><<<grid, WG_WAVES * 64, 0, s>>>(S, tile8t, n, d, dd, gp);
+        else spconv_wgrad_t_k<4, false><<<grid, WG_WAVES * 64, 0, s>>>(S, tile8t, n, d, dd, gp);
         return linr_launch_rc();
     }
 #define GO(XQ, CO)                                                                                                           \
     do {                                                                                                                     \
-        if (idx == 1) spconv_wgrad_mfma_k<XQ, CO, false, 1><<<grid, WG_WAVES * 64, 0, s>>>(S, nbr, nbr_ld, n, d, dd, g0);   \
-        else spconv_wgrad_mfma_k<XQ, CO, false, 0><<<grid, WG_WAVES * 64, 0, s>>>(S, nbr, nbr_ld, n, d, dd, g0);            \
+        if (idx == 1) spconv_wgrad_mfma_k<XQ, CO, false, 1><<<grid, WG_WAVES * 64, 0, s>>>(S, nbr, nbr_ld, n, d, dd, gp);   \
+        else spconv_wgrad_mfma_k<XQ, CO, false, 0><<<grid, WG_WAVES * 64, 0, s>>>(S, nbr, nbr_ld, n, d, dd, gp);            \
         return linr_launch_rc();                                                                                             \
     } while (0)
     if (cin == 8 && cout == 8) GO(2, 8);
@@ -1008,22 +1034,27 @@ int linr_conv3_wgrad_mfma(const float* in, int in_ld, const float* gout, int gou
 }
 
 // both 4->4 convolutions of an Inception block: in = H [n][8]; conv 0 reads H[:,0:4] with gradient g0, conv 1 H[:,4:8] with g1
-int linr_conv3_wgrad_dual44(const float* H, const float* g0, int g0_ld, const float* g1, int g1_ld, const int32_t* nbr,
-                            int64_t nbr_ld, int64_t n, float* big, int64_t block_stride, int64_t w_off0, int64_t b_off0,
-                            int64_t w_off1, int64_t b_off1, int nblocks, hipStream_t s, const Grp* gp, int ngroups,
-                            const int32_t* tile8t) {
+int linr_conv3_wgrad_dual44(const Dual44BwdGroup* g, int ng, int gI_ld, int gM_ld, const int32_t* nbr, int64_t nbr_ld, int64_t n,
+                            const int32_t* tile8t, float* big, int64_t block_stride, int nblocks, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
     const int idx = (nbr_ld % 4 == 0 && linr_aligned16(nbr)) ? 1 : 0;
-    const Grp grp = gp ? *gp : Grp();
-    const dim3 grid(nblocks, ngroups);
-    WgradSrc S = {H, 8, g0, g0_ld, g1, g1_ld};
-    LinrWgradDst d = {big, block_stride, w_off0, b_off0, 4};
-    WgradDual dd = {w_off1, b_off1};
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].H - g[0].H; gp.res[i] = g[i].gI - g[0].gI; gp.act[i] = g[i].gM - g[0].gM;
+        gp.w[i] = g[i].w01_off - g[0].w01_off; gp.b[i] = g[i].b01_off - g[0].b01_off;
+        gp.e0[i] = g[i].w11_off - g[0].w11_off; gp.e1[i] = g[i].b11_off - g[0].b11_off;
+    }
+    const float* H = g[0].H;
+    const dim3 grid(nblocks, ng);
+    WgradSrc S = {H, 8, g[0].gI, gI_ld, g[0].gM, gM_ld};
+    LinrWgradDst d = {big, block_stride, g[0].w01_off, g[0].b01_off, 4};
+    WgradDual dd = {g[0].w11_off, g[0].b11_off};
     if (tile8t && linr_aligned16(H) && linr_aligned16(tile8t)) {
-        spconv_wgrad_t_k<4, true><<<grid, WG_WAVES * 64, 0, s>>>(S, tile8t, n, d, dd, grp);
+        spconv_wgrad_t_k<4, true><<<grid, WG_WAVES * 64, 0, s>>>(S, tile8t, n, d, dd, gp);
         return linr_launch_rc();
     }
-    if (idx == 1) spconv_wgrad_mfma_k<2, 4, true, 1><<<grid, WG_WAVES * 64, 0, s>>>(S, nbr, nbr_ld, n, d, dd, grp);
-    else spconv_wgrad_mfma_k<2, 4, true, 0><<<grid, WG_WAVES * 64, 0, s>>>(S, nbr, nbr_ld, n, d, dd, grp);
+    if (idx == 1) spconv_wgrad_mfma_k<2, 4, true, 1><<<grid, WG_WAVES * 64, 0, s>>>(S, nbr, nbr_ld, n, d, dd, gp);
+    else spconv_wgrad_mfma_k<2, 4, true, 0><<<grid, WG_WAVES * 64, 0, s>>>(S, nbr, nbr_ld, n, d, dd, gp);
     return linr_launch_rc();
 }
 
@@ -1073,33 +1104,43 @@ static int hb_cus() {
 
 // rows_written == nullptr: slab rows 0 .. nblocks - 1 are all written (rows beyond the active blocks get zeros); otherwise only the
 // active blocks' rows are written and *rows_written tells the caller how many (its reduction must stop there)
-int linr_head_bwd_launch(const float* c, const float* p, const float* target, int target_ld, const float* w1,
-                         const float* b1, const float* w2, float gscale, float* gc, int64_t n, float* big,
-                         int64_t block_stride, int64_t off_w1, int64_t off_b1, int64_t off_w2, int64_t off_b2,
-                         hipStream_t s, const Grp* gp, int ngroups, int nblocks, int* rows_written) {
+int linr_head_bwd_launch(const HeadBwdGroup* g, int ng, int target_ld, float gscale, int64_t n, float* big, int64_t block_stride,
+                         int nblocks, int* rows_written, hipStream_t s) {
     if (rows_written) *rows_written = 0;
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
     if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    const int active = hb_blocks(n, ngroups, hb_cus(), nblocks);
-    HeadBwdArgs A = {c, p, target, target_ld, w1, b1, w2, gscale, gc, big, block_stride, off_w1, off_b1, off_w2, off_b2, active};
-    head_bwd_k<<<dim3(rows_written ? active : nblocks, ngroups), HB_WAVES * 64, 0, s>>>(A, n, g0);
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].c - g[0].c; gp.e0[i] = g[i].p - g[0].p; gp.e1[i] = g[i].target - g[0].target; gp.w[i] = g[i].w1 - g[0].w1;
+        gp.b[i] = g[i].b1 - g[0].b1; gp.e2[i] = g[i].w2 - g[0].w2; gp.out[i] = g[i].gc - g[0].gc;
+        gp.e3[i] = g[i].w1_off - g[0].w1_off; gp.e4[i] = g[i].b1_off - g[0].b1_off; gp.e5[i] = g[i].w2_off - g[0].w2_off;
+        gp.e6[i] = g[i].b2_off - g[0].b2_off;
+    }
+    const int active = hb_blocks(n, ng, hb_cus(), nblocks);
+    HeadBwdArgs A = {g[0].c, g[0].p, g[0].target, target_ld, g[0].w1, g[0].b1, g[0].w2, gscale, g[0].gc, big, block_stride,
+                     g[0].w1_off, g[0].b1_off, g[0].w2_off, g[0].b2_off, active};
+    head_bwd_k<<<dim3(rows_written ? active : nblocks, ng), HB_WAVES * 64, 0, s>>>(A, n, gp);
     if (rows_written) *rows_written = active;
     return linr_launch_rc();
 }
 
 // executor entry: all matrices are arena matrices (16-byte aligned rows, ld in {4, 8}, pad row present).  The kernel writes 4 or
 // 8 channels, so the backward-data of an outter block's first conv into 1..3 or 5..7 occupancy channels is refused (nothing needs it).
-int linr_cconv_launch(bool bwd, const float* in, int in_ld, const int32_t* lo, const uint32_t* mask, int64_t ld,
-                      int64_t n, const float* W, const float* bias, int cin, int cout, const float* res, int res_ld,
-                      const float* act, int act_ld, float* out, int out_ld, unsigned flags, hipStream_t s, const Grp* gp,
-                      int ngroups) {
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    const dim3 grid(linr_grid(n, LINR_CONV_BLOCK), ngroups);
+int linr_cconv_launch(bool bwd, LinrCmap m, const ConvGroup* g, int ng, int in_ld, int cin, int cout, int res_ld, int act_ld,
+                      int out_ld, unsigned flags, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].in - g[0].in; gp.w[i] = g[i].W - g[0].W; gp.b[i] = g[i].bias - g[0].bias; gp.res[i] = g[i].res - g[0].res;
+        gp.act[i] = g[i].act - g[0].act; gp.out[i] = g[i].out - g[0].out;
+    }
+    const dim3 grid(linr_grid(m.n, LINR_CONV_BLOCK), ng);
 #define GO(GI, GO_, B)                                                                                                  \
     do {                                                                                                                \
         cconv_mfma_k<GI, GO_, B, ((GI + 3) / 4 * 4)><<<grid, LINR_CONV_BLOCK, 0, s>>>(                                  \
-            in, in_ld, lo, mask, ld, n, W, bias, res, res_ld, act, act_ld, out, out_ld, flags, HeadArgs(), PwArgs(), g0); \
+            g[0].in, in_ld, m.lo, m.mask, m.ld, m.n, g[0].W, g[0].bias, g[0].res, res_ld, g[0].act, act_ld, g[0].out, out_ld, flags, \
+            HeadArgs(), PwArgs(), gp);                                                                                  \
         return linr_launch_rc();                                                                                        \
     } while (0)
 #define FWD(CI, CO) if (!bwd && cin == CI && cout == CO) GO(CI, CO, false);
@@ -1142,8 +1183,8 @@ extern "C" int linr_head_fwd(const float* prior, const int32_t* lo, const uint32
         if (((uintptr_t)ws) & 7u) return LINR_EALIGN;
         part = (double*)ws;
     }
-    int rc = linr_cconv_head_launch(prior, lo, mask, ld, n, Wp, bp, c_out, w1, b1, w2, b2, target, target_ld, p_out, part,
-                                    (hipStream_t)stream);
+    const HeadFwdGroup g = {prior, Wp, bp, c_out, w1, b1, w2, b2, target, p_out, part};
+    int rc = linr_cconv_head_launch({lo, mask, ld, n}, &g, 1, target_ld, (hipStream_t)stream);
     if (rc) return rc;
     if (bits_acc) return linr_bits_finish_launch(part, (int)linr_grid(n, LINR_CONV_BLOCK), bits_acc, (hipStream_t)stream);
     return 0;
@@ -1160,7 +1201,8 @@ extern "C" int linr_head_bwd(const float* c, const float* p, const float* target
     if (!linr_aligned16(c) || !linr_aligned16(gc) || !linr_aligned16(ws)) return LINR_EALIGN;
     float* slab = (float*)ws;
     // gscale multiplies BITS (like linr_bce_bits_bwd); the kernel works in nats: d bits / d nats = 1 / ln 2
-    int rc = linr_head_bwd_launch(c, p, target, target_ld, w1, b1, w2, gscale * 1.4426950408889634f, gc, n, slab, HEAD_PARAMS, 0, 192, 216, 240,
+    const HeadBwdGroup g = {c, p, target, w1, b1, w2, gc, 0, 192, 216, 240};
+    int rc = linr_head_bwd_launch(&g, 1, target_ld, gscale * 1.4426950408889634f, n, slab, HEAD_PARAMS, LINR_WG_BLOCKS, nullptr,
                                   (hipStream_t)stream);
     if (rc) return rc;
     return linr_slab_reduce_launch(slab, LINR_WG_BLOCKS, HEAD_PARAMS, ghead, (hipStream_t)stream);
@@ -1177,9 +1219,12 @@ extern "C" int linr_inception_fwd(const float* x, const int32_t* lo, const uint3
     if (!cmap_ok(x, lo, mask, ld, n) || !inc_ok(q) || !H || !M || !I) return LINR_EINVAL;
     if (!linr_aligned16(x) || !linr_aligned16(H) || !linr_aligned16(M) || !linr_aligned16(I)) return LINR_EALIGN;
     if (!linr_rows_fit32(n)) return LINR_EINVAL;
-    int rc = linr_conv_pw_fwd_launch(x, lo, mask, ld, n, q->w00, q->b00, q->w10, q->b10, H, (hipStream_t)stream);
+    const LinrCmap m = {lo, mask, ld, n};
+    const ConvPwGroup g0 = {x, q->w00, q->b00, q->w10, q->b10, H};
+    int rc = linr_conv_pw_fwd_launch(m, &g0, 1, (hipStream_t)stream);
     if (rc) return rc;
-    return linr_dual44_fwd_launch(H, lo, mask, ld, n, q->w01, q->b01, q->w11, q->b11, x, q->w12, q->b12, M, I, (hipStream_t)stream);
+    const Dual44FwdGroup g1 = {H, q->w01, q->b01, q->w11, q->b11, x, q->w12, q->b12, M, I};
+    return linr_dual44_fwd_launch(m, &g1, 1, (hipStream_t)stream);
 }
 
 extern "C" int linr_inception_bwd_data(const float* gI, const float* x, const float* H, const float* M, const int32_t* lo,
@@ -1197,9 +1242,12 @@ extern "C" int linr_inception_bwd_data(const float* gI, const float* x, const fl
     // I[:,4:8] = M @ W12 + b12 + x[:,4:8], M = relu(.)  =>  gM = (gI[:,4:8] @ W12^T) * (M > 0)
     int rc = linr_linear_launch(gI + 4, 8, n, q->w12, 1, 4, nullptr, 4, 4, nullptr, 0, M, 4, gM, 4, LINR_RELU_MASK, s);
     if (rc) return rc;
-    rc = linr_dual44_bwd_launch(gI, gM, lo, mask, ld, n, q->w01, q->w11, H, gH, s);
+    const LinrCmap m = {lo, mask, ld, n};
+    const Dual44BwdGroup g0 = {gI, gM, H, q->w01, q->w11, gH, 0, 0, 0, 0};
+    rc = linr_dual44_bwd_launch(m, &g0, 1, s);
     if (rc) return rc;
-    return linr_conv_bwd_ga_launch(gH, lo, mask, ld, n, q->w00, q->w10, gI, x, gX, flags, s);
+    const Conv84BwdGroup g1 = {gH, x, gI, q->w00, q->w10, gX, 0, 0, 0, 0};
+    return linr_conv_bwd_ga_launch(m, &g1, 1, flags, s);
 }
 
 extern "C" int linr_occ_conv7(const float* occ, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
@@ -1212,7 +1260,7 @@ extern "C" int linr_occ_conv7(const float* occ, const int32_t* lo, const uint32_
     for (int g = 0; g < 7; ++g)
         if (w_off_h[g] < 0 || b_off_h[g] < 0 || (out_off_h[g] & 3)) return LINR_EINVAL;
     if (!linr_rows_fit32(n)) return LINR_EINVAL;
-    return linr_occ_conv7_launch(occ, lo, mask, ld, n, params, w_off_h, b_off_h, out, out_off_h, (hipStream_t)stream);
+    return linr_occ_conv7_launch(occ, {lo, mask, ld, n}, params, w_off_h, b_off_h, out, out_off_h, (hipStream_t)stream);
 }
 
 extern "C" int linr_spconv_wgrad_dual44(const float* H, const float* g0, int32_t g0_ld, const float* g1, int32_t g1_ld,
@@ -1223,6 +1271,6 @@ extern "C" int linr_spconv_wgrad_dual44(const float* H, const float* g0, int32_t
     if (!linr_aligned16(H)) return LINR_EALIGN;
     if (!linr_rows_fit32(n)) return LINR_EINVAL;
     // per block: [W01 432 | b01 4 | W11 432 | b11 4]
-    return linr_conv3_wgrad_dual44(H, g0, g0_ld, g1, g1_ld, nbr, ld, n, slab, 872, 0, 432, 436, 868, LINR_WG_BLOCKS,
-                                   (hipStream_t)stream, nullptr, 1, tile8t);
+    const Dual44BwdGroup g = {g0, g1, H, nullptr, nullptr, nullptr, 0, 432, 436, 868};
+    return linr_conv3_wgrad_dual44(&g, 1, g0_ld, g1_ld, nbr, ld, n, tile8t, slab, 872, LINR_WG_BLOCKS, (hipStream_t)stream);
 }

@@ -585,66 +585,91 @@ int linr_fused_bwd_rows(int64_t n, int nb, int ngroups) {
     return blocks;
 }
 
-// g: output gradient (gathered), xin: the convolution's input, W: its kernel; out: input gradient; slab partials into d.
-// rows_written == nullptr: rows 0 .. nb - 1 of the slab are all written (the rows beyond the grid's blocks get zeros);
-// otherwise only the grid's rows are written and *rows_written tells the caller how many (its reduction must stop there).
-// pw != nullptr selects the gM epilogue, which also produces conv1_2's kernel / bias gradient (M^T gin[:, 4:8]; slab offsets
+// Conv88BwdGroup: g = output gradient (gathered), xin = the convolution's input, W = its kernel; out = input gradient; slab partials
+// at w_off / b_off.  rows_written == nullptr: rows 0 .. nb - 1 of the slab are all written (the rows beyond the grid's blocks get
+// zeros); otherwise only the grid's rows are written and *rows_written tells the caller how many (its reduction must stop there).
+// w12 != nullptr selects the gM epilogue, which also produces conv1_2's kernel / bias gradient (M^T gin[:, 4:8]; slab offsets
 // w12_off / b12_off).
-int linr_conv88_bwd_wgrad_launch(const float* g, const float* xin, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                                 const float* W, float* out, const PwArgs* pw, LinrWgradDst d, int nb, hipStream_t s,
-                                 const Grp* gp, int ngroups, int* rows_written, int64_t w12_off, int64_t b12_off) {
+int linr_conv88_bwd_wgrad_launch(LinrCmap m, const Conv88BwdGroup* g, int ng, float* big, int64_t block_stride, int nb,
+                                 int* rows_written, hipStream_t s) {
     if (rows_written) *rows_written = 0;
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    FbArgs a = {g, nullptr, xin, W, nullptr, nullptr, out, 0u, 1, rows_written ? 0 : nb};
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    const bool gm = g[0].w12 != nullptr;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].g - g[0].g; gp.res[i] = g[i].xin - g[0].xin; gp.w[i] = g[i].W - g[0].W; gp.out[i] = g[i].out - g[0].out;
+        gp.e3[i] = g[i].w_off - g[0].w_off; gp.e4[i] = g[i].b_off - g[0].b_off;
+        if ((g[i].w12 != nullptr) != gm) return LINR_EINVAL;          // the epilogue is one choice for the whole launch
+        if (!gm) continue;
+        gp.e0[i] = g[i].w12 - g[0].w12; gp.e1[i] = g[i].M - g[0].M; gp.e2[i] = g[i].gM - g[0].gM;
+        gp.e5[i] = g[i].w12_off - g[0].w12_off; gp.e6[i] = g[i].b12_off - g[0].b12_off;
+    }
+    FbArgs a = {g[0].g, nullptr, g[0].xin, g[0].W, nullptr, nullptr, g[0].out, 0u, 1, rows_written ? 0 : nb};
     int blocks = 1;
-    fb_grid(n, nb, ngroups, a.tiles_per_wave, blocks);
+    fb_grid(m.n, nb, ng, a.tiles_per_wave, blocks);
     if (rows_written) *rows_written = blocks;
-    const dim3 grid(blocks, ngroups);
+    const dim3 grid(blocks, ng);
+    const LinrWgradDst d = {big, block_stride, g[0].w_off, g[0].b_off, 8};
+    const PwArgs pw = gm ? PwArgs{g[0].w12, nullptr, g[0].M, g[0].gM} : PwArgs();
+    const FbDst2 d2 = gm ? FbDst2{g[0].w12_off, g[0].b12_off} : FbDst2{0, 0};
     if (fb_split()) {
-        if (pw) conv_bwd_wgrad_k<0, 3><<<grid, FS_THREADS, 0, s>>>(a, lo, mask, ld, n, *pw, d, FbDst2{w12_off, b12_off}, g0);
-        else conv_bwd_wgrad_k<0, 0><<<grid, FS_THREADS, 0, s>>>(a, lo, mask, ld, n, PwArgs(), d, FbDst2{0, 0}, g0);
-    } else if (pw) conv_bwd_wgrad_single_k<0, 3><<<grid, FB_WAVES * 64, 0, s>>>(a, lo, mask, ld, n, *pw, d, FbDst2{w12_off, b12_off}, g0);
-    else conv_bwd_wgrad_single_k<0, 0><<<grid, FB_WAVES * 64, 0, s>>>(a, lo, mask, ld, n, PwArgs(), d, FbDst2{0, 0}, g0);
+        if (gm) conv_bwd_wgrad_k<0, 3><<<grid, FS_THREADS, 0, s>>>(a, m.lo, m.mask, m.ld, m.n, pw, d, d2, gp);
+        else conv_bwd_wgrad_k<0, 0><<<grid, FS_THREADS, 0, s>>>(a, m.lo, m.mask, m.ld, m.n, pw, d, d2, gp);
+    } else if (gm) conv_bwd_wgrad_single_k<0, 3><<<grid, FB_WAVES * 64, 0, s>>>(a, m.lo, m.mask, m.ld, m.n, pw, d, d2, gp);
+    else conv_bwd_wgrad_single_k<0, 0><<<grid, FB_WAVES * 64, 0, s>>>(a, m.lo, m.mask, m.ld, m.n, pw, d, d2, gp);
     return linr_launch_rc();
 }
 
 // both 4->4 convolutions of an Inception layer: gH = [bwd(gI[:, 0:4]; W01) | bwd(gM; W11)] * (H > 0) and the two kernel / bias
 // gradients from one gather of [gI[:, 0:4] | gM]
-int linr_dual44_bwd_wgrad_launch(const float* gI, const float* gM, const float* H, const int32_t* lo, const uint32_t* mask,
-                                 int64_t ld, int64_t n, const float* w01, const float* w11, float* gH, float* big,
-                                 int64_t block_stride, int64_t w_off0, int64_t b_off0, int64_t w_off1, int64_t b_off1, int nb,
-                                 hipStream_t s, const Grp* gp, int ngroups, int* rows_written) {
+int linr_dual44_bwd_wgrad_launch(LinrCmap m, const Dual44BwdGroup* g, int ng, float* big, int64_t block_stride, int nb,
+                                 int* rows_written, hipStream_t s) {
     if (rows_written) *rows_written = 0;
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    FbArgs a = {gI, gM, H, w01, w11, nullptr, gH, 0u, 1, rows_written ? 0 : nb};
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].gI - g[0].gI; gp.e5[i] = g[i].gM - g[0].gM; gp.res[i] = g[i].H - g[0].H; gp.w[i] = g[i].w01 - g[0].w01;
+        gp.e6[i] = g[i].w11 - g[0].w11; gp.out[i] = g[i].gH - g[0].gH;
+        gp.e3[i] = g[i].w01_off - g[0].w01_off; gp.e4[i] = g[i].b01_off - g[0].b01_off;
+        gp.e0[i] = g[i].w11_off - g[0].w11_off; gp.e1[i] = g[i].b11_off - g[0].b11_off;
+    }
+    FbArgs a = {g[0].gI, g[0].gM, g[0].H, g[0].w01, g[0].w11, nullptr, g[0].gH, 0u, 1, rows_written ? 0 : nb};
     int blocks = 1;
-    fb_grid(n, nb, ngroups, a.tiles_per_wave, blocks);
+    fb_grid(m.n, nb, ng, a.tiles_per_wave, blocks);
     if (rows_written) *rows_written = blocks;
-    LinrWgradDst d = {big, block_stride, w_off0, b_off0, 4};
-    if (fb_split()) conv_bwd_wgrad_k<1, 0><<<dim3(blocks, ngroups), FS_THREADS, 0, s>>>(a, lo, mask, ld, n, PwArgs(), d, FbDst2{w_off1, b_off1}, g0);
-    else conv_bwd_wgrad_single_k<1, 0><<<dim3(blocks, ngroups), FB_WAVES * 64, 0, s>>>(a, lo, mask, ld, n, PwArgs(), d, FbDst2{w_off1, b_off1}, g0);
+    const LinrWgradDst d = {big, block_stride, g[0].w01_off, g[0].b01_off, 4};
+    const FbDst2 d2 = {g[0].w11_off, g[0].b11_off};
+    if (fb_split()) conv_bwd_wgrad_k<1, 0><<<dim3(blocks, ng), FS_THREADS, 0, s>>>(a, m.lo, m.mask, m.ld, m.n, PwArgs(), d, d2, gp);
+    else conv_bwd_wgrad_single_k<1, 0><<<dim3(blocks, ng), FB_WAVES * 64, 0, s>>>(a, m.lo, m.mask, m.ld, m.n, PwArgs(), d, d2, gp);
     return linr_launch_rc();
 }
 
 // conv0_0 (8->4) of an Inception layer: gA = (bwd(gH[:, 0:4]; W00) + gI (+ old gA: LINR_ACCUM) + gH[:, 4:8] @ W10^T) (* (A > 0):
 // LINR_RELU_MASK) and the kernel / bias gradient of conv0_0 from one gather of gH[:, 0:4]; the kernel / bias gradient of the 1x1
 // conv1_0 (A^T gH[:, 4:8]) comes out of the same launch (slab offsets w10_off / b10_off)
-int linr_conv84_bwd_wgrad_launch(const float* gH, const float* A, const float* gI, const int32_t* lo, const uint32_t* mask,
-                                 int64_t ld, int64_t n, const float* w00, const float* w10, float* gA, unsigned flags,
-                                 LinrWgradDst d, int64_t w10_off, int64_t b10_off, int nb, hipStream_t s, const Grp* gp, int ngroups,
-                                 int* rows_written) {
+int linr_conv84_bwd_wgrad_launch(LinrCmap m, const Conv84BwdGroup* g, int ng, unsigned flags, float* big, int64_t block_stride,
+                                 int nb, int* rows_written, hipStream_t s) {
     if (rows_written) *rows_written = 0;
-    if (n == 0) return 0;
-    const Grp g0 = gp ? *gp : Grp();
-    FbArgs a = {gH, nullptr, A, w00, nullptr, gI, gA, flags & (LINR_RELU_MASK | LINR_ACCUM), 1, rows_written ? 0 : nb};
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
+    if (m.n == 0) return 0;
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].gH - g[0].gH; gp.res[i] = g[i].A - g[0].A; gp.w[i] = g[i].w00 - g[0].w00; gp.act[i] = g[i].gI - g[0].gI;
+        gp.out[i] = g[i].gA - g[0].gA; gp.e0[i] = g[i].w10 - g[0].w10;
+        gp.e3[i] = g[i].w00_off - g[0].w00_off; gp.e4[i] = g[i].b00_off - g[0].b00_off;
+        gp.e1[i] = g[i].w10_off - g[0].w10_off; gp.e2[i] = g[i].b10_off - g[0].b10_off;
+    }
+    FbArgs a = {g[0].gH, nullptr, g[0].A, g[0].w00, nullptr, g[0].gI, g[0].gA, flags & (LINR_RELU_MASK | LINR_ACCUM), 1, rows_written ? 0 : nb};
     int blocks = 1;
-    fb_grid(n, nb, ngroups, a.tiles_per_wave, blocks);
+    fb_grid(m.n, nb, ng, a.tiles_per_wave, blocks);
     if (rows_written) *rows_written = blocks;
-    PwArgs pw = {w10, nullptr, nullptr, nullptr};
-    if (fb_split()) conv_bwd_wgrad_k<2, 0><<<dim3(blocks, ngroups), FS_THREADS, 0, s>>>(a, lo, mask, ld, n, pw, d, FbDst2{w10_off, b10_off}, g0);
-    else conv_bwd_wgrad_single_k<2, 0><<<dim3(blocks, ngroups), FB_WAVES * 64, 0, s>>>(a, lo, mask, ld, n, pw, d, FbDst2{w10_off, b10_off}, g0);
+    const LinrWgradDst d = {big, block_stride, g[0].w00_off, g[0].b00_off, 8};
+    const FbDst2 d2 = {g[0].w10_off, g[0].b10_off};
+    PwArgs pw = {g[0].w10, nullptr, nullptr, nullptr};
+    if (fb_split()) conv_bwd_wgrad_k<2, 0><<<dim3(blocks, ng), FS_THREADS, 0, s>>>(a, m.lo, m.mask, m.ld, m.n, pw, d, d2, gp);
+    else conv_bwd_wgrad_single_k<2, 0><<<dim3(blocks, ng), FB_WAVES * 64, 0, s>>>(a, m.lo, m.mask, m.ld, m.n, pw, d, d2, gp);
     return linr_launch_rc();
 }
 
@@ -655,8 +680,8 @@ extern "C" int linr_spconv_bwd_fused(const float* gout, const float* in, const i
     if (!gout || !in || !lo || !mask || !W || !gin || !slab) return LINR_EINVAL;
     if (!linr_aligned16(gout) || !linr_aligned16(gin)) return LINR_EALIGN;
     if (!linr_rows_fit32(n) || !linr_cmap_fits32(ld)) return LINR_EINVAL;
-    LinrWgradDst d = {slab, 1736, 0, 1728, 8};
-    return linr_conv88_bwd_wgrad_launch(gout, in, lo, mask, ld, n, W, gin, nullptr, d, nblocks, (hipStream_t)stream, nullptr, 1, nullptr);
+    const Conv88BwdGroup g = {gout, in, W, gin, 0, 1728, nullptr, nullptr, nullptr, 0, 0};
+    return linr_conv88_bwd_wgrad_launch({lo, mask, ld, n}, &g, 1, slab, 1736, nblocks, nullptr, (hipStream_t)stream);
 }
 
 // The Inception layer's backward with its two conv pairs fused (what the executor launches): gM by the caller (tail conv
@@ -673,9 +698,10 @@ extern "C" int linr_inception_bwd_fused(const float* gI, const float* gM, const 
         !linr_aligned16(x)) return LINR_EALIGN;
     if (!linr_rows_fit32(n) || !linr_cmap_fits32(ld)) return LINR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    int rc = linr_dual44_bwd_wgrad_launch(gI, gM, H, lo, mask, ld, n, q->w01, q->w11, gH, slab, 1776, 868, 1300, 1304, 1736, nblocks, s,
-                                          nullptr, 1, nullptr);
+    const LinrCmap m = {lo, mask, ld, n};
+    const Dual44BwdGroup g0 = {gI, gM, H, q->w01, q->w11, gH, 868, 1300, 1304, 1736};
+    int rc = linr_dual44_bwd_wgrad_launch(m, &g0, 1, slab, 1776, nblocks, nullptr, s);
     if (rc) return rc;
-    LinrWgradDst d = {slab, 1776, 0, 864, 8};
-    return linr_conv84_bwd_wgrad_launch(gH, x, gI, lo, mask, ld, n, q->w00, q->w10, gX, flags, d, 1740, 1772, nblocks, s, nullptr, 1, nullptr);
+    const Conv84BwdGroup g1 = {gH, x, gI, q->w00, q->w10, gX, 0, 864, 1740, 1772};
+    return linr_conv84_bwd_wgrad_launch(m, &g1, 1, flags, slab, 1776, nblocks, nullptr, s);
 }

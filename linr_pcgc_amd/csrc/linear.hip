@@ -202,12 +202,17 @@ __global__ __launch_bounds__(XTG_WAVES * 64) void xtg_wgrad_k(const float* __res
     }
 }
 
-int linr_linear_wgrad_partial(const float* in, int in_ld, const float* gout, int gout_ld, int64_t n, int cin, int cout,
-                              LinrLinDst d, int nblocks, hipStream_t s, const Grp* gp, int ngroups) {
+int linr_linear_wgrad_partial(const WgradGroup* g, int ng, int in_ld, int gout_ld, int64_t n, int cin, int cout, float* big,
+                              int64_t block_stride, int ws_ci, int ws_co, int nblocks, hipStream_t s) {
+    if (ng < 1 || ng > LINR_MAXG) return LINR_EINVAL;
     const int mt = (cin + 1 + 15) / 16, nt = (cout + 15) / 16;
-    const Grp g0 = gp ? *gp : Grp();
-    const dim3 grid(nblocks, ngroups);
-#define LINR_GO(A, B) do { xtg_wgrad_k<A, B><<<grid, XTG_WAVES * 64, 0, s>>>(in, in_ld, cin, gout, gout_ld, cout, n, d, g0); return linr_launch_rc(); } while (0)
+    Grp gp = Grp();
+    for (int i = 0; i < ng; ++i) {
+        gp.in[i] = g[i].in - g[0].in; gp.res[i] = g[i].gout - g[0].gout; gp.w[i] = g[i].w_off - g[0].w_off; gp.b[i] = g[i].b_off - g[0].b_off;
+    }
+    const LinrLinDst d = {big, block_stride, g[0].w_off, ws_ci, ws_co, g[0].b_off};
+    const dim3 grid(nblocks, ng);
+#define LINR_GO(A, B) do { xtg_wgrad_k<A, B><<<grid, XTG_WAVES * 64, 0, s>>>(g[0].in, in_ld, cin, g[0].gout, gout_ld, cout, n, d, gp); return linr_launch_rc(); } while (0)
     if (mt == 1 && nt == 1) LINR_GO(1, 1);
     if (mt == 2 && nt == 1) LINR_GO(2, 1);
     if (mt == 1 && nt == 2) LINR_GO(1, 2);
@@ -279,8 +284,8 @@ extern "C" int linr_linear_bwd_weight(const float* in, int32_t in_ld, const floa
     hipStream_t s = (hipStream_t)stream;
     const int nb = lin_blocks(n);
     // dense [cin+1][cout] partial per block (bias = row cin); the reduce pass scatters to the caller's strides
-    LinrLinDst d = {(float*)ws, (int64_t)(cin + 1) * cout, 0, cout, 1, (int64_t)cin * cout};
-    int rc = linr_linear_wgrad_partial(in, in_ld, gout, gout_ld, n, cin, cout, d, nb, s);
+    const WgradGroup g = {in, gout, 0, (int64_t)cin * cout, 0};
+    int rc = linr_linear_wgrad_partial(&g, 1, in_ld, gout_ld, n, cin, cout, (float*)ws, (int64_t)(cin + 1) * cout, cout, 1, nb, s);
     if (rc) return rc;
     return linr_linear_slab_reduce_launch((const float*)ws, nb, (int64_t)(cin + 1) * cout, cin, cout, gW, ws_ci, ws_co, gb, flags, s);
 }

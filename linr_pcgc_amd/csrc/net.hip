@@ -437,15 +437,12 @@ struct Ctx {
     int64_t R;
     int64_t nbr_ld;
     int nb;                  // persistent blocks of the weight-gradient kernels = partial rows of the slab for this frame
-    struct Short { int64_t b, e; int rows; };
-    std::vector<Short> shortr;      // parameter ranges of this backward pass that hold fewer than nb slab rows (fused launches)
+    std::vector<LinrShortRange> shortr;      // parameter ranges of this backward pass that hold fewer than nb slab rows (fused launches)
     // a fused launch writes only `rows` slab rows for parameters [b, e) (no zero fill): the final reduction stops there.  The
     // table holds every range of a backward pass: 8 blocks x 2 + the prune convs + block_in's first conv + the 7 outter first
     // convs + up to 16 scale-context MLPs = 41
     void note_short(int64_t b, int64_t e, int rows) {
-        if (rows >= nb) return;
-        if ((int)shortr.size() >= MAX_SHORT) abort();          // cannot happen (see above); a silent drop would read unwritten rows
-        shortr.push_back({b, e, rows});
+        if (rows < nb) shortr.push_back({b, e, rows});          // (short_push aborts if the kernel's table of MAX_SHORT overflows)
     }
 };
 
@@ -470,7 +467,7 @@ int linr_wg_blocks_for(int64_t rows) { return wg_blocks_for(rows); }
 #define LINR_PROF_MAX 4096
 enum { PK_FUSED88 = 0, PK_CONV88 = 1, PK_FUSED_DUAL = 2, PK_FUSED_C00 = 3, PK_HEAD_FWD = 4, PK_CONVPW_FWD = 5, PK_DUAL_FWD = 6,
        PK_OCC7 = 7, PK_HEAD_BWD = 8, PK_WGRAD = 9, PK_LIN_WGRAD = 10, PK_SCE = 11, PK_MISC = 12, PK_BWD_DATA = 13 };
-struct ProfRec { hipEvent_t e0, e1; int passes; };
+struct ProfRec { hipEvent_t ev0, ev1; int passes; };
 static std::atomic<bool> g_prof_on{false};
 static std::atomic<uint32_t> g_prof_mask{3u};
 static std::mutex g_prof_mu;                    // guards the vectors below
@@ -530,12 +527,12 @@ struct ProfScope {
         r = g_prof_free.back();
         g_prof_free.pop_back();
         r.passes = passes;
-        live = hipEventRecord(r.e0, s) == hipSuccess;
+        live = hipEventRecord(r.ev0, s) == hipSuccess;
         if (!live) g_prof_free.push_back(r);
     }
     ~ProfScope() {
         if (!live) return;
-        (void)hipEventRecord(r.e1, s);
+        (void)hipEventRecord(r.ev1, s);
         std::lock_guard<std::mutex> lk(g_prof_mu);
         g_prof[kind].push_back(r);
     }
@@ -561,8 +558,8 @@ extern "C" int linr_prof_enable(int32_t mode) {          // 0: stop (records kep
     while (g_prof_free.size() + used < LINR_PROF_MAX) {
         ProfRec r;
         r.passes = 0;
-        if (hipEventCreate(&r.e0) != hipSuccess) break;
-        if (hipEventCreate(&r.e1) != hipSuccess) { (void)hipEventDestroy(r.e0); break; }
+        if (hipEventCreate(&r.ev0) != hipSuccess) break;
+        if (hipEventCreate(&r.ev1) != hipSuccess) { (void)hipEventDestroy(r.ev0); break; }
         g_prof_free.push_back(r);
     }
     g_prof_on = true;
@@ -575,9 +572,9 @@ extern "C" int linr_prof_read(int32_t kind, double* total_ms, int64_t* launches,
     double t = 0.0;
     int64_t np = 0;
     for (auto& r : g_prof[kind]) {
-        TRY(linr_hip_rc(hipEventSynchronize(r.e1)));
+        TRY(linr_hip_rc(hipEventSynchronize(r.ev1)));
         float ms = 0.0f;
-        TRY(linr_hip_rc(hipEventElapsedTime(&ms, r.e0, r.e1)));
+        TRY(linr_hip_rc(hipEventElapsedTime(&ms, r.ev0, r.ev1)));
         t += ms;
         np += r.passes;
     }
@@ -587,8 +584,7 @@ extern "C" int linr_prof_read(int32_t kind, double* total_ms, int64_t* launches,
 
 // index source of the conv kernels: the compressed map (the full neighbour table is 5 % slower also after the shift
 // addressing of round 2: 2.565 vs 2.438 ms/step, profiles/r02_ab_conv_table.txt)
-static const int32_t* clo(const Ctx& c) { return c.f->nbr_lo; }
-static const uint32_t* cmk(const Ctx& c) { return c.f->nbr_mask; }
+static LinrCmap cmap(const Ctx& c) { return {c.f->nbr_lo, c.f->nbr_mask, c.nbr_ld, c.R}; }
 
 // block_in joins the grouped launches of the outter blocks when it has their shape (one Inception layer)
 static bool join_block_in(const Ctx& c) { return c.L.block_in.nl == 1; }
@@ -604,17 +600,17 @@ static bool fused_bwd(const Ctx& c) {
 static int conv3(Ctx& c, bool bwd, const float* in, int in_ld, const float* W, const float* bias, int cin, int cout,
                  const float* res, int res_ld, const float* act, int act_ld, float* out, int out_ld, unsigned flags) {
     ProfScope ps(c.s, bwd ? PK_BWD_DATA : PK_CONV88, 1);
-    return linr_cconv_launch(bwd, in, in_ld, clo(c), cmk(c), c.nbr_ld, c.R, W, bias, cin, cout, res, res_ld,
-                             act, act_ld, out, out_ld, flags, c.s);
+    const ConvGroup g = {in, W, bias, res, act, out};
+    return linr_cconv_launch(bwd, cmap(c), &g, 1, in_ld, cin, cout, res_ld, act_ld, out_ld, flags, c.s);
 }
 
 // transposed tiled table of the stand-alone weight-gradient kernels (csrc/fused.hip: spconv_wgrad_t_k), or NULL: indices from nbr
 static const int32_t* wg_t8t(const Ctx& c) { return c.f->nbr8t; }
 static int conv3_wgrad(Ctx& c, const float* in, int in_ld, const float* gout, int gout_ld, int cin, int cout,
                        int64_t w_off, int64_t b_off) {
-    LinrWgradDst d = {c.A.BIG, c.L.total, w_off, b_off, cin};
     ProfScope ps(c.s, PK_WGRAD, 1);
-    return linr_conv3_wgrad_mfma(in, in_ld, gout, gout_ld, c.f->nbr, c.nbr_ld, c.R, cin, cout, d, c.nb, c.s, nullptr, 1, wg_t8t(c));
+    const WgradGroup g = {in, gout, w_off, b_off, 0};
+    return linr_conv3_wgrad_mfma(&g, 1, in_ld, gout_ld, c.f->nbr, c.nbr_ld, c.R, wg_t8t(c), cin, cout, c.A.BIG, c.L.total, c.nb, c.s);
 }
 
 static int linear(Ctx& c, const float* in, int in_ld, int64_t n, const float* W, int ws_ci, int ws_co, const float* bias,
@@ -626,9 +622,9 @@ static int linear(Ctx& c, const float* in, int in_ld, int64_t n, const float* W,
 
 static int linear_wgrad(Ctx& c, const float* in, int in_ld, const float* gout, int gout_ld, int64_t n, int cin, int cout,
                         int64_t w_off, int ws_ci, int ws_co, int64_t b_off) {
-    LinrLinDst d = {c.A.BIG, c.L.total, w_off, ws_ci, ws_co, b_off};
     ProfScope ps(c.s, PK_LIN_WGRAD, 1);
-    return linr_linear_wgrad_partial(in, in_ld, gout, gout_ld, n, cin, cout, d, c.nb, c.s);
+    const WgradGroup g = {in, gout, w_off, b_off, 0};
+    return linr_linear_wgrad_partial(&g, 1, in_ld, gout_ld, n, cin, cout, c.A.BIG, c.L.total, ws_ci, ws_co, c.nb, c.s);
 }
 
 // Per-layer matrices of block slot b (0 = block_in, 1..7 = outter blocks): layer 0 uses the slot's own H/M/I, the extra
@@ -638,6 +634,36 @@ static LayerBufs layer_bufs(Arena& a, int b, int l) {
     if (l == 0) return {a.H[b], a.M[b], a.I[b], a.gI[b], a.gM[b], a.gH[b]};
     return {a.Hx[l - 1], a.Mx[l - 1], a.Ix[l - 1], a.gIx[l - 1], a.gMx[l - 1], a.gHx[l - 1]};
 }
+
+// Block of slot b, and the launchers' per-group operands (common.h) of its pieces: Inception layer q with input X and matrices t;
+// the block's tail conv with output gradient gO behind that layer; head k.  The grouped launches fill one array element per slot
+// with these, the staged / per-block paths launch a single one.
+static const BlockP& slot_block(const Layout& L, int b) { return b == 0 ? L.block_in : L.outter[b - 1]; }
+static ConvPwGroup pw_fwd_group(const float* P, const IncP& q, const float* X, const LayerBufs& t) {
+    return {X, P + q.c00_w, P + q.c00_b, P + q.c10_w, P + q.c10_b, t.H};
+}
+static Dual44FwdGroup dual_fwd_group(const float* P, const IncP& q, const float* X, const LayerBufs& t) {
+    return {t.H, P + q.c01_w, P + q.c01_b, P + q.c11_w, P + q.c11_b, X, P + q.c12_w, P + q.c12_b, t.M, t.I};
+}
+static Conv88BwdGroup tail_bwd_group(const float* P, const BlockP& bp, const IncP& q, const float* gO, const LayerBufs& t) {
+    return {gO, t.I, P + bp.b_w, t.gI, bp.b_w, bp.b_b, P + q.c12_w, t.M, t.gM, q.c12_w, q.c12_b};
+}
+static Dual44BwdGroup dual_bwd_group(const float* P, const IncP& q, const LayerBufs& t) {
+    return {t.gI, t.gM, t.H, P + q.c01_w, P + q.c11_w, t.gH, q.c01_w, q.c01_b, q.c11_w, q.c11_b};
+}
+static Conv84BwdGroup c00_bwd_group(const float* P, const IncP& q, const float* A, const LayerBufs& t, float* gA) {
+    return {t.gH, A, t.gI, P + q.c00_w, P + q.c10_w, gA, q.c00_w, q.c00_b, q.c10_w, q.c10_b};
+}
+static HeadFwdGroup head_fwd_group(Ctx& c, int k, bool bits) {          // bits: BCE partials into the arena slab, linr_grid(R, 256) per head
+    const Arena& a = c.A;
+    const Layout& L = c.L;
+    double* part = bits ? (double*)a.slab + (int64_t)k * linr_grid(c.R, LINR_BLOCK) : nullptr;
+    return {a.O[k], c.P + L.pr_w[k], c.P + L.pr_b[k], a.C[k], c.P + L.h0_w[k], c.P + L.h0_b[k], c.P + L.h2_w[k], c.P + L.h2_b[k],
+            a.OCC + k, a.P[k], part};
+}
+// the two-kernel schedule reads the same operands through the stand-alone launchers
+static WgradGroup wgrad_of(const Conv88BwdGroup& g) { return {g.xin, g.g, g.w_off, g.b_off, 0}; }
+static ConvGroup bwd_data_of(const Conv88BwdGroup& g) { return {g.g, g.W, nullptr, nullptr, nullptr, g.out}; }
 
 // make_block (models/upsample.py:88-97): conv3(cin->8)+ReLU -> ResNetBlock(nl x Inception, extra skip if nl > 1) ->
 // conv3(8->8) (+ res)
@@ -651,10 +677,10 @@ static int block_fwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
         const LayerBufs t = layer_bufs(a, b, l);
         // Inception layer in two launches (csrc/fused.hip): [conv0_0 | conv1_0 centre tap] -> H, then the two 4->4 convs
         // as one pass with conv1_2 and the residual in the epilogue -> M, I
-        TRY(linr_conv_pw_fwd_launch(X, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c00_w, P + q.c00_b, P + q.c10_w,
-                                    P + q.c10_b, t.H, c.s));
-        TRY(linr_dual44_fwd_launch(t.H, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c01_w, P + q.c01_b, P + q.c11_w,
-                                   P + q.c11_b, X, P + q.c12_w, P + q.c12_b, t.M, t.I, c.s));
+        const ConvPwGroup g0 = pw_fwd_group(P, q, X, t);
+        TRY(linr_conv_pw_fwd_launch(cmap(c), &g0, 1, c.s));
+        const Dual44FwdGroup g1 = dual_fwd_group(P, q, X, t);
+        TRY(linr_dual44_fwd_launch(cmap(c), &g1, 1, c.s));
         X = t.I;
     }
     float* Il = layer_bufs(a, b, bp.nl - 1).I;
@@ -679,15 +705,16 @@ static int block_bwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
         float* gX = l == 0 ? a.gA[b] : layer_bufs(a, b, l - 1).gI;           // where its input gradient goes
         // gI of this layer: from the block's tail conv (last layer) or written by layer l+1 as its input gradient
         // I[:,4:8] = M @ c12 + b12 + X[:,4:8]  =>  gM = (gI[:,4:8] @ W12^T) * (M > 0)
-        if (l == nl - 1)   // gI = bwd(gO; Wb) with gM in the epilogue (csrc/fused.hip)
-            TRY(linr_conv_bwd_gm_launch(gO, clo(c), cmk(c), c.nbr_ld, c.R, P + bp.b_w, P + q.c12_w, t.M, t.gI, t.gM, c.s));
-        else
+        if (l == nl - 1) {   // gI = bwd(gO; Wb) with gM in the epilogue (csrc/fused.hip)
+            const Conv88BwdGroup g = tail_bwd_group(P, bp, q, gO, t);
+            TRY(linr_conv_bwd_gm_launch(cmap(c), &g, 1, c.s));
+        } else
             TRY(linear(c, t.gI + 4, 8, c.R, P + q.c12_w, 1, 4, nullptr, 4, 4, nullptr, 0, t.M, 4, t.gM, 4, LINR_RELU_MASK));
         TRY(linear_wgrad(c, t.M, 4, t.gI + 4, 8, c.R, 4, 4, q.c12_w, 4, 1, q.c12_b));
         // I[:,0:4] = conv3(H0; c01) + X[:,0:4], M = relu(conv3(H1; c11))
-        TRY(linr_conv3_wgrad_dual44(t.H, t.gI, 8, t.gM, 4, c.f->nbr, c.nbr_ld, c.R, a.BIG, c.L.total, q.c01_w, q.c01_b,
-                                    q.c11_w, q.c11_b, c.nb, c.s, nullptr, 1, wg_t8t(c)));
-        TRY(linr_dual44_bwd_launch(t.gI, t.gM, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c01_w, P + q.c11_w, t.H, t.gH, c.s));
+        const Dual44BwdGroup gd = dual_bwd_group(P, q, t);
+        TRY(linr_conv3_wgrad_dual44(&gd, 1, 8, 4, c.f->nbr, c.nbr_ld, c.R, wg_t8t(c), a.BIG, c.L.total, c.nb, c.s));
+        TRY(linr_dual44_bwd_launch(cmap(c), &gd, 1, c.s));
         // H0 = relu(conv3(X; c00)), H1 = relu(X @ c10)
         TRY(conv3_wgrad(c, X, 8, t.gH, 8, 8, 4, q.c00_w, q.c00_b));
         TRY(linear_wgrad(c, X, 8, t.gH + 4, 8, c.R, 8, 4, q.c10_w, 4, 1, q.c10_b));
@@ -696,8 +723,8 @@ static int block_bwd(Ctx& c, const BlockP& bp, const float* in, int in_ld, int b
         const bool skip = (l == 0 && nl > 1);
         if (skip)
             TRY(linr_hip_rc(hipMemcpyAsync(gX, last.gI, (size_t)c.R * 8 * sizeof(float), hipMemcpyDeviceToDevice, c.s)));
-        TRY(linr_conv_bwd_ga_launch(t.gH, clo(c), cmk(c), c.nbr_ld, c.R, P + q.c00_w, P + q.c10_w, t.gI, l == 0 ? a.A[b] : nullptr,
-                                    gX, (l == 0 ? LINR_RELU_MASK : 0u) | (skip ? LINR_ACCUM : 0u), c.s));
+        const Conv84BwdGroup ga = c00_bwd_group(P, q, l == 0 ? a.A[b] : nullptr, t, gX);
+        TRY(linr_conv_bwd_ga_launch(cmap(c), &ga, 1, (l == 0 ? LINR_RELU_MASK : 0u) | (skip ? LINR_ACCUM : 0u), c.s));
     }
     // A = relu(conv3(in; a))
     TRY(conv3_wgrad(c, in, in_ld, a.gA[b], 8, bp.cin, 8, bp.a_w, bp.a_b));
@@ -725,10 +752,6 @@ static int check_frame(const linr_frame* f, const void* params, const void* aren
     return 0;
 }
 
-static void goffs(int64_t* dst, const float* const* ptrs, int n) {
-    for (int i = 0; i < n; ++i) dst[i] = ptrs[i] - ptrs[0];
-}
-
 // Teacher-forced forward of all 8 stages with the 7 outter blocks and the 8 heads as grouped launches (their inputs -
 // the ground-truth occupancy and x_glob - are all known up front).  Same kernels and per-row arithmetic as the staged
 // path below, so the decoder reproduces these probabilities bit for bit.
@@ -736,68 +759,45 @@ static int forward_batched(Ctx& c, float* probs, double* bits_acc) {
     Arena& a = c.A;
     const float* P = c.P;
     const Layout& L = c.L;
-    const int32_t* lo = clo(c);
-    const uint32_t* mk = cmk(c);
+    const LinrCmap m = cmap(c);
     const int64_t nblk = linr_grid(c.R, LINR_BLOCK);
     // join: block_in (arena slot 0; its first conv has already run) rides as group 0 of the Inception-layer launches - the
     // eight blocks have the same structure behind their first conv (models/upsample.py:88-97) and do not depend on each
     // other until prior_k = x_glob + outter_k.  g0 = first slot in the grouped launches, ng = their group count; the
-    // occupancy conv and the tail conv (which needs x_glob as residual) always cover slots 1..7 = arrays + o7.
+    // occupancy conv and the tail conv (which needs x_glob as residual) always cover slots 1..7.
     const bool join = join_block_in(c);
-    const int g0 = join ? 0 : 1, ng = 8 - g0, o7 = 1 - g0;
-    const float *pA[8], *pH[8], *pM[8], *pI[8], *pO[8], *p_ab[8], *p_c00w[8], *p_c00b[8], *p_c10w[8], *p_c10b[8], *p_c01w[8],
-        *p_c01b[8], *p_c11w[8], *p_c11b[8], *p_c12w[8], *p_c12b[8], *p_bw[8], *p_bb[8];
-    for (int g = 0; g < ng; ++g) {
-        const int b = g0 + g;
-        const BlockP& bp = b == 0 ? L.block_in : L.outter[b - 1];
-        pA[g] = a.A[b]; pH[g] = a.H[b]; pM[g] = a.M[b]; pI[g] = a.I[b]; pO[g] = a.O[b];
-        p_ab[g] = P + bp.a_b; p_c00w[g] = P + bp.inc[0].c00_w; p_c00b[g] = P + bp.inc[0].c00_b; p_c10w[g] = P + bp.inc[0].c10_w; p_c10b[g] = P + bp.inc[0].c10_b;
-        p_c01w[g] = P + bp.inc[0].c01_w; p_c01b[g] = P + bp.inc[0].c01_b; p_c11w[g] = P + bp.inc[0].c11_w; p_c11b[g] = P + bp.inc[0].c11_b;
-        p_c12w[g] = P + bp.inc[0].c12_w; p_c12b[g] = P + bp.inc[0].c12_b; p_bw[g] = P + bp.b_w; p_bb[g] = P + bp.b_b;
-    }
+    const int g0 = join ? 0 : 1, ng = 8 - g0;
     {   // first conv of every outter block: A[b] = relu(conv3(occ[:, :b]; a) + a_b), one shared gather (csrc/fused.hip)
         int64_t w_off[7], b_off[7], o_off[7];
         for (int g = 0; g < 7; ++g) { w_off[g] = L.outter[g].a_w; b_off[g] = L.outter[g].a_b; o_off[g] = a.A[g + 1] - a.A[1]; }
         ProfScope ps(c.s, PK_OCC7, 7);
-        TRY(linr_occ_conv7_launch(a.OCC, lo, mk, c.nbr_ld, c.R, P, w_off, b_off, a.A[1], o_off, c.s));
+        TRY(linr_occ_conv7_launch(a.OCC, m, P, w_off, b_off, a.A[1], o_off, c.s));
     }
     {   // H = [relu(conv0_0(A)) | relu(conv1_0(A))]
-        Grp gp = Grp();
-        goffs(gp.in, pA, ng); goffs(gp.w, p_c00w, ng); goffs(gp.b, p_c00b, ng); goffs(gp.out, pH, ng);
-        goffs(gp.e0, p_c10w, ng); goffs(gp.e1, p_c10b, ng);
+        ConvPwGroup g[8];
+        for (int i = 0; i < ng; ++i) g[i] = pw_fwd_group(P, slot_block(L, g0 + i).inc[0], a.A[g0 + i], layer_bufs(a, g0 + i, 0));
         ProfScope ps(c.s, PK_CONVPW_FWD, ng);
-        TRY(linr_conv_pw_fwd_launch(pA[0], lo, mk, c.nbr_ld, c.R, p_c00w[0], p_c00b[0], p_c10w[0], p_c10b[0], a.H[g0], c.s, &gp, ng));
+        TRY(linr_conv_pw_fwd_launch(m, g, ng, c.s));
     }
     {   // both 4->4 convs + conv1_2 + residual -> M, I
-        Grp gp = Grp();
-        goffs(gp.in, pH, ng); goffs(gp.w, p_c01w, ng); goffs(gp.b, p_c01b, ng); goffs(gp.e1, p_c11w, ng); goffs(gp.e2, p_c11b, ng);
-        goffs(gp.res, pA, ng); goffs(gp.e3, p_c12w, ng); goffs(gp.e4, p_c12b, ng); goffs(gp.e5, pM, ng); goffs(gp.out, pI, ng);
+        Dual44FwdGroup g[8];
+        for (int i = 0; i < ng; ++i) g[i] = dual_fwd_group(P, slot_block(L, g0 + i).inc[0], a.A[g0 + i], layer_bufs(a, g0 + i, 0));
         ProfScope ps(c.s, PK_DUAL_FWD, ng);
-        TRY(linr_dual44_fwd_launch(pH[0], lo, mk, c.nbr_ld, c.R, p_c01w[0], p_c01b[0], p_c11w[0], p_c11b[0], pA[0], p_c12w[0],
-                                   p_c12b[0], a.M[g0], a.I[g0], c.s, &gp, ng));
+        TRY(linr_dual44_fwd_launch(m, g, ng, c.s));
     }
     if (join)   // x_glob = O[0] = conv3(I[0]; b) of block_in: the one tail conv the others wait for
         TRY(conv3(c, false, a.I[0], 8, P + L.block_in.b_w, P + L.block_in.b_b, 8, 8, nullptr, 0, nullptr, 0, a.O[0], 8, 0));
     {   // O[b] = conv3(I; b) + x_glob
-        Grp gp = Grp();
-        goffs(gp.in, pI + o7, 7); goffs(gp.w, p_bw + o7, 7); goffs(gp.b, p_bb + o7, 7); goffs(gp.out, pO + o7, 7);
+        ConvGroup g[7];
+        for (int b = 1; b < 8; ++b) g[b - 1] = {a.I[b], P + L.outter[b - 1].b_w, P + L.outter[b - 1].b_b, a.O[0], nullptr, a.O[b]};
         ProfScope ps(c.s, PK_CONV88, 7);
-        TRY(linr_cconv_launch(false, pI[o7], 8, lo, mk, c.nbr_ld, c.R, p_bw[o7], p_bb[o7], 8, 8, a.O[0], 8, nullptr, 0, a.O[1], 8, 0,
-                              c.s, &gp, 7));
+        TRY(linr_cconv_launch(false, m, g, 7, 8, 8, 8, 8, 0, 8, 0, c.s));
     }
     {   // the 8 occupancy heads
-        const float *hO[8], *hC[8], *hP[8], *h_prw[8], *h_prb[8], *h_w1[8], *h_b1[8], *h_w2[8], *h_b2[8];
-        for (int k = 0; k < 8; ++k) {
-            hO[k] = a.O[k]; hC[k] = a.C[k]; hP[k] = a.P[k]; h_prw[k] = P + L.pr_w[k]; h_prb[k] = P + L.pr_b[k];
-            h_w1[k] = P + L.h0_w[k]; h_b1[k] = P + L.h0_b[k]; h_w2[k] = P + L.h2_w[k]; h_b2[k] = P + L.h2_b[k];
-        }
-        Grp gp = Grp();
-        goffs(gp.in, hO, 8); goffs(gp.w, h_prw, 8); goffs(gp.b, h_prb, 8); goffs(gp.out, hC, 8);
-        goffs(gp.e0, h_w1, 8); goffs(gp.e1, h_b1, 8); goffs(gp.e2, h_w2, 8); goffs(gp.e3, h_b2, 8); goffs(gp.e5, hP, 8);
-        for (int k = 0; k < 8; ++k) { gp.e4[k] = k; gp.e6[k] = (int64_t)k * nblk; }
+        HeadFwdGroup g[8];
+        for (int k = 0; k < 8; ++k) g[k] = head_fwd_group(c, k, bits_acc != nullptr);
         ProfScope ps(c.s, PK_HEAD_FWD, 8);
-        TRY(linr_cconv_head_launch(a.O[0], lo, mk, c.nbr_ld, c.R, h_prw[0], h_prb[0], a.C[0], h_w1[0], h_b1[0], h_w2[0], h_b2[0],
-                                   a.OCC, 8, a.P[0], bits_acc ? (double*)a.slab : nullptr, c.s, &gp, 8));
+        TRY(linr_cconv_head_launch(m, g, 8, 8, c.s));
     }
     if (bits_acc) {
         ProfScope ps(c.s, PK_MISC, 0);
@@ -848,10 +848,8 @@ extern "C" int linr_net_forward(const linr_frame* f, const float* params, float*
         // prior_k = x_glob + outter_blocks[k-1](occ[:, :k])   (upsample.py:206-214; always the original x_glob)
         if (k > 0) TRY(block_fwd(c, c.L.outter[k - 1], a.OCC, 8, k, a.O[0]));
         // prune conv + MLP + sigmoid + BCE partials in one launch (csrc/fused.hip)
-        double* part = bits_acc ? (double*)a.slab + (int64_t)k * nblk : nullptr;
-        TRY(linr_cconv_head_launch(a.O[k], clo(c), cmk(c), c.nbr_ld, c.R, P + c.L.pr_w[k], P + c.L.pr_b[k],
-                                   a.C[k], P + c.L.h0_w[k], P + c.L.h0_b[k], P + c.L.h2_w[k], P + c.L.h2_b[k],
-                                   a.OCC + k, 8, a.P[k], part, c.s));
+        const HeadFwdGroup g = head_fwd_group(c, k, bits_acc != nullptr);
+        TRY(linr_cconv_head_launch(cmap(c), &g, 1, 8, c.s));
         if (probs)
             TRY(linr_hip_rc(hipMemcpyAsync(probs + (int64_t)k * c.R, a.P[k], (size_t)c.R * sizeof(float),
                                            hipMemcpyDeviceToDevice, c.s)));
@@ -887,6 +885,48 @@ extern "C" int linr_sce_bwd(const float* params, const linr_frame* f, const floa
     return linr_launch_rc();
 }
 
+// What the scale context's backward needs per frame, for linr_sce_bwd_params and linr_bwd_tail_launch alike: sa with the slab rows of
+// every scale (wg_off: one workgroup per 256 rows, at most nb; a scale with fewer leaves a short range, appended to sr), the ranges
+// the reduction writes zeros for (zr: the scale embedding and the context MLPs of absent scales get no partials) and the
+// embedding-gradient table of the ns row ranges that have rows.  sr starts with the caller's ranges sh[0 .. nsh) that hold fewer than
+// nb rows.  false: two of the frame's row ranges belong to one scale.
+struct SceBwdPlan { SceArgs sa; ZeroRanges zr; ShortRanges sr; EmbArgs ea; int ns; };
+static void short_push(ShortRanges& sr, int64_t b, int64_t e, int rows) {
+    if (sr.n >= MAX_SHORT) abort();          // cannot happen (struct Ctx: 41); a silent drop would read unwritten rows
+    sr.b[sr.n] = b; sr.e[sr.n] = e; sr.rows[sr.n] = rows; ++sr.n;
+}
+static bool sce_bwd_plan(const linr_frame* f, const Layout& L, int nb, const LinrShortRange* sh, int nsh, SceBwdPlan& p) {
+    p.sr.n = 0;
+    for (int i = 0; i < nsh; ++i)
+        if (sh[i].rows < nb) short_push(p.sr, sh[i].b, sh[i].e, sh[i].rows);
+    const int64_t total = L.block_in.a_w;                 // the scale context's parameters lead the layout
+    p.sa = sce_args(f, L);
+    p.zr.n = 0; p.zr.prefix = total;
+    p.zr.b[p.zr.n] = L.emb; p.zr.e[p.zr.n] = L.emb + (int64_t)L.S * 8; ++p.zr.n;
+    p.ns = 0;
+    bool present[MAX_SCALES] = {}, distinct = true;
+    p.sa.wg_off[0] = 0;
+    for (int j = 0; j < f->n_scales; ++j) {
+        const int64_t nj = f->row_off_h[j + 1] - f->row_off_h[j];
+        int64_t wg = nj > 0 ? (nj + LINR_BLOCK - 1) / LINR_BLOCK : 0;
+        if (wg > nb) wg = nb;
+        p.sa.wg_off[j + 1] = p.sa.wg_off[j] + (int)wg;
+        if (wg == 0) continue;
+        const int si = f->scale_idx_h[j];
+        if (present[si]) distinct = false;
+        present[si] = true;
+        if (wg < nb) short_push(p.sr, L.m0_w[si], L.m2_b[si] + 8, (int)wg);
+        p.ea.gb1[p.ns] = L.m0_b[si]; p.ea.w1[p.ns] = L.m0_w[si]; p.ea.gemb[p.ns] = L.emb + si * 8; ++p.ns;
+    }
+    for (int si = 0; si < L.S; ++si)
+        if (!present[si]) {
+            p.zr.b[p.zr.n] = L.m0_w[si];
+            p.zr.e[p.zr.n] = si + 1 < L.S ? L.m0_w[si + 1] : total;
+            ++p.zr.n;
+        }
+    return distinct;
+}
+
 // The whole backward of the scale context as one call (what linr_net_backward launches for it): the gradients of scale_emb and of
 // every scale MLP of the frame into grads[0 .. linr_sce_param_count) - the scale context's parameters lead the flat layout whatever
 // the width of the rest of the network - from gx0 [rows][8] and the hid [rows][16] that linr_sce_fwd kept.  The MLPs of scales the
@@ -911,37 +951,11 @@ extern "C" int linr_sce_bwd_params(const float* params, const linr_frame* f, con
     if (slab_bytes < (size_t)SCE_SLAB_ROWS * (size_t)total * sizeof(float)) return LINR_ENOSPC;
     hipStream_t s = (hipStream_t)stream;
     const int nb = SCE_SLAB_ROWS;
-    SceArgs sa = sce_args(f, L);
-    ZeroRanges zr;
-    zr.n = 0; zr.prefix = total;
-    zr.b[zr.n] = L.emb; zr.e[zr.n] = L.emb + (int64_t)L.S * 8; ++zr.n;
-    ShortRanges sr;
-    sr.n = 0;
-    bool present[MAX_SCALES] = {};
-    EmbArgs ea;
-    int ns = 0;
-    sa.wg_off[0] = 0;
-    for (int j = 0; j < f->n_scales; ++j) {
-        const int64_t nj = f->row_off_h[j + 1] - f->row_off_h[j];
-        int64_t wg = nj > 0 ? (nj + LINR_BLOCK - 1) / LINR_BLOCK : 0;
-        if (wg > nb) wg = nb;
-        sa.wg_off[j + 1] = sa.wg_off[j] + (int)wg;
-        if (wg == 0) continue;
-        const int si = f->scale_idx_h[j];
-        if (present[si]) return LINR_EINVAL;                 // two row ranges of one scale would share slab rows
-        present[si] = true;
-        if (wg < nb) { sr.b[sr.n] = L.m0_w[si]; sr.e[sr.n] = L.m2_b[si] + 8; sr.rows[sr.n] = (int)wg; ++sr.n; }
-        ea.gb1[ns] = L.m0_b[si]; ea.w1[ns] = L.m0_w[si]; ea.gemb[ns] = L.emb + si * 8; ++ns;
-    }
-    for (int si = 0; si < L.S; ++si)
-        if (!present[si]) {
-            zr.b[zr.n] = L.m0_w[si];
-            zr.e[zr.n] = si + 1 < L.S ? L.m0_w[si + 1] : total;
-            ++zr.n;
-        }
-    if (ns > 0) sce_bwd_all_k<<<sa.wg_off[f->n_scales], SB_WAVES * 64, 0, s>>>(params, f->offset_feat, sa, gx0, hid, slab, total);
-    wgrad_reduce_k<<<linr_grid(total, LINR_BLOCK / RED_SPLIT), LINR_BLOCK, 0, s>>>(slab, nb, total, grads, zr, sr);
-    if (ns > 0) sce_emb_grad_all_k<<<ns, LINR_WAVE, 0, s>>>(params, grads, ea);
+    SceBwdPlan pl;
+    if (!sce_bwd_plan(f, L, nb, nullptr, 0, pl)) return LINR_EINVAL;      // two row ranges of one scale would share slab rows
+    if (pl.ns > 0) sce_bwd_all_k<<<pl.sa.wg_off[f->n_scales], SB_WAVES * 64, 0, s>>>(params, f->offset_feat, pl.sa, gx0, hid, slab, total);
+    wgrad_reduce_k<<<linr_grid(total, LINR_BLOCK / RED_SPLIT), LINR_BLOCK, 0, s>>>(slab, nb, total, grads, pl.zr, pl.sr);
+    if (pl.ns > 0) sce_emb_grad_all_k<<<pl.ns, LINR_WAVE, 0, s>>>(params, grads, pl.ea);
     return linr_launch_rc();
 }
 
@@ -967,61 +981,42 @@ __global__ __launch_bounds__(LINR_BLOCK) void sum8_k(Ptr8 src, int64_t n, float*
     dst[i] = t;
 }
 
-static void goffs_i(int64_t* dst, const int64_t* v, int n) {
-    for (int i = 0; i < n; ++i) dst[i] = v[i] - v[0];
-}
-
 // Backward of the 8 heads and the 7 outter blocks as grouped launches (one launch per layer, gridDim.y = group).
 static int backward_batched(Ctx& c, float gz_scale) {
     Arena& a = c.A;
     const float* P = c.P;
     const Layout& L = c.L;
-    const int32_t* lo = clo(c);
-    const uint32_t* mk = cmk(c);
+    const LinrCmap m = cmap(c);
     {
-        const float *hC[8], *hP[8], *hO[8], *h_gC[8], *h_gO[8], *h_prw[8], *h_w1[8], *h_b1[8], *h_w2[8];
-        int64_t o_w1[8], o_b1[8], o_w2[8], o_b2[8], o_prw[8], o_prb[8];
-        for (int k = 0; k < 8; ++k) {
-            hC[k] = a.C[k]; hP[k] = a.P[k]; hO[k] = a.O[k]; h_gC[k] = a.gC[k]; h_gO[k] = a.gO[k]; h_prw[k] = P + L.pr_w[k];
-            h_w1[k] = P + L.h0_w[k]; h_b1[k] = P + L.h0_b[k]; h_w2[k] = P + L.h2_w[k];
-            o_w1[k] = L.h0_w[k]; o_b1[k] = L.h0_b[k]; o_w2[k] = L.h2_w[k]; o_b2[k] = L.h2_b[k];
-            o_prw[k] = L.pr_w[k]; o_prb[k] = L.pr_b[k];
-        }
         {   // heads: gC and the four head-parameter gradients
-            Grp gp = Grp();
-            goffs(gp.in, hC, 8); goffs(gp.e0, hP, 8); goffs(gp.w, h_w1, 8); goffs(gp.b, h_b1, 8); goffs(gp.e2, h_w2, 8);
-            goffs(gp.out, h_gC, 8);
-            for (int k = 0; k < 8; ++k) gp.e1[k] = k;
-            goffs_i(gp.e3, o_w1, 8); goffs_i(gp.e4, o_b1, 8); goffs_i(gp.e5, o_w2, 8); goffs_i(gp.e6, o_b2, 8);
+            HeadBwdGroup g[8];
+            for (int k = 0; k < 8; ++k)
+                g[k] = {a.C[k], a.P[k], a.OCC + k, P + L.h0_w[k], P + L.h0_b[k], P + L.h2_w[k], a.gC[k], L.h0_w[k], L.h0_b[k], L.h2_w[k], L.h2_b[k]};
             ProfScope ps(c.s, PK_HEAD_BWD, 8);
             int hrows = 0;
-            TRY(linr_head_bwd_launch(a.C[0], a.P[0], a.OCC, 8, h_w1[0], h_b1[0], h_w2[0], gz_scale, a.gC[0], c.R, a.BIG, L.total,
-                                     o_w1[0], o_b1[0], o_w2[0], o_b2[0], c.s, &gp, 8, c.nb, &hrows));
+            TRY(linr_head_bwd_launch(g, 8, 8, gz_scale, c.R, a.BIG, L.total, c.nb, &hrows, c.s));
             c.note_short(L.h0_w[0], L.h2_b[7] + 1, hrows);          // the heads' parameters are one contiguous range
         }
-        if (fused_bwd(c)) {   // C = conv3(prior_k; prune_k): gO[k] = bwd(gC[k]) and the weight gradients from one gather of gC
-            Grp gp = Grp();
-            goffs(gp.in, h_gC, 8); goffs(gp.res, hO, 8); goffs(gp.w, h_prw, 8); goffs(gp.out, h_gO, 8);
-            goffs_i(gp.e3, o_prw, 8); goffs_i(gp.e4, o_prb, 8);
-            LinrWgradDst d = {a.BIG, L.total, o_prw[0], o_prb[0], 8};
+        // C = conv3(prior_k; prune_k)
+        Conv88BwdGroup pr[8];
+        for (int k = 0; k < 8; ++k) pr[k] = {a.gC[k], a.O[k], P + L.pr_w[k], a.gO[k], L.pr_w[k], L.pr_b[k], nullptr, nullptr, nullptr, 0, 0};
+        if (fused_bwd(c)) {   // gO[k] = bwd(gC[k]) and the weight gradients from one gather of gC
             ProfScope ps(c.s, PK_FUSED88, 8);
             int rows = 0;
-            TRY(linr_conv88_bwd_wgrad_launch(a.gC[0], a.O[0], lo, mk, c.nbr_ld, c.R, h_prw[0], a.gO[0], nullptr, d, c.nb, c.s, &gp, 8, &rows));
+            TRY(linr_conv88_bwd_wgrad_launch(m, pr, 8, a.BIG, L.total, c.nb, &rows, c.s));
             c.note_short(L.pr_w[0], L.pr_b[7] + 8, rows);
         } else {
-        {   // C = conv3(prior_k; prune_k): weight gradients ...
-            Grp gp = Grp();
-            goffs(gp.in, hO, 8); goffs(gp.res, h_gC, 8); goffs_i(gp.w, o_prw, 8); goffs_i(gp.b, o_prb, 8);
-            LinrWgradDst d = {a.BIG, L.total, o_prw[0], o_prb[0], 8};
+        {   // weight gradients ...
+            WgradGroup g[8];
+            for (int k = 0; k < 8; ++k) g[k] = wgrad_of(pr[k]);
             ProfScope ps(c.s, PK_WGRAD, 8);
-            TRY(linr_conv3_wgrad_mfma(a.O[0], 8, a.gC[0], 8, c.f->nbr, c.nbr_ld, c.R, 8, 8, d, c.nb, c.s, &gp, 8, wg_t8t(c)));
+            TRY(linr_conv3_wgrad_mfma(g, 8, 8, 8, c.f->nbr, c.nbr_ld, c.R, wg_t8t(c), 8, 8, a.BIG, L.total, c.nb, c.s));
         }
         {   // ... and gO[k] = bwd(gC[k])
-            Grp gp = Grp();
-            goffs(gp.in, h_gC, 8); goffs(gp.w, h_prw, 8); goffs(gp.out, h_gO, 8);
+            ConvGroup g[8];
+            for (int k = 0; k < 8; ++k) g[k] = bwd_data_of(pr[k]);
             ProfScope ps(c.s, PK_BWD_DATA, 8);
-            TRY(linr_cconv_launch(true, a.gC[0], 8, lo, mk, c.nbr_ld, c.R, h_prw[0], nullptr, 8, 8, nullptr, 0, nullptr, 0, a.gO[0],
-                                  8, 0, c.s, &gp, 8));
+            TRY(linr_cconv_launch(true, m, g, 8, 8, 8, 8, 0, 0, 8, 0, c.s));
         }
         }
         Ptr8 src;
@@ -1033,136 +1028,94 @@ static int backward_batched(Ctx& c, float gz_scale) {
     // (output gradient gXG = the sum above): one group per slot, g0 = first slot, ng = group count
     const bool join = join_block_in(c);
     const int g0 = join ? 0 : 1, ng = 8 - g0;
-    const float *pA[8], *pH[8], *pM[8], *pI[8], *p_gO[8], *p_gI[8], *p_gM[8], *p_gH[8], *p_gA[8], *p_bw[8], *p_c12w[8], *p_c01w[8],
-        *p_c11w[8], *p_c00w[8], *p_c10w[8], *p_in[8];
-    int64_t o_bw[8], o_bb[8], o_c12w[8], o_c12b[8], o_c01w[8], o_c01b[8], o_c11w[8], o_c11b[8], o_c00w[8], o_c00b[8], o_c10w[8],
-        o_c10b[8], o_aw[8], o_ab[8];
-    for (int g = 0; g < ng; ++g) {
-        const int b = g0 + g;
-        const BlockP& bp = b == 0 ? L.block_in : L.outter[b - 1];
-        pA[g] = a.A[b]; pH[g] = a.H[b]; pM[g] = a.M[b]; pI[g] = a.I[b]; p_gO[g] = b == 0 ? a.gXG : a.gO[b]; p_gI[g] = a.gI[b];
-        p_gM[g] = a.gM[b]; p_gH[g] = a.gH[b]; p_gA[g] = a.gA[b]; p_in[g] = b == 0 ? a.X0 : a.OCC;
-        p_bw[g] = P + bp.b_w; p_c12w[g] = P + bp.inc[0].c12_w; p_c01w[g] = P + bp.inc[0].c01_w; p_c11w[g] = P + bp.inc[0].c11_w;
-        p_c00w[g] = P + bp.inc[0].c00_w; p_c10w[g] = P + bp.inc[0].c10_w;
-        o_bw[g] = bp.b_w; o_bb[g] = bp.b_b; o_c12w[g] = bp.inc[0].c12_w; o_c12b[g] = bp.inc[0].c12_b; o_c01w[g] = bp.inc[0].c01_w; o_c01b[g] = bp.inc[0].c01_b;
-        o_c11w[g] = bp.inc[0].c11_w; o_c11b[g] = bp.inc[0].c11_b; o_c00w[g] = bp.inc[0].c00_w; o_c00b[g] = bp.inc[0].c00_b; o_c10w[g] = bp.inc[0].c10_w;
-        o_c10b[g] = bp.inc[0].c10_b; o_aw[g] = bp.a_w; o_ab[g] = bp.a_b;
+    Conv88BwdGroup tail[8];          // O = conv3(I; b) with conv1_2 behind it
+    Dual44BwdGroup dual[8];          // conv0_1, conv1_1
+    Conv84BwdGroup c00[8];           // conv0_0, conv1_0
+    WgradGroup first[8];             // A = relu(conv3(in; a)): the occupancy rows' first b channels (outter block b) or all 8 of x0 (block_in)
+    for (int i = 0; i < ng; ++i) {
+        const int b = g0 + i;
+        const BlockP& bp = slot_block(L, b);
+        const LayerBufs t = layer_bufs(a, b, 0);
+        tail[i] = tail_bwd_group(P, bp, bp.inc[0], b == 0 ? a.gXG : a.gO[b], t);
+        dual[i] = dual_bwd_group(P, bp.inc[0], t);
+        c00[i] = c00_bwd_group(P, bp.inc[0], a.A[b], t, a.gA[b]);
+        first[i] = {b == 0 ? a.X0 : a.OCC, a.gA[b], bp.a_w, bp.a_b, b == 0 ? 8 : b};
     }
+    WgradGroup wg[8];                // operands of the stand-alone weight-gradient launches (two-kernel schedule)
     if (fused_bwd(c)) {   // O = conv3(I; b): gI = bwd(gO; b), gM = (gI[:,4:8] @ W12^T) * (M > 0) and the weight gradient, one gather of gO
-        Grp gp = Grp();
-        goffs(gp.in, p_gO, ng); goffs(gp.res, pI, ng); goffs(gp.w, p_bw, ng); goffs(gp.out, p_gI, ng);
-        goffs(gp.e0, p_c12w, ng); goffs(gp.e1, pM, ng); goffs(gp.e2, p_gM, ng); goffs_i(gp.e3, o_bw, ng); goffs_i(gp.e4, o_bb, ng);
-        goffs_i(gp.e5, o_c12w, ng); goffs_i(gp.e6, o_c12b, ng);
-        LinrWgradDst d = {a.BIG, L.total, o_bw[0], o_bb[0], 8};
-        PwArgs pw = {p_c12w[0], nullptr, pM[0], a.gM[g0]};
         ProfScope ps(c.s, PK_FUSED88, ng);
         int rows = 0;
-        TRY(linr_conv88_bwd_wgrad_launch(p_gO[0], pI[0], lo, mk, c.nbr_ld, c.R, p_bw[0], a.gI[g0], &pw, d, c.nb, c.s, &gp, ng, &rows,
-                                         o_c12w[0], o_c12b[0]));
+        TRY(linr_conv88_bwd_wgrad_launch(m, tail, ng, a.BIG, L.total, c.nb, &rows, c.s));
         // everything of a block behind its first conv comes from fused launches over the same groups (conv1_2 rides in this one,
         // conv0_0 / conv0_1 / conv1_0 / conv1_1 come below): one contiguous range of `rows` slab rows per block
-        for (int g = 0; g < ng; ++g) c.note_short(o_c00w[g], o_bb[g] + 8, rows);
+        for (int i = 0; i < ng; ++i) c.note_short(c00[i].w00_off, tail[i].b_off + 8, rows);
     } else {
     {   // O = conv3(I; b): weight gradient
-        Grp gp = Grp();
-        goffs(gp.in, pI, ng); goffs(gp.res, p_gO, ng); goffs_i(gp.w, o_bw, ng); goffs_i(gp.b, o_bb, ng);
-        LinrWgradDst d = {a.BIG, L.total, o_bw[0], o_bb[0], 8};
+        for (int i = 0; i < ng; ++i) wg[i] = wgrad_of(tail[i]);
         ProfScope ps(c.s, PK_WGRAD, ng);
-        TRY(linr_conv3_wgrad_mfma(pI[0], 8, p_gO[0], 8, c.f->nbr, c.nbr_ld, c.R, 8, 8, d, c.nb, c.s, &gp, ng, wg_t8t(c)));
+        TRY(linr_conv3_wgrad_mfma(wg, ng, 8, 8, c.f->nbr, c.nbr_ld, c.R, wg_t8t(c), 8, 8, a.BIG, L.total, c.nb, c.s));
     }
     {   // gI = bwd(gO; b), gM = (gI[:,4:8] @ W12^T) * (M > 0)
-        Grp gp = Grp();
-        goffs(gp.in, p_gO, ng); goffs(gp.w, p_bw, ng); goffs(gp.out, p_gI, ng); goffs(gp.e0, p_c12w, ng); goffs(gp.e1, pM, ng);
-        goffs(gp.e2, p_gM, ng);
         ProfScope ps(c.s, PK_BWD_DATA, ng);
-        TRY(linr_conv_bwd_gm_launch(p_gO[0], lo, mk, c.nbr_ld, c.R, p_bw[0], p_c12w[0], pM[0], a.gI[g0], a.gM[g0], c.s, &gp, ng));
+        TRY(linr_conv_bwd_gm_launch(m, tail, ng, c.s));
     }
-    }
-    if (!fused_bwd(c)) {   // conv1_2 weight gradient: M^T gI[:,4:8]  (the fused tail-conv launch above produces it on the side)
-        Grp gp = Grp();
-        goffs(gp.in, pM, ng); goffs(gp.res, p_gI, ng); goffs_i(gp.w, o_c12w, ng); goffs_i(gp.b, o_c12b, ng);
-        LinrLinDst d = {a.BIG, L.total, o_c12w[0], 4, 1, o_c12b[0]};
+    {   // conv1_2 weight gradient: M^T gI[:,4:8]  (the fused tail-conv launch above produces it on the side)
+        for (int i = 0; i < ng; ++i) wg[i] = {tail[i].M, tail[i].out + 4, tail[i].w12_off, tail[i].b12_off, 0};
         ProfScope ps(c.s, PK_LIN_WGRAD, ng);
-        TRY(linr_linear_wgrad_partial(pM[0], 4, p_gI[0] + 4, 8, c.R, 4, 4, d, c.nb, c.s, &gp, ng));
+        TRY(linr_linear_wgrad_partial(wg, ng, 4, 8, c.R, 4, 4, a.BIG, L.total, 4, 1, c.nb, c.s));
+    }
     }
     if (fused_bwd(c)) {   // both 4->4 convs: gH and the two kernel / bias gradients from one gather of [gI[:,0:4] | gM]
-        Grp gp = Grp();
-        goffs(gp.in, p_gI, ng); goffs(gp.e5, p_gM, ng); goffs(gp.res, pH, ng); goffs(gp.w, p_c01w, ng); goffs(gp.e6, p_c11w, ng);
-        goffs(gp.out, p_gH, ng); goffs_i(gp.e3, o_c01w, ng); goffs_i(gp.e4, o_c01b, ng); goffs_i(gp.e0, o_c11w, ng); goffs_i(gp.e1, o_c11b, ng);
         ProfScope ps(c.s, PK_FUSED_DUAL, ng);
         int rows_inc = 0;
-        TRY(linr_dual44_bwd_wgrad_launch(p_gI[0], p_gM[0], pH[0], lo, mk, c.nbr_ld, c.R, p_c01w[0], p_c11w[0], a.gH[g0], a.BIG, L.total,
-                                         o_c01w[0], o_c01b[0], o_c11w[0], o_c11b[0], c.nb, c.s, &gp, ng, &rows_inc));
+        TRY(linr_dual44_bwd_wgrad_launch(m, dual, ng, a.BIG, L.total, c.nb, &rows_inc, c.s));
         if (rows_inc != linr_fused_bwd_rows(c.R, c.nb, ng)) return LINR_EINVAL;        // (its parameters were registered with the tail conv)
     } else {   // both 4->4 convs: weight gradients, then gH
-        Grp gp = Grp();
-        goffs(gp.in, pH, ng); goffs(gp.res, p_gI, ng); goffs(gp.act, p_gM, ng); goffs_i(gp.w, o_c01w, ng); goffs_i(gp.b, o_c01b, ng);
-        goffs_i(gp.e0, o_c11w, ng); goffs_i(gp.e1, o_c11b, ng);
         {
             ProfScope ps(c.s, PK_WGRAD, ng);
-            TRY(linr_conv3_wgrad_dual44(pH[0], p_gI[0], 8, p_gM[0], 4, c.f->nbr, c.nbr_ld, c.R, a.BIG, L.total, o_c01w[0], o_c01b[0],
-                                        o_c11w[0], o_c11b[0], c.nb, c.s, &gp, ng, wg_t8t(c)));
+            TRY(linr_conv3_wgrad_dual44(dual, ng, 8, 4, c.f->nbr, c.nbr_ld, c.R, wg_t8t(c), a.BIG, L.total, c.nb, c.s));
         }
-        Grp gq = Grp();
-        goffs(gq.in, p_gI, ng); goffs(gq.out, p_gH, ng); goffs(gq.e0, p_gM, ng); goffs(gq.w, p_c01w, ng); goffs(gq.e1, p_c11w, ng);
-        goffs(gq.act, pH, ng);
         ProfScope ps(c.s, PK_BWD_DATA, ng);
-        TRY(linr_dual44_bwd_launch(p_gI[0], p_gM[0], lo, mk, c.nbr_ld, c.R, p_c01w[0], p_c11w[0], pH[0], a.gH[g0], c.s, &gq, ng));
-    }
-    if (!fused_bwd(c)) {   // conv1_0 (1x1 8->4) weight gradient (the fused conv0_0 launch below produces it on the side)
-        Grp gq = Grp();
-        goffs(gq.in, pA, ng); goffs(gq.res, p_gH, ng); goffs_i(gq.w, o_c10w, ng); goffs_i(gq.b, o_c10b, ng);
-        LinrLinDst dl = {a.BIG, L.total, o_c10w[0], 4, 1, o_c10b[0]};
-        ProfScope ps(c.s, PK_LIN_WGRAD, ng);
-        TRY(linr_linear_wgrad_partial(pA[0], 8, p_gH[0] + 4, 8, c.R, 8, 4, dl, c.nb, c.s, &gq, ng));
+        TRY(linr_dual44_bwd_launch(m, dual, ng, c.s));
     }
     if (fused_bwd(c)) {   // conv0_0 (8->4): gA = (bwd(gH[:,0:4]; W00) + gI + gH[:,4:8] @ W10^T) * (A > 0) and its weight gradient, one gather
-        Grp gp = Grp();
-        goffs(gp.in, p_gH, ng); goffs(gp.res, pA, ng); goffs(gp.w, p_c00w, ng); goffs(gp.act, p_gI, ng); goffs(gp.out, p_gA, ng);
-        goffs(gp.e0, p_c10w, ng); goffs_i(gp.e3, o_c00w, ng); goffs_i(gp.e4, o_c00b, ng); goffs_i(gp.e1, o_c10w, ng); goffs_i(gp.e2, o_c10b, ng);
-        LinrWgradDst d = {a.BIG, L.total, o_c00w[0], o_c00b[0], 8};
         ProfScope ps(c.s, PK_FUSED_C00, ng);
         int rows_c00 = 0;
-        TRY(linr_conv84_bwd_wgrad_launch(p_gH[0], pA[0], p_gI[0], lo, mk, c.nbr_ld, c.R, p_c00w[0], p_c10w[0], a.gA[g0], LINR_RELU_MASK, d,
-                                         o_c10w[0], o_c10b[0], c.nb, c.s, &gp, ng, &rows_c00));
+        TRY(linr_conv84_bwd_wgrad_launch(m, c00, ng, LINR_RELU_MASK, a.BIG, L.total, c.nb, &rows_c00, c.s));
         if (rows_c00 != linr_fused_bwd_rows(c.R, c.nb, ng)) return LINR_EINVAL;       // (registered with the tail conv)
     } else {
+    {   // conv1_0 (1x1 8->4) weight gradient (the fused conv0_0 launch above produces it on the side)
+        for (int i = 0; i < ng; ++i) wg[i] = {c00[i].A, c00[i].gH + 4, c00[i].w10_off, c00[i].b10_off, 0};
+        ProfScope ps(c.s, PK_LIN_WGRAD, ng);
+        TRY(linr_linear_wgrad_partial(wg, ng, 8, 8, c.R, 8, 4, a.BIG, L.total, 4, 1, c.nb, c.s));
+    }
     {   // conv0_0 (8->4) weight gradient
-        Grp gp = Grp();
-        goffs(gp.in, pA, ng); goffs(gp.res, p_gH, ng); goffs_i(gp.w, o_c00w, ng); goffs_i(gp.b, o_c00b, ng);
-        LinrWgradDst d = {a.BIG, L.total, o_c00w[0], o_c00b[0], 8};
+        for (int i = 0; i < ng; ++i) wg[i] = {c00[i].A, c00[i].gH, c00[i].w00_off, c00[i].b00_off, 0};
         ProfScope ps(c.s, PK_WGRAD, ng);
-        TRY(linr_conv3_wgrad_mfma(pA[0], 8, p_gH[0], 8, c.f->nbr, c.nbr_ld, c.R, 8, 4, d, c.nb, c.s, &gp, ng, wg_t8t(c)));
+        TRY(linr_conv3_wgrad_mfma(wg, ng, 8, 8, c.f->nbr, c.nbr_ld, c.R, wg_t8t(c), 8, 4, a.BIG, L.total, c.nb, c.s));
     }
     {   // gA = (bwd(gH[:,0:4]; W00) + gI + gH[:,4:8] @ W10^T) * (A > 0)
-        Grp gp = Grp();
-        goffs(gp.in, p_gH, ng); goffs(gp.w, p_c00w, ng); goffs(gp.res, p_gI, ng); goffs(gp.act, pA, ng); goffs(gp.out, p_gA, ng);
-        goffs(gp.e0, p_c10w, ng); goffs(gp.e1, p_gH, ng);
         ProfScope ps(c.s, PK_BWD_DATA, ng);
-        TRY(linr_conv_bwd_ga_launch(p_gH[0], lo, mk, c.nbr_ld, c.R, p_c00w[0], p_c10w[0], p_gI[0], pA[0], a.gA[g0], LINR_RELU_MASK, c.s, &gp, ng));
+        TRY(linr_conv_bwd_ga_launch(m, c00, ng, LINR_RELU_MASK, c.s));
     }
     }
-    {   // A = relu(conv3(in; a)): weight gradient on the first b channels of the occupancy rows (outter block b) or on all 8
-        // channels of the scale context x0 (block_in)
+    {   // first convs: weight gradient
         // (with the fused backward block_in's first conv - slot 0 - gets its weight gradient from the launch that also produces
         // its input gradient, backward_core; the grouped launch then covers the outter blocks only)
         const int s0 = (join && fused_bwd(c)) ? 1 : 0, nq = ng - s0;
-        bool same_in = nq == 7 && g0 + s0 == 1;
-        for (int g = 0; g < nq && same_in; ++g) same_in = p_in[s0 + g] == a.OCC;
-        if (same_in && fused_bwd(c)) {
+        if (g0 + s0 == 1 && fused_bwd(c)) {
             // the 7 outter blocks read the SAME occupancy rows: all seven weight gradients from one gather (csrc/occ_wgrad.hip)
+            const float* gA7[7];
+            int64_t w_off[7], b_off[7];
+            for (int i = 0; i < 7; ++i) { gA7[i] = first[s0 + i].gout; w_off[i] = first[s0 + i].w_off; b_off[i] = first[s0 + i].b_off; }
             ProfScope ps(c.s, PK_WGRAD, nq);
             int rows = 0;
-            TRY(linr_occ_wgrad7_launch(a.OCC, p_gA + s0, lo, mk, c.nbr_ld, c.R, a.BIG, L.total, o_aw + s0, o_ab + s0, c.nb, c.s, &rows));
-            for (int g = 0; g < nq; ++g) c.note_short(o_aw[s0 + g], o_ab[s0 + g] + 8, rows);
+            TRY(linr_occ_wgrad7_launch(a.OCC, gA7, m, a.BIG, L.total, w_off, b_off, c.nb, c.s, &rows));
+            for (int i = 0; i < 7; ++i) c.note_short(w_off[i], b_off[i] + 8, rows);
             return 0;
         }
-        Grp gp = Grp();
-        goffs(gp.in, p_in + s0, nq); goffs(gp.res, p_gA + s0, nq); goffs_i(gp.w, o_aw + s0, nq); goffs_i(gp.b, o_ab + s0, nq);
-        for (int g = 0; g < nq; ++g) gp.e2[g] = (g0 + s0 + g == 0) ? 8 : g0 + s0 + g;
-        LinrWgradDst d = {a.BIG, L.total, o_aw[s0], o_ab[s0], 1};
         ProfScope ps(c.s, PK_WGRAD, nq);
-        TRY(linr_conv3_wgrad_mfma(p_in[s0], 8, p_gA[s0], 8, c.f->nbr, c.nbr_ld, c.R, 1, 8, d, c.nb, c.s, &gp, nq, wg_t8t(c)));
+        TRY(linr_conv3_wgrad_mfma(first + s0, nq, 8, 8, c.f->nbr, c.nbr_ld, c.R, wg_t8t(c), 1, 8, a.BIG, L.total, c.nb, c.s));
     }
     return 0;
 }
@@ -1173,56 +1126,16 @@ static int backward_batched(Ctx& c, float gz_scale) {
 // ranges whose producers wrote fewer than nb slab rows - and the scale-embedding gradients derived from the reduced sums.
 int linr_bwd_tail_launch(const linr_frame* f, const Layout& L, const float* P, const float* gx0, const float* hid, float* big,
                          float* gsum, int nb, const LinrShortRange* sh, int nsh, hipStream_t stream) {
-    Ctx c;
-    c.f = f; c.L = L; c.s = stream; c.nb = nb;
-    for (int i = 0; i < nsh; ++i) c.note_short(sh[i].b, sh[i].e, sh[i].rows);
-    int ns = 0, sl[MAX_SCALES];
-    for (int s = 0; s < f->n_scales; ++s)
-        if (f->row_off_h[s + 1] > f->row_off_h[s]) sl[ns++] = s;
-    if (ns >= 1) {          // ghid and all four parameter gradients of every scale's context MLP in one launch
-        ProfScope ps(c.s, PK_SCE, 1);
-        SceArgs sa = sce_args(c.f, c.L);
-        // slab rows per scale: one workgroup per 256 rows, at most nb; a scale with fewer leaves a short range for the reduction
-        sa.wg_off[0] = 0;
-        for (int j = 0; j < f->n_scales; ++j) {
-            const int64_t nj = f->row_off_h[j + 1] - f->row_off_h[j];
-            int64_t wg = nj > 0 ? (nj + LINR_BLOCK - 1) / LINR_BLOCK : 0;
-            if (wg > c.nb) wg = c.nb;
-            sa.wg_off[j + 1] = sa.wg_off[j] + (int)wg;
-            if (wg > 0) {
-                const int si = f->scale_idx_h[j];
-                c.note_short(c.L.m0_w[si], c.L.m2_b[si] + 8, (int)wg);
-            }
-        }
-        sce_bwd_all_k<<<sa.wg_off[f->n_scales], SB_WAVES * 64, 0, c.s>>>(P, f->offset_feat, sa, gx0, hid, big, c.L.total);
+    SceBwdPlan pl;
+    (void)sce_bwd_plan(f, L, nb, sh, nsh, pl);
+    if (pl.ns >= 1) {          // ghid and all four parameter gradients of every scale's context MLP in one launch
+        ProfScope ps(stream, PK_SCE, 1);
+        sce_bwd_all_k<<<pl.sa.wg_off[f->n_scales], SB_WAVES * 64, 0, stream>>>(P, f->offset_feat, pl.sa, gx0, hid, big, L.total);
     }
     // one pass sums every parameter's per-block partials in fixed order
-    ProfScope ps_tail(c.s, PK_MISC, 0);
-    {   // the scale embedding and the context MLPs of absent scales get no partials: the reduction writes their zeros itself
-        ZeroRanges zr;
-        zr.n = 0; zr.prefix = c.L.block_in.a_w;
-        zr.b[zr.n] = c.L.emb; zr.e[zr.n] = c.L.emb + (int64_t)c.L.S * 8; ++zr.n;
-        bool present[MAX_SCALES] = {};
-        for (int j = 0; j < ns; ++j) present[f->scale_idx_h[sl[j]]] = true;
-        for (int si = 0; si < c.L.S; ++si)
-            if (!present[si]) {
-                zr.b[zr.n] = c.L.m0_w[si];
-                zr.e[zr.n] = si + 1 < c.L.S ? c.L.m0_w[si + 1] : c.L.block_in.a_w;
-                ++zr.n;
-            }
-        ShortRanges sr;
-        sr.n = (int)c.shortr.size();
-        for (int i = 0; i < sr.n; ++i) { sr.b[i] = c.shortr[i].b; sr.e[i] = c.shortr[i].e; sr.rows[i] = c.shortr[i].rows; }
-        wgrad_reduce_k<<<linr_grid(c.L.total, LINR_BLOCK / RED_SPLIT), LINR_BLOCK, 0, c.s>>>(big, c.nb, c.L.total, gsum, zr, sr);
-    }
-    if (ns > 0) {
-        EmbArgs ea;
-        for (int j = 0; j < ns; ++j) {
-            const int si = f->scale_idx_h[sl[j]];
-            ea.gb1[j] = c.L.m0_b[si]; ea.w1[j] = c.L.m0_w[si]; ea.gemb[j] = c.L.emb + si * 8;
-        }
-        sce_emb_grad_all_k<<<ns, LINR_WAVE, 0, c.s>>>(P, gsum, ea);
-    }
+    ProfScope ps_tail(stream, PK_MISC, 0);
+    wgrad_reduce_k<<<linr_grid(L.total, LINR_BLOCK / RED_SPLIT), LINR_BLOCK, 0, stream>>>(big, nb, L.total, gsum, pl.zr, pl.sr);
+    if (pl.ns > 0) sce_emb_grad_all_k<<<pl.ns, LINR_WAVE, 0, stream>>>(P, gsum, pl.ea);
     return linr_launch_rc();
 }
 
@@ -1235,19 +1148,17 @@ static int backward_core(Ctx& c, float gscale) {
     TRY(backward_batched(c, gz_scale));
     const BlockP& bi = c.L.block_in;
     if (join_block_in(c) && fused_bwd(c)) {      // first conv of block_in: input gradient and weight gradient from one gather of gA[0]
-        LinrWgradDst d = {a.BIG, c.L.total, bi.a_w, bi.a_b, 8};
+        const Conv88BwdGroup g = {a.gA[0], a.X0, P + bi.a_w, a.gX0, bi.a_w, bi.a_b, nullptr, nullptr, nullptr, 0, 0};
         ProfScope ps(c.s, PK_FUSED88, 1);
         int rows = 0;
-        TRY(linr_conv88_bwd_wgrad_launch(a.gA[0], a.X0, clo(c), cmk(c), c.nbr_ld, c.R, P + bi.a_w, a.gX0, nullptr, d, c.nb, c.s, nullptr, 1, &rows));
+        TRY(linr_conv88_bwd_wgrad_launch(cmap(c), &g, 1, a.BIG, c.L.total, c.nb, &rows, c.s));
         c.note_short(bi.a_w, bi.a_b + 8, rows);
     } else if (join_block_in(c)) {      // everything but the input gradient of its first conv was part of the grouped launches
         TRY(conv3(c, true, a.gA[0], 8, P + bi.a_w, nullptr, bi.cin, 8, nullptr, 0, nullptr, 0, a.gX0, 8, 0));
     } else {
         TRY(block_bwd(c, bi, a.X0, 8, 0, a.gXG, a.gX0));
     }
-    std::vector<LinrShortRange> sh(c.shortr.size());
-    for (size_t i = 0; i < sh.size(); ++i) sh[i] = {c.shortr[i].b, c.shortr[i].e, c.shortr[i].rows};
-    return linr_bwd_tail_launch(f, c.L, P, a.gX0, nullptr, a.BIG, a.GSUM, c.nb, sh.data(), (int)sh.size(), c.s);
+    return linr_bwd_tail_launch(f, c.L, P, a.gX0, nullptr, a.BIG, a.GSUM, c.nb, c.shortr.data(), (int)c.shortr.size(), c.s);
 }
 
 extern "C" int linr_net_backward(const linr_frame* f, const float* params, float* arena, size_t arena_bytes, float gscale,

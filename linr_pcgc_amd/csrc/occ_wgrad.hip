@@ -230,9 +230,9 @@ int linr_occ_wgrad7_rows(int64_t n, int nb, int cus, int* tiles_per_wave) {
 
 // occ: occupancy [n][8] with the zero row in front; g[b]: gradient of block b + 1's first-conv output (after its ReLU mask) [n][8];
 // w_off / b_off: slab offsets of the seven kernels [27][b + 1][8] / biases; *rows_written: slab rows written (the grid's blocks)
-int linr_occ_wgrad7_launch(const float* occ, const float* const* g, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                           float* big, int64_t block_stride, const int64_t* w_off, const int64_t* b_off, int nb, hipStream_t s,
-                           int* rows_written) {
+int linr_occ_wgrad7_launch(const float* occ, const float* const* g, LinrCmap m, float* big, int64_t block_stride,
+                           const int64_t* w_off, const int64_t* b_off, int nb, hipStream_t s, int* rows_written) {
+    const int64_t n = m.n;
     if (rows_written) *rows_written = 0;
     if (n == 0) return 0;
     static const int cus = [] {
@@ -245,7 +245,7 @@ int linr_occ_wgrad7_launch(const float* occ, const float* const* g, const int32_
     for (int b = 0; b < 7; ++b) { a.goff[b] = g[b] - g[0]; a.w_off[b] = w_off[b]; a.b_off[b] = b_off[b]; }
     const int blocks = linr_occ_wgrad7_rows(n, nb, cus, &a.tiles_per_wave);
     if (rows_written) *rows_written = blocks;
-    occ_wgrad7_k<<<blocks, OW_WAVES * 64, 0, s>>>(a, lo, mask, ld, n);
+    occ_wgrad7_k<<<blocks, OW_WAVES * 64, 0, s>>>(a, m.lo, m.mask, m.ld, n);
     return linr_launch_rc();
 }
 
@@ -265,7 +265,7 @@ extern "C" int linr_occ_wgrad7(const float* occ, const float* const* gout7_h, co
     int64_t w_off[7], b_off[7], cur = 0;
     for (int b = 0; b < 7; ++b) { w_off[b] = cur; cur += 27 * (b + 1) * 8; b_off[b] = cur; cur += 8; }
     int rows = 0;
-    const int rc = linr_occ_wgrad7_launch(occ, gout7_h, lo, mask, ld, n, slab, 6104, w_off, b_off, nblocks, (hipStream_t)stream, &rows);
+    const int rc = linr_occ_wgrad7_launch(occ, gout7_h, {lo, mask, ld, n}, slab, 6104, w_off, b_off, nblocks, (hipStream_t)stream, &rows);
     *rows_written_h = rows;
     return rc;
 }

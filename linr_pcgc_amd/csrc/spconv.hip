@@ -449,10 +449,16 @@ extern "C" int linr_spconv_bwd_weight(const float* in, int32_t in_ld, const floa
     if (vec && ((cin == 8 && (cout == 8 || cout == 4)) || (cin == 4 && cout == 4) || (cin < 8 && cout == 8 && in_ld >= 8))) {
         const int nb = wg_blocks(n);
         const int elems = (27 * cin + 1) * cout;
-        LinrWgradDst d = {(float*)ws, elems, 0, 27 * cin * cout, cin};
-        // rows with a zero pad row in front (LINR_PAD_ROW) take the executor's matrix-core kernel (csrc/fused.hip)
-        int rc = ((flags & LINR_PAD_ROW) && (in_ld == 4 || in_ld == 8)) ? linr_conv3_wgrad_mfma(in, in_ld, gout, gout_ld, nbr, nbr_ld, n, cin, cout, d, nb, s)
-                                        : linr_conv3_wgrad_partial(in, in_ld, gout, gout_ld, nbr, nbr_ld, n, cin, cout, d, nb, flags, s);
+        // slab row: kernel [27][cin][cout], then the bias.  Rows with a zero pad row in front (LINR_PAD_ROW) take the executor's
+        // matrix-core kernel (csrc/fused.hip)
+        int rc;
+        if ((flags & LINR_PAD_ROW) && (in_ld == 4 || in_ld == 8)) {
+            const WgradGroup g = {in, gout, 0, 27 * cin * cout, 0};
+            rc = linr_conv3_wgrad_mfma(&g, 1, in_ld, gout_ld, nbr, nbr_ld, n, nullptr, cin, cout, (float*)ws, elems, nb, s);
+        } else {
+            LinrWgradDst d = {(float*)ws, elems, 0, 27 * cin * cout, cin};
+            rc = linr_conv3_wgrad_partial(in, in_ld, gout, gout_ld, nbr, nbr_ld, n, cin, cout, d, nb, flags, s);
+        }
         if (rc) return rc;
         slab_reduce_k<<<linr_grid(elems, SR_ELEMS), LINR_BLOCK, 0, s>>>((const float*)ws, nb, elems, 27 * cin * cout, gW, gb, flags);
         return linr_launch_rc();

@@ -688,17 +688,12 @@ extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, con
     } else
     for (int p0 = 0; p0 < npairs; p0 += LINR_MAXG) {
         const int ng = npairs - p0 < LINR_MAXG ? npairs - p0 : LINR_MAXG;
-        Grp gp = Grp();
+        WgradGroup pr[LINR_MAXG];
         for (int g = 0; g < ng; ++g) {
             const int p = p0 + g, bi = p / nbo, bo = p % nbo;
-            gp.in[g] = in_h[bi] - in_h[0];
-            gp.res[g] = g_h[bo] - g_h[0];                       // linr_conv3_wgrad_mfma: res = the output gradient's offset
-            gp.w[g] = (int64_t)p * WW_PAIR;
-            gp.b[g] = (int64_t)p * WW_PAIR;
-            gp.e2[g] = cin - 8 * bi < 8 ? cin - 8 * bi : 8;      // live input channels of the block
+            pr[g] = {in_h[bi], g_h[bo], (int64_t)p * WW_PAIR, (int64_t)p * WW_PAIR + 1728, cin - 8 * bi < 8 ? cin - 8 * bi : 8};
         }
-        LinrWgradDst d = {slab, (int64_t)npairs * WW_PAIR, 0, 1728, 8};
-        const int rc = linr_conv3_wgrad_mfma(in_h[0], 8, g_h[0], 8, nbr, ld, n, 8, 8, d, LINR_WG_BLOCKS, s, &gp, ng, tile8t);
+        const int rc = linr_conv3_wgrad_mfma(pr, ng, 8, 8, nbr, ld, n, tile8t, 8, 8, slab, (int64_t)npairs * WW_PAIR, LINR_WG_BLOCKS, s);
         if (rc) return rc;
     }
     if (!gW) return linr_launch_rc();                   // partials only: the caller reduces them with linr_wide_reduce_many
@@ -900,17 +895,11 @@ extern "C" int linr_linear_wgrad_wide(const float* const* in_h, int32_t cin, int
     linr_poison_hook(s, 16);
     const int nb = linr_lin_blocks(n);
     const int64_t stride = (int64_t)(cin + 2) * cout;                             // [cin + 1][cout] + a dump row for the duplicate bias sums
-    Grp gp = Grp();
+    WgradGroup pr[LINR_MAXG];
     for (int pi = 0; pi < ni; ++pi)
-        for (int po = 0; po < no; ++po) {
-            const int g = pi * no + po;
-            gp.in[g] = in_h[pi] - in_h[0];
-            gp.res[g] = g_h[po] - g_h[0];
-            gp.w[g] = (int64_t)(mi * pi) * cout + nn * po;
-            gp.b[g] = (int64_t)(pi == 0 ? cin : cin + 1) * cout + nn * po;        // the column sums of g: kept from the first input piece
-        }
-    LinrLinDst d = {(float*)ws, stride, 0, cout, 1, 0};
-    const int rc = linr_linear_wgrad_partial(in_h[0], mi, g_h[0], nn, n, mi, nn, d, nb, s, &gp, ni * no);
+        for (int po = 0; po < no; ++po)           // (the column sums of g: kept from the first input piece)
+            pr[pi * no + po] = {in_h[pi], g_h[po], (int64_t)(mi * pi) * cout + nn * po, (int64_t)(pi == 0 ? cin : cin + 1) * cout + nn * po, 0};
+    const int rc = linr_linear_wgrad_partial(pr, ni * no, mi, nn, n, mi, nn, (float*)ws, stride, cout, 1, nb, s);
     if (rc || !gW) return rc;                            // gW == NULL: partials only (linr_wide_reduce_many)
     return linr_linear_slab_reduce_launch((const float*)ws, nb, stride, cin, cout, gW, ws_ci, ws_co, gb, flags, s);
 }
