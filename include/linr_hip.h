@@ -98,13 +98,20 @@ LINR_API int linr_octree_level(const int32_t* child, int64_t m, int32_t coord_bi
 /* ALL octree levels of a frame as one call, without a sort (csrc/octree.hip; the loop of datautils/custom_dataset.py:289-344 over
  * octree_level.forward, models/module_utils.py:86-110): the parents of a sorted unique child list are the set bits of a bitmap over
  * their compact x-major keys, read in word order.  child: int32 [m,3] sorted x-major and unique, coordinates in [0, 2^coord_bits),
- * 2 <= coord_bits <= 11 (12-bit clouds and deeper: linr_octree_level per level); m_dev: NULL, or a DEVICE int64 holding the live row
+ * 2 <= coord_bits <= 20 (not validated: rows that break this give meaningless output, but no kernel writes outside its buffers);
+ * m_dev: NULL, or a DEVICE int64 holding the live row
  * count (<= m: the count linr_coords_sort_unique left on the device - no host read between the two calls).  Level l = 0 ..
  * linr_octree_levels_count(coord_bits, max_levels) - 1 has child coordinates of coord_bits - l bits; its parents (int32 rows) and their
  * child occupancy (float32 [.,8], column 4 dx + 2 dy + dz) are written BACK TO BACK into parents / occ, level after level, each
  * buffer with room for linr_octree_levels_rows(m, coord_bits, max_levels) rows; counts: DEVICE int64 [levels] = rows of every level
  * (the caller reads them once, behind the call, and slices).  Bit-identical to linr_octree_level applied level by level.
- * ws: linr_octree_levels_workspace_bytes(m, coord_bits, max_levels) bytes, 256-byte aligned. */
+ * Two kinds of level, planned from (m, coord_bits) alone, level by level: a DENSE level is the bitmap above - 2^(3 pb) bits, pb = the
+ * bits of the parents' coordinates - and is taken for pb <= 10 while the bitmap has at most 12 32-bit words per possible row (or at
+ * most 2^19 words); every other level is SPARSE: head-of-parent flags over the sorted child rows, one scan, the rank of every parent
+ * from lower bounds in the child keys - work and workspace follow the rows, whatever the depth.
+ * ws: linr_octree_levels_workspace_bytes(m, coord_bits, max_levels) bytes, 256-byte aligned: at most 24 (m + 1) bytes (two key lists
+ * of 8 bytes per row, flags and scan of 4 each) + for the dense levels 4 bytes per word of every bitmap and 8 per word of the largest
+ * (its counts and scan) + 1 MB (the scan's own scratch, alignment). */
 LINR_API int32_t linr_octree_levels_count(int32_t coord_bits, int32_t max_levels);
 LINR_API int64_t linr_octree_levels_rows(int64_t m, int32_t coord_bits, int32_t max_levels);
 LINR_API size_t linr_octree_levels_workspace_bytes(int64_t m, int32_t coord_bits, int32_t max_levels);

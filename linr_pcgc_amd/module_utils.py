@@ -224,8 +224,9 @@ def prepare_frame(points, scale_num=None, min_point_num=64, device='cpu', with_o
     info = []
     limit = 100000 if scale_num is None else scale_num
     s0 = 0
-    if dev.type == 'cuda' and not pts.dtype.is_floating_point and 2 <= bits <= 11 and not os.environ.get('LINR_OCTREE_PER_LEVEL'):
-        # every level in one library call and one host read (csrc/octree.hip: no sort, counts chained on the device); the per-level
+    if dev.type == 'cuda' and not pts.dtype.is_floating_point and 2 <= bits <= 20 and not os.environ.get('LINR_OCTREE_PER_LEVEL'):
+        # every level in one library call and one host read (csrc/octree.hip: no sort, counts chained on the device, bitmap or
+        # row-proportional levels as the library plans them; 20 bits is what the keys of the kernel map hold); the per-level
         # loop below only continues where this leaves off (it does not: the stop criterion is met inside unless scale_num asks for
         # levels whose coordinates have no bits left)
         from . import ops

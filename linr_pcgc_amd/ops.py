@@ -441,11 +441,14 @@ def octree_level(child, coord_bits=20):
 
 
 def octree_levels(child, coord_bits, max_levels, count_dev=None):
-    """All octree levels below a sorted unique child list in ONE library call (linr_octree_levels: bitmap of the parents' compact keys,
-    no sort, counts chained on the device) and ONE host read.  child: int32 [m,3] on the GPU, coordinates in [0, 2^coord_bits),
-    coord_bits <= 11; count_dev: None or the device int64 live row count (<= m).  Returns (parents int32 [total,3], occ float32
-    [total,8], counts list): level l's rows are parents[sum(counts[:l]) : sum(counts[:l + 1])] - exact-size buffers shared by the
-    levels - or None when the library has no such levels (coord_bits out of range)."""
+    """All octree levels below a sorted unique child list in ONE library call (linr_octree_levels: no sort, counts chained on the
+    device; a level is a bitmap of the parents' compact keys where the bounding volume is small against the rows, else heads / scan /
+    rank over the rows - the library plans it level by level) and ONE host read.  child: int32 [m,3] on the GPU, coord_bits <= 20;
+    count_dev: None or the device int64 live row count (<= m).  Precondition, not checked: the rows are sorted x-major, unique and
+    every coordinate is in [0, 2^coord_bits) (prepare_frame guarantees it); anything else gives meaningless rows, though no kernel
+    writes outside its buffers.  Returns (parents int32 [total,3], occ float32 [total,8], counts list): level l's rows are
+    parents[sum(counts[:l]) : sum(counts[:l + 1])] - exact-size buffers shared by the levels - or None when the library has no such
+    levels (coord_bits out of range)."""
     _dev(child, torch.int32, 'child')
     L = _lib.lib()
     m = child.shape[0]
