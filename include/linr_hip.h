@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 13
+#define LINR_ABI_VERSION 14
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -620,6 +620,28 @@ LINR_API int     linr_ac_decode_cdf16(const uint16_t* cdf_h, int32_t lp, int32_t
 LINR_API int linr_ac_encode_binary_batch(const float* const* prob_h, const uint8_t* const* sym_h, const int64_t* n,
                                 int32_t n_streams, uint8_t* const* out_h, const int64_t* cap,
                                 int64_t* out_len, int32_t n_threads);
+/* The same coder fed with code values instead of probabilities (BinaryArithmeticCoding, models/module_utils.py:8-40; callers
+ * models/upsample.py:224-239): c1_h[i] = (rint((1 - p[i]) * 65534) + 1) & 0xFFFF, the one cdf entry a binary symbol needs,
+ * and the symbols as bits - symbol i is bit i & 31 of sym_h[i >> 5] (ceil(n / 32) words are read).  Interval update,
+ * renormalisation and termination are those of linr_ac_encode_binary / _decode_binary (one loop body serves both forms), so
+ * code values computed as above give the same bytes.  The decoder writes one byte per symbol, like linr_ac_decode_binary. */
+LINR_API int64_t linr_ac_encode_binary_codes(const uint16_t* c1_h, const uint32_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap);
+LINR_API int     linr_ac_decode_binary_codes(const uint16_t* c1_h, int64_t n, const uint8_t* in_h, int64_t in_len, uint8_t* sym_h);
+LINR_API int linr_ac_encode_binary_codes_batch(const uint16_t* const* c1_h, const uint32_t* const* sym_h, const int64_t* n,
+                                      int32_t n_streams, uint8_t* const* out_h, const int64_t* cap,
+                                      int64_t* out_len, int32_t n_threads);
+/* Those inputs computed on the DEVICE (csrc/ac_codes.hip), one launch on `stream`: what BinaryArithmeticCoding.encode
+ * (models/module_utils.py:8-40) derives from the probabilities and occupancy of CNP.encode (models/upsample.py:224-239) on the
+ * host.  probs [8][probs_ld] fp32 in [0, 1] (plane k = stage k, as linr_net_forward writes them), occ [n][occ_ld] fp32, 0 or
+ * non-zero, column k = stage k (a frame's occupancy BEHIND its zero row).  c1 [8][c1_ld] uint16 receives the code values - fp32
+ * 1 - p, then fp32 * 65534, two roundings as on the host, then round to nearest even, + 1, & 0xFFFF; sym [8][sym_ld] uint32 the
+ * bit planes: bit i & 31 of word i >> 5 of plane k = (occ[i][k] != 0), the unused high bits of word linr_ac_codes_sym_words(n) - 1
+ * zero.  Elements [n, c1_ld) of a code plane and words beyond linr_ac_codes_sym_words(n) = ceil(n / 32) are not written.  LINR_EINVAL
+ * for a NULL pointer, n < 0, probs_ld < n, c1_ld < n, sym_ld < words, occ_ld < 8 or n >= 2^27 - 1; n == 0 launches nothing.
+ * The kernel uses no LDS and belongs to no linr_prof_* / linr_debug_poison class (all 24 are taken). */
+LINR_API size_t linr_ac_codes_sym_words(int64_t n);
+LINR_API int linr_ac_codes(const float* probs, int64_t probs_ld, const float* occ, int32_t occ_ld, int64_t n, uint16_t* c1,
+                  int64_t c1_ld, uint32_t* sym, int64_t sym_ld, void* stream);
 
 /* ---- frame input (host) ----------------------------------------------------------------------------------------------
  * Body of an ASCII PLY (datautils/custom_dataset.py:9-14 read_ply_o3d - open3d's C++ reader - followed by :263-269, which keeps

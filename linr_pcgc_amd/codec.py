@@ -15,7 +15,7 @@ import torch
 
 from .function_utils import pack_bitstream, unpack_bitstream
 from .model_codec import Model_Estimate
-from .model_core import encode_streams
+from .model_core import codes_word_off, encode_streams, encode_streams_codes
 from .module_utils import octree_level_obj, qscTensor, unique_sorted  # noqa: F401
 
 # The probabilities the range coder sees must be reproduced BIT FOR BIT by the decoder, so the fp32 evaluation order of the
@@ -53,10 +53,13 @@ def model_shape(model):
     return {'scale_num': int(model.scale_num), 'block_layers': int(model.block_layers), 'hidden_channel_conv': int(model.hidden)}
 
 
-def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32'):
+def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32', device_codes=False):
     """encoder.encode_one_gop: quantise the model, then per frame ONE forward over all scales and 8 x scales
     independent arithmetic-coded streams (thread pool).  precision='bf16': the forward runs on the bf16 / uint8-weight
-    executor (BASELINE config[4]); the choice is recorded in side_info so that the decoder reproduces it."""
+    executor (BASELINE config[4]); the choice is recorded in side_info so that the decoder reproduces it.
+    device_codes=True: the coder's inputs are prepared on the GPU (model.frame_codes): 16-bit code values and one symbol bit cross to
+    the host per symbol instead of an fp32 probability and a byte, and the coder threads read the code values instead of computing
+    them.  The streams are byte for byte those of the default path, so nothing about it is recorded."""
     if n_threads is None:
         n_threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else 8))
     comp = Model_Estimate().compress_model(model, bitdepth, True, model_ori)
@@ -79,13 +82,17 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     per_job = max(1, n_threads // workers)
 
     def code(p_host, occ_host, row_off, n_scales):
-        ps, ss = [], []
+        # device_codes: p_host holds code values, occ_host bit planes in which every scale has words of its own (model.frame_codes)
+        ps, ss, ns = [], [], []
+        col_off = codes_word_off(row_off) if device_codes else row_off
         for i in range(n_scales):
             a, b = int(row_off[i]), int(row_off[i + 1])
+            sa, sb = int(col_off[i]), int(col_off[i + 1])
             for k in range(8):
                 ps.append(p_host[k, a:b])
-                ss.append(occ_host[k, a:b])
-        streams = encode_streams(ps, ss, per_job)
+                ss.append(occ_host[k, sa:sb])
+                ns.append(b - a)
+        streams = encode_streams_codes(ps, ss, ns, per_job) if device_codes else encode_streams(ps, ss, per_job)
         return [pack_bitstream(streams[8 * i:8 * i + 8]) for i in range(n_scales)]
 
     # Device side: forward of frame i+1 on the caller's stream while a copy stream moves the probabilities (fp32) and the
@@ -94,16 +101,22 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     RING = 4
     max_rows = max(f.rows for f in gop.frames)
     dev = gop.frames[0].device
-    p_pin = [torch.empty(8 * max_rows, dtype=torch.float32, pin_memory=True) for _ in range(RING)]
-    o_pin = [torch.empty(8 * max_rows, dtype=torch.uint8, pin_memory=True) for _ in range(RING)]
+    if device_codes:
+        max_cols = max(int(codes_word_off(f.row_off)[-1]) for f in gop.frames)
+        p_pin = [torch.empty(8 * max_rows, dtype=torch.uint16, pin_memory=True) for _ in range(RING)]
+        o_pin = [torch.empty(8 * max_cols, dtype=torch.uint32, pin_memory=True) for _ in range(RING)]
+    else:
+        p_pin = [torch.empty(8 * max_rows, dtype=torch.float32, pin_memory=True) for _ in range(RING)]
+        o_pin = [torch.empty(8 * max_rows, dtype=torch.uint8, pin_memory=True) for _ in range(RING)]
     copy_stream = torch.cuda.Stream(device=dev)
     jobs, bits_dev, pending = [], [], []
 
     def hand_over(entry, coder):
         slot, rows, f, keep, ev_c = entry
         ev_c.synchronize()
+        cols = keep[1].shape[1]
         p_host = p_pin[slot][:8 * rows].view(8, rows).numpy()
-        occ_host = o_pin[slot][:8 * rows].view(8, rows).numpy()
+        occ_host = o_pin[slot][:8 * cols].view(8, cols).numpy()
         jobs.append(coder.submit(code, p_host, occ_host, f.row_off, f.n_scales))
 
     with ThreadPoolExecutor(max_workers=workers) as coder:
@@ -111,15 +124,18 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
             slot = i % RING
             if i >= RING:
                 jobs[i - RING].result()                     # the worker that read this slot's buffers has finished
-            probs, bits = coded_model.frame_probs(f)
+            if device_codes:
+                probs, occ_t, bits = coded_model.frame_codes(f)          # code values and symbol bit planes: no transpose, no cast
+            else:
+                probs, bits = coded_model.frame_probs(f)
+                occ_t = f.occ.t().to(torch.uint8).contiguous()
             bits_dev.append(bits)
-            occ_t = f.occ.t().to(torch.uint8).contiguous()
             ev_f = torch.cuda.Event()
             ev_f.record()
             with torch.cuda.stream(copy_stream):
                 copy_stream.wait_event(ev_f)
                 p_pin[slot][:8 * f.rows].view(8, f.rows).copy_(probs, non_blocking=True)
-                o_pin[slot][:8 * f.rows].view(8, f.rows).copy_(occ_t, non_blocking=True)
+                o_pin[slot][:8 * occ_t.shape[1]].view(8, occ_t.shape[1]).copy_(occ_t, non_blocking=True)
                 ev_c = torch.cuda.Event()
                 ev_c.record(copy_stream)
             pending.append((slot, f.rows, f, (probs, occ_t), ev_c))         # keeps the device tensors alive until copied

@@ -169,21 +169,38 @@ inline void c1_block(const float* p, int n, uint32_t* c1) {
     for (; i < n; ++i) c1[i] = binary_c1(p[i]);
 }
 
-}  // namespace
+// Where the serial loops take their code values and symbols from.  A source hands out the code values of symbols
+// [base, base + m), m <= AC_CHUNK: from probabilities they are computed into a block (c1_block), ready-made ones (csrc/ac_codes.hip
+// computes them on the device) are read in place.
+struct CodesFromProbs {
+    const float* p; uint32_t c1[AC_CHUNK];
+    inline const uint32_t* block(int64_t base, int m) { c1_block(p + base, m, c1); return c1; }
+};
+struct CodesReady {
+    const uint16_t* c;
+    inline const uint16_t* block(int64_t base, int) const { return c + base; }
+};
+struct SymBytes {            // one byte per symbol, non-zero = 1
+    const uint8_t* s;
+    inline uint32_t mask(int64_t i) const { return s[i] ? 0xFFFFFFFFu : 0u; }
+};
+struct SymBits {             // bit i & 31 of word i >> 5
+    const uint32_t* w;
+    inline uint32_t mask(int64_t i) const { return 0u - ((w[i >> 5] >> (i & 31)) & 1u); }
+};
 
-extern "C" int64_t linr_ac_encode_binary(const float* prob_h, const uint8_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap) {
-    if (n < 0 || cap < 0 || (n > 0 && (!prob_h || !sym_h)) || (cap > 0 && !out_h)) return LINR_EINVAL;
+template <class Codes, class Syms>
+inline int64_t encode_binary_body(Codes codes, Syms syms, int64_t n, uint8_t* out_h, int64_t cap) {
     BitSinkFast sink(out_h, cap);
     uint32_t low = 0, high = 0xFFFFFFFFu;
     uint64_t pending = 0;
-    uint32_t c1[AC_CHUNK];
     for (int64_t base = 0; base < n; base += AC_CHUNK) {
         const int m = (int)(n - base < AC_CHUNK ? n - base : AC_CHUNK);
-        c1_block(prob_h + base, m, c1);
+        const auto* c1 = codes.block(base, m);
         for (int i = 0; i < m; ++i) {
             const uint64_t span = (uint64_t)high - (uint64_t)low + 1;
             const uint32_t t = (uint32_t)((span * c1[i]) >> 16);
-            const uint32_t one = sym_h[base + i] ? 0xFFFFFFFFu : 0u;
+            const uint32_t one = syms.mask(base + i);
             const uint32_t lt = low + t;
             high = (high & one) | ((lt - 1u) & ~one);
             low = (lt & one) | (low & ~one);
@@ -221,6 +238,20 @@ extern "C" int64_t linr_ac_encode_binary(const float* prob_h, const uint8_t* sym
     return sink.len <= cap ? sink.len : (int64_t)LINR_ENOSPC;
 }
 
+}  // namespace
+
+extern "C" int64_t linr_ac_encode_binary(const float* prob_h, const uint8_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap) {
+    if (n < 0 || cap < 0 || (n > 0 && (!prob_h || !sym_h)) || (cap > 0 && !out_h)) return LINR_EINVAL;
+    CodesFromProbs codes;
+    codes.p = prob_h;
+    return encode_binary_body(codes, SymBytes{sym_h}, n, out_h, cap);
+}
+
+extern "C" int64_t linr_ac_encode_binary_codes(const uint16_t* c1_h, const uint32_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap) {
+    if (n < 0 || cap < 0 || (n > 0 && (!c1_h || !sym_h)) || (cap > 0 && !out_h)) return LINR_EINVAL;
+    return encode_binary_body(CodesReady{c1_h}, SymBits{sym_h}, n, out_h, cap);
+}
+
 namespace {
 
 // Bit window of the binary decoder: 64 bits, MSB-aligned, refilled eight bytes at a time while eight whole bytes remain
@@ -252,17 +283,14 @@ struct BitWindow {
     }
 };
 
-}  // namespace
-
-extern "C" int linr_ac_decode_binary(const float* prob_h, int64_t n, const uint8_t* in_h, int64_t in_len, uint8_t* sym_h) {
-    if (n < 0 || in_len < 0 || (n > 0 && (!prob_h || !sym_h)) || (in_len > 0 && !in_h)) return LINR_EINVAL;
+template <class Codes>
+inline void decode_binary_body(Codes codes, int64_t n, const uint8_t* in_h, int64_t in_len, uint8_t* sym_h) {
     BitWindow src(in_h, in_len);
     src.refill();
     uint32_t low = 0, high = 0xFFFFFFFFu, value = src.take(32);
-    uint32_t c1[AC_CHUNK];
     for (int64_t base = 0; base < n; base += AC_CHUNK) {
         const int m = (int)(n - base < AC_CHUNK ? n - base : AC_CHUNK);
-        c1_block(prob_h + base, m, c1);
+        const auto* c1 = codes.block(base, m);
         for (int i = 0; i < m; ++i) {
             // torchac's binary search over [0, c1, *] returns symbol 1 iff target >= c1, i.e. iff
             //   ((value - low + 1) * 2^16 - 1) / span >= c1  <=>  (value - low + 1) * 2^16 > c1 * span
@@ -296,6 +324,21 @@ extern "C" int linr_ac_decode_binary(const float* prob_h, int64_t n, const uint8
             }
         }
     }
+}
+
+}  // namespace
+
+extern "C" int linr_ac_decode_binary(const float* prob_h, int64_t n, const uint8_t* in_h, int64_t in_len, uint8_t* sym_h) {
+    if (n < 0 || in_len < 0 || (n > 0 && (!prob_h || !sym_h)) || (in_len > 0 && !in_h)) return LINR_EINVAL;
+    CodesFromProbs codes;
+    codes.p = prob_h;
+    decode_binary_body(codes, n, in_h, in_len, sym_h);
+    return 0;
+}
+
+extern "C" int linr_ac_decode_binary_codes(const uint16_t* c1_h, int64_t n, const uint8_t* in_h, int64_t in_len, uint8_t* sym_h) {
+    if (n < 0 || in_len < 0 || (n > 0 && (!c1_h || !sym_h)) || (in_len > 0 && !in_h)) return LINR_EINVAL;
+    decode_binary_body(CodesReady{c1_h}, n, in_h, in_len, sym_h);
     return 0;
 }
 
@@ -335,10 +378,11 @@ extern "C" int linr_ac_decode_cdf16(const uint16_t* cdf_h, int32_t lp, int32_t c
     return 0;
 }
 
-extern "C" int linr_ac_encode_binary_batch(const float* const* prob_h, const uint8_t* const* sym_h, const int64_t* n,
-                                           int32_t n_streams, uint8_t* const* out_h, const int64_t* cap, int64_t* out_len,
-                                           int32_t n_threads) {
-    if (n_streams < 0 || (n_streams > 0 && (!prob_h || !sym_h || !n || !out_h || !cap || !out_len))) return LINR_EINVAL;
+namespace {
+
+// n_streams independent streams on a pool of threads that take them in order; one(i) codes stream i and returns its length
+template <class One>
+inline int encode_batch(int32_t n_streams, int32_t n_threads, int64_t* out_len, One one) {
     if (n_threads < 1) n_threads = 1;
     if (n_threads > n_streams) n_threads = n_streams;
     std::atomic<int> next(0);
@@ -347,7 +391,7 @@ extern "C" int linr_ac_encode_binary_batch(const float* const* prob_h, const uin
         for (;;) {
             const int i = next.fetch_add(1);
             if (i >= n_streams) return;
-            const int64_t r = linr_ac_encode_binary(prob_h[i], sym_h[i], n[i], out_h[i], cap[i]);
+            const int64_t r = one(i);
             out_len[i] = r;
             if (r < 0) err.store((int)r);
         }
@@ -360,4 +404,22 @@ extern "C" int linr_ac_encode_binary_batch(const float* const* prob_h, const uin
         for (auto& t : pool) t.join();
     }
     return err.load();
+}
+
+}  // namespace
+
+extern "C" int linr_ac_encode_binary_batch(const float* const* prob_h, const uint8_t* const* sym_h, const int64_t* n,
+                                           int32_t n_streams, uint8_t* const* out_h, const int64_t* cap, int64_t* out_len,
+                                           int32_t n_threads) {
+    if (n_streams < 0 || (n_streams > 0 && (!prob_h || !sym_h || !n || !out_h || !cap || !out_len))) return LINR_EINVAL;
+    return encode_batch(n_streams, n_threads, out_len,
+                        [&](int i) { return linr_ac_encode_binary(prob_h[i], sym_h[i], n[i], out_h[i], cap[i]); });
+}
+
+extern "C" int linr_ac_encode_binary_codes_batch(const uint16_t* const* c1_h, const uint32_t* const* sym_h, const int64_t* n,
+                                                 int32_t n_streams, uint8_t* const* out_h, const int64_t* cap, int64_t* out_len,
+                                                 int32_t n_threads) {
+    if (n_streams < 0 || (n_streams > 0 && (!c1_h || !sym_h || !n || !out_h || !cap || !out_len))) return LINR_EINVAL;
+    return encode_batch(n_streams, n_threads, out_len,
+                        [&](int i) { return linr_ac_encode_binary_codes(c1_h[i], sym_h[i], n[i], out_h[i], cap[i]); });
 }

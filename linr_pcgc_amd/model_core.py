@@ -265,6 +265,25 @@ class LINR_PCGC_Model(nn.Module):
         return probs, bits
 
     @torch.no_grad()
+    def frame_codes(self, frame, precision=None):
+        """frame_probs, then the range coder's inputs on the GPU (linr_ac_codes, csrc/ac_codes.hip) on the current stream:
+        c1 uint16 [8, rows], the code value of every probability; sym uint32 [8, words], the occupancy as bit planes; bits float64[1].
+        The coder cuts a frame into per-scale streams and the scales' row offsets are no multiples of 32, so every scale gets words of
+        its own: scale i's symbols are bits 0 .. n_i - 1 of the words from codes_word_off(frame.row_off)[i] on (one launch per scale)."""
+        probs, bits = self.frame_probs(frame, precision)
+        woff = codes_word_off(frame.row_off)
+        rows, words = frame.rows, int(woff[-1])
+        c1 = torch.empty((8, rows), dtype=torch.uint16, device=frame.device)
+        sym = torch.empty((8, words), dtype=torch.uint32, device=frame.device)
+        L, st = _lib.lib(), _lib.current_stream_handle()
+        for i in range(frame.n_scales):
+            a, n = int(frame.row_off[i]), int(frame.row_off[i + 1] - frame.row_off[i])
+            if n:
+                _lib.check(L.linr_ac_codes(probs.data_ptr() + 4 * a, rows, frame.occ.data_ptr() + 32 * a, 8, n, c1.data_ptr() + 2 * a, rows,
+                                           sym.data_ptr() + 4 * int(woff[i]), words, st), 'linr_ac_codes')
+        return c1, sym, bits
+
+    @torch.no_grad()
     def codec(self, inargs):
         """models/model_core.py:169-227: one forward, the 8 stages as ONE arithmetic-coded stream, timed enc/dec."""
         st1 = time.time()
@@ -399,6 +418,36 @@ def encode_streams(probs, symbols, n_threads=8):
     arr_l = (ctypes.c_int64 * n)()
     _lib.check(_lib.lib().linr_ac_encode_binary_batch(arr_p, arr_s, arr_n, n, arr_o, arr_c, arr_l, n_threads),
                'linr_ac_encode_binary_batch')
+    return [outs[i][:arr_l[i]].tobytes() for i in range(n)]
+
+
+def codes_word_off(row_off):
+    """Word offsets of the scales' symbol bit planes in what frame_codes returns: scale i owns ceil(n_i / 32) words."""
+    n = np.diff(np.asarray(row_off, dtype=np.int64))
+    off = np.zeros(len(n) + 1, dtype=np.int64)
+    off[1:] = np.cumsum((n + 31) // 32)
+    return off
+
+
+def encode_streams_codes(c1s, syms, ns, n_threads=8):
+    """encode_streams from code values and symbol bit planes (linr_ac_encode_binary_codes_batch): stream i has ns[i] symbols,
+    c1s[i] uint16 [>= ns[i]], syms[i] uint32 [>= ceil(ns[i] / 32)], bit j & 31 of word j >> 5 = symbol j."""
+    import ctypes
+    n = len(c1s)
+    ns = [int(v) for v in ns]
+    c1s = [np.ascontiguousarray(c, dtype=np.uint16).reshape(-1) for c in c1s]
+    syms = [np.ascontiguousarray(w, dtype=np.uint32).reshape(-1) for w in syms]
+    if any(c.size < m or w.size < (m + 31) // 32 for c, w, m in zip(c1s, syms, ns)):
+        raise ValueError('a stream has fewer code values or symbol words than symbols')
+    outs = [np.empty(2 * m + 64, dtype=np.uint8) for m in ns]
+    arr_c = (ctypes.c_void_p * n)(*[c.ctypes.data for c in c1s])
+    arr_s = (ctypes.c_void_p * n)(*[w.ctypes.data for w in syms])
+    arr_o = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
+    arr_n = (ctypes.c_int64 * n)(*ns)
+    arr_cap = (ctypes.c_int64 * n)(*[o.size for o in outs])
+    arr_l = (ctypes.c_int64 * n)()
+    _lib.check(_lib.lib().linr_ac_encode_binary_codes_batch(arr_c, arr_s, arr_n, n, arr_o, arr_cap, arr_l, n_threads),
+               'linr_ac_encode_binary_codes_batch')
     return [outs[i][:arr_l[i]].tobytes() for i in range(n)]
 
 

@@ -53,6 +53,9 @@ def parse(argv=None):
     ap.add_argument('--train-precision', '--train_precision', dest='train_precision', default=None, choices=['f32', 'bf16'],
                     help='arithmetic of the overfit step: f32 (the headline), or bf16 feature / gradient rows with fp32 master weights and '
                          'accumulation (BASELINE config[4] "bf16 SparseConv"; hidden_channel_conv 8, block_layers 1).  Default: follows --precision')
+    ap.add_argument('--device-codes', '--device_codes', dest='device_codes', action='store_true',
+                    help="the range coder's 16-bit code values and symbol bits are computed on the GPU (linr_ac_codes): 17 bits per symbol "
+                         'cross to the host instead of 40; the streams are byte for byte those of the default path')
     ap.add_argument('--decode', action='store_true', help='decode every GOP again and check it is lossless')
     ap.add_argument('--mid-test', action='store_true',
                     help='main.py --mid_test: measure the model through Test_one_gop (model.codec) at epochs 0..9 and every --check-freq-th '
@@ -204,7 +207,8 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
         torch.cuda.synchronize()
         t1 = time.time()
         enc = codec.encode_gop(model, overfit.gen_model(gop.scale_num, device, block_layers=getattr(args, 'block_layers', 1), hidden=getattr(args, 'hidden_channel_conv', 8)), gop,
-                               getattr(args, 'model_bitdepth', 8), precision=getattr(args, 'precision', 'f32'))
+                               getattr(args, 'model_bitdepth', 8), precision=getattr(args, 'precision', 'f32'),
+                               device_codes=getattr(args, 'device_codes', False))
         res_dir = os.path.join(args.out, 'result_enc', gop_parallel.gop_name(group))
         codec.write_gop(enc, res_dir)
         torch.cuda.synchronize()
