@@ -350,6 +350,83 @@ __global__ __launch_bounds__(LINR_BLOCK) void bconv_k(BArgs a) {
     }
 }
 
+// ---- one group's operands, per MODE (the pattern of common.h: ConvGroup ...) ------------------------------------------------------
+// A caller describes every group of a launch with one of these (a plain launch is an array of one); bfill alone writes BArgs' per-group
+// slots: base pointers from element 0, the differences of the others, every slot bconv_k<MODE> reads.  Matrices are the group's own
+// pointers, NULL in every group where the launch has none; parameters stay OFFSETS into the flat vector (SRC 0 indexes both the codes
+// and their de-quantised copy with them).  The executors set what all groups share (map, parameters, weight images) beforehand.
+struct BConvGroup {          // MODE 0: out = conv3(in; w) + b (+ res) (ReLU per launch); the kernel is [27][cin_live][8]
+    static constexpr int MODE = 0;
+    const bf16_t* in; bf16_t* out; const bf16_t* res;
+    int64_t w, b;
+    int cin_live;
+};
+struct BHeadGroup {          // MODE 1: c = conv3(in; w) + b -> c_out (training only), p = sigmoid(h_w2 . relu(h_w1 c + h_b1) + h_b2)
+    static constexpr int MODE = 1;
+    const bf16_t* in; bf16_t* c_out;
+    int64_t w, b, h_w1, h_b1, h_w2, h_b2;
+    int stage;               // the target column, the slice of p_out [8][n] and of the bits' block partials
+};
+struct BPwGroup {            // MODE 2: H = [relu(conv3(A; w00) + b00) | relu(A @ w10 + b10)]
+    static constexpr int MODE = 2;
+    const bf16_t* A; bf16_t* H;
+    int64_t w00, b00, w10, b10;
+};
+struct BDualGroup {          // MODE 3: M = relu(conv3(H[:, 4:8]; w11) + b11) (stored in training only), I = [conv3(H[:, 0:4]; w01) + b01 | M @ w12 + b12] + X
+    static constexpr int MODE = 3;
+    const bf16_t *H, *X; bf16_t *I, *M;
+    int64_t w01, b01, w11, b11, w12, b12;
+};
+static inline BHeadGroup bhead_group(const Layout& L, int k, const bf16_t* in, bf16_t* c_out) {
+    return {in, c_out, L.pr_w[k], L.pr_b[k], L.h0_w[k], L.h0_b[k], L.h2_w[k], L.h2_b[k], k};
+}
+static inline BPwGroup bpw_group(const IncP& q, const bf16_t* A, bf16_t* H) { return {A, H, q.c00_w, q.c00_b, q.c10_w, q.c10_b}; }
+static inline BDualGroup bdual_group(const IncP& q, const bf16_t* H, const bf16_t* X, bf16_t* I, bf16_t* M) {
+    return {H, X, I, M, q.c01_w, q.c01_b, q.c11_w, q.c11_b, q.c12_w, q.c12_b};
+}
+
+static inline int64_t bdiff(const bf16_t* p, const bf16_t* p0) { return p0 ? p - p0 : 0; }
+static inline int bfill(BArgs& a, const BConvGroup* g, int ng, int relu) {
+    if (ng < 1 || ng > BMAXG) return LINR_EINVAL;
+    a.in = g[0].in; a.out = g[0].out; a.res = g[0].res; a.relu = relu;
+    for (int i = 0; i < ng; ++i) {
+        a.g_in[i] = bdiff(g[i].in, a.in); a.g_out[i] = bdiff(g[i].out, a.out); a.g_res[i] = bdiff(g[i].res, a.res);
+        a.w[i] = g[i].w; a.b[i] = g[i].b; a.cin[i] = g[i].cin_live;
+    }
+    return 0;
+}
+// target: the occupancy fp32 [n][8] the bits are taken against (read only with partial != NULL); partial: [8][linr_grid(n, 256)] or NULL
+static inline int bfill(BArgs& a, const BHeadGroup* g, int ng, const float* target, float* p_out, double* partial) {
+    if (ng < 1 || ng > BMAXG) return LINR_EINVAL;
+    a.in = g[0].in; a.out = g[0].c_out;
+    a.target = target; a.target_ld = 8; a.p_out = p_out; a.partial = partial;
+    for (int i = 0; i < ng; ++i) {
+        a.g_in[i] = bdiff(g[i].in, a.in); a.g_out[i] = bdiff(g[i].c_out, a.out);
+        a.w[i] = g[i].w; a.b[i] = g[i].b;
+        a.h_w1[i] = g[i].h_w1; a.h_b1[i] = g[i].h_b1; a.h_w2[i] = g[i].h_w2; a.h_b2[i] = g[i].h_b2;
+        a.t_col[i] = g[i].stage; a.p_off[i] = g[i].stage * a.n; a.part_off[i] = (int64_t)g[i].stage * linr_grid(a.n, LINR_BLOCK);
+    }
+    return 0;
+}
+static inline int bfill(BArgs& a, const BPwGroup* g, int ng) {
+    if (ng < 1 || ng > BMAXG) return LINR_EINVAL;
+    a.in = g[0].A; a.out = g[0].H;
+    for (int i = 0; i < ng; ++i) {
+        a.g_in[i] = bdiff(g[i].A, a.in); a.g_out[i] = bdiff(g[i].H, a.out);
+        a.w[i] = g[i].w00; a.b[i] = g[i].b00; a.w2[i] = g[i].w10; a.b2[i] = g[i].b10;
+    }
+    return 0;
+}
+static inline int bfill(BArgs& a, const BDualGroup* g, int ng) {
+    if (ng < 1 || ng > BMAXG) return LINR_EINVAL;
+    a.in = g[0].H; a.out = g[0].I; a.res = g[0].X; a.m_out = g[0].M;
+    for (int i = 0; i < ng; ++i) {
+        a.g_in[i] = bdiff(g[i].H, a.in); a.g_out[i] = bdiff(g[i].I, a.out); a.g_res[i] = bdiff(g[i].X, a.res); a.g_m[i] = bdiff(g[i].M, a.m_out);
+        a.w[i] = g[i].w01; a.b[i] = g[i].b01; a.w2[i] = g[i].w11; a.b2[i] = g[i].b11; a.w3[i] = g[i].w12; a.b3[i] = g[i].b12;
+    }
+    return 0;
+}
+
 
 // occupancy fp32 [n][8] -> bf16 [n][8] (exact: 0 / 1)
 [[maybe_unused]] static __global__ __launch_bounds__(LINR_BLOCK) void occ_bf16_k(const float* __restrict__ occ, int64_t n, bf16_t* __restrict__ out) {

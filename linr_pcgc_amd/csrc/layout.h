@@ -51,6 +51,8 @@ static inline void layout_block(BlockP& b, int cin, int nl, int64_t& cur) {
     b.b_w = take(cur, 27 * 8 * 8);    b.b_b = take(cur, 8);
 }
 
+static inline const BlockP& slot_block(const Layout& L, int b) { return b == 0 ? L.block_in : L.outter[b - 1]; }   // block of slot b
+
 static inline bool make_layout(Layout& L, int S, int BL = 1) {
     if (S < 1 || S > MAX_SCALES || BL < 1 || BL > MAX_BL) return false;
     L.S = S;
@@ -82,6 +84,17 @@ static inline int linr_frame_layout(const linr_frame* f, int block_layers, Layou
     if (f->row_off_h[0] != 0 || f->row_off_h[f->n_scales] != f->rows) return LINR_EINVAL;
     for (int s = 0; s < f->n_scales; ++s)
         if (f->row_off_h[s + 1] < f->row_off_h[s] || f->scale_idx_h[s] < 0 || f->scale_idx_h[s] >= f->model_scale_num) return LINR_EINVAL;
+    return 0;
+}
+
+// scale_steps_h of the training steps (NULL: none), for a frame that has passed linr_frame_layout with L: no negative entry, and a scale
+// that has rows in this frame cannot be "never started".  LINR_EINVAL or 0.
+static inline int linr_scale_steps_check(const linr_frame* f, const Layout& L, const int64_t* scale_steps_h) {
+    if (!scale_steps_h) return 0;
+    for (int s = 0; s < L.S; ++s)
+        if (scale_steps_h[s] < 0) return LINR_EINVAL;
+    for (int j = 0; j < f->n_scales; ++j)
+        if (f->row_off_h[j + 1] > f->row_off_h[j] && scale_steps_h[f->scale_idx_h[j]] < 1) return LINR_EINVAL;
     return 0;
 }
 

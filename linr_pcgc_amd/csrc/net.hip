@@ -428,7 +428,7 @@ __global__ __launch_bounds__(LINR_BLOCK) void wgrad_reduce_k(const float* __rest
     if (q == 0 && p < total) gsum[p] = ((part[0][lp] + part[1][lp]) + part[2][lp]) + part[3][lp];
 }
 
-struct Ctx {
+struct Ctx : LinrShortList {
     const linr_frame* f;
     const float* P;
     Arena A;
@@ -436,14 +436,6 @@ struct Ctx {
     hipStream_t s;           // the caller's stream
     int64_t R;
     int64_t nbr_ld;
-    int nb;                  // persistent blocks of the weight-gradient kernels = partial rows of the slab for this frame
-    std::vector<LinrShortRange> shortr;      // parameter ranges of this backward pass that hold fewer than nb slab rows (fused launches)
-    // a fused launch writes only `rows` slab rows for parameters [b, e) (no zero fill): the final reduction stops there.  The
-    // table holds every range of a backward pass: 8 blocks x 2 + the prune convs + block_in's first conv + the 7 outter first
-    // convs + up to 16 scale-context MLPs = 41
-    void note_short(int64_t b, int64_t e, int rows) {
-        if (rows < nb) shortr.push_back({b, e, rows});          // (short_push aborts if the kernel's table of MAX_SHORT overflows)
-    }
 };
 
 // Persistent blocks per weight-gradient launch (multiples of 32: wgrad_reduce_k's association).  Every block ends with a fold
@@ -635,10 +627,9 @@ static LayerBufs layer_bufs(Arena& a, int b, int l) {
     return {a.Hx[l - 1], a.Mx[l - 1], a.Ix[l - 1], a.gIx[l - 1], a.gMx[l - 1], a.gHx[l - 1]};
 }
 
-// Block of slot b, and the launchers' per-group operands (common.h) of its pieces: Inception layer q with input X and matrices t;
+// Block of slot b (layout.h: slot_block), and the launchers' per-group operands (common.h) of its pieces: Inception layer q with input X and matrices t;
 // the block's tail conv with output gradient gO behind that layer; head k.  The grouped launches fill one array element per slot
 // with these, the staged / per-block paths launch a single one.
-static const BlockP& slot_block(const Layout& L, int b) { return b == 0 ? L.block_in : L.outter[b - 1]; }
 static ConvPwGroup pw_fwd_group(const float* P, const IncP& q, const float* X, const LayerBufs& t) {
     return {X, P + q.c00_w, P + q.c00_b, P + q.c10_w, P + q.c10_b, t.H};
 }
@@ -1237,12 +1228,7 @@ extern "C" int linr_net_train_step(const linr_frame* f, float* params, float* ar
     if (!exp_avg || !exp_avg_sq || !bits_acc || step < 1) return LINR_EINVAL;
     Ctx c;
     TRY(check_frame(f, params, arena, arena_bytes, c));
-    if (scale_steps_h) {          // checked before anything is launched
-        for (int s = 0; s < c.L.S; ++s)
-            if (scale_steps_h[s] < 0) return LINR_EINVAL;
-        for (int j = 0; j < f->n_scales; ++j)          // a scale of this frame cannot be "never started"
-            if (f->row_off_h[j + 1] > f->row_off_h[j] && scale_steps_h[f->scale_idx_h[j]] < 1) return LINR_EINVAL;
-    }
+    TRY(linr_scale_steps_check(f, c.L, scale_steps_h));          // before anything is launched
     TRY(linr_net_forward(f, params, arena, arena_bytes, 0, 8, nullptr, bits_acc, stream));
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;

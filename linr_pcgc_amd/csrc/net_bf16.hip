@@ -84,49 +84,17 @@ static BArgs base_args(const BCtx& c) {
     BArgs a = BArgs();
     a.lo = c.f->nbr_lo; a.mask = c.f->nbr_mask; a.ld = c.f->nbr_ld; a.n = c.R;
     a.codes = c.codes; a.minv = c.minv; a.range = c.range; a.pf = c.A.PF;
-    for (int g = 0; g < BMAXG; ++g) a.cin[g] = 8;
     return a;
 }
 
-template <int MODE>
-static int blaunch(const BCtx& c, const BArgs& a, int groups) {
+// the one launch of bconv_k<G::MODE>: g[0 .. ng) are the groups (bf16_common.h), x what bfill takes per launch
+template <class G, class... X>
+static int blaunch(const BCtx& c, const G* g, int ng, X... x) {
+    BArgs a = base_args(c);
+    TRY(bfill(a, g, ng, x...));
     linr_poison_hook(c.s, 14);
-    bconv_k<MODE><<<dim3(linr_grid(c.R, LINR_BLOCK), groups), LINR_BLOCK, 0, c.s>>>(a);
+    bconv_k<G::MODE><<<dim3(linr_grid(c.R, LINR_BLOCK), ng), LINR_BLOCK, 0, c.s>>>(a);
     return linr_launch_rc();
-}
-
-// conv3 cin->8: groups share `in`/`out`/`res` base pointers through element offsets
-static int bconv_plain(const BCtx& c, const bf16_t* in, bf16_t* out, const bf16_t* res, int relu, int groups, const int64_t* g_in,
-                       const int64_t* g_out, const int64_t* g_res, const int64_t* w, const int64_t* b, const int* cin) {
-    BArgs a = base_args(c);
-    a.in = in; a.out = out; a.res = res; a.relu = relu;
-    for (int g = 0; g < groups; ++g) {
-        a.g_in[g] = g_in ? g_in[g] : 0; a.g_out[g] = g_out ? g_out[g] : 0; a.g_res[g] = g_res ? g_res[g] : 0;
-        a.w[g] = w[g]; a.b[g] = b[g]; a.cin[g] = cin ? cin[g] : 8;
-    }
-    return blaunch<0>(c, a, groups);
-}
-
-// one Inception layer: X -> H -> I (two launches), per group
-static int binception(const BCtx& c, const bf16_t* X, bf16_t* H, bf16_t* I, int groups, const int64_t* gX, const int64_t* gH,
-                      const int64_t* gI, const IncP* const* q) {
-    {
-        BArgs a = base_args(c);
-        a.in = X; a.out = H;
-        for (int g = 0; g < groups; ++g) {
-            a.g_in[g] = gX ? gX[g] : 0; a.g_out[g] = gH ? gH[g] : 0;
-            a.w[g] = q[g]->c00_w; a.b[g] = q[g]->c00_b; a.w2[g] = q[g]->c10_w; a.b2[g] = q[g]->c10_b;
-        }
-        TRY(blaunch<2>(c, a, groups));
-    }
-    BArgs a = base_args(c);
-    a.in = H; a.out = I; a.res = X;
-    for (int g = 0; g < groups; ++g) {
-        a.g_in[g] = gH ? gH[g] : 0; a.g_out[g] = gI ? gI[g] : 0; a.g_res[g] = gX ? gX[g] : 0;
-        a.w[g] = q[g]->c01_w; a.b[g] = q[g]->c01_b; a.w2[g] = q[g]->c11_w; a.b2[g] = q[g]->c11_b;
-        a.w3[g] = q[g]->c12_w; a.b3[g] = q[g]->c12_b;
-    }
-    return blaunch<3>(c, a, groups);
 }
 
 __global__ __launch_bounds__(LINR_BLOCK) void badd_rows_k(const bf16_t* __restrict__ src, int64_t n, bf16_t* __restrict__ dst) {
@@ -143,36 +111,28 @@ __global__ __launch_bounds__(LINR_BLOCK) void badd_rows_k(const bf16_t* __restri
 // make_block for one block slot (upsample.py:88-97), single launch group
 static int bblock(const BCtx& c, const BlockP& bp, const bf16_t* in, int slot, const bf16_t* res) {
     const BArena& a = c.A;
-    const int cin = bp.cin;
-    TRY(bconv_plain(c, in, a.A[slot], nullptr, 1, 1, nullptr, nullptr, nullptr, &bp.a_w, &bp.a_b, &cin));
+    const BConvGroup first = {in, a.A[slot], nullptr, bp.a_w, bp.a_b, bp.cin};
+    TRY(blaunch(c, &first, 1, 1));
     const bf16_t* X = a.A[slot];
     bf16_t* Il = nullptr;
-    for (int l = 0; l < bp.nl; ++l) {
+    for (int l = 0; l < bp.nl; ++l) {          // one Inception layer: X -> H -> I (two launches)
         bf16_t* H = l == 0 ? a.H[slot] : a.Hx[l - 1];
         bf16_t* I = l == 0 ? a.I[slot] : a.Ix[l - 1];
-        const IncP* q = &bp.inc[l];
-        TRY(binception(c, X, H, I, 1, nullptr, nullptr, nullptr, &q));
+        const BPwGroup pw = bpw_group(bp.inc[l], X, H);
+        TRY(blaunch(c, &pw, 1));
+        const BDualGroup du = bdual_group(bp.inc[l], H, X, I, nullptr);
+        TRY(blaunch(c, &du, 1));
         X = I; Il = I;
     }
     if (bp.nl > 1) badd_rows_k<<<linr_grid(c.R, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(a.A[slot], c.R, Il);     // resnet.py:160-161
-    return bconv_plain(c, Il, a.O[slot], res, 0, 1, nullptr, nullptr, nullptr, &bp.b_w, &bp.b_b, nullptr);
+    const BConvGroup last = {Il, a.O[slot], res, bp.b_w, bp.b_b, 8};
+    return blaunch(c, &last, 1, 0);
 }
 
 static int bheads(const BCtx& c, int k0, int k1, float* probs_stage_major, double* part) {
-    const BArena& a = c.A;
-    BArgs h = base_args(c);
-    h.in = a.O[k0];
-    h.target = part ? c.f->occ : nullptr; h.target_ld = 8;
-    h.p_out = probs_stage_major; h.partial = part;
-    const int64_t nblk = linr_grid(c.R, LINR_BLOCK);
-    for (int k = k0; k < k1; ++k) {
-        const int g = k - k0;
-        h.g_in[g] = a.O[k] - a.O[k0];
-        h.w[g] = c.L.pr_w[k]; h.b[g] = c.L.pr_b[k];
-        h.h_w1[g] = c.L.h0_w[k]; h.h_b1[g] = c.L.h0_b[k]; h.h_w2[g] = c.L.h2_w[k]; h.h_b2[g] = c.L.h2_b[k];
-        h.t_col[g] = k; h.p_off[g] = (int64_t)k * c.R; h.part_off[g] = (int64_t)k * nblk;
-    }
-    return blaunch<1>(c, h, k1 - k0);
+    BHeadGroup h[8];
+    for (int k = k0; k < k1; ++k) h[k - k0] = bhead_group(c.L, k, c.A.O[k], nullptr);
+    return blaunch(c, h, k1 - k0, part ? c.f->occ : nullptr, probs_stage_major, part);
 }
 
 extern "C" int linr_net_forward_bf16(const linr_frame* f, const uint8_t* codes, float min_param, float max_param, void* arena,
@@ -207,17 +167,21 @@ extern "C" int linr_net_forward_bf16(const linr_frame* f, const uint8_t* codes, 
     if (stage_begin == 0 && stage_end == 8) {
         // teacher-forced: the 7 outter blocks and the 8 heads as grouped launches (same kernels, same per-row arithmetic as
         // the staged path below)
-        int64_t gA[7], gH[7], gI[7], gO[7], zero7[7], aw[7], ab[7], bw[7], bb[7];
-        int cin[7];
-        const IncP* q[7];
+        BConvGroup first[7], last[7];
+        BPwGroup pw[7];
+        BDualGroup du[7];
         for (int g = 0; g < 7; ++g) {
             const BlockP& bp = L.outter[g];
-            gA[g] = a.A[g + 1] - a.A[1]; gH[g] = a.H[g + 1] - a.H[1]; gI[g] = a.I[g + 1] - a.I[1]; gO[g] = a.O[g + 1] - a.O[1];
-            zero7[g] = 0; aw[g] = bp.a_w; ab[g] = bp.a_b; bw[g] = bp.b_w; bb[g] = bp.b_b; cin[g] = g + 1; q[g] = &bp.inc[0];
+            const int s = g + 1;
+            first[g] = {a.OCC, a.A[s], nullptr, bp.a_w, bp.a_b, bp.cin};
+            pw[g] = bpw_group(bp.inc[0], a.A[s], a.H[s]);
+            du[g] = bdual_group(bp.inc[0], a.H[s], a.A[s], a.I[s], nullptr);
+            last[g] = {a.I[s], a.O[s], a.O[0], bp.b_w, bp.b_b, 8};
         }
-        TRY(bconv_plain(c, a.OCC, a.A[1], nullptr, 1, 7, zero7, gA, nullptr, aw, ab, cin));
-        TRY(binception(c, a.A[1], a.H[1], a.I[1], 7, gA, gH, gI, q));
-        TRY(bconv_plain(c, a.I[1], a.O[1], a.O[0], 0, 7, gI, gO, zero7, bw, bb, nullptr));
+        TRY(blaunch(c, first, 7, 1));
+        TRY(blaunch(c, pw, 7));
+        TRY(blaunch(c, du, 7));
+        TRY(blaunch(c, last, 7, 0));
         TRY(bheads(c, 0, 8, probs, part));
     } else {
         for (int k = stage_begin; k < stage_end; ++k) {

@@ -2,8 +2,19 @@
 #pragma once
 #include "common.h"
 #include "layout.h"
+#include <vector>
 
 struct LinrShortRange { int64_t b, e; int rows; };     // parameters [b, e) hold partials in the first `rows` slab rows only
+// Base of both training executors' contexts: a fused launch writes only `rows` slab rows for parameters [b, e) (no zero fill), the
+// final reduction stops there.  The table holds every such range of a backward pass: 8 blocks x 2 + the prune convs + block_in's
+// first conv + the 7 outter first convs + up to 16 scale-context MLPs = 41
+struct LinrShortList {
+    int nb;                  // persistent blocks of the weight-gradient kernels = partial rows of the slab for this frame
+    std::vector<LinrShortRange> shortr;
+    void note_short(int64_t b, int64_t e, int rows) {
+        if (rows < nb) shortr.push_back({b, e, rows});          // (csrc/net.hip: short_push aborts if the kernel's table overflows)
+    }
+};
 __attribute__((visibility("hidden")))
 int linr_bwd_tail_launch(const linr_frame* f, const Layout& L, const float* P, const float* gx0, const float* hid, float* big,
                          float* gsum, int nb, const LinrShortRange* sh, int nsh, hipStream_t stream);

@@ -84,6 +84,56 @@ struct BbArgs {
     int64_t wp[TB_MAXG], bp[TB_MAXG];          // EPI 3: conv1_2;  KIND 2: conv1_0
     int cin[TB_MAXG];                          // KIND 0: input channels of the kernel [27][cin][8]
 };
+// One group's operands per KIND (the pattern of common.h: Conv88BwdGroup ...): matrices are the group's own pointers, *_off offsets
+// into the flat parameter vector = into a row of the weight-gradient slab.  bb_fill alone writes BbArgs' per-group slots.
+struct Bb88Group {           // KIND 0: out = bwd(g; W) and the gradients of W / its bias from xin
+    static constexpr int KIND = 0;
+    const bf16_t *g, *xin; bf16_t* out;
+    int64_t w_off, b_off;
+    int cin;
+    const bf16_t* M; bf16_t* G2;         // EPI 3: G2 = [out[:, 0:4] | (out[:, 4:8] @ W12^T) * (M > 0)], conv1_2's gradients
+    int64_t w12_off, b12_off;
+    float* out_f32;                      // TB_OUT_F32 (a single group): out as fp32 [n][8] instead
+};
+struct BbDualGroup {         // KIND 1: gH = [bwd(G2[:, 0:4]; W01) | bwd(G2[:, 4:8]; W11)] * (H > 0)
+    static constexpr int KIND = 1;
+    const bf16_t *G2, *H; bf16_t* gH;
+    int64_t w01_off, b01_off, w11_off, b11_off;
+};
+struct BbC00Group {          // KIND 2: gA = (bwd(gH[:, 0:4]; W00) + gI + gH[:, 4:8] @ W10^T) * (A > 0)
+    static constexpr int KIND = 2;
+    const bf16_t *gH, *A, *gI; bf16_t* gA;
+    int64_t w00_off, b00_off, w10_off, b10_off;
+};
+static int bb_fill(BbArgs& a, const Bb88Group* g, int ng) {
+    if (ng < 1 || ng > TB_MAXG || (g[0].out_f32 && ng != 1)) return LINR_EINVAL;
+    a.g = g[0].g; a.xin = g[0].xin; a.out = g[0].out; a.m = g[0].M; a.g2 = g[0].G2;
+    a.out_f32 = g[0].out_f32; a.flags = g[0].out_f32 ? TB_OUT_F32 : 0u;
+    for (int i = 0; i < ng; ++i) {
+        a.g_g[i] = g[i].g - a.g; a.g_x[i] = g[i].xin - a.xin; a.g_out[i] = bdiff(g[i].out, a.out);
+        a.g_m[i] = bdiff(g[i].M, a.m); a.g_g2[i] = bdiff(g[i].G2, a.g2);
+        a.w[i] = g[i].w_off; a.b[i] = g[i].b_off; a.wp[i] = g[i].w12_off; a.bp[i] = g[i].b12_off; a.cin[i] = g[i].cin;
+    }
+    return 0;
+}
+static int bb_fill(BbArgs& a, const BbDualGroup* g, int ng) {
+    if (ng < 1 || ng > TB_MAXG) return LINR_EINVAL;
+    a.g = g[0].G2; a.xin = g[0].H; a.out = g[0].gH;
+    for (int i = 0; i < ng; ++i) {
+        a.g_g[i] = g[i].G2 - a.g; a.g_x[i] = g[i].H - a.xin; a.g_out[i] = g[i].gH - a.out;
+        a.w[i] = g[i].w01_off; a.b[i] = g[i].b01_off; a.w1[i] = g[i].w11_off; a.b1[i] = g[i].b11_off;
+    }
+    return 0;
+}
+static int bb_fill(BbArgs& a, const BbC00Group* g, int ng) {
+    if (ng < 1 || ng > TB_MAXG) return LINR_EINVAL;
+    a.g = g[0].gH; a.xin = g[0].A; a.out = g[0].gA; a.res = g[0].gI;
+    for (int i = 0; i < ng; ++i) {
+        a.g_g[i] = g[i].gH - a.g; a.g_x[i] = g[i].A - a.xin; a.g_out[i] = g[i].gA - a.out; a.g_res[i] = g[i].gI - a.res;
+        a.w[i] = g[i].w00_off; a.b[i] = g[i].b00_off; a.wp[i] = g[i].w10_off; a.bp[i] = g[i].b10_off;
+    }
+    return 0;
+}
 
 template <int KIND> struct BbT {
     static constexpr int CT = KIND == 0 ? 4 : 8;                // taps per chunk = taps per weight-gradient instruction
@@ -501,6 +551,15 @@ static void tb_grid(int64_t n, int nb, int ngroups, int& tiles_per_wave, int& bl
     blocks = (int)((t64 + BB_WAVES * m - 1) / (BB_WAVES * m));
     if (blocks < 1) blocks = 1;
 }
+// the one launch of bbwd_k<G::KIND, EPI>: `a` holds what the groups share, g[0 .. ng) the groups; *rows = slab rows written (at most nb)
+template <int EPI, class G>
+static int bb_run(BbArgs a, const G* g, int ng, int nb, int* rows, hipStream_t s) {
+    TRY(bb_fill(a, g, ng));
+    if (EPI == 3 && (!a.m || !a.g2)) return LINR_EINVAL;
+    tb_grid(a.n, nb, ng, a.tiles_per_wave, *rows);
+    bbwd_k<G::KIND, EPI><<<dim3(*rows, ng), BB_WAVES * 64, 0, s>>>(a);
+    return linr_launch_rc();
+}
 
 // ---- weight-block images of the forward kernels, packed once per step ------------------------------------------------------------------
 // Every forward convolution keeps its bf16 weight blocks (the A operands of v_mfma_f32_4x4x4_16b_bf16) in registers; building them from
@@ -596,6 +655,11 @@ struct BoArgs {
     const int32_t* lo;  const uint32_t* mask;  int64_t ld, n;
     int64_t b[7], g_out[7];
 };
+struct BOcc7Group { bf16_t* A[7]; };                   // the seven outputs; the biases are the Layout's outter[g].a_b
+static void bo_fill(BoArgs& o, const BOcc7Group& v, const Layout& L) {
+    o.out = v.A[0];
+    for (int g = 0; g < 7; ++g) { o.b[g] = L.outter[g].a_b; o.g_out[g] = v.A[g] - v.A[0]; }
+}
 
 // forward: lane = output row, 540 weight blocks (27 taps x 20, images TP_OCC.. of tpack_k) in 68 registers, 14 accumulators; the arithmetic
 // of bconv_k<0> per group (same blocks, same tap order, fp32 accumulation from the bias) - bit-identical to seven separate launches
@@ -783,6 +847,11 @@ struct OwArgs {
     float* big;  int64_t block_stride;
     int64_t g_g[7], w[7], b[7];
 };
+struct BOcc7WgradGroup { const bf16_t* gA[7]; };       // the seven output gradients; kernels / biases are the Layout's outter[g].a_w / a_b
+static void ow_fill(OwArgs& o, const BOcc7WgradGroup& v, const Layout& L) {
+    o.g = v.gA[0];
+    for (int g = 0; g < 7; ++g) { o.g_g[g] = v.gA[g] - v.gA[0]; o.w[g] = L.outter[g].a_w; o.b[g] = L.outter[g].a_b; }
+}
 
 __global__ __launch_bounds__(OW_WAVES * 64, 2) void bocc_wgrad7_k(OwArgs a) {
     extern __shared__ uint4 smem[];                                            // OW_WAVES * OW_SLOTS * BB_SLOT bytes
@@ -912,6 +981,19 @@ struct THeadArgs {
     int64_t w1[8], b1[8], w2[8], b2[8];
     int active;
 };
+struct THeadGroup {          // one head: the stored C, its probabilities and target column in, gC out; offsets of the MLP's parameters
+    const bf16_t* c; const float *p, *target; bf16_t* gc;
+    int64_t w1_off, b1_off, w2_off, b2_off;
+};
+static int th_fill(THeadArgs& h, const THeadGroup* g, int ng) {
+    if (ng < 1 || ng > 8) return LINR_EINVAL;
+    h.c = g[0].c; h.p = g[0].p; h.target = g[0].target; h.gc = g[0].gc;
+    for (int i = 0; i < ng; ++i) {
+        h.g_c[i] = g[i].c - h.c; h.g_p[i] = g[i].p - h.p; h.g_t[i] = g[i].target - h.target; h.g_gc[i] = g[i].gc - h.gc;
+        h.w1[i] = g[i].w1_off; h.b1[i] = g[i].b1_off; h.w2[i] = g[i].w2_off; h.b2[i] = g[i].b2_off;
+    }
+    return 0;
+}
 
 __global__ __launch_bounds__(HB_WAVES * 64, 2) void thead_bwd_k(THeadArgs A) {
     __shared__ float lds[HB_LDS_FLOATS];
@@ -1021,7 +1103,7 @@ extern "C" int linr_occ_to_bf16(const float* occ, int64_t rows, uint16_t* out_pa
 }
 
 // ---- executor -------------------------------------------------------------------------------------------------------------------------
-struct TCtx {
+struct TCtx : LinrShortList {
     const linr_frame* f;
     Layout L;
     TArena A;
@@ -1029,9 +1111,6 @@ struct TCtx {
     const bf16_t* OCC;               // bf16 occupancy rows (zero row in front): the caller's copy or the arena's
     hipStream_t s;
     int64_t R;
-    int nb;
-    std::vector<LinrShortRange> shortr;
-    void note_short(int64_t b, int64_t e, int rows) { if (rows < nb) shortr.push_back({b, e, rows}); }
 };
 
 static int tcheck(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16, TCtx& c) {
@@ -1054,28 +1133,23 @@ static BArgs tbase(const TCtx& c) {
     BArgs a = BArgs();
     a.lo = c.f->nbr_lo; a.mask = c.f->nbr_mask; a.ld = c.f->nbr_ld; a.n = c.R;
     a.codes = nullptr; a.minv = 0.0f; a.range = 0.0f; a.pf = c.P; a.wimg = c.A.WIMG;
-    for (int g = 0; g < BMAXG; ++g) a.cin[g] = 8;
     return a;
 }
 
-template <int MODE>
-static int tlaunch(const TCtx& c, const BArgs& a, int groups) {
-    LinrProf ps(c.s, TK_FWD, groups);
-    bconv_k<MODE, 2, true><<<dim3(linr_grid(c.R, LINR_BLOCK), groups), LINR_BLOCK, 0, c.s>>>(a);
+// the one launch of bconv_k<G::MODE>: g[0 .. ng) are the groups (bf16_common.h), x what bfill takes per launch; group i loads tpack_k's
+// images from image0 + i layers on (7 images per layer of MODE 0 / 1, 4 of MODE 2 / 3)
+template <class G, class... X>
+static int tlaunch(const TCtx& c, int image0, const G* g, int ng, X... x) {
+    BArgs a = tbase(c);
+    TRY(bfill(a, g, ng, x...));
+    for (int i = 0; i < ng; ++i) a.wi[i] = image0 + (G::MODE < 2 ? 7 : 4) * i;
+    LinrProf ps(c.s, TK_FWD, ng);
+    bconv_k<G::MODE, 2, true><<<dim3(linr_grid(c.R, LINR_BLOCK), ng), LINR_BLOCK, 0, c.s>>>(a);
     return linr_launch_rc();
 }
 
-// conv3 cin->8 (+ res) (ReLU) over `groups` layers; ptrs[g] are the groups' matrices (offsets are taken against ptrs[0])
-static int tconv(const TCtx& c, const bf16_t* const* in, bf16_t* const* out, const bf16_t* const* res, int relu, int groups,
-                 const int64_t* w, const int64_t* b, int layer0) {
-    BArgs a = tbase(c);
-    a.in = in[0]; a.out = out[0]; a.res = res ? res[0] : nullptr; a.relu = relu;
-    for (int g = 0; g < groups; ++g) {
-        a.g_in[g] = in[g] - in[0]; a.g_out[g] = out[g] - out[0]; a.g_res[g] = res ? res[g] - res[0] : 0;
-        a.w[g] = w[g]; a.b[g] = b[g]; a.cin[g] = 8; a.wi[g] = TP_CONV0 + 7 * (layer0 + g);       // (layers of tpack_k's first range)
-    }
-    return tlaunch<0>(c, a, groups);
-}
+// conv3 cin->8 (+ res) (ReLU) of consecutive layers of tpack_k's first image range, layer0 the first
+static int tconv(const TCtx& c, int layer0, const BConvGroup* g, int ng, int relu) { return tlaunch(c, TP_CONV0 + 7 * layer0, g, ng, relu); }
 
 // the teacher-forced forward of all 8 stages with every activation the backward pass needs kept in the arena
 static int tforward(TCtx& c, float* probs, double* bits_acc) {
@@ -1090,7 +1164,7 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
         tp.conv0_w[0] = L.block_in.a_w; tp.conv0_w[1] = L.block_in.b_w;
         for (int g = 0; g < 7; ++g) { tp.conv0_w[2 + g] = L.outter[g].b_w; tp.occ_w[g] = L.outter[g].a_w; }
         for (int k = 0; k < 8; ++k) {
-            const IncP& q = (k == 0 ? L.block_in : L.outter[k - 1]).inc[0];
+            const IncP& q = slot_block(L, k).inc[0];
             tp.pr_w[k] = L.pr_w[k]; tp.c00_w[k] = q.c00_w; tp.c01_w[k] = q.c01_w; tp.c11_w[k] = q.c11_w;
         }
         tpack_k<<<TP_IMAGES + a.pads.n, 64, 0, c.s>>>(c.P, tp, a.WIMG, a.mats, a.pads);
@@ -1100,12 +1174,13 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
         sce_fwd_k<bf16_t><<<sa.blk_off[sa.n_scales], LINR_BLOCK, 0, c.s>>>(c.P, f->offset_feat, sa, c.R, nullptr, nullptr, a.X0, nullptr, none);
     }
     {   // A[0] = relu(conv3(x_low)) (block_in) and A[b] = relu(conv3(occ[:, :b])) (outter block b)
-        const bf16_t* in0[1] = {a.X0};
-        bf16_t* out0[1] = {a.A[0]};
-        TRY(tconv(c, in0, out0, nullptr, 1, 1, &L.block_in.a_w, &L.block_in.a_b, 0));
+        const BConvGroup first = {a.X0, a.A[0], nullptr, L.block_in.a_w, L.block_in.a_b, 8};
+        TRY(tconv(c, 0, &first, 1, 1));
         BoArgs o;
-        o.occ = c.OCC; o.out = a.A[1]; o.P = c.P; o.wimg = a.WIMG; o.lo = f->nbr_lo; o.mask = f->nbr_mask; o.ld = f->nbr_ld; o.n = c.R;
-        for (int g = 0; g < 7; ++g) { o.b[g] = L.outter[g].a_b; o.g_out[g] = a.A[g + 1] - a.A[1]; }
+        o.occ = c.OCC; o.P = c.P; o.wimg = a.WIMG; o.lo = f->nbr_lo; o.mask = f->nbr_mask; o.ld = f->nbr_ld; o.n = c.R;
+        BOcc7Group og;
+        for (int g = 0; g < 7; ++g) og.A[g] = a.A[g + 1];
+        bo_fill(o, og, L);
         LinrProf ps(c.s, TK_FWD, 7);
         const char* e16 = getenv("LINR_BOCC7_MFMA16");       // 0: bocc7_k (v_mfma_f32_4x4x4_16b_bf16); read per call: tests compare the two
         const int mfma16 = e16 ? atoi(e16) : 1;
@@ -1119,62 +1194,40 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
         TRY(linr_launch_rc());
     }
     {   // the Inception layer of all eight blocks: H = [relu(conv0_0(A)) | relu(conv1_0(A))], then I, M
-        BArgs h = tbase(c), i2 = tbase(c);
-        h.in = a.A[0]; h.out = a.H[0];
-        i2.in = a.H[0]; i2.out = a.I[0]; i2.res = a.A[0]; i2.m_out = a.M[0];
+        BPwGroup pw[8];
+        BDualGroup du[8];
         for (int g = 0; g < 8; ++g) {
-            const IncP& q = (g == 0 ? L.block_in : L.outter[g - 1]).inc[0];
-            h.g_in[g] = a.A[g] - a.A[0]; h.g_out[g] = a.H[g] - a.H[0];
-            h.w[g] = q.c00_w; h.b[g] = q.c00_b; h.w2[g] = q.c10_w; h.b2[g] = q.c10_b; h.wi[g] = TP_C00 + 4 * g;
-            i2.g_in[g] = a.H[g] - a.H[0]; i2.g_out[g] = a.I[g] - a.I[0]; i2.g_res[g] = a.A[g] - a.A[0]; i2.g_m[g] = a.M[g] - a.M[0];
-            i2.w[g] = q.c01_w; i2.b[g] = q.c01_b; i2.w2[g] = q.c11_w; i2.b2[g] = q.c11_b; i2.w3[g] = q.c12_w; i2.b3[g] = q.c12_b;
-            i2.wi[g] = TP_DUAL + 4 * g;
+            const IncP& q = slot_block(L, g).inc[0];
+            pw[g] = bpw_group(q, a.A[g], a.H[g]);
+            du[g] = bdual_group(q, a.H[g], a.A[g], a.I[g], a.M[g]);
         }
-        TRY(tlaunch<2>(c, h, 8));
-        TRY(tlaunch<3>(c, i2, 8));
+        TRY(tlaunch(c, TP_C00, pw, 8));
+        TRY(tlaunch(c, TP_DUAL, du, 8));
     }
     {   // x_glob = O[0] = conv3(I[0]); prior_b = O[b] = conv3(I[b]) + x_glob
-        const bf16_t* in0[1] = {a.I[0]};
-        bf16_t* out0[1] = {a.O[0]};
-        TRY(tconv(c, in0, out0, nullptr, 0, 1, &L.block_in.b_w, &L.block_in.b_b, 1));
-        const bf16_t* in[7]; bf16_t* out[7]; const bf16_t* res[7]; int64_t w[7], b[7];
-        for (int g = 0; g < 7; ++g) { in[g] = a.I[g + 1]; out[g] = a.O[g + 1]; res[g] = a.O[0]; w[g] = L.outter[g].b_w; b[g] = L.outter[g].b_b; }
-        TRY(tconv(c, in, out, res, 0, 7, w, b, 2));
+        const BConvGroup glob = {a.I[0], a.O[0], nullptr, L.block_in.b_w, L.block_in.b_b, 8};
+        TRY(tconv(c, 1, &glob, 1, 0));
+        BConvGroup last[7];
+        for (int g = 0; g < 7; ++g) last[g] = {a.I[g + 1], a.O[g + 1], a.O[0], L.outter[g].b_w, L.outter[g].b_b, 8};
+        TRY(tconv(c, 2, last, 7, 0));
     }
     {   // the 8 heads: C_k = prune conv(prior_k) (stored), p_k, bits partials
-        BArgs h = tbase(c);
-        h.in = a.O[0]; h.out = a.C[0];
-        h.target = f->occ; h.target_ld = 8;
-        h.p_out = a.PR; h.partial = a.part;
-        for (int k = 0; k < 8; ++k) {
-            h.g_in[k] = a.O[k] - a.O[0]; h.g_out[k] = a.C[k] - a.C[0];
-            h.w[k] = L.pr_w[k]; h.b[k] = L.pr_b[k]; h.wi[k] = TP_PRUNE + 7 * k;
-            h.h_w1[k] = L.h0_w[k]; h.h_b1[k] = L.h0_b[k]; h.h_w2[k] = L.h2_w[k]; h.h_b2[k] = L.h2_b[k];
-            h.t_col[k] = k; h.p_off[k] = (int64_t)k * c.R; h.part_off[k] = (int64_t)k * nblk;
-        }
-        TRY(tlaunch<1>(c, h, 8));
+        BHeadGroup h[8];
+        for (int k = 0; k < 8; ++k) h[k] = bhead_group(L, k, a.O[k], a.C[k]);
+        TRY(tlaunch(c, TP_PRUNE, h, 8, f->occ, a.PR, a.part));
     }
     if (bits_acc) TRY(linr_bits_finish_launch(a.part, (int)(8 * nblk), bits_acc, c.s));
     if (probs) TRY(linr_hip_rc(hipMemcpyAsync(probs, a.PR, (size_t)c.R * 8 * sizeof(float), hipMemcpyDeviceToDevice, c.s)));
     return linr_launch_rc();
 }
 
-static BbArgs bb_base(const TCtx& c) {
+template <int EPI, class G>
+static int bb_launch(TCtx& c, const G* g, int ng, int kind_prof, int* rows) {
     BbArgs a = BbArgs();
     a.P = c.P; a.lo = c.f->nbr_lo; a.mask = c.f->nbr_mask; a.ld = c.f->nbr_ld; a.n = c.R;
     a.big = c.A.BIG; a.block_stride = c.L.total;
-    for (int g = 0; g < TB_MAXG; ++g) a.cin[g] = 8;
-    return a;
-}
-
-template <int KIND, int EPI>
-static int bb_launch(TCtx& c, BbArgs& a, int groups, int kind_prof, int* rows) {
-    int blocks = 1;
-    tb_grid(c.R, c.nb, groups, a.tiles_per_wave, blocks);
-    *rows = blocks;
-    LinrProf ps(c.s, kind_prof, groups);
-    bbwd_k<KIND, EPI><<<dim3(blocks, groups), BB_WAVES * 64, 0, c.s>>>(a);
-    return linr_launch_rc();
+    LinrProf ps(c.s, kind_prof, ng);
+    return bb_run<EPI>(a, g, ng, c.nb, rows, c.s);
 }
 
 // backward of gscale * bits: leaves the parameter gradient in the arena's GSUM (flat, parameters() order)
@@ -1185,27 +1238,22 @@ static int tbackward(TCtx& c, float gscale) {
     c.shortr.clear();
     {   // heads: gC and the four head-parameter gradients
         THeadArgs h = THeadArgs();
-        h.c = a.C[0]; h.p = a.PR; h.target = c.f->occ; h.target_ld = 8; h.P = c.P; h.gscale = gz_scale; h.gc = a.gC[0]; h.n = c.R;
+        h.target_ld = 8; h.P = c.P; h.gscale = gz_scale; h.n = c.R;
         h.big = a.BIG; h.block_stride = L.total;
-        for (int k = 0; k < 8; ++k) {
-            h.g_c[k] = a.C[k] - a.C[0]; h.g_p[k] = (int64_t)k * c.R; h.g_t[k] = k; h.g_gc[k] = a.gC[k] - a.gC[0];
-            h.w1[k] = L.h0_w[k]; h.b1[k] = L.h0_b[k]; h.w2[k] = L.h2_w[k]; h.b2[k] = L.h2_b[k];
-        }
+        THeadGroup hg[8];
+        for (int k = 0; k < 8; ++k) hg[k] = {a.C[k], a.PR + (int64_t)k * c.R, c.f->occ + k, a.gC[k], L.h0_w[k], L.h0_b[k], L.h2_w[k], L.h2_b[k]};
+        TRY(th_fill(h, hg, 8));
         h.active = hb_blocks(c.R, 8, tb_cus(), c.nb);
         LinrProf ps(c.s, TK_HEAD_BWD, 8);
         thead_bwd_k<<<dim3(h.active, 8), HB_WAVES * 64, 0, c.s>>>(h);
         TRY(linr_launch_rc());
         c.note_short(L.h0_w[0], L.h2_b[7] + 1, h.active);          // the heads' parameters are one contiguous range
     }
-    int rows = 0;
+    int rows = 0, r2 = 0;
     {   // C_k = conv3(prior_k; prune_k): gO[k] = bwd(gC[k]) and the kernel / bias gradients, one gather of gC
-        BbArgs b = bb_base(c);
-        b.g = a.gC[0]; b.xin = a.O[0]; b.out = a.gO[0];
-        for (int k = 0; k < 8; ++k) {
-            b.g_g[k] = a.gC[k] - a.gC[0]; b.g_x[k] = a.O[k] - a.O[0]; b.g_out[k] = a.gO[k] - a.gO[0];
-            b.w[k] = L.pr_w[k]; b.b[k] = L.pr_b[k];
-        }
-        TRY((bb_launch<0, 0>(c, b, 8, TK_BWD88, &rows)));
+        Bb88Group g[8];
+        for (int k = 0; k < 8; ++k) g[k] = {a.gC[k], a.O[k], a.gO[k], L.pr_w[k], L.pr_b[k], 8};
+        TRY(bb_launch<0>(c, g, 8, TK_BWD88, &rows));
         c.note_short(L.pr_w[0], L.pr_b[7] + 8, rows);
     }
     {   // prior_k = x_glob (+ outter block k): x_glob receives every gO
@@ -1215,52 +1263,35 @@ static int tbackward(TCtx& c, float gscale) {
         tsum8_k<<<linr_grid(c.R, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(src, c.R, a.gXG);
         TRY(linr_launch_rc());
     }
-    {   // O = conv3(I; b): gI = bwd(gO), gM, G2 = [gI[:, 0:4] | gM], the kernel / bias gradients and conv1_2's
-        BbArgs b = bb_base(c);
-        const bf16_t* gO0 = a.gXG;                             // slot 0 = block_in, whose output gradient is the fan-in sum
-        b.g = gO0; b.xin = a.I[0]; b.out = a.gI[0]; b.m = a.M[0]; b.g2 = a.G2[0];
+    {   // the eight blocks behind their first convs, three fused launches over the same groups:
+        //   O = conv3(I; b): gI = bwd(gO), gM, G2 = [gI[:, 0:4] | gM], the kernel / bias gradients and conv1_2's
+        //   both 4->4 convs: gH = [bwd(gI[:, 0:4]; W01) | bwd(gM; W11)] * (H > 0) and their gradients, one gather of G2
+        //   conv0_0 (8->4): gA = (bwd(gH[:, 0:4]; W00) + gI + gH[:, 4:8] @ W10^T) * (A > 0), its gradients and conv1_0's
+        Bb88Group tail[8];
+        BbDualGroup dual[8];
+        BbC00Group c00[8];
         for (int g = 0; g < 8; ++g) {
-            const BlockP& bp = g == 0 ? L.block_in : L.outter[g - 1];
-            b.g_g[g] = (g == 0 ? a.gXG : a.gO[g]) - gO0; b.g_x[g] = a.I[g] - a.I[0]; b.g_out[g] = a.gI[g] - a.gI[0];
-            b.g_m[g] = a.M[g] - a.M[0]; b.g_g2[g] = a.G2[g] - a.G2[0];
-            b.w[g] = bp.b_w; b.b[g] = bp.b_b; b.wp[g] = bp.inc[0].c12_w; b.bp[g] = bp.inc[0].c12_b;
+            const BlockP& bp = slot_block(L, g);
+            const IncP& q = bp.inc[0];
+            const bf16_t* gO = g == 0 ? a.gXG : a.gO[g];       // slot 0 = block_in, whose output gradient is the fan-in sum
+            tail[g] = {gO, a.I[g], a.gI[g], bp.b_w, bp.b_b, 8, a.M[g], a.G2[g], q.c12_w, q.c12_b};
+            dual[g] = {a.G2[g], a.H[g], a.gH[g], q.c01_w, q.c01_b, q.c11_w, q.c11_b};
+            c00[g] = {a.gH[g], a.A[g], a.gI[g], a.gA[g], q.c00_w, q.c00_b, q.c10_w, q.c10_b};
         }
-        TRY((bb_launch<0, 3>(c, b, 8, TK_BWD88, &rows)));
-        // everything of a block behind its first conv comes from fused launches over the same groups: one range per block
-        for (int g = 0; g < 8; ++g) {
-            const BlockP& bp = g == 0 ? L.block_in : L.outter[g - 1];
-            c.note_short(bp.inc[0].c00_w, bp.b_b + 8, rows);
-        }
-    }
-    {   // both 4->4 convs: gH = [bwd(gI[:, 0:4]; W01) | bwd(gM; W11)] * (H > 0) and their gradients, one gather of G2
-        BbArgs b = bb_base(c);
-        b.g = a.G2[0]; b.xin = a.H[0]; b.out = a.gH[0];
-        for (int g = 0; g < 8; ++g) {
-            const IncP& q = (g == 0 ? L.block_in : L.outter[g - 1]).inc[0];
-            b.g_g[g] = a.G2[g] - a.G2[0]; b.g_x[g] = a.H[g] - a.H[0]; b.g_out[g] = a.gH[g] - a.gH[0];
-            b.w[g] = q.c01_w; b.b[g] = q.c01_b; b.w1[g] = q.c11_w; b.b1[g] = q.c11_b;
-        }
-        int r2 = 0;
-        TRY((bb_launch<1, 0>(c, b, 8, TK_BWD_DUAL, &r2)));
+        TRY(bb_launch<3>(c, tail, 8, TK_BWD88, &rows));
+        for (int g = 0; g < 8; ++g) c.note_short(c00[g].w00_off, tail[g].b_off + 8, rows);      // one range per block
+        TRY(bb_launch<0>(c, dual, 8, TK_BWD_DUAL, &r2));
         if (r2 != rows) return LINR_EINVAL;
-    }
-    {   // conv0_0 (8->4): gA = (bwd(gH[:, 0:4]; W00) + gI + gH[:, 4:8] @ W10^T) * (A > 0), its gradients and conv1_0's
-        BbArgs b = bb_base(c);
-        b.g = a.gH[0]; b.xin = a.A[0]; b.out = a.gA[0]; b.res = a.gI[0];
-        for (int g = 0; g < 8; ++g) {
-            const IncP& q = (g == 0 ? L.block_in : L.outter[g - 1]).inc[0];
-            b.g_g[g] = a.gH[g] - a.gH[0]; b.g_x[g] = a.A[g] - a.A[0]; b.g_out[g] = a.gA[g] - a.gA[0]; b.g_res[g] = a.gI[g] - a.gI[0];
-            b.w[g] = q.c00_w; b.b[g] = q.c00_b; b.wp[g] = q.c10_w; b.bp[g] = q.c10_b;
-        }
-        int r2 = 0;
-        TRY((bb_launch<2, 0>(c, b, 8, TK_BWD_C00, &r2)));
+        TRY(bb_launch<0>(c, c00, 8, TK_BWD_C00, &r2));
         if (r2 != rows) return LINR_EINVAL;
     }
     {   // A[b] = relu(conv3(occ[:, :b]; a)): kernel / bias gradients of the seven first convolutions from ONE gather of the occupancy
         OwArgs o;
-        o.occ = c.OCC; o.g = a.gA[1]; o.lo = c.f->nbr_lo; o.mask = c.f->nbr_mask; o.ld = c.f->nbr_ld; o.n = c.R;
+        o.occ = c.OCC; o.lo = c.f->nbr_lo; o.mask = c.f->nbr_mask; o.ld = c.f->nbr_ld; o.n = c.R;
         o.big = a.BIG; o.block_stride = L.total;
-        for (int g = 0; g < 7; ++g) { o.g_g[g] = a.gA[g + 1] - a.gA[1]; o.w[g] = L.outter[g].a_w; o.b[g] = L.outter[g].a_b; }
+        BOcc7WgradGroup og;
+        for (int g = 0; g < 7; ++g) og.gA[g] = a.gA[g + 1];
+        ow_fill(o, og, L);
         const int64_t t64 = (c.R + 63) >> 6;
         int64_t target = tb_cus();                            // one 8-wave block per CU (two waves per SIMD)
         if (target > c.nb) target = c.nb;
@@ -1275,10 +1306,9 @@ static int tbackward(TCtx& c, float gscale) {
         for (int g = 0; g < 7; ++g) c.note_short(L.outter[g].a_w, L.outter[g].a_b + 8, rows);
     }
     {   // A[0] = relu(conv3(x_low; a)) of block_in: gx_low (fp32 for the scale context's backward) and its gradients
-        BbArgs b = bb_base(c);
-        b.g = a.gA[0]; b.xin = a.X0; b.out_f32 = a.gX0; b.flags = TB_OUT_F32;
-        b.w[0] = L.block_in.a_w; b.b[0] = L.block_in.a_b;
-        TRY((bb_launch<0, 0>(c, b, 1, TK_BWD88, &rows)));
+        Bb88Group g = {a.gA[0], a.X0, nullptr, L.block_in.a_w, L.block_in.a_b, 8};
+        g.out_f32 = a.gX0;
+        TRY(bb_launch<0>(c, &g, 1, TK_BWD88, &rows));
         c.note_short(L.block_in.a_w, L.block_in.a_b + 8, rows);
     }
     return linr_bwd_tail_launch(c.f, L, c.P, a.gX0, nullptr, a.BIG, a.GSUM, c.nb, c.shortr.data(), (int)c.shortr.size(), c.s);
@@ -1312,12 +1342,7 @@ extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void
     if (!exp_avg || !exp_avg_sq || !bits_acc || step < 1) return LINR_EINVAL;
     TCtx c;
     TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
-    if (scale_steps_h) {          // checked before anything is launched
-        for (int s = 0; s < c.L.S; ++s)
-            if (scale_steps_h[s] < 0) return LINR_EINVAL;
-        for (int j = 0; j < f->n_scales; ++j)
-            if (f->row_off_h[j + 1] > f->row_off_h[j] && scale_steps_h[f->scale_idx_h[j]] < 1) return LINR_EINVAL;
-    }
+    TRY(linr_scale_steps_check(f, c.L, scale_steps_h));          // before anything is launched
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;
     TRY(tforward(c, nullptr, bits_acc));
@@ -1336,12 +1361,8 @@ extern "C" int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* 
     if ((((uintptr_t)gout) & 15u) || (((uintptr_t)in) & 15u) || (((uintptr_t)gin) & 15u)) return LINR_EALIGN;
     if (!linr_rows_fit32(n)) return LINR_EINVAL;
     BbArgs a = BbArgs();
-    a.g = gout; a.xin = in; a.P = W; a.out = gin; a.lo = lo; a.mask = mask; a.ld = ld; a.n = n;
+    a.P = W; a.lo = lo; a.mask = mask; a.ld = ld; a.n = n;
     a.big = slab; a.block_stride = 1736;
-    a.w[0] = 0; a.b[0] = 1728; a.cin[0] = 8;
-    int blocks = 1;
-    tb_grid(n, nblocks, 1, a.tiles_per_wave, blocks);
-    *rows_written = blocks;
-    bbwd_k<0, 0><<<dim3(blocks, 1), BB_WAVES * 64, 0, (hipStream_t)stream>>>(a);
-    return linr_launch_rc();
+    const Bb88Group g = {gout, in, gin, 0, 1728, 8};          // the slab row: the kernel [27][8][8], then the bias
+    return bb_run<0>(a, &g, 1, nblocks, rows_written, (hipStream_t)stream);
 }
