@@ -43,7 +43,7 @@ def _grad_or_zero(leaf):
     return leaf.grad.detach().double().cpu()
 
 
-def _grads_close_per_tensor(grads, sdo, rtol=1e-3, floor=1e-9, sd64=None, slack=None):
+def _grads_close_per_tensor(grads, sdo, rtol=1e-3, floor=1e-9, sd64=None, slack=None, report=None):
     """Every tensor against ITS OWN largest gradient (a tensor whose gradients are orders of magnitude below the model's
     largest one must still be right).  A gradient entry is a sum over all rows with heavy cancellation (bias gradients
     most of all), so two fp32 evaluations in different summation orders (the oracle adds the taps in ascending order, the
@@ -52,7 +52,8 @@ def _grads_close_per_tensor(grads, sdo, rtol=1e-3, floor=1e-9, sd64=None, slack=
     same leaves evaluated by the oracle in float64: the HIP gradient must be as accurate as the fp32 oracle is,
         err_hip(f64) <= max(3 * err_oracle32(f64), 1e-4 * max|g_tensor|).
     grads: the executor's flat gradient in the order of sdo; sdo / sd64: leaves on any device.  slack (_relu_tie_slack): per tensor, what
-    the ReLU inputs at fp32 resolution of a fixed cloud can move the gradient by, added to the float64-anchored bound."""
+    the ReLU inputs at fp32 resolution of a fixed cloud can move the gradient by, added to the float64-anchored bound.  report: a list
+    that receives (name, err_hip, err_oracle32, own max) of every tensor checked against sd64, before its assertion."""
     off, worst = 0, (0.0, '')
     for name, v in sdo.items():
         n = v.numel()
@@ -65,6 +66,8 @@ def _grads_close_per_tensor(grads, sdo, rtol=1e-3, floor=1e-9, sd64=None, slack=
             truth = _grad_or_zero(sd64[name])
             e_hip, e_o32 = float((mine - truth).abs().max()), float((ref - truth).abs().max())
             tie = slack[name] if slack else 0.0
+            if report is not None:
+                report.append((name, e_hip, e_o32, gmax))
             assert e_hip <= max(3.0 * e_o32, 1e-4 * gmax) + tie + floor, \
                 'grad %s vs float64: HIP %.3e, fp32 oracle %.3e (own max %.3e, ReLU-tie slack %.3e)' % (name, e_hip, e_o32, gmax, tie)
         if gmax > 0 and err / gmax > worst[0]:
