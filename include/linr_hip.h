@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 14
+#define LINR_ABI_VERSION 15
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -62,6 +62,14 @@ LINR_API int64_t linr_param_count(int32_t scale_num, int32_t block_layers);
 LINR_API size_t linr_kmap_workspace_bytes(int64_t n);
 LINR_API int linr_kmap_build(const int32_t* coords, int64_t n, int32_t* nbr, int64_t ld, int64_t row_base,
                     void* ws, size_t ws_bytes, void* stream);
+/* The same map for the lists of n_seg frames, back to back, with ONE key launch and ONE search launch (the lock-step GOP decoder,
+ * linr_decode_scale_batch): coords int32 [N,3] = n_seg sorted unique x-major lists; seg_off_h (HOST) [n_seg + 1] rises from 0 to N
+ * (empty segments allowed), 1 <= n_seg <= LINR_DECODE_MAX_FRAMES.  A row looks its neighbours up inside its own segment only, so two
+ * frames with equal or adjacent coordinates never see each other; entries are global rows or -1, bitwise what n_seg calls of
+ * linr_kmap_build with row_base = seg_off_h[f] write.  ws: linr_kmap_workspace_bytes(N) bytes, 8-byte aligned. */
+#define LINR_DECODE_MAX_FRAMES 64
+LINR_API int linr_kmap_build_segments(const int32_t* coords, const int64_t* seg_off_h, int32_t n_seg, int32_t* nbr, int64_t ld,
+                             void* ws, size_t ws_bytes, void* stream);
 /* Compressed form of the same map for x-major sorted coordinates: the dz = -1,0,+1 neighbours of a (dx,dy) column are
  * consecutive rows, so lo[q*ld + j] = row of the first present neighbour of column q = (dx+1)+3(dy+1) and bit
  * q*3 + (dz+1) of mask[j] says which are present: 40 B/row instead of 108.  Rows of nbr must hold global row ids. */
@@ -511,6 +519,44 @@ LINR_API int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_id
                       float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
                       void* stream);
 
+/* The lock-step GOP decoder: ONE scale of n_frames frames per call (decoder.decode_one_frame's loop body, decoder.py:153-176, for
+ * every frame of a group at once; octree_level.upper_layer, models/module_utils.py:117-127, without a sort).  A row's arithmetic
+ * depends neither on the tiling nor on the rows that share its launch, so the frames' levels, back to back, are one row space with
+ * one scale index as long as the kernel map never links two frames (linr_kmap_build_segments); a stage then costs one launch set,
+ * one copy each way and n_frames range decoders on host threads.
+ *
+ * linr_children_segments: coords int32 [N,3] and occ fp32 [N][8] (0 / non-zero, octant 4 dx + 2 dy + dz) of n_seg frames back to
+ * back, every frame sorted x-major, seg_off_h (HOST) [n_seg + 1] from 0 to N, N < 2^26.  Writes the children 2 p + (dx, dy, dz) of
+ * every occupied octant to child_xyz [child_cap][3], x-major sorted within a frame, frames back to back, and child_off_h (HOST)
+ * [n_seg + 1].  The parents are sorted already, so a child's position is a closed form of four prefix sums over the rows (counts of
+ * the (dx, dy) pairs) and of the bounds of the row's (frame, x) and (frame, x, y) runs: one scan, one scatter, no sort, no atomics.
+ * LINR_ENOSPC when there are more than child_cap children (nothing is written past the cap).  ws: linr_children_segments_ws_bytes(N)
+ * bytes, 256-byte aligned.  Synchronises the stream (one host read of the n_seg + 1 offsets).
+ *
+ * linr_net_decode_stages_segments: linr_net_decode_stages for a frame object of ONE scale whose rows are n_seg segments (seg_off_h),
+ * each with its own 8 stage streams (streams_h / stream_len_h [n_seg][8]); the n_seg range decoders of a stage run on up to
+ * n_threads host threads (linr_ac_decode_binary_batch).
+ *
+ * linr_decode_scale_batch: linr_decode_scale for n_frames frames (1..LINR_DECODE_MAX_FRAMES) with N = seg_off_h[n_frames] rows
+ * (N < 2^26): segmented kernel map, its compressed form and offset features, the 8 stages in lock step, the children.  streams_h /
+ * stream_len_h: HOST [n_frames][8]; p_pinned / s_pinned: pinned HOST buffers of N floats / N bytes; child_xyz: DEVICE int32
+ * [child_cap][3] (8 N is always enough); child_off_h: HOST [n_frames + 1].  ws: linr_decode_scale_batch_ws_bytes(N, n_frames,
+ * block_layers, codes != NULL) bytes, 256-byte aligned.  Arguments are checked before the first launch: LINR_EINVAL, LINR_ENOSPC
+ * (short ws), LINR_EALIGN as linr_decode_scale.  The new kernels belong to poison class 15 and to no linr_prof_* class. */
+LINR_API size_t linr_children_segments_ws_bytes(int64_t n);
+LINR_API int linr_children_segments(const int32_t* coords, const float* occ, const int64_t* seg_off_h, int32_t n_seg, int32_t* child_xyz,
+                           int64_t child_cap, int64_t* child_off_h, void* ws, size_t ws_bytes, void* stream);
+LINR_API int linr_net_decode_stages_segments(const linr_frame* f, const float* params, const uint8_t* codes, float min_param,
+                                    float max_param, void* arena, size_t arena_bytes, const int64_t* seg_off_h, int32_t n_seg,
+                                    const uint8_t* const* streams_h, const int64_t* stream_len_h, float* probs, float* p_pinned,
+                                    uint8_t* s_pinned, uint8_t* s_dev, int32_t n_threads, void* stream);
+LINR_API size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16);
+LINR_API int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                            int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                            float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                            void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap,
+                            int64_t* child_off_h, int32_t n_threads, void* stream);
+
 /* ---- the executor's fused layers as stand-alone ops ------------------------------------------------------------
  * What linr_net_forward / _backward launch for one layer, callable (and testable) on its own.  All of them work on the
  * compressed kernel map (linr_kmap_compress) and follow the LINR_PAD_ROW contract: every matrix that a kernel GATHERS
@@ -620,6 +666,11 @@ LINR_API int     linr_ac_decode_cdf16(const uint16_t* cdf_h, int32_t lp, int32_t
 LINR_API int linr_ac_encode_binary_batch(const float* const* prob_h, const uint8_t* const* sym_h, const int64_t* n,
                                 int32_t n_streams, uint8_t* const* out_h, const int64_t* cap,
                                 int64_t* out_len, int32_t n_threads);
+/* The decode twin: n_streams independent binary streams decoded on a thread pool (the frames of a lock-step decode group are
+ * independent streams).  Stream i: n[i] symbols from in_h[i] / in_len[i] against prob_h[i] into sym_h[i], as linr_ac_decode_binary.
+ * Returns the first non-zero code a stream returned, else 0; no thread is left running on return. */
+LINR_API int linr_ac_decode_binary_batch(const float* const* prob_h, const int64_t* n, const uint8_t* const* in_h,
+                                const int64_t* in_len, int32_t n_streams, uint8_t* const* sym_h, int32_t n_threads);
 /* The same coder fed with code values instead of probabilities (BinaryArithmeticCoding, models/module_utils.py:8-40; callers
  * models/upsample.py:224-239): c1_h[i] = (rint((1 - p[i]) * 65534) + 1) & 0xFFFF, the one cdf entry a binary symbol needs,
  * and the symbols as bits - symbol i is bit i & 31 of sym_h[i >> 5] (ceil(n / 32) words are read).  Interval update,

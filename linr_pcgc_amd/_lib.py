@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('LINR_HIP_LIB') or os.path.join(_HERE, 'liblinr_hip.so
 
 LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 16
 LINR_FRAME_OCC_PADDED = 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -163,6 +163,15 @@ _PROTOS = {
     'linr_decode_scale_ws_bytes': (c_size, [c_i64, c_i32, c_i32]),
     'linr_decode_scale': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_size,
                                          c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    'linr_kmap_build_segments': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_size, c_ptr]),
+    'linr_children_segments_ws_bytes': (c_size, [c_i64]),
+    'linr_children_segments': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    'linr_net_decode_stages_segments': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_size, c_ptr, c_i32,
+                                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr]),
+    'linr_decode_scale_batch_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    'linr_decode_scale_batch': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
+                                               c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_ptr]),
+    'linr_ac_decode_binary_batch': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i32]),
     'linr_ac_encode_cdf16': (c_i64, [c_ptr, c_i32, c_i32, c_ptr, c_i64, c_ptr, c_i64]),
     'linr_ac_decode_cdf16': (ctypes.c_int, [c_ptr, c_i32, c_i32, c_i64, c_ptr, c_i64, c_ptr]),
     'linr_ply_parse_ascii': (ctypes.c_int, [c_ptr, c_size, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr]),

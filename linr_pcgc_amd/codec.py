@@ -183,9 +183,46 @@ def decode_one_frame_stagewise(model, frame_enc_bytes, xyz_low):
     return {'dec_coord': lowx}
 
 
-def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=None):
+LOCKSTEP_MAX_FRAMES = 64                  # LINR_DECODE_MAX_FRAMES of include/linr_hip.h
+LOCKSTEP_MAX_ROWS = (1 << 26) - 64        # rows of one lock-step call: the compressed kernel map's 32-bit bound (linr_cmap_fits32)
+
+
+def _lockstep_scale(model, lows, s_idx, encs, n_threads):
+    """One scale of a lock-step group; a group whose levels together pass the row bound of one call is halved."""
+    if len(lows) > 1 and sum(int(c.shape[0]) for c in lows) > LOCKSTEP_MAX_ROWS:
+        h = len(lows) // 2
+        return _lockstep_scale(model, lows[:h], s_idx, encs[:h], n_threads) + _lockstep_scale(model, lows[h:], s_idx, encs[h:], n_threads)
+    return model.decode_scale_batch(lows, s_idx, encs, n_threads)
+
+
+def decode_frames_lockstep(model, frames_enc_bytes, xyz_lows, n_threads=8):
+    """decode_one_frame for a group of frames with the same number of scales, in lock step: coarse to fine, every scale of the whole
+    group is ONE call into the library (model.decode_scale_batch -> linr_decode_scale_batch).  Returns the frames' coordinates."""
+    lows = [unique_sorted(x) for x in xyz_lows]
+    for s_idx in range(len(frames_enc_bytes[0]) - 1, -1, -1):
+        lows = _lockstep_scale(model, lows, s_idx, [f[s_idx] for f in frames_enc_bytes], n_threads)
+    return lows
+
+
+def lockstep_groups(todo, n_scales, lockstep):
+    """`todo` cut into groups of up to `lockstep` consecutive entries whose frames have the same number of scale streams."""
+    groups = []
+    for i in todo:
+        if groups and len(groups[-1]) < lockstep and n_scales[groups[-1][0]] == n_scales[i]:
+            groups[-1].append(i)
+        else:
+            groups.append([i])
+    return groups
+
+
+def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=None, lockstep=0, n_threads=None):
     """decoder.decode_one_gop: rebuild the model from model.bin, then every frame from its streams alone.
-    `timing` (a dict) receives 'setup_s': the once-per-GOP part (model.bin -> parameters, the coarsest coordinates).
+    lockstep=B > 0 (opt-in; 0 = the per-frame path below, untouched): the requested frames are decoded in groups of up to B
+    consecutive entries, the scales of a group from coarsest to finest in lock step (decode_frames_lockstep), the group's range
+    decoders on `n_threads` host threads (default: the cores this process may use, at most 16).  `workers` then means groups in
+    flight, each on its own stream.  Models of hidden_channel_conv 16 / 32 ignore it.  The streams are the same either way.
+    `timing` (a dict) receives 'setup_s': the once-per-GOP part (model.bin -> parameters, the coarsest coordinates), and with
+    lockstep 'lockstep_ws_bytes': the largest device workspace of a lock-step call.
     Frames are independent once the model is known; with workers > 1 they are decoded by a host thread pool, each
     thread on its own HIP stream (a frame's own chain - 56 stage forwards with a serial range decode in between - cannot
     be parallelised, but the range decoding of one frame overlaps the stage forwards and copies of the others; the
@@ -220,6 +257,12 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
 
     if getattr(model, '_wide', None) is not None:
         workers = 1          # the channel-blocked executor keeps per-call state on the model: frames one after the other
+        lockstep = 0
+    if lockstep and lockstep > 0 and todo:
+        out = _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, min(int(lockstep), LOCKSTEP_MAX_FRAMES), n_threads)
+        if timing is not None:
+            timing['lockstep_ws_bytes'] = int(getattr(model, '_lockstep_ws_peak', 0))          # the largest workspace of a call
+        return out
     if workers <= 1 or len(todo) <= 1:
         return [one(i) for i in todo]
     from concurrent.futures import ThreadPoolExecutor
@@ -237,6 +280,37 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
 
     with ThreadPoolExecutor(max_workers=workers) as pool:
         return list(pool.map(job, todo))
+
+
+def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads):
+    if n_threads is None:
+        n_threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else 8))
+    groups = lockstep_groups(todo, {i: len(enc['frames'][i]) for i in set(todo)}, lockstep)
+    workers = max(1, min(int(workers), len(groups)))
+    per_group = max(1, n_threads // workers)
+
+    def one(group):
+        xyz_lows = [torch.tensor(lows[i].astype(np.int32), device=device) for i in group]
+        dec = decode_frames_lockstep(model, [list(enc['frames'][i]) for i in group], xyz_lows, per_group)
+        return [d + torch.tensor(mins[i], device=device, dtype=torch.int32) for i, d in zip(group, dec)]
+
+    if workers <= 1:
+        return [x for g in groups for x in one(g)]
+    from concurrent.futures import ThreadPoolExecutor
+    main_stream = torch.cuda.current_stream()
+    dev_index = torch.cuda.current_device()
+
+    def job(group):
+        torch.cuda.set_device(dev_index)
+        st = torch.cuda.Stream()
+        st.wait_stream(main_stream)                 # the decompressed parameters were written on the caller's stream
+        with torch.cuda.stream(st):
+            out = one(group)
+        st.synchronize()
+        return out
+
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        return [x for out in pool.map(job, groups) for x in out]
 
 
 def write_gop(enc, result_dir):

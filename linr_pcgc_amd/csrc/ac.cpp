@@ -416,6 +416,33 @@ extern "C" int linr_ac_encode_binary_batch(const float* const* prob_h, const uin
                         [&](int i) { return linr_ac_encode_binary(prob_h[i], sym_h[i], n[i], out_h[i], cap[i]); });
 }
 
+extern "C" int linr_ac_decode_binary_batch(const float* const* prob_h, const int64_t* n, const uint8_t* const* in_h,
+                                           const int64_t* in_len, int32_t n_streams, uint8_t* const* sym_h, int32_t n_threads) {
+    if (n_streams < 0 || (n_streams > 0 && (!prob_h || !n || !in_h || !in_len || !sym_h))) return LINR_EINVAL;
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > n_streams) n_threads = n_streams;
+    std::atomic<int> next(0);
+    std::atomic<int> err(0);
+    auto work = [&]() {
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n_streams) return;
+            const int r = linr_ac_decode_binary(prob_h[i], n[i], in_h[i], in_len[i], sym_h[i]);
+            int none = 0;
+            if (r != 0) err.compare_exchange_strong(none, r);          // the first non-zero code wins
+        }
+    };
+    if (n_threads <= 1) {
+        work();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
+        work();                                                        // the caller is one of the workers
+        for (auto& t : pool) t.join();
+    }
+    return err.load();
+}
+
 extern "C" int linr_ac_encode_binary_codes_batch(const uint16_t* const* c1_h, const uint32_t* const* sym_h, const int64_t* n,
                                                  int32_t n_streams, uint8_t* const* out_h, const int64_t* cap, int64_t* out_len,
                                                  int32_t n_threads) {

@@ -240,3 +240,22 @@ __attribute__((visibility("hidden"))) void linr_poison_hook(hipStream_t s, int k
 __attribute__((visibility("hidden")))
 int linr_occ_wgrad7_launch(const float* occ, const float* const* g, LinrCmap m, float* big, int64_t block_stride,
                            const int64_t* w_off, const int64_t* b_off, int nb, hipStream_t s, int* rows_written);
+
+// ---- the levels of several frames back to back (the lock-step GOP decoder: csrc/kmap.hip, csrc/decode.hip) --------------------
+// The segment table travels by value: off[i] = first row of segment i for i <= n_seg, INT32_MAX behind.  A row finds the bounds of
+// its segment with LINR_DECODE_MAX_FRAMES uniform compares (empty segments drop out: the last start <= r and the first start > r).
+struct LinrSegTab { int32_t off[LINR_DECODE_MAX_FRAMES + 1]; };
+
+__device__ __forceinline__ void linr_seg_bounds(const LinrSegTab& t, int32_t r, int32_t& lo, int32_t& hi) {
+    lo = 0;
+    hi = INT32_MAX;
+#pragma unroll
+    for (int i = 1; i <= LINR_DECODE_MAX_FRAMES; ++i) {
+        const int32_t v = t.off[i];          // non-decreasing
+        lo = v <= r ? v : lo;
+        hi = (v > r && v < hi) ? v : hi;
+    }
+}
+// HOST offsets -> by-value table (csrc/kmap.hip); LINR_EINVAL unless 1 <= n_seg <= LINR_DECODE_MAX_FRAMES and the offsets rise from
+// 0 to *n < 2^31 - 1
+__attribute__((visibility("hidden"))) int linr_seg_tab(const int64_t* seg_off_h, int32_t n_seg, LinrSegTab* tab, int64_t* n);

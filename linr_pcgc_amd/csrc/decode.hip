@@ -3,6 +3,7 @@
 // linr_net_decode_stages) and the next level's coordinates (octree_level.upper_layer, models/module_utils.py:117-127: the children
 // 2 p + (dx, dy, dz) of every occupied octant, sorted x-major).  Between two scales the caller only allocates the next
 // workspace, so a frame's decode holds the Python GIL for a few hundred microseconds instead of ~7 ms.
+// linr_decode_scale_batch below does the same for the frames of a GOP in lock step, with a sort-free child expansion.
 #include "common.h"
 #include "layout.h"
 #include <hipcub/hipcub.hpp>
@@ -167,6 +168,240 @@ extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_
     }
     *child_n_h = total;
     return linr_launch_rc();
+}
+
+// ---- the same for the frames of a GOP in lock step: one scale of n_frames frames per call, children without a sort ------------------
+// (decoder.decode_one_frame's loop body, decoder.py:153-176, and octree_level.upper_layer, models/module_utils.py:117-127, for all
+// frames of a group at once.)  The rows of the group are sorted by (frame, x, y, z), so the children are, too, once every row knows
+// where its own go: with c_q[r] = the children of row r in the (dx, dy) pair q = 2 dx + dy, S_q their exclusive prefix sums and
+// T = S_0 + S_1 + S_2 + S_3, the children of the (frame, x) run [xs, xe) start at T[xs]; inside it come all dx = 0 children, then
+// all dx = 1; inside a dx half the (frame, x, y) runs [ys, ye) in order, each with its dy = 0 children first; inside a (dx, dy)
+// pair the rows in z order, dz = 0 before dz = 1.
+namespace {
+
+struct alignas(16) Cnt4 { int32_t q[4]; };
+struct Cnt4Sum {
+    __host__ __device__ __forceinline__ Cnt4 operator()(const Cnt4& a, const Cnt4& b) const {
+        return Cnt4{{a.q[0] + b.q[0], a.q[1] + b.q[1], a.q[2] + b.q[2], a.q[3] + b.q[3]}};
+    }
+};
+struct ChildWs { size_t cnt, sum, bounds, cub, total, cub_bytes; };
+
+ChildWs child_layout(int64_t n) {
+    ChildWs w;
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { size_t o = cur; cur += up256(bytes); return o; };
+    w.cnt = take((size_t)(n + 1) * sizeof(Cnt4));
+    w.sum = take((size_t)(n + 1) * sizeof(Cnt4));
+    w.bounds = take((size_t)(LINR_DECODE_MAX_FRAMES + 1) * 4);
+    w.cub_bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveScan(nullptr, w.cub_bytes, (const Cnt4*)nullptr, (Cnt4*)nullptr, Cnt4Sum(), Cnt4{{0, 0, 0, 0}},
+                                            (int)(n + 1));
+    w.cub = take(w.cub_bytes);
+    w.total = cur;
+    return w;
+}
+
+// cnt[r].q[2 dx + dy] = occupied octants 4 dx + 2 dy, 4 dx + 2 dy + 1 of row r (cnt[n] = 0 closes the scan)
+__global__ __launch_bounds__(LINR_BLOCK) void child_pair_count_k(const float* __restrict__ occ, int64_t n, Cnt4* __restrict__ cnt) {
+    const int64_t r = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
+    if (r > n) return;
+    Cnt4 c = {{0, 0, 0, 0}};
+    if (r < n) {
+        const float4 a = *reinterpret_cast<const float4*>(occ + r * 8);
+        const float4 b = *reinterpret_cast<const float4*>(occ + r * 8 + 4);
+        c.q[0] = (a.x != 0.f) + (a.y != 0.f);
+        c.q[1] = (a.z != 0.f) + (a.w != 0.f);
+        c.q[2] = (b.x != 0.f) + (b.y != 0.f);
+        c.q[3] = (b.z != 0.f) + (b.w != 0.f);
+    }
+    cnt[r] = c;
+}
+
+// out[i] = T[first row of segment i], i <= n_seg: the segments' child offsets (the last one is the total)
+__global__ void child_bounds_k(const Cnt4* __restrict__ S, LinrSegTab tab, int n_seg, int32_t* __restrict__ out) {
+    const int i = threadIdx.x;
+    if (i > n_seg) return;
+    int32_t row = 0;
+#pragma unroll
+    for (int j = 0; j <= LINR_DECODE_MAX_FRAMES; ++j) row = j == i ? tab.off[j] : row;
+    const Cnt4 s = S[row];
+    out[i] = s.q[0] + s.q[1] + s.q[2] + s.q[3];
+}
+
+struct __attribute__((packed, aligned(4))) Xyz { int32_t x, y, z; };
+struct __attribute__((packed, aligned(4))) Xyz2 { Xyz a, b; };
+
+// lane = row: the bounds of the row's (frame, x) and (frame, x, y) runs by searches in the coordinates, then its children
+__global__ __launch_bounds__(LINR_BLOCK) void children_scatter_k(const int32_t* __restrict__ coord, const float* __restrict__ occ,
+                                                                 const Cnt4* __restrict__ S, int64_t n, LinrSegTab tab,
+                                                                 int32_t* __restrict__ child, int64_t cap) {
+    const int64_t r64 = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
+    if (r64 >= n) return;
+    const int32_t r = (int32_t)r64;
+    int32_t s0, s1;
+    linr_seg_bounds(tab, r, s0, s1);
+    const int32_t X = coord[3 * r64], Y = coord[3 * r64 + 1], Z = coord[3 * r64 + 2];
+    int32_t lo = s0, hi = r;                 // xs: first row of the segment with x >= X
+    while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (coord[3 * (int64_t)mid] < X) lo = mid + 1; else hi = mid; }
+    const int32_t xs = lo;
+    lo = r + 1; hi = s1;                     // xe: first row behind r with x > X (or the segment's end)
+    while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (coord[3 * (int64_t)mid] <= X) lo = mid + 1; else hi = mid; }
+    const int32_t xe = lo;
+    lo = xs; hi = r;                         // ys: first row of the x run with y >= Y
+    while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (coord[3 * (int64_t)mid + 1] < Y) lo = mid + 1; else hi = mid; }
+    const int32_t ys = lo;
+    lo = r + 1; hi = xe;                     // ye: first row behind r in the x run with y > Y (or the run's end)
+    while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (coord[3 * (int64_t)mid + 1] <= Y) lo = mid + 1; else hi = mid; }
+    const int32_t ye = lo;
+    const Cnt4 Sxs = S[xs], Sxe = S[xe], Sys = S[ys], Sye = S[ye], Sr = S[r];
+    const float4 oa = *reinterpret_cast<const float4*>(occ + r64 * 8);
+    const float4 ob = *reinterpret_cast<const float4*>(occ + r64 * 8 + 4);
+    const bool o[8] = {oa.x != 0.f, oa.y != 0.f, oa.z != 0.f, oa.w != 0.f, ob.x != 0.f, ob.y != 0.f, ob.z != 0.f, ob.w != 0.f};
+    const int32_t t_xs = Sxs.q[0] + Sxs.q[1] + Sxs.q[2] + Sxs.q[3];
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+        const int32_t half = t_xs + (dx ? (Sxe.q[0] - Sxs.q[0]) + (Sxe.q[1] - Sxs.q[1]) : 0) + (Sys.q[2 * dx] - Sxs.q[2 * dx]) +
+                             (Sys.q[2 * dx + 1] - Sxs.q[2 * dx + 1]);
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int q = 2 * dx + dy;
+            const int64_t pos = half + (dy ? Sye.q[2 * dx] - Sys.q[2 * dx] : 0) + (Sr.q[q] - Sys.q[q]);
+            const bool o0 = o[2 * q], o1 = o[2 * q + 1];
+            const Xyz c0 = {2 * X + dx, 2 * Y + dy, 2 * Z}, c1 = {2 * X + dx, 2 * Y + dy, 2 * Z + 1};
+            if (o0 && o1 && pos + 1 < cap) {
+                *reinterpret_cast<Xyz2*>(child + 3 * pos) = Xyz2{c0, c1};
+            } else {
+                if (o0 && pos < cap) *reinterpret_cast<Xyz*>(child + 3 * pos) = c0;
+                if (o1 && pos + (o0 ? 1 : 0) < cap) *reinterpret_cast<Xyz*>(child + 3 * (pos + (o0 ? 1 : 0))) = c1;
+            }
+        }
+    }
+}
+
+// the body of linr_children_segments behind its argument checks (n > 0)
+int children_segments(const int32_t* coord, const float* occ, const LinrSegTab& tab, int64_t n, int n_seg, int32_t* child_xyz,
+                      int64_t child_cap, int64_t* child_off_h, char* base, const ChildWs& w, hipStream_t s) {
+    Cnt4* cnt = (Cnt4*)(base + w.cnt);
+    Cnt4* sum = (Cnt4*)(base + w.sum);
+    int32_t* bounds = (int32_t*)(base + w.bounds);
+    linr_poison_hook(s, 15);
+    child_pair_count_k<<<linr_grid(n + 1, LINR_BLOCK), LINR_BLOCK, 0, s>>>(occ, n, cnt);
+    size_t cb = w.cub_bytes;
+    int rc = linr_hip_rc(hipcub::DeviceScan::ExclusiveScan(base + w.cub, cb, cnt, sum, Cnt4Sum(), Cnt4{{0, 0, 0, 0}}, (int)(n + 1), s));
+    if (rc) return rc;
+    child_bounds_k<<<1, 128, 0, s>>>(sum, tab, n_seg, bounds);
+    int32_t bounds_h[LINR_DECODE_MAX_FRAMES + 1];
+    rc = linr_hip_rc(hipMemcpyAsync(bounds_h, bounds, (size_t)(n_seg + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (rc) return rc;
+    children_scatter_k<<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(coord, occ, sum, n, tab, child_xyz, child_cap);
+    rc = linr_launch_rc();
+    if (rc) return rc;
+    rc = linr_hip_rc(hipStreamSynchronize(s));                  // the offsets are on the host now
+    if (rc) return rc;
+    for (int i = 0; i <= n_seg; ++i) child_off_h[i] = bounds_h[i];
+    return bounds_h[n_seg] > child_cap ? LINR_ENOSPC : 0;
+}
+
+struct BatchWs { size_t nbr, lo, mask, feat, occ, probs, sdev, kws, child, arena, total; int64_t ld; size_t arena_bytes; ChildWs cw; };
+
+BatchWs batch_layout(int64_t n, int block_layers, int bf16) {
+    BatchWs w;
+    w.ld = (n + 63) / 64 * 64;
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { size_t o = cur; cur += up256(bytes); return o; };
+    w.nbr = take((size_t)27 * w.ld * 4);
+    w.lo = take((size_t)9 * w.ld * 4);
+    w.mask = take((size_t)w.ld * 4);
+    w.feat = take((size_t)n * 7 * 4);
+    w.occ = take((size_t)(n + 1) * 8 * 4);
+    w.probs = take((size_t)8 * n * 4);
+    w.sdev = take((size_t)n);
+    w.kws = take(linr_kmap_workspace_bytes(n));
+    w.cw = child_layout(n);
+    w.child = take(w.cw.total);
+    w.arena_bytes = bf16 ? linr_net_bf16_arena_bytes(n, block_layers) : linr_net_arena_bytes(n, block_layers);
+    w.arena = take(w.arena_bytes);
+    w.total = cur;
+    return w;
+}
+
+}  // namespace
+
+extern "C" size_t linr_children_segments_ws_bytes(int64_t n) { return n < 0 || n >= ((int64_t)1 << 26) ? 0 : child_layout(n).total; }
+
+extern "C" int linr_children_segments(const int32_t* coords, const float* occ, const int64_t* seg_off_h, int32_t n_seg,
+                                      int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h, void* ws, size_t ws_bytes,
+                                      void* stream) {
+    LinrSegTab tab;
+    int64_t n = 0;
+    const int rc = linr_seg_tab(seg_off_h, n_seg, &tab, &n);
+    if (rc) return rc;
+    if (!child_off_h || child_cap < 0 || n >= ((int64_t)1 << 26)) return LINR_EINVAL;
+    for (int i = 0; i <= n_seg; ++i) child_off_h[i] = 0;
+    if (n == 0) return 0;
+    if (!coords || !occ || !child_xyz || !ws) return LINR_EINVAL;
+    if ((((uintptr_t)ws) & 255u) || !linr_aligned16(occ)) return LINR_EALIGN;
+    const ChildWs w = child_layout(n);
+    if (ws_bytes < w.total) return LINR_ENOSPC;
+    return children_segments(coords, occ, tab, n, n_seg, child_xyz, child_cap, child_off_h, (char*)ws, w, (hipStream_t)stream);
+}
+
+extern "C" size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16) {
+    if (n_total < 0 || n_total >= ((int64_t)1 << 26) || n_frames < 1 || n_frames > LINR_DECODE_MAX_FRAMES || block_layers < 1) return 0;
+    return batch_layout(n_total, block_layers, bf16 ? 1 : 0).total + 256;
+}
+
+extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                       int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                       float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                                       void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
+                                       int64_t child_cap, int64_t* child_off_h, int32_t n_threads, void* stream) {
+    LinrSegTab tab;
+    int64_t n = 0;
+    int rc = linr_seg_tab(seg_off_h, n_frames, &tab, &n);
+    if (rc) return rc;
+    if (!child_off_h || block_layers < 1 || child_cap < 0) return LINR_EINVAL;
+    const int64_t ld = (n + 63) / 64 * 64;
+    if (!linr_cmap_fits32(ld) || !linr_rows_fit32(n)) return LINR_EINVAL;
+    for (int i = 0; i <= n_frames; ++i) child_off_h[i] = 0;
+    if (n == 0) return 0;
+    if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !p_pinned || !s_pinned || !child_xyz) return LINR_EINVAL;
+    if (((uintptr_t)ws) & 255u) return LINR_EALIGN;
+    const BatchWs w = batch_layout(n, block_layers, codes ? 1 : 0);
+    if (ws_bytes < w.total) return LINR_ENOSPC;
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)ws;
+    int32_t* nbr = (int32_t*)(base + w.nbr);
+    int32_t* lo = (int32_t*)(base + w.lo);
+    uint32_t* mask = (uint32_t*)(base + w.mask);
+    float* feat = (float*)(base + w.feat);
+    float* occ_buf = (float*)(base + w.occ);
+    float* occ = occ_buf + 8;                                   // zero row in front (LINR_FRAME_OCC_PADDED)
+    // the segmented kernel map (padding columns of nbr / lo / mask: no neighbour), its compressed form, the scale context's features
+    rc = linr_hip_rc(hipMemsetAsync(nbr, 0xFF, (size_t)27 * w.ld * 4, s));
+    if (rc) return rc;
+    rc = linr_hip_rc(hipMemsetAsync(lo, 0, w.mask + (size_t)w.ld * 4 - w.lo, s));            // lo and mask are adjacent
+    if (rc) return rc;
+    rc = linr_kmap_build_segments(coord, seg_off_h, n_frames, nbr, w.ld, base + w.kws, linr_kmap_workspace_bytes(n), stream);
+    if (rc) return rc;
+    rc = linr_kmap_compress(nbr, w.ld, n, lo, mask, w.ld, stream);
+    if (rc) return rc;
+    rc = linr_kmap_offset_feat(nbr, w.ld, 0, n, feat, stream);
+    if (rc) return rc;
+    rc = linr_hip_rc(hipMemsetAsync(occ_buf, 0, (size_t)(n + 1) * 8 * 4, s));
+    if (rc) return rc;
+    int64_t row_off[2] = {0, n};
+    int32_t sidx[1] = {scale_idx};
+    linr_frame f;
+    f.rows = n; f.n_scales = 1; f.model_scale_num = model_scale_num; f.block_layers = block_layers; f.flags = LINR_FRAME_OCC_PADDED;
+    f.row_off_h = row_off; f.scale_idx_h = sidx; f.nbr = nbr; f.nbr_ld = w.ld; f.nbr_lo = lo; f.nbr_mask = mask;
+    f.offset_feat = feat; f.occ = occ; f.nbr8t = nullptr;
+    rc = linr_net_decode_stages_segments(&f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, seg_off_h, n_frames,
+                                         streams_h, stream_len_h, (float*)(base + w.probs), p_pinned, s_pinned,
+                                         (uint8_t*)(base + w.sdev), n_threads, stream);
+    if (rc) return rc;
+    return children_segments(coord, occ, tab, n, n_frames, child_xyz, child_cap, child_off_h, base + w.child, w.cw, s);
 }
 
 // ---- sorted unique coordinate list, optionally of the parents (coords >> shift); one octree level as one call ------------------------

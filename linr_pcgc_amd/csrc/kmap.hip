@@ -66,6 +66,63 @@ extern "C" int linr_kmap_build(const int32_t* coords, int64_t n, int32_t* nbr, i
     return linr_launch_rc();
 }
 
+// ---- the lists of several frames back to back: one key launch, one search launch ------------------------------------------------
+// kmap_search_k with the lower bound run inside the row's own segment [s0, s1): entries are global rows
+__global__ __launch_bounds__(LINR_BLOCK) void kmap_search_seg_k(const long long* __restrict__ keys, const int32_t* __restrict__ coords,
+                                                                int64_t n, LinrSegTab tab, int32_t* __restrict__ nbr, int64_t ld) {
+    int64_t idx = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
+    if (idx >= 9 * n) return;
+    const int q = (int)(idx / n);            // (dx,dy) column: consecutive threads -> consecutive rows
+    const int64_t j = idx - (int64_t)q * n;
+    int32_t s0, s1;
+    linr_seg_bounds(tab, (int32_t)j, s0, s1);
+    const int dx = q % 3 - 1, dy = q / 3 - 1;
+    const int x = coords[3 * j] + dx, y = coords[3 * j + 1] + dy, z = coords[3 * j + 2];
+    const long long key0 = linr_key(x, y, z - 1);
+    int64_t lo = s0, hi = s1;                // lower_bound(key0) in the segment
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] < key0) lo = mid + 1; else hi = mid;
+    }
+#pragma unroll
+    for (int dz = 0; dz < 3; ++dz) {
+        const long long target = key0 + dz;  // z+1 < 2^21: never carries into y
+        if (lo < s1 && keys[lo] < target) ++lo;   // keys are unique within a segment: at most one step per dz
+        const bool hit = lo < s1 && keys[lo] == target;
+        const int k = q + 9 * dz;
+        nbr[(int64_t)k * ld + j] = hit ? (int32_t)lo : -1;
+    }
+}
+
+int linr_seg_tab(const int64_t* seg_off_h, int32_t n_seg, LinrSegTab* tab, int64_t* n) {
+    if (!seg_off_h || n_seg < 1 || n_seg > LINR_DECODE_MAX_FRAMES || seg_off_h[0] != 0) return LINR_EINVAL;
+    for (int i = 0; i < n_seg; ++i)
+        if (seg_off_h[i + 1] < seg_off_h[i]) return LINR_EINVAL;
+    if (seg_off_h[n_seg] >= INT32_MAX) return LINR_EINVAL;
+    for (int i = 0; i <= LINR_DECODE_MAX_FRAMES; ++i) tab->off[i] = i <= n_seg ? (int32_t)seg_off_h[i] : INT32_MAX;
+    *n = seg_off_h[n_seg];
+    return 0;
+}
+
+extern "C" int linr_kmap_build_segments(const int32_t* coords, const int64_t* seg_off_h, int32_t n_seg, int32_t* nbr, int64_t ld,
+                                        void* ws, size_t ws_bytes, void* stream) {
+    LinrSegTab tab;
+    int64_t n = 0;
+    const int rc = linr_seg_tab(seg_off_h, n_seg, &tab, &n);
+    if (rc) return rc;
+    if (ld < n) return LINR_EINVAL;
+    if (n == 0) return 0;
+    if (!coords || !nbr || !ws) return LINR_EINVAL;
+    if (ws_bytes < linr_kmap_workspace_bytes(n)) return LINR_ENOSPC;
+    if (((uintptr_t)ws) & 7u) return LINR_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    long long* keys = (long long*)ws;
+    linr_poison_hook(s, 15);
+    kmap_keys_k<<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(coords, n, keys);
+    kmap_search_seg_k<<<linr_grid(9 * n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(keys, coords, n, tab, nbr, ld);
+    return linr_launch_rc();
+}
+
 extern "C" int linr_kmap_validate(const int32_t* coords, int64_t n, int32_t* bad, void* stream) {
     if (n < 0 || !bad) return LINR_EINVAL;
     if (n == 0) return 0;

@@ -41,7 +41,7 @@ def decode_one_gop(inargs):
 
 
 def main(argv=None):
-    """python -m linr_pcgc_amd.decoder --enc-dir OUT/result_enc --dec-dir OUT/dec [--ori-dir frames --ori-type ply]
+    """python -m linr_pcgc_amd.decoder --enc-dir OUT/result_enc --dec-dir OUT/dec [--ori-dir frames --ori-type ply] [--lockstep B]
     The decoder as its own program (decoder.py:179-200): every GOP under --enc-dir from its files alone, frames written as
     frameXXXX.ply; with --ori-dir each one is also compared with the input.  The model's shape travels in side_info.json (the
     reference hard-codes it, decoder.py:189); for streams without it the scale count is read off the stream files and width /
@@ -55,6 +55,8 @@ def main(argv=None):
     ap.add_argument('--ori-type', default='ply', choices=['ply', 'npy'])
     ap.add_argument('--hidden-channel-conv', type=int, default=8)
     ap.add_argument('--block-layers', type=int, default=1)
+    ap.add_argument('--lockstep', type=int, default=0,
+                    help='decode the frames of a GOP in groups of up to this many, all scales in lock step (codec.decode_gop lockstep=; 0: frame by frame)')
     args = ap.parse_args(argv)
     names = sorted((n for n in os.listdir(args.enc_dir) if n.startswith('gop_')), key=lambda n: gop_bounds(n)[0])
     if not names:
@@ -74,7 +76,10 @@ def main(argv=None):
                  'hidden_channel_conv': int(side.get('hidden_channel_conv', args.hidden_channel_conv)),
                  'block_layers': int(side.get('block_layers', args.block_layers)), 'outstage': 8, 'instage': 1}
         gen = lambda: LINR_PCGC_Model(shape).to(dev)
-        decoded = codec.decode_gop(gen(), enc, dev, workers=1 if shape['hidden_channel_conv'] != 8 else 4)
+        if args.lockstep > 0:
+            decoded = codec.decode_gop(gen(), enc, dev, lockstep=args.lockstep)
+        else:
+            decoded = codec.decode_gop(gen(), enc, dev, workers=1 if shape['hidden_channel_conv'] != 8 else 4)
         if len(decoded) != last - first + 1:
             raise ValueError('%s holds %d frames, its name says %d' % (name, len(decoded), last - first + 1))
         for i, dec in enumerate(decoded):

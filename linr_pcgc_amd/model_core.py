@@ -356,6 +356,47 @@ class LINR_PCGC_Model(nn.Module):
                    'linr_decode_scale')
         return child[:m.value]
 
+    @torch.no_grad()
+    def decode_scale_batch(self, coords_list, scale_idx, enc_bytes_list, n_threads=8):
+        """decode_scale for several frames in lock step as ONE C call (linr_decode_scale_batch): the frames' levels `coords_list`
+        (int32 [n_i,3] on the GPU, each sorted x-major) are one row space whose kernel map never links two frames, every decode stage
+        is one launch set and one copy each way for all of them, their range decoders run on `n_threads` host threads, and the
+        children come from prefix sums instead of a sort.  Returns the list of the next finer levels' coordinates (int32 [m_i,3])."""
+        import ctypes
+        L = _lib.lib()
+        nf = len(coords_list)
+        if nf < 1 or nf > 64 or len(enc_bytes_list) != nf:
+            raise ValueError('decode_scale_batch takes 1 to 64 frames and one packed stream per frame')
+        seg = np.zeros(nf + 1, dtype=np.int64)
+        seg[1:] = np.cumsum([int(c.shape[0]) for c in coords_list])
+        n = int(seg[-1])
+        dev = coords_list[0].device
+        if n == 0:
+            return [c.new_zeros((0, 3)) for c in coords_list]
+        coord = torch.cat(coords_list, dim=0).contiguous() if nf > 1 else coords_list[0].contiguous()
+        bufs = [np.frombuffer(b, dtype=np.uint8) for e in enc_bytes_list for b in unpack_bitstream(e)]
+        if len(bufs) != 8 * nf:
+            raise ValueError('every frame needs the 8 stage streams of the scale')
+        ptrs = (ctypes.c_void_p * (8 * nf))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (ctypes.c_int64 * (8 * nf))(*[int(b.size) for b in bufs])
+        bf16 = self._precision(None) == 'bf16'
+        need = L.linr_decode_scale_batch_ws_bytes(n, nf, self.block_layers, 1 if bf16 else 0)
+        if need == 0:
+            raise ValueError('%d rows in one decode group: the bound is 2^26 - 64' % n)
+        ws = _lib.scratch(need + 256, dev)
+        base = (ws.data_ptr() + 255) & ~255
+        child = torch.empty((8 * n, 3), dtype=torch.int32, device=dev)
+        p_host, s_host = self._host_buffers(n)
+        off = (ctypes.c_int64 * (nf + 1))()
+        codes, lo, hi, params = (self._qcodes.data_ptr(), float(self._qrange[0]), float(self._qrange[1]), None) if bf16 else \
+            (None, 0.0, 0.0, self._flat.data_ptr())
+        _lib.check(L.linr_decode_scale_batch(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num, self.block_layers,
+                                             params, codes, lo, hi, ptrs, lens, base, need, p_host.data_ptr(), s_host.data_ptr(),
+                                             child.data_ptr(), 8 * n, off, int(n_threads), torch.cuda.current_stream().cuda_stream),
+                   'linr_decode_scale_batch')
+        self._lockstep_ws_peak = max(getattr(self, '_lockstep_ws_peak', 0), int(need))
+        return [child[off[i]:off[i + 1]] for i in range(nf)]
+
     def _host_buffers(self, rows):
         """Pinned staging buffers of the staged decoder (probabilities down, decoded symbols up), grown on demand."""
         import threading

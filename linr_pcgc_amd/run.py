@@ -57,6 +57,9 @@ def parse(argv=None):
                     help="the range coder's 16-bit code values and symbol bits are computed on the GPU (linr_ac_codes): 17 bits per symbol "
                          'cross to the host instead of 40; the streams are byte for byte those of the default path')
     ap.add_argument('--decode', action='store_true', help='decode every GOP again and check it is lossless')
+    ap.add_argument('--decode-lockstep', '--decode_lockstep', dest='decode_lockstep', type=int, default=0,
+                    help='with --decode: decode the frames of a GOP in groups of up to this many, all scales in lock step '
+                         '(codec.decode_gop lockstep=; 0: frame by frame on 4 workers)')
     ap.add_argument('--mid-test', action='store_true',
                     help='main.py --mid_test: measure the model through Test_one_gop (model.codec) at epochs 0..9 and every --check-freq-th '
                          'epoch of every GOP; results under <out>/output/<gop>/<epoch>/ and <out>/output/<gop>/result.json')
@@ -216,8 +219,9 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
         ok = None
         if args.decode:
             todo = list(range(len(group))) if decode_frames is None else list(range(min(decode_frames, len(group))))
+            lockstep = int(getattr(args, 'decode_lockstep', 0) or 0)
             dec = codec.decode_gop(overfit.gen_model(gop.scale_num, device, block_layers=getattr(args, 'block_layers', 1), hidden=getattr(args, 'hidden_channel_conv', 8)),
-                                   codec.read_gop(res_dir), device, frames=todo, workers=4)
+                                   codec.read_gop(res_dir), device, frames=todo, **({'lockstep': lockstep} if lockstep > 0 else {'workers': 4}))
             ok = all(torch.equal(d, torch.as_tensor(gop.infos[i]['ori']).cuda() +
                                  torch.tensor(gop.coord_mins[i], device='cuda', dtype=torch.int32))
                      for d, i in zip(dec, todo))
