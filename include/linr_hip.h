@@ -305,7 +305,7 @@ LINR_API int linr_prof_mask(uint32_t mask);
  * linr_net_forward / _backward / _train_step whose kernel class (the list above) has its bit set in kind_mask is preceded by a kernel that fills the LDS of every CU with 0xFFFFFFFF (a NaN
  * pattern) - results must not change: a kernel may not read on-chip state it did not write (on a GPU shared with another
  * process the leftovers are not one's own finite numbers). */
-LINR_API int linr_debug_poison(uint32_t kind_mask);          /* bits 0..13: the classes above; 14: bf16 executor; 15: linr_decode_scale; 16: the entries of csrc/wide.hip */
+LINR_API int linr_debug_poison(uint32_t kind_mask);          /* bits 0..13: the classes above; 14: bf16 executor; 15: the decoder scales of csrc/decode.hip (linr_decode_scale, linr_decode_scale_batch, linr_children_segments) and linr_kmap_build_segments; 16: the entries of csrc/wide.hip */
 LINR_API int linr_debug_poison_now(void* stream);           /* the same poisoning, once, on `stream` (in front of an op-level call) */
 LINR_API int linr_prof_enable(int32_t mode);
 LINR_API int linr_prof_read(int32_t kind, double* total_ms, int64_t* launches, int64_t* passes);
@@ -497,7 +497,9 @@ LINR_API int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* in
  * lengths; f->occ must be writable device memory (the frame's occupancy, zeroed by the caller; LINR_FRAME_OCC_PADDED honoured);
  * probs [8][rows] device scratch (holds all 8 stages' probabilities afterwards); p_pinned [rows] floats and s_pinned [rows]
  * bytes of page-locked host memory; s_dev [rows] bytes of device scratch.  codes == NULL: fp32 executor with `params`;
- * otherwise the bf16 / uint8-weight executor with codes, min_param, max_param (then `arena` is a linr_net_bf16_arena_bytes one). */
+ * otherwise the bf16 / uint8-weight executor with codes, min_param, max_param (then `arena` is a linr_net_bf16_arena_bytes one).
+ * A scale without rows is skipped, its streams unread.  A stream the range decoder refuses ends the call with the code of the first
+ * such scale, before anything more is launched.  (csrc/decode.hip: decode_stages, the loop linr_net_decode_stages_segments shares.) */
 LINR_API int linr_net_decode_stages(const linr_frame* f, const float* params, const uint8_t* codes, float min_param,
                            float max_param, void* arena, size_t arena_bytes, const uint8_t* const* streams_h,
                            const int64_t* stream_len_h, float* probs, float* p_pinned, uint8_t* s_pinned, uint8_t* s_dev,
@@ -535,14 +537,17 @@ LINR_API int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_id
  *
  * linr_net_decode_stages_segments: linr_net_decode_stages for a frame object of ONE scale whose rows are n_seg segments (seg_off_h),
  * each with its own 8 stage streams (streams_h / stream_len_h [n_seg][8]); the n_seg range decoders of a stage run on up to
- * n_threads host threads (linr_ac_decode_binary_batch).
+ * n_threads host threads (linr_ac_decode_binary_batch).  The same loop (csrc/decode.hip: decode_stages) with the segments in the place
+ * of the frame's scales: an empty segment is skipped, its streams unread.
  *
  * linr_decode_scale_batch: linr_decode_scale for n_frames frames (1..LINR_DECODE_MAX_FRAMES) with N = seg_off_h[n_frames] rows
  * (N < 2^26): segmented kernel map, its compressed form and offset features, the 8 stages in lock step, the children.  streams_h /
  * stream_len_h: HOST [n_frames][8]; p_pinned / s_pinned: pinned HOST buffers of N floats / N bytes; child_xyz: DEVICE int32
  * [child_cap][3] (8 N is always enough); child_off_h: HOST [n_frames + 1].  ws: linr_decode_scale_batch_ws_bytes(N, n_frames,
  * block_layers, codes != NULL) bytes, 256-byte aligned.  Arguments are checked before the first launch: LINR_EINVAL, LINR_ENOSPC
- * (short ws), LINR_EALIGN as linr_decode_scale.  The new kernels belong to poison class 15 and to no linr_prof_* class. */
+ * (short ws), LINR_EALIGN as linr_decode_scale.  Both scale entries share their workspace layout, everything in front of the stages and
+ * the stage loop (csrc/decode.hip: layout, scale_prologue, decode_stages); they differ in the kernel-map call and the child expansion.
+ * Their kernels belong to poison class 15 and to no linr_prof_* class. */
 LINR_API size_t linr_children_segments_ws_bytes(int64_t n);
 LINR_API int linr_children_segments(const int32_t* coords, const float* occ, const int64_t* seg_off_h, int32_t n_seg, int32_t* child_xyz,
                            int64_t child_cap, int64_t* child_off_h, void* ws, size_t ws_bytes, void* stream);

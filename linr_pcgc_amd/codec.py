@@ -263,23 +263,30 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
         if timing is not None:
             timing['lockstep_ws_bytes'] = int(getattr(model, '_lockstep_ws_peak', 0))          # the largest workspace of a call
         return out
-    if workers <= 1 or len(todo) <= 1:
-        return [one(i) for i in todo]
+    return _map_on_streams(one, todo, workers)
+
+
+def _map_on_streams(fn, items, workers):
+    """[fn(x) for x in items] on a pool of `workers` host threads, every call on a fresh HIP stream of the caller's device that
+    waits on the caller's stream first and is synchronised before the call's result is handed back; serial on the caller's stream
+    with one worker or one item."""
+    if workers <= 1 or len(items) <= 1:
+        return [fn(x) for x in items]
     from concurrent.futures import ThreadPoolExecutor
     main_stream = torch.cuda.current_stream()
     dev_index = torch.cuda.current_device()
 
-    def job(i):
+    def job(x):
         torch.cuda.set_device(dev_index)
         st = torch.cuda.Stream()
         st.wait_stream(main_stream)                 # the decompressed parameters were written on the caller's stream
         with torch.cuda.stream(st):
-            out = one(i)
+            out = fn(x)
         st.synchronize()
         return out
 
     with ThreadPoolExecutor(max_workers=workers) as pool:
-        return list(pool.map(job, todo))
+        return list(pool.map(job, items))
 
 
 def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads):
@@ -294,23 +301,7 @@ def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep
         dec = decode_frames_lockstep(model, [list(enc['frames'][i]) for i in group], xyz_lows, per_group)
         return [d + torch.tensor(mins[i], device=device, dtype=torch.int32) for i, d in zip(group, dec)]
 
-    if workers <= 1:
-        return [x for g in groups for x in one(g)]
-    from concurrent.futures import ThreadPoolExecutor
-    main_stream = torch.cuda.current_stream()
-    dev_index = torch.cuda.current_device()
-
-    def job(group):
-        torch.cuda.set_device(dev_index)
-        st = torch.cuda.Stream()
-        st.wait_stream(main_stream)                 # the decompressed parameters were written on the caller's stream
-        with torch.cuda.stream(st):
-            out = one(group)
-        st.synchronize()
-        return out
-
-    with ThreadPoolExecutor(max_workers=workers) as pool:
-        return [x for out in pool.map(job, groups) for x in out]
+    return [x for out in _map_on_streams(one, groups, workers) for x in out]
 
 
 def write_gop(enc, result_dir):

@@ -1,22 +1,33 @@
-// One scale of the staged decoder as ONE call (decoder.decode_one_frame's loop body, decoder.py:153-176): the kernel map of the
-// coarser level's coordinates, the 7-neighbour features read off it, the 8 decode stages (stage forward, D2H, range decoder, H2D:
-// linr_net_decode_stages) and the next level's coordinates (octree_level.upper_layer, models/module_utils.py:117-127: the children
-// 2 p + (dx, dy, dz) of every occupied octant, sorted x-major).  Between two scales the caller only allocates the next
-// workspace, so a frame's decode holds the Python GIL for a few hundred microseconds instead of ~7 ms.
-// linr_decode_scale_batch below does the same for the frames of a GOP in lock step, with a sort-free child expansion.
+// The staged decoder.  The 8 decode stages of a frame object (decode_stages: stage forward, D2H, range decoders, H2D, occupancy
+// column; exported as linr_net_decode_stages for a frame's scales and as linr_net_decode_stages_segments for one scale of several
+// frames), and one scale of the decoder as ONE call (decoder.decode_one_frame's loop body, decoder.py:153-176): the kernel map of
+// the coarser level's coordinates, the 7-neighbour features read off it, the 8 stages and the next level's coordinates
+// (octree_level.upper_layer, models/module_utils.py:117-127: the children 2 p + (dx, dy, dz) of every occupied octant, sorted
+// x-major).  Between two scales the caller only allocates the next workspace, so a frame's decode holds the Python GIL for a few
+// hundred microseconds instead of ~7 ms.  linr_decode_scale does it for one frame and linr_decode_scale_batch for the frames of a GOP
+// in lock step; they share the workspace layout (layout), everything in front of the stages (scale_prologue) and the stage loop, and
+// differ in the kernel map (one list / segments) and in the child expansion (radix sort / prefix sums).
 #include "common.h"
 #include "layout.h"
 #include <hipcub/hipcub.hpp>
+
+#define TRY(e) do { int rc_ = (e); if (rc_) return rc_; } while (0)
+
+// decoded byte column -> float column k of the occupancy matrix [rows][8] (outside the namespace: it keeps the name that kernel
+// traces have known it by)
+__global__ __launch_bounds__(LINR_BLOCK) void occ_col_from_u8_k(const uint8_t* __restrict__ sym, int64_t n, float* __restrict__ occ_col) {
+    const int64_t r = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
+    if (r < n) occ_col[r * 8] = (float)sym[r];
+}
 
 namespace {
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-struct DecodeWs {              // byte offsets into the caller's workspace
-    size_t nbr, lo, mask, feat, occ, probs, sdev, kws, cnt, pos, keys0, keys1, cub, arena, total;
-    int64_t ld;
-    size_t arena_bytes, cub_bytes;
-};
+// the child expansion's part of the workspace: byte offsets into it
+struct SortWs { size_t cnt, pos, keys0, keys1, cub, total, cub_bytes; };       // one frame: count, scan, keys, radix sort
+struct ChildWs { size_t cnt, sum, bounds, cub, total, cub_bytes; };            // frames in lock step: pair counts, one scan
+ChildWs child_layout(int64_t n);
 
 size_t cub_bytes_for(int64_t n) {
     size_t a = 0, b = 0;
@@ -26,8 +37,32 @@ size_t cub_bytes_for(int64_t n) {
     return a > b ? a : b;
 }
 
-DecodeWs layout(int64_t n, int block_layers, int bf16) {
-    DecodeWs w;
+SortWs sort_layout(int64_t n) {
+    SortWs w;
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { size_t o = cur; cur += up256(bytes); return o; };
+    w.cnt = take((size_t)(n + 1) * 4);
+    w.pos = take((size_t)(n + 1) * 4);
+    w.keys0 = take((size_t)8 * n * 8);
+    w.keys1 = take((size_t)8 * n * 8);
+    w.cub_bytes = cub_bytes_for(n);
+    w.cub = take(w.cub_bytes);
+    w.total = cur;
+    return w;
+}
+
+// byte offsets of one decoder scale of n rows into the caller's workspace; the region `child` is laid out by sort (linr_decode_scale)
+// or by scan (linr_decode_scale_batch), whichever layout() was asked for: `is_scan` says which member is set
+struct ScaleWs {
+    size_t nbr, lo, mask, feat, occ, probs, sdev, kws, child, arena, total;
+    int64_t ld;
+    size_t arena_bytes;
+    bool is_scan;
+    union { SortWs sort; ChildWs scan; };
+};
+
+ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan) {
+    ScaleWs w;
     w.ld = (n + 63) / 64 * 64;
     size_t cur = 0;
     auto take = [&](size_t bytes) { size_t o = cur; cur += up256(bytes); return o; };
@@ -39,16 +74,45 @@ DecodeWs layout(int64_t n, int block_layers, int bf16) {
     w.probs = take((size_t)8 * n * 4);
     w.sdev = take((size_t)n);
     w.kws = take(linr_kmap_workspace_bytes(n));
-    w.cnt = take((size_t)(n + 1) * 4);
-    w.pos = take((size_t)(n + 1) * 4);
-    w.keys0 = take((size_t)8 * n * 8);
-    w.keys1 = take((size_t)8 * n * 8);
-    w.cub_bytes = cub_bytes_for(n);
-    w.cub = take(w.cub_bytes);
+    w.is_scan = scan;
+    if (scan) w.scan = child_layout(n); else w.sort = sort_layout(n);
+    w.child = take(scan ? w.scan.total : w.sort.total);
     w.arena_bytes = bf16 ? linr_net_bf16_arena_bytes(n, block_layers) : linr_net_arena_bytes(n, block_layers);
     w.arena = take(w.arena_bytes);
     w.total = cur;
     return w;
+}
+
+// the frame object of one decoder scale (its host arrays live beside it)
+struct ScaleFrame { linr_frame f; int64_t row_off[2]; int32_t sidx[1]; };
+
+// Everything of a decoder scale in front of its stages: the kernel map of the n rows of `coord` (padding columns of nbr / lo / mask:
+// no neighbour) - of one list, or with seg_off_h of n_seg lists back to back whose rows never see each other -, its compressed form,
+// the scale context's features, the zeroed occupancy and the one-scale frame over them.
+int scale_prologue(const int32_t* coord, int64_t n, const int64_t* seg_off_h, int n_seg, int scale_idx, int model_scale_num,
+                   int block_layers, char* base, const ScaleWs& w, ScaleFrame& sf, hipStream_t s) {
+    int32_t* nbr = (int32_t*)(base + w.nbr);
+    int32_t* lo = (int32_t*)(base + w.lo);
+    uint32_t* mask = (uint32_t*)(base + w.mask);
+    float* feat = (float*)(base + w.feat);
+    float* occ_buf = (float*)(base + w.occ);
+    TRY(linr_hip_rc(hipMemsetAsync(nbr, 0xFF, (size_t)27 * w.ld * 4, s)));
+    TRY(linr_hip_rc(hipMemsetAsync(lo, 0, w.mask + (size_t)w.ld * 4 - w.lo, s)));            // lo and mask are adjacent
+    if (seg_off_h) {
+        TRY(linr_kmap_build_segments(coord, seg_off_h, n_seg, nbr, w.ld, base + w.kws, linr_kmap_workspace_bytes(n), s));
+    } else {
+        linr_poison_hook(s, 15);
+        TRY(linr_kmap_build(coord, n, nbr, w.ld, 0, base + w.kws, linr_kmap_workspace_bytes(n), s));
+    }
+    TRY(linr_kmap_compress(nbr, w.ld, n, lo, mask, w.ld, s));
+    TRY(linr_kmap_offset_feat(nbr, w.ld, 0, n, feat, s));
+    TRY(linr_hip_rc(hipMemsetAsync(occ_buf, 0, (size_t)(n + 1) * 8 * 4, s)));
+    sf.row_off[0] = 0; sf.row_off[1] = n; sf.sidx[0] = scale_idx;
+    linr_frame& f = sf.f;
+    f.rows = n; f.n_scales = 1; f.model_scale_num = model_scale_num; f.block_layers = block_layers; f.flags = LINR_FRAME_OCC_PADDED;
+    f.row_off_h = sf.row_off; f.scale_idx_h = sf.sidx; f.nbr = nbr; f.nbr_ld = w.ld; f.nbr_lo = lo; f.nbr_mask = mask;
+    f.offset_feat = feat; f.occ = occ_buf + 8; f.nbr8t = nullptr;     // zero row in front of the occupancy (LINR_FRAME_OCC_PADDED)
+    return 0;
 }
 
 // cnt[r] = occupied octants of row r (cnt[n] = 0 closes the scan)
@@ -89,11 +153,75 @@ __global__ __launch_bounds__(LINR_BLOCK) void keys_to_coord_k(const uint64_t* __
     xyz[3 * i + 2] = (int32_t)(k & msk);
 }
 
+// The 8 decode stages of the frame object f, whose rows are n_seg segments (seg_off_h, HOST) with 8 streams each.  The stage's forward
+// checks f (linr_frame_layout) before seg_off_h is read, so that may be f's own row_off_h.  An empty segment is left out with its
+// streams unread.  The range decoders return the first failing segment's code (in order on this thread with n_threads 1); they
+// decode the segments behind it, too, but those bytes stay in s_pinned: the call returns before anything more is launched.
+int decode_stages(const linr_frame* f, const float* params, const uint8_t* codes, float min_param, float max_param, void* arena,
+                  size_t arena_bytes, const int64_t* seg_off_h, int n_seg, const uint8_t* const* streams_h,
+                  const int64_t* stream_len_h, float* probs, float* p_pinned, uint8_t* s_pinned, uint8_t* s_dev, int n_threads,
+                  hipStream_t s) {
+    const int64_t R = f->rows;
+    if (R == 0) return 0;
+    float* occ = const_cast<float*>(f->occ);
+    static_assert(LINR_DECODE_MAX_FRAMES >= MAX_SCALES, "the per-segment arrays also hold a frame's scales");
+    const float* p_h[LINR_DECODE_MAX_FRAMES];
+    uint8_t* s_h[LINR_DECODE_MAX_FRAMES];
+    const uint8_t* in_h[LINR_DECODE_MAX_FRAMES];
+    int64_t n_h[LINR_DECODE_MAX_FRAMES], len_h[LINR_DECODE_MAX_FRAMES];
+    for (int k = 0; k < 8; ++k) {
+        if (codes) TRY(linr_net_forward_bf16(f, codes, min_param, max_param, arena, arena_bytes, k, k + 1, probs, nullptr, s));
+        else TRY(linr_net_forward(f, params, (float*)arena, arena_bytes, k, k + 1, probs, nullptr, s));
+        TRY(linr_hip_rc(hipMemcpyAsync(p_pinned, probs + (int64_t)k * R, (size_t)R * sizeof(float), hipMemcpyDeviceToHost, s)));
+        TRY(linr_hip_rc(hipStreamSynchronize(s)));
+        int m = 0;
+        for (int i = 0; i < n_seg; ++i) {
+            const int64_t r0 = seg_off_h[i], n = seg_off_h[i + 1] - r0;
+            if (n <= 0) continue;
+            p_h[m] = p_pinned + r0; s_h[m] = s_pinned + r0; n_h[m] = n;
+            in_h[m] = streams_h[i * 8 + k]; len_h[m] = stream_len_h[i * 8 + k];
+            ++m;
+        }
+        TRY(linr_ac_decode_binary_batch(p_h, n_h, in_h, len_h, m, s_h, n_threads));
+        TRY(linr_hip_rc(hipMemcpyAsync(s_dev, s_pinned, (size_t)R, hipMemcpyHostToDevice, s)));
+        occ_col_from_u8_k<<<linr_grid(R, LINR_BLOCK), LINR_BLOCK, 0, s>>>(s_dev, R, occ + k);
+        TRY(linr_launch_rc());
+    }
+    return linr_hip_rc(hipStreamSynchronize(s));       // s_pinned / p_pinned may be reused by the caller right away
+}
+
 }  // namespace
+
+extern "C" int linr_net_decode_stages(const linr_frame* f, const float* params, const uint8_t* codes, float min_param,
+                                      float max_param, void* arena, size_t arena_bytes, const uint8_t* const* streams_h,
+                                      const int64_t* stream_len_h, float* probs, float* p_pinned, uint8_t* s_pinned,
+                                      uint8_t* s_dev, void* stream) {
+    if (!f || !arena || !streams_h || !stream_len_h || !probs || !p_pinned || !s_pinned || !s_dev || !f->occ) return LINR_EINVAL;
+    if (!codes && !params) return LINR_EINVAL;
+    return decode_stages(f, params, codes, min_param, max_param, arena, arena_bytes, f->row_off_h, f->n_scales, streams_h, stream_len_h,
+                         probs, p_pinned, s_pinned, s_dev, 1, (hipStream_t)stream);
+}
+
+// The same for a frame of ONE scale whose rows are the levels of n_seg frames back to back (linr_decode_scale_batch): a stage is one
+// forward, one copy each way and n_seg range decoders on host threads.
+extern "C" int linr_net_decode_stages_segments(const linr_frame* f, const float* params, const uint8_t* codes, float min_param,
+                                               float max_param, void* arena, size_t arena_bytes, const int64_t* seg_off_h,
+                                               int32_t n_seg, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                                               float* probs, float* p_pinned, uint8_t* s_pinned, uint8_t* s_dev, int32_t n_threads,
+                                               void* stream) {
+    if (!f || !arena || !seg_off_h || !streams_h || !stream_len_h || !probs || !p_pinned || !s_pinned || !s_dev || !f->occ) return LINR_EINVAL;
+    if (!codes && !params) return LINR_EINVAL;
+    if (n_seg < 1 || n_seg > LINR_DECODE_MAX_FRAMES || f->n_scales != 1) return LINR_EINVAL;
+    if (seg_off_h[0] != 0 || seg_off_h[n_seg] != f->rows) return LINR_EINVAL;
+    for (int i = 0; i < n_seg; ++i)
+        if (seg_off_h[i + 1] < seg_off_h[i]) return LINR_EINVAL;
+    return decode_stages(f, params, codes, min_param, max_param, arena, arena_bytes, seg_off_h, n_seg, streams_h, stream_len_h, probs,
+                         p_pinned, s_pinned, s_dev, n_threads, (hipStream_t)stream);
+}
 
 extern "C" size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16) {
     if (n < 0 || block_layers < 1) return 0;
-    return layout(n, block_layers, bf16 ? 1 : 0).total + 256;
+    return layout(n, block_layers, bf16 ? 1 : 0, false).total + 256;
 }
 
 extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
@@ -108,62 +236,33 @@ extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_
     // (one row looser than linr_rows_fit32, which the executor's frame check then applies to the frame built below)
     if (child_cap < 0 || n >= ((int64_t)1 << 27)) return LINR_EINVAL;
     if (((uintptr_t)ws) & 255u) return LINR_EALIGN;
-    const DecodeWs w = layout(n, block_layers, codes ? 1 : 0);
+    const ScaleWs w = layout(n, block_layers, codes ? 1 : 0, false);
     if (ws_bytes < w.total) return LINR_ENOSPC;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
-    int32_t* nbr = (int32_t*)(base + w.nbr);
-    int32_t* lo = (int32_t*)(base + w.lo);
-    uint32_t* mask = (uint32_t*)(base + w.mask);
-    float* feat = (float*)(base + w.feat);
-    float* occ_buf = (float*)(base + w.occ);
-    float* occ = occ_buf + 8;                                   // zero row in front (LINR_FRAME_OCC_PADDED)
-    float* probs = (float*)(base + w.probs);
-    uint8_t* s_dev = (uint8_t*)(base + w.sdev);
-    int32_t* cnt = (int32_t*)(base + w.cnt);
-    int32_t* pos = (int32_t*)(base + w.pos);
-    uint64_t* keys0 = (uint64_t*)(base + w.keys0);
-    uint64_t* keys1 = (uint64_t*)(base + w.keys1);
-    // kernel map of this level (padding columns of nbr / lo / mask: no neighbour), its compressed form, the scale context's features
-    int rc = linr_hip_rc(hipMemsetAsync(nbr, 0xFF, (size_t)27 * w.ld * 4, s));
-    if (rc) return rc;
-    rc = linr_hip_rc(hipMemsetAsync(lo, 0, w.mask + (size_t)w.ld * 4 - w.lo, s));            // lo and mask are adjacent
-    if (rc) return rc;
-    linr_poison_hook(s, 15);
-    rc = linr_kmap_build(coord, n, nbr, w.ld, 0, base + w.kws, linr_kmap_workspace_bytes(n), stream);
-    if (rc) return rc;
-    rc = linr_kmap_compress(nbr, w.ld, n, lo, mask, w.ld, stream);
-    if (rc) return rc;
-    rc = linr_kmap_offset_feat(nbr, w.ld, 0, n, feat, stream);
-    if (rc) return rc;
-    rc = linr_hip_rc(hipMemsetAsync(occ_buf, 0, (size_t)(n + 1) * 8 * 4, s));
-    if (rc) return rc;
-    int64_t row_off[2] = {0, n};
-    int32_t sidx[1] = {scale_idx};
-    linr_frame f;
-    f.rows = n; f.n_scales = 1; f.model_scale_num = model_scale_num; f.block_layers = block_layers; f.flags = LINR_FRAME_OCC_PADDED;
-    f.row_off_h = row_off; f.scale_idx_h = sidx; f.nbr = nbr; f.nbr_ld = w.ld; f.nbr_lo = lo; f.nbr_mask = mask;
-    f.offset_feat = feat; f.occ = occ; f.nbr8t = nullptr;
-    rc = linr_net_decode_stages(&f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, streams_h, stream_len_h, probs,
-                                p_pinned, s_pinned, s_dev, stream);
-    if (rc) return rc;
+    ScaleFrame sf;
+    TRY(scale_prologue(coord, n, nullptr, 0, scale_idx, model_scale_num, block_layers, base, w, sf, s));
+    TRY(decode_stages(&sf.f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, sf.row_off, 1, streams_h, stream_len_h,
+                      (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), 1, s));
     // upper_layer: children of the occupied octants, sorted x-major
+    const float* occ = sf.f.occ;
+    char* cbase = base + w.child;
+    int32_t* cnt = (int32_t*)(cbase + w.sort.cnt);
+    int32_t* pos = (int32_t*)(cbase + w.sort.pos);
+    uint64_t* keys0 = (uint64_t*)(cbase + w.sort.keys0);
+    uint64_t* keys1 = (uint64_t*)(cbase + w.sort.keys1);
     linr_poison_hook(s, 15);
     child_count_k<<<linr_grid(n + 1, LINR_BLOCK), LINR_BLOCK, 0, s>>>(occ, n, cnt);
-    size_t cb = w.cub_bytes;
-    rc = linr_hip_rc(hipcub::DeviceScan::ExclusiveSum(base + w.cub, cb, cnt, pos, (int)(n + 1), s));
-    if (rc) return rc;
+    size_t cb = w.sort.cub_bytes;
+    TRY(linr_hip_rc(hipcub::DeviceScan::ExclusiveSum(cbase + w.sort.cub, cb, cnt, pos, (int)(n + 1), s)));
     int32_t total = 0;
-    rc = linr_hip_rc(hipMemcpyAsync(&total, pos + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (rc) return rc;
+    TRY(linr_hip_rc(hipMemcpyAsync(&total, pos + n, sizeof(int32_t), hipMemcpyDeviceToHost, s)));
     child_keys_k<<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(coord, occ, pos, n, child_bits, keys0);
-    rc = linr_hip_rc(hipStreamSynchronize(s));                  // `total` is on the host now
-    if (rc) return rc;
+    TRY(linr_hip_rc(hipStreamSynchronize(s)));                  // `total` is on the host now
     if (total > child_cap) return LINR_ENOSPC;
     if (total > 0) {
-        cb = w.cub_bytes;
-        rc = linr_hip_rc(hipcub::DeviceRadixSort::SortKeys(base + w.cub, cb, keys0, keys1, (int)total, 0, 3 * child_bits, s));
-        if (rc) return rc;
+        cb = w.sort.cub_bytes;
+        TRY(linr_hip_rc(hipcub::DeviceRadixSort::SortKeys(cbase + w.sort.cub, cb, keys0, keys1, (int)total, 0, 3 * child_bits, s)));
         keys_to_coord_k<<<linr_grid(total, LINR_BLOCK), LINR_BLOCK, 0, s>>>(keys1, pos + n, child_bits, child_xyz, child_cap);
     }
     *child_n_h = total;
@@ -185,7 +284,6 @@ struct Cnt4Sum {
         return Cnt4{{a.q[0] + b.q[0], a.q[1] + b.q[1], a.q[2] + b.q[2], a.q[3] + b.q[3]}};
     }
 };
-struct ChildWs { size_t cnt, sum, bounds, cub, total, cub_bytes; };
 
 ChildWs child_layout(int64_t n) {
     ChildWs w;
@@ -303,29 +401,6 @@ int children_segments(const int32_t* coord, const float* occ, const LinrSegTab& 
     return bounds_h[n_seg] > child_cap ? LINR_ENOSPC : 0;
 }
 
-struct BatchWs { size_t nbr, lo, mask, feat, occ, probs, sdev, kws, child, arena, total; int64_t ld; size_t arena_bytes; ChildWs cw; };
-
-BatchWs batch_layout(int64_t n, int block_layers, int bf16) {
-    BatchWs w;
-    w.ld = (n + 63) / 64 * 64;
-    size_t cur = 0;
-    auto take = [&](size_t bytes) { size_t o = cur; cur += up256(bytes); return o; };
-    w.nbr = take((size_t)27 * w.ld * 4);
-    w.lo = take((size_t)9 * w.ld * 4);
-    w.mask = take((size_t)w.ld * 4);
-    w.feat = take((size_t)n * 7 * 4);
-    w.occ = take((size_t)(n + 1) * 8 * 4);
-    w.probs = take((size_t)8 * n * 4);
-    w.sdev = take((size_t)n);
-    w.kws = take(linr_kmap_workspace_bytes(n));
-    w.cw = child_layout(n);
-    w.child = take(w.cw.total);
-    w.arena_bytes = bf16 ? linr_net_bf16_arena_bytes(n, block_layers) : linr_net_arena_bytes(n, block_layers);
-    w.arena = take(w.arena_bytes);
-    w.total = cur;
-    return w;
-}
-
 }  // namespace
 
 extern "C" size_t linr_children_segments_ws_bytes(int64_t n) { return n < 0 || n >= ((int64_t)1 << 26) ? 0 : child_layout(n).total; }
@@ -349,7 +424,7 @@ extern "C" int linr_children_segments(const int32_t* coords, const float* occ, c
 
 extern "C" size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16) {
     if (n_total < 0 || n_total >= ((int64_t)1 << 26) || n_frames < 1 || n_frames > LINR_DECODE_MAX_FRAMES || block_layers < 1) return 0;
-    return batch_layout(n_total, block_layers, bf16 ? 1 : 0).total + 256;
+    return layout(n_total, block_layers, bf16 ? 1 : 0, true).total + 256;
 }
 
 extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
@@ -368,40 +443,15 @@ extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_
     if (n == 0) return 0;
     if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !p_pinned || !s_pinned || !child_xyz) return LINR_EINVAL;
     if (((uintptr_t)ws) & 255u) return LINR_EALIGN;
-    const BatchWs w = batch_layout(n, block_layers, codes ? 1 : 0);
+    const ScaleWs w = layout(n, block_layers, codes ? 1 : 0, true);
     if (ws_bytes < w.total) return LINR_ENOSPC;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
-    int32_t* nbr = (int32_t*)(base + w.nbr);
-    int32_t* lo = (int32_t*)(base + w.lo);
-    uint32_t* mask = (uint32_t*)(base + w.mask);
-    float* feat = (float*)(base + w.feat);
-    float* occ_buf = (float*)(base + w.occ);
-    float* occ = occ_buf + 8;                                   // zero row in front (LINR_FRAME_OCC_PADDED)
-    // the segmented kernel map (padding columns of nbr / lo / mask: no neighbour), its compressed form, the scale context's features
-    rc = linr_hip_rc(hipMemsetAsync(nbr, 0xFF, (size_t)27 * w.ld * 4, s));
-    if (rc) return rc;
-    rc = linr_hip_rc(hipMemsetAsync(lo, 0, w.mask + (size_t)w.ld * 4 - w.lo, s));            // lo and mask are adjacent
-    if (rc) return rc;
-    rc = linr_kmap_build_segments(coord, seg_off_h, n_frames, nbr, w.ld, base + w.kws, linr_kmap_workspace_bytes(n), stream);
-    if (rc) return rc;
-    rc = linr_kmap_compress(nbr, w.ld, n, lo, mask, w.ld, stream);
-    if (rc) return rc;
-    rc = linr_kmap_offset_feat(nbr, w.ld, 0, n, feat, stream);
-    if (rc) return rc;
-    rc = linr_hip_rc(hipMemsetAsync(occ_buf, 0, (size_t)(n + 1) * 8 * 4, s));
-    if (rc) return rc;
-    int64_t row_off[2] = {0, n};
-    int32_t sidx[1] = {scale_idx};
-    linr_frame f;
-    f.rows = n; f.n_scales = 1; f.model_scale_num = model_scale_num; f.block_layers = block_layers; f.flags = LINR_FRAME_OCC_PADDED;
-    f.row_off_h = row_off; f.scale_idx_h = sidx; f.nbr = nbr; f.nbr_ld = w.ld; f.nbr_lo = lo; f.nbr_mask = mask;
-    f.offset_feat = feat; f.occ = occ; f.nbr8t = nullptr;
-    rc = linr_net_decode_stages_segments(&f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, seg_off_h, n_frames,
-                                         streams_h, stream_len_h, (float*)(base + w.probs), p_pinned, s_pinned,
-                                         (uint8_t*)(base + w.sdev), n_threads, stream);
-    if (rc) return rc;
-    return children_segments(coord, occ, tab, n, n_frames, child_xyz, child_cap, child_off_h, base + w.child, w.cw, s);
+    ScaleFrame sf;
+    TRY(scale_prologue(coord, n, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, base, w, sf, s));
+    TRY(decode_stages(&sf.f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, seg_off_h, n_frames, streams_h,
+                      stream_len_h, (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, s));
+    return children_segments(coord, sf.f.occ, tab, n, n_frames, child_xyz, child_cap, child_off_h, base + w.child, w.scan, s);
 }
 
 // ---- sorted unique coordinate list, optionally of the parents (coords >> shift); one octree level as one call ------------------------

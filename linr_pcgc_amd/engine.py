@@ -187,14 +187,20 @@ def net_forward_bf16(frame, codes, min_param, max_param, stage_begin, stage_end,
                                            0 if bits is None else bits.data_ptr(), _stream()), 'linr_net_forward_bf16')
 
 
+def stream_arrays(streams):
+    """Byte strings -> the HOST pointer and length arrays the decoder entries read them through (an empty stream: NULL, 0), and the
+    arrays that own the bytes: keep them until the call has returned."""
+    bufs = [np.frombuffer(b, dtype=np.uint8) for b in streams]
+    ptrs = (ctypes.c_void_p * len(bufs))(*[b.ctypes.data if b.size else None for b in bufs])
+    lens = (ctypes.c_int64 * len(bufs))(*[int(b.size) for b in bufs])
+    return ptrs, lens, bufs
+
+
 def net_decode_stages(frame, flat_params, streams_per_scale, probs, p_pinned, s_pinned, s_dev, qcodes=None, qrange=None):
     """linr_net_decode_stages: the 8 decode stages of a frame object (stage forward, D2H, range decoder, H2D, occupancy column)
     in one C call that does not hold the GIL.  streams_per_scale: [n_scales][8] byte strings; qcodes / qrange select the bf16 /
     uint8-weight executor.  frame.occ must be zeroed by the caller and holds the decoded occupancy afterwards."""
-    n = frame.n_scales
-    bufs = [np.frombuffer(streams_per_scale[i][k], dtype=np.uint8) for i in range(n) for k in range(8)]
-    ptrs = (ctypes.c_void_p * (8 * n))(*[b.ctypes.data if b.size else None for b in bufs])
-    lens = (ctypes.c_int64 * (8 * n))(*[int(b.size) for b in bufs])
+    ptrs, lens, _bufs = stream_arrays([streams_per_scale[i][k] for i in range(frame.n_scales) for k in range(8)])
     if qcodes is None:
         arena, codes, lo, hi = frame.arena, None, 0.0, 0.0
         base, nbytes = arena.data_ptr(), arena.numel()

@@ -11,6 +11,7 @@ Two ways in:
   * fast path used by ``overfit.py`` / ``bench.py``: ``Frame`` with all scales batched + ``train_step`` (forward,
     backward and the fused Adam update without touching autograd).
 """
+import ctypes
 import time
 
 import numpy as np
@@ -326,35 +327,40 @@ class LINR_PCGC_Model(nn.Module):
         frame = self.make_frame([s], with_arena=self._precision(None) == 'f32')
         return self.decode_frame(frame, [streams])
 
+    def _decode_scale_args(self, size_fn, size_args, coord, streams):
+        """What decode_scale and decode_scale_batch hand their C entry alike, in the entries' order: (params, codes, lo, hi, stream
+        pointers, stream lengths, aligned workspace, its bytes, pinned probabilities, pinned symbols, child buffer, its rows), the
+        workspace bytes (size_fn(*size_args, block_layers, bf16); 0: the entry refuses the size, nothing else is returned) and the
+        objects that own that memory, child buffer first: keep them until the call has returned."""
+        n = int(coord.shape[0])
+        ptrs, lens, bufs = engine.stream_arrays(streams)
+        bf16 = self._precision(None) == 'bf16'
+        need = size_fn(*size_args, self.block_layers, 1 if bf16 else 0)
+        if need == 0:
+            return None, 0, None
+        ws = _lib.scratch(need + 256, coord.device)
+        child = torch.empty((8 * n, 3), dtype=torch.int32, device=coord.device)
+        p_host, s_host = self._host_buffers(n)
+        codes, lo, hi, params = (self._qcodes.data_ptr(), float(self._qrange[0]), float(self._qrange[1]), None) if bf16 else \
+            (None, 0.0, 0.0, self._flat.data_ptr())
+        return (params, codes, lo, hi, ptrs, lens, (ws.data_ptr() + 255) & ~255, need, p_host.data_ptr(), s_host.data_ptr(),
+                child.data_ptr(), 8 * n), need, (child, ws, bufs)
+
     @torch.no_grad()
     def decode_scale(self, coord, scale_idx, enc_bytes, child_bits):
         """One scale of decoder.decode_one_frame (decoder.py:153-176) as ONE C call that does not hold the GIL
         (linr_decode_scale): kernel map of `coord` (int32 [n,3] on the GPU, sorted x-major), the 8 decode stages against the
         packed stream `enc_bytes`, octree_level.upper_layer.  Returns the next finer level's coordinates (int32 [m,3])."""
-        import ctypes
         L = _lib.lib()
         n = int(coord.shape[0])
         if n == 0:
             return coord.new_zeros((0, 3))
         coord = coord.contiguous()
-        streams = unpack_bitstream(enc_bytes)
-        bufs = [np.frombuffer(b, dtype=np.uint8) for b in streams]
-        ptrs = (ctypes.c_void_p * 8)(*[b.ctypes.data if b.size else None for b in bufs])
-        lens = (ctypes.c_int64 * 8)(*[int(b.size) for b in bufs])
-        bf16 = self._precision(None) == 'bf16'
-        need = L.linr_decode_scale_ws_bytes(n, self.block_layers, 1 if bf16 else 0)
-        ws = _lib.scratch(need + 256, coord.device)
-        base = (ws.data_ptr() + 255) & ~255
-        child = torch.empty((8 * n, 3), dtype=torch.int32, device=coord.device)
-        p_host, s_host = self._host_buffers(n)
+        shared, _, keep = self._decode_scale_args(L.linr_decode_scale_ws_bytes, (n,), coord, unpack_bitstream(enc_bytes))
         m = ctypes.c_int64(0)
-        codes, lo, hi, params = (self._qcodes.data_ptr(), float(self._qrange[0]), float(self._qrange[1]), None) if bf16 else \
-            (None, 0.0, 0.0, self._flat.data_ptr())
-        _lib.check(L.linr_decode_scale(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits), params,
-                                       codes, lo, hi, ptrs, lens, base, need, p_host.data_ptr(), s_host.data_ptr(),
-                                       child.data_ptr(), 8 * n, ctypes.byref(m), torch.cuda.current_stream().cuda_stream),
-                   'linr_decode_scale')
-        return child[:m.value]
+        _lib.check(L.linr_decode_scale(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits), *shared,
+                                       ctypes.byref(m), torch.cuda.current_stream().cuda_stream), 'linr_decode_scale')
+        return keep[0][:m.value]
 
     @torch.no_grad()
     def decode_scale_batch(self, coords_list, scale_idx, enc_bytes_list, n_threads=8):
@@ -362,7 +368,6 @@ class LINR_PCGC_Model(nn.Module):
         (int32 [n_i,3] on the GPU, each sorted x-major) are one row space whose kernel map never links two frames, every decode stage
         is one launch set and one copy each way for all of them, their range decoders run on `n_threads` host threads, and the
         children come from prefix sums instead of a sort.  Returns the list of the next finer levels' coordinates (int32 [m_i,3])."""
-        import ctypes
         L = _lib.lib()
         nf = len(coords_list)
         if nf < 1 or nf > 64 or len(enc_bytes_list) != nf:
@@ -370,32 +375,21 @@ class LINR_PCGC_Model(nn.Module):
         seg = np.zeros(nf + 1, dtype=np.int64)
         seg[1:] = np.cumsum([int(c.shape[0]) for c in coords_list])
         n = int(seg[-1])
-        dev = coords_list[0].device
         if n == 0:
             return [c.new_zeros((0, 3)) for c in coords_list]
         coord = torch.cat(coords_list, dim=0).contiguous() if nf > 1 else coords_list[0].contiguous()
-        bufs = [np.frombuffer(b, dtype=np.uint8) for e in enc_bytes_list for b in unpack_bitstream(e)]
-        if len(bufs) != 8 * nf:
+        streams = [b for e in enc_bytes_list for b in unpack_bitstream(e)]
+        if len(streams) != 8 * nf:
             raise ValueError('every frame needs the 8 stage streams of the scale')
-        ptrs = (ctypes.c_void_p * (8 * nf))(*[b.ctypes.data if b.size else None for b in bufs])
-        lens = (ctypes.c_int64 * (8 * nf))(*[int(b.size) for b in bufs])
-        bf16 = self._precision(None) == 'bf16'
-        need = L.linr_decode_scale_batch_ws_bytes(n, nf, self.block_layers, 1 if bf16 else 0)
+        shared, need, keep = self._decode_scale_args(L.linr_decode_scale_batch_ws_bytes, (n, nf), coord, streams)
         if need == 0:
             raise ValueError('%d rows in one decode group: the bound is 2^26 - 64' % n)
-        ws = _lib.scratch(need + 256, dev)
-        base = (ws.data_ptr() + 255) & ~255
-        child = torch.empty((8 * n, 3), dtype=torch.int32, device=dev)
-        p_host, s_host = self._host_buffers(n)
         off = (ctypes.c_int64 * (nf + 1))()
-        codes, lo, hi, params = (self._qcodes.data_ptr(), float(self._qrange[0]), float(self._qrange[1]), None) if bf16 else \
-            (None, 0.0, 0.0, self._flat.data_ptr())
         _lib.check(L.linr_decode_scale_batch(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num, self.block_layers,
-                                             params, codes, lo, hi, ptrs, lens, base, need, p_host.data_ptr(), s_host.data_ptr(),
-                                             child.data_ptr(), 8 * n, off, int(n_threads), torch.cuda.current_stream().cuda_stream),
+                                             *shared, off, int(n_threads), torch.cuda.current_stream().cuda_stream),
                    'linr_decode_scale_batch')
         self._lockstep_ws_peak = max(getattr(self, '_lockstep_ws_peak', 0), int(need))
-        return [child[off[i]:off[i + 1]] for i in range(nf)]
+        return [keep[0][off[i]:off[i + 1]] for i in range(nf)]
 
     def _host_buffers(self, rows):
         """Pinned staging buffers of the staged decoder (probabilities down, decoded symbols up), grown on demand."""
@@ -422,7 +416,6 @@ class LINR_PCGC_Model(nn.Module):
         precision = self._precision(precision)
         if self._wide is not None:          # stage loop in Python: stage forward, D2H, range decoder, H2D
             L = _lib.lib()
-            import ctypes
             for k in range(8):
                 self._stage_forward(frame, k, k + 1, probs, None, precision)
                 p_host[:rows].copy_(probs[k])
@@ -436,7 +429,7 @@ class LINR_PCGC_Model(nn.Module):
                                                        ctypes.c_void_p(s_host.data_ptr() + r0)), 'linr_ac_decode_binary')
                 frame.occ[:, k].copy_(s_host[:rows].to(frame.device, torch.float32))
             return [frame.occ[:, k:k + 1].clone() for k in range(8)]
-        # the whole stage loop is one C call (csrc/net.hip: linr_net_decode_stages): no Python between the stages, no GIL held
+        # the whole stage loop is one C call (csrc/decode.hip: linr_net_decode_stages): no Python between the stages, no GIL held
         if precision == 'bf16':
             engine.net_decode_stages(frame, None, streams_per_scale, probs, p_host, s_host, s_dev, self._qcodes, self._qrange)
         else:
@@ -446,7 +439,6 @@ class LINR_PCGC_Model(nn.Module):
 
 def encode_streams(probs, symbols, n_threads=8):
     """Codes independent binary streams on a host thread pool (linr_ac_encode_binary_batch)."""
-    import ctypes
     n = len(probs)
     probs = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in probs]
     symbols = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1) for s in symbols]
@@ -473,7 +465,6 @@ def codes_word_off(row_off):
 def encode_streams_codes(c1s, syms, ns, n_threads=8):
     """encode_streams from code values and symbol bit planes (linr_ac_encode_binary_codes_batch): stream i has ns[i] symbols,
     c1s[i] uint16 [>= ns[i]], syms[i] uint32 [>= ceil(ns[i] / 32)], bit j & 31 of word j >> 5 = symbol j."""
-    import ctypes
     n = len(c1s)
     ns = [int(v) for v in ns]
     c1s = [np.ascontiguousarray(c, dtype=np.uint16).reshape(-1) for c in c1s]

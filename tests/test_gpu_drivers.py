@@ -184,6 +184,87 @@ def test_decode_scale_call_equals_stagewise_decode(pkg, precision):
     assert L.linr_decode_scale(*args(base, 8 * n)) == 0 and 0 < cnt.value <= 8 * n
 
 
+def _random_scale(n, idx, seed):
+    """A scale of n distinct voxels in a box at ~1/3 occupancy with a random occupancy matrix (numpy scale dict); n = 0: an empty scale."""
+    rng = np.random.default_rng(seed)
+    side = max(6, int(round((3 * n) ** (1 / 3))) + 2)
+    c = ooct.unique_sorted(rng.integers(0, side, size=(4 * n, 3)))[:n].astype(np.int32).reshape(-1, 3)
+    assert len(c) == n
+    return {'coord': c, 'occ': (rng.random((n, 8)) < 0.5).astype(np.float32), 'offset_tensor': ooct.offset_tensor(c).reshape(-1, 7),
+            'scale_idx': idx}
+
+
+def _frame_and_streams(model, scales, precision=None):
+    """The encoder's side of a frame of numpy scales: (decoder frame without the occupancy, [n_scales][8] streams - b'' for an empty
+    scale -, the encoder's probabilities [8, rows], the occupancy [rows, 8])"""
+    from linr_pcgc_amd.model_core import encode_streams
+    enc_frame = model.make_frame(scales)
+    probs, _ = model.frame_probs(enc_frame, precision)
+    p_host = probs.cpu().numpy()
+    occ = np.concatenate([s['occ'] for s in scales], axis=0)
+    streams = []
+    for i in range(enc_frame.n_scales):
+        sl = enc_frame.scale_slice(i)
+        streams.append(encode_streams([p_host[k, sl] for k in range(8)], [occ[sl, k].astype(np.uint8) for k in range(8)])
+                       if sl.stop > sl.start else [b''] * 8)
+    return model.make_frame([{k: v for k, v in s.items() if k != 'occ'} for s in scales]), streams, probs, occ
+
+
+@pytest.mark.parametrize('rows', [(300, 0, 40), (300, 40, 0)])
+@pytest.mark.parametrize('precision', ['f32', 'bf16'])
+def test_decode_frame_with_an_empty_scale(pkg, precision, rows):
+    """linr_net_decode_stages on a three-scale frame with a zero-row scale in the middle / at the end: the stage loop leaves the empty
+    scale out of its range decoders (its streams are b'': NULL, 0) and keeps the rows behind it at their offsets.  The decoded
+    occupancy is the encoder's, and the probabilities the loop left behind are bit for bit the encoder's one-shot ones."""
+    from linr_pcgc_amd import engine, overfit
+    model = overfit.gen_model(3, 'cuda', seed=8807)
+    if precision == 'bf16':
+        from linr_pcgc_amd.model_codec import Model_Estimate
+        model = Model_Estimate().compress_model(model, 8, True, overfit.gen_model(3, 'cuda'))['new_model']
+    scales = [_random_scale(n, i, 100 + i) for i, n in enumerate(rows)]
+    frame, streams, want_probs, occ = _frame_and_streams(model, scales, precision)
+    assert frame.rows == sum(rows) and [len(s) for s in streams] == [8, 8, 8]
+    out = model.decode_frame(frame, streams, precision)
+    assert np.array_equal(torch.cat(out, dim=1).cpu().numpy(), occ)
+    # the same call with a probability buffer of the test's own
+    frame.occ.zero_()
+    probs = torch.full((8, frame.rows), float('nan'), dtype=torch.float32, device='cuda')
+    s_dev = torch.empty(frame.rows, dtype=torch.uint8, device='cuda')
+    p_host, s_host = model._host_buffers(frame.rows)
+    if precision == 'bf16':
+        engine.net_decode_stages(frame, None, streams, probs, p_host, s_host, s_dev, model._qcodes, model._qrange)
+    else:
+        engine.net_decode_stages(frame, model.flat_parameters(), streams, probs, p_host, s_host, s_dev)
+    assert torch.equal(probs, want_probs)
+    assert np.array_equal(frame.occ.cpu().numpy(), occ)
+
+
+def test_decode_stages_returns_the_first_scale_s_error(pkg):
+    """A NULL stream of non-zero length on the first scale: the range decoder refuses it (LINR_EINVAL, host code) and
+    linr_net_decode_stages returns that code before anything more is launched - the occupancy is untouched, and a valid call on the
+    same buffers decodes the frame."""
+    from linr_pcgc_amd import _lib, engine, overfit
+    model = overfit.gen_model(2, 'cuda', seed=8807)
+    scales = [_random_scale(40, i, 200 + i) for i in range(2)]
+    frame, streams, _, occ = _frame_and_streams(model, scales)
+    ptrs, lens, _bufs = engine.stream_arrays([streams[i][k] for i in range(2) for k in range(8)])
+    probs = torch.empty((8, frame.rows), dtype=torch.float32, device='cuda')
+    s_dev = torch.empty(frame.rows, dtype=torch.uint8, device='cuda')
+    p_host, s_host = model._host_buffers(frame.rows)
+    call = lambda: _lib.lib().linr_net_decode_stages(frame.cref(), model.flat_parameters().data_ptr(), None, 0.0, 0.0,
+                                                     frame.arena.data_ptr(), frame.arena.numel(), ptrs, lens, probs.data_ptr(),
+                                                     p_host.data_ptr(), s_host.data_ptr(), s_dev.data_ptr(),
+                                                     torch.cuda.current_stream().cuda_stream)
+    good = (ptrs[0], lens[0])
+    assert good[0] and good[1] > 0
+    ptrs[0], lens[0] = None, 1
+    assert call() == -1
+    assert int(frame.occ.count_nonzero()) == 0
+    ptrs[0], lens[0] = good
+    assert call() == 0
+    assert np.array_equal(frame.occ.cpu().numpy(), occ)
+
+
 @pytest.mark.parametrize('precision', ['f32', 'bf16'])
 def test_committed_stream_still_decodes(pkg, golden_dir, precision):
     """The fp32 evaluation order of the forward is part of the stream format (codec.ARITH_VERSION).  A stream coded by the build
