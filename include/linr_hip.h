@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 15
+#define LINR_ABI_VERSION 16
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -708,6 +708,25 @@ LINR_API int linr_ac_codes(const float* probs, int64_t probs_ld, const float* oc
  * Host pointers only; no GPU involved; thread-safe (linr_pcgc_amd/ply.py reads the frames of a GOP on a thread pool). */
 LINR_API int linr_ply_parse_ascii(const char* text_h, size_t len, int64_t n_rows, int32_t n_cols, int32_t cx, int32_t cy,
                          int32_t cz, int64_t* xyz_h, int64_t* rows_parsed_h);
+
+/* ---- frame output (device) -------------------------------------------------------------------------------------------
+ * Body of an ASCII PLY formatted on the DEVICE (csrc/ply_format.hip): what write_ply_ascii (datautils/custom_dataset.py:37-58,
+ * called from decoder.py:144-146) hands to np.savetxt(fmt='%d').  xyz [n][3] int32, 4-byte aligned; text receives n lines
+ * "%d %d %d\n" back to back - decimal, '-' only for negatives, no leading zeros, one blank between columns - and *text_len (DEVICE
+ * int64, 8-byte aligned) their byte count; bytes of text at and past *text_len are not written.  A line is 6 .. 36 bytes
+ * (LINR_PLY_FORMAT_MAX_LINE: three times "-2147483648"), byte offsets are 32-bit: n <= LINR_PLY_FORMAT_MAX_ROWS.
+ * text_cap >= linr_ply_format_text_bytes(n) = 36 n, the capacity no input can overflow; ws: linr_ply_format_ws_bytes(n) bytes,
+ * 256-byte aligned, uninitialised (the n + 1 row offsets and the scan's own scratch).  Both sizes are 0 for n <= 0 and for n over
+ * the bound.  Arguments are checked before the first launch: LINR_EINVAL for n < 0, n over the bound or a NULL pointer with n > 0,
+ * LINR_ENOSPC for a short text_cap or workspace, LINR_EALIGN for a misaligned xyz, ws or text_len.  n == 0 returns 0, launches
+ * nothing and leaves *text_len untouched.  Stream-ordered, nothing allocated; the kernels use no LDS and belong to no
+ * linr_prof_* / linr_debug_poison class (all 24 are taken). */
+#define LINR_PLY_FORMAT_MAX_LINE 36
+#define LINR_PLY_FORMAT_MAX_ROWS (2147483647 / LINR_PLY_FORMAT_MAX_LINE)
+LINR_API size_t linr_ply_format_text_bytes(int64_t n);
+LINR_API size_t linr_ply_format_ws_bytes(int64_t n);
+LINR_API int    linr_ply_format_ascii(const int32_t* xyz_d, int64_t n, char* text_d, size_t text_cap, void* ws_d, size_t ws_bytes,
+                             int64_t* text_len_d, void* stream);
 
 #ifdef __cplusplus
 }

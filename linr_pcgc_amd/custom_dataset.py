@@ -25,10 +25,18 @@ def read_ply_o3d(filedir, dtype='int32'):
 
 
 def write_ply_ascii(filedir, coords, dtype='int32'):
-    """custom_dataset.py:37-58: ASCII PLY with float x / y / z properties holding the integer coordinates."""
+    """custom_dataset.py:37-58: ASCII PLY with float x / y / z properties holding the integer coordinates.  An integer CUDA tensor
+    (with dtype 'int32') is formatted on the GPU (ply.format_ascii_device); arrays, CPU tensors and other dtypes go through
+    np.savetxt.  The file is the same either way."""
+    if isinstance(coords, torch.Tensor) and coords.is_cuda and not coords.is_floating_point() and np.dtype(dtype) == np.int32:
+        text = ply.format_ascii_device(coords)
+        with open(filedir, 'wb') as f:
+            f.write((ply.ASCII_HEADER % (coords.numel() // 3)).encode('ascii'))
+            f.write(text.cpu().numpy())
+        return
     coords = np.asarray(coords).astype(dtype).reshape(-1, 3)
     with open(filedir, 'w') as f:
-        f.write('ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\nend_header\n' % coords.shape[0])
+        f.write(ply.ASCII_HEADER % coords.shape[0])
         np.savetxt(f, coords, fmt='%d')
 
 

@@ -8,7 +8,8 @@ import torch
 
 from . import codec
 from .codec import decode_one_frame          # noqa: F401  (decoder.py:153-176: the drivers import it from here)
-from .custom_dataset import Read_Data_with_cache, write_ply_ascii
+from .custom_dataset import Read_Data_with_cache
+from .ply import PlyWriter
 from .encoder import gop_bounds
 
 
@@ -30,13 +31,14 @@ def decode_one_gop(inargs):
     enc = codec.read_gop(os.path.join(inargs['result_enc_dir'], inargs['gop_name']))
     dev = 'cuda' if torch.cuda.is_available() else 'cpu'
     decoded = codec.decode_gop(inargs['Gen_Model'](), enc, dev, frames=list(range(inargs['frame_num'])), workers=1)
-    for frame_idx, dec in enumerate(decoded):
-        truth = inargs['reading_data'][frame_idx]
-        if dec.shape != truth.shape or bool((dec.to(truth.dtype) != truth).any()):
-            raise AssertionError('frame %d of %s does not decode to the input' % (frame_idx, inargs['gop_name']))
-        if inargs['write_flag']:
-            name = 'frame%s.ply' % str(inargs['gop_bound'][0] + frame_idx).zfill(4)
-            write_ply_ascii(os.path.join(inargs['result_dec_dir'], name), dec.cpu().numpy())
+    with PlyWriter() as writer:          # formatted on the GPU, written by the writer's thread; closed before this returns or raises
+        for frame_idx, dec in enumerate(decoded):
+            truth = inargs['reading_data'][frame_idx]
+            if dec.shape != truth.shape or bool((dec.to(truth.dtype) != truth).any()):
+                raise AssertionError('frame %d of %s does not decode to the input' % (frame_idx, inargs['gop_name']))
+            if inargs['write_flag']:
+                name = 'frame%s.ply' % str(inargs['gop_bound'][0] + frame_idx).zfill(4)
+                writer.submit(os.path.join(inargs['result_dec_dir'], name), dec)
     return decoded
 
 
@@ -68,27 +70,28 @@ def main(argv=None):
         truth = MytestDataset(args.ori_dir, ori_type=args.ori_type)
     dev = 'cuda' if torch.cuda.is_available() else 'cpu'
     frames = 0
-    for name in names:
-        first, last = gop_bounds(name)
-        enc = codec.read_gop(os.path.join(args.enc_dir, name))
-        side = enc['side_info']          # streams of this package carry the model's shape; others: the flags, and the most scales a frame has
-        shape = {'scale_num': int(side.get('scale_num', max(len(f) for f in enc['frames']))), 'in_channel': 7,
-                 'hidden_channel_conv': int(side.get('hidden_channel_conv', args.hidden_channel_conv)),
-                 'block_layers': int(side.get('block_layers', args.block_layers)), 'outstage': 8, 'instage': 1}
-        gen = lambda: LINR_PCGC_Model(shape).to(dev)
-        if args.lockstep > 0:
-            decoded = codec.decode_gop(gen(), enc, dev, lockstep=args.lockstep)
-        else:
-            decoded = codec.decode_gop(gen(), enc, dev, workers=1 if shape['hidden_channel_conv'] != 8 else 4)
-        if len(decoded) != last - first + 1:
-            raise ValueError('%s holds %d frames, its name says %d' % (name, len(decoded), last - first + 1))
-        for i, dec in enumerate(decoded):
-            if truth is not None:
-                want = torch.unique(truth[first + i], dim=0)
-                if dec.shape != want.shape or bool((dec.to(want.dtype) != want).any()):
-                    raise AssertionError('frame %d does not decode to the input' % (first + i))
-            write_ply_ascii(os.path.join(args.dec_dir, 'frame%s.ply' % str(first + i).zfill(4)), dec.cpu().numpy())
-            frames += 1
+    with PlyWriter() as writer:          # closed - every file complete - before main returns or raises
+        for name in names:
+            first, last = gop_bounds(name)
+            enc = codec.read_gop(os.path.join(args.enc_dir, name))
+            side = enc['side_info']          # streams of this package carry the model's shape; others: the flags, and the most scales a frame has
+            shape = {'scale_num': int(side.get('scale_num', max(len(f) for f in enc['frames']))), 'in_channel': 7,
+                     'hidden_channel_conv': int(side.get('hidden_channel_conv', args.hidden_channel_conv)),
+                     'block_layers': int(side.get('block_layers', args.block_layers)), 'outstage': 8, 'instage': 1}
+            gen = lambda: LINR_PCGC_Model(shape).to(dev)
+            if args.lockstep > 0:
+                decoded = codec.decode_gop(gen(), enc, dev, lockstep=args.lockstep)
+            else:
+                decoded = codec.decode_gop(gen(), enc, dev, workers=1 if shape['hidden_channel_conv'] != 8 else 4)
+            if len(decoded) != last - first + 1:
+                raise ValueError('%s holds %d frames, its name says %d' % (name, len(decoded), last - first + 1))
+            for i, dec in enumerate(decoded):
+                if truth is not None:
+                    want = torch.unique(truth[first + i], dim=0)
+                    if dec.shape != want.shape or bool((dec.to(want.dtype) != want).any()):
+                        raise AssertionError('frame %d does not decode to the input' % (first + i))
+                writer.submit(os.path.join(args.dec_dir, 'frame%s.ply' % str(first + i).zfill(4)), dec)
+                frames += 1
     print('decoded %d frames of %d GOPs into %s%s' % (frames, len(names), args.dec_dir, '' if truth is None else ' (all equal to the input)'))
 
 
