@@ -295,6 +295,7 @@ LINR_API int linr_spconv_bwd_fused(const float* gout, const float* in, const int
  *  17 fused backward 8->8 (bbwd_k<0>)            18 fused backward of the two 4->4 convs 19 fused backward of conv0_0 8->4
  *  20 forward convolutions (bconv_k)             21 head backward                       22 first-conv weight gradients
  *  23 scale context forward, sums, conversions, Adam
+ * (the library's names for these numbers: enum ProfKind in csrc/prof.h)
  * linr_prof_mask selects the classes that are recorded (default: 0 and 1; an event pair costs a few microseconds of stream
  * time).  linr_prof_read waits for the recorded events and returns their summed elapsed time, the number of launches and the
  * number of row passes (a grouped launch over g layers counts g).  mode 1 = clear the records and start, 2 = resume,

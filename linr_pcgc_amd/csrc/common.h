@@ -82,6 +82,7 @@ int linr_adam_launch(float* params, const float* grads, float* exp_avg, float* e
                      double bc2_sqrt, double beta1, double beta2, double eps, double weight_decay,
                      const LinrAdamRanges* rg, hipStream_t s);
 #define LINR_WG_BLOCKS 512   // persistent blocks of every weight-gradient kernel (2 per CU; sweep: tools/wg_blocks_sweep.sh)
+#define LINR_TILE8T_SPARE 12 // all -1 groups behind a transposed tiled table (csrc/kmap.hip: linr_kmap_tile8t) for the prefetches of csrc/wgrad.hip
 
 // Grouped launches: independent layers of equal shape (the 7 outter blocks, the 8 occupancy heads, whose inputs are the
 // ground-truth occupancy and x_glob during overfitting / encoding) run as ONE launch with gridDim.y = groups.  Group g adds
@@ -194,8 +195,6 @@ __attribute__((visibility("hidden")))
 int linr_head_bwd_launch(const HeadBwdGroup* g, int ng, int target_ld, float gscale, int64_t n, float* big, int64_t block_stride,
                          int nblocks, int* rows_written, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_slab_reduce_launch(const float* big, int nblocks, int64_t total, float* gsum, hipStream_t s);
-__attribute__((visibility("hidden")))
 int linr_bits_finish_launch(const double* partial, int count, double* bits_acc, hipStream_t s);
 __attribute__((visibility("hidden")))
 int linr_dual44_fwd_launch(LinrCmap m, const Dual44FwdGroup* g, int ng, hipStream_t s);
@@ -211,7 +210,7 @@ __attribute__((visibility("hidden")))
 int linr_occ_conv7_launch(const float* occ, LinrCmap m, const float* P, const int64_t* w_off, const int64_t* b_off, float* out,
                           const int64_t* out_off, hipStream_t s);
 // cin, cout: the kernel's width (a group with fewer live input channels says so in cin_live); tile8t: the transposed tiled
-// table (csrc/fused.hip: spconv_wgrad_t_k), or NULL: indices from nbr
+// table (csrc/wgrad.hip: spconv_wgrad_t_k), or NULL: indices from nbr
 __attribute__((visibility("hidden")))
 int linr_conv3_wgrad_mfma(const WgradGroup* g, int ng, int in_ld, int gout_ld, const int32_t* nbr, int64_t nbr_ld, int64_t n,
                           const int32_t* tile8t, int cin, int cout, float* big, int64_t block_stride, int nblocks, hipStream_t s);
@@ -233,9 +232,6 @@ __attribute__((visibility("hidden")))
 int linr_conv3_wgrad_dual44(const Dual44BwdGroup* g, int ng, int gI_ld, int gM_ld, const int32_t* nbr, int64_t nbr_ld, int64_t n,
                             const int32_t* tile8t, float* big, int64_t block_stride, int nblocks, hipStream_t s);
 
-// test hook (include/linr_hip.h: linr_debug_poison): poisons LDS and vector registers of every CU on `s` when bit `kind` of the
-// mask is set; kinds 0..13 = the linr_prof_* classes of the fp32 executor, 14 = the bf16 executor, 15 = the decoder's own kernels
-__attribute__((visibility("hidden"))) void linr_poison_hook(hipStream_t s, int kind);
 // csrc/occ_wgrad.hip: weight gradients of the first convolutions of the 7 outter blocks from one gather of the occupancy rows
 __attribute__((visibility("hidden")))
 int linr_occ_wgrad7_launch(const float* occ, const float* const* g, LinrCmap m, float* big, int64_t block_stride,

@@ -1,4 +1,4 @@
-// Device helpers shared by the compressed-map convolution kernels (csrc/fused.hip, csrc/fused_bwd.hip).  Not part of the C-ABI.
+// Device helpers shared by the compressed-map convolution kernels (csrc/fused.hip, csrc/wgrad.hip, csrc/fused_bwd.hip).  Not part of the C-ABI.
 #pragma once
 #include "common.h"
 #include <utility>

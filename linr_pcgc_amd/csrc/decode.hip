@@ -9,6 +9,7 @@
 // differ in the kernel map (one list / segments) and in the child expansion (radix sort / prefix sums).
 #include "common.h"
 #include "layout.h"
+#include "prof.h"
 #include <hipcub/hipcub.hpp>
 
 #define TRY(e) do { int rc_ = (e); if (rc_) return rc_; } while (0)
@@ -101,7 +102,7 @@ int scale_prologue(const int32_t* coord, int64_t n, const int64_t* seg_off_h, in
     if (seg_off_h) {
         TRY(linr_kmap_build_segments(coord, seg_off_h, n_seg, nbr, w.ld, base + w.kws, linr_kmap_workspace_bytes(n), s));
     } else {
-        linr_poison_hook(s, 15);
+        linr_poison_hook(s, PK_DECODE);
         TRY(linr_kmap_build(coord, n, nbr, w.ld, 0, base + w.kws, linr_kmap_workspace_bytes(n), s));
     }
     TRY(linr_kmap_compress(nbr, w.ld, n, lo, mask, w.ld, s));
@@ -251,7 +252,7 @@ extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_
     int32_t* pos = (int32_t*)(cbase + w.sort.pos);
     uint64_t* keys0 = (uint64_t*)(cbase + w.sort.keys0);
     uint64_t* keys1 = (uint64_t*)(cbase + w.sort.keys1);
-    linr_poison_hook(s, 15);
+    linr_poison_hook(s, PK_DECODE);
     child_count_k<<<linr_grid(n + 1, LINR_BLOCK), LINR_BLOCK, 0, s>>>(occ, n, cnt);
     size_t cb = w.sort.cub_bytes;
     TRY(linr_hip_rc(hipcub::DeviceScan::ExclusiveSum(cbase + w.sort.cub, cb, cnt, pos, (int)(n + 1), s)));
@@ -383,7 +384,7 @@ int children_segments(const int32_t* coord, const float* occ, const LinrSegTab& 
     Cnt4* cnt = (Cnt4*)(base + w.cnt);
     Cnt4* sum = (Cnt4*)(base + w.sum);
     int32_t* bounds = (int32_t*)(base + w.bounds);
-    linr_poison_hook(s, 15);
+    linr_poison_hook(s, PK_DECODE);
     child_pair_count_k<<<linr_grid(n + 1, LINR_BLOCK), LINR_BLOCK, 0, s>>>(occ, n, cnt);
     size_t cb = w.cub_bytes;
     int rc = linr_hip_rc(hipcub::DeviceScan::ExclusiveScan(base + w.cub, cb, cnt, sum, Cnt4Sum(), Cnt4{{0, 0, 0, 0}}, (int)(n + 1), s));

@@ -3,6 +3,7 @@
 // The list is already sorted by the x-major key, so a neighbour lookup is a binary search, and the three
 // dz = -1,0,+1 neighbours of one (dx,dy) column are adjacent in the list: 9 searches per voxel, not 27.
 #include "common.h"
+#include "prof.h"
 
 __device__ __forceinline__ long long linr_key(int x, int y, int z) {
     return ((long long)(x + 1) << 42) | ((long long)(y + 1) << 21) | (long long)(z + 1);
@@ -117,7 +118,7 @@ extern "C" int linr_kmap_build_segments(const int32_t* coords, const int64_t* se
     if (((uintptr_t)ws) & 7u) return LINR_EALIGN;
     hipStream_t s = (hipStream_t)stream;
     long long* keys = (long long*)ws;
-    linr_poison_hook(s, 15);
+    linr_poison_hook(s, PK_DECODE);
     kmap_keys_k<<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(coords, n, keys);
     kmap_search_seg_k<<<linr_grid(9 * n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(keys, coords, n, tab, nbr, ld);
     return linr_launch_rc();
@@ -186,5 +187,65 @@ extern "C" int linr_octree_occupancy(const int32_t* child, int64_t m, const int3
     long long* keys = (long long*)ws;
     if (m > 0) kmap_keys_k<<<linr_grid(m, LINR_BLOCK), LINR_BLOCK, 0, s>>>(child, m, keys);
     octree_occ_k<<<linr_grid(4 * n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(keys, m, parent, n, occ);
+    return linr_launch_rc();
+}
+
+// ---- derived forms of the map -----------------------------------------------------------------------------------------------
+// Compressed kernel map (what the convolutions of csrc/fused.hip read; the layout is described there): lo[q] = row of the first
+// present neighbour of column q = (dx+1)+3(dy+1), mask = the 27 presence bits
+__global__ __launch_bounds__(LINR_BLOCK) void kmap_compress_k(const int32_t* __restrict__ nbr, int64_t nbr_ld, int64_t n,
+                                                              int32_t* __restrict__ lo, uint32_t* __restrict__ mask,
+                                                              int64_t ld) {
+    const int64_t row = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
+    if (row >= n) return;
+    uint32_t m = 0;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+        const int32_t a = nbr[(int64_t)q * nbr_ld + row];
+        const int32_t b = nbr[(int64_t)(q + 9) * nbr_ld + row];
+        const int32_t c = nbr[(int64_t)(q + 18) * nbr_ld + row];
+        const uint32_t m3 = (a >= 0 ? 1u : 0u) | (b >= 0 ? 2u : 0u) | (c >= 0 ? 4u : 0u);
+        lo[(int64_t)q * ld + row] = a >= 0 ? a : (b >= 0 ? b : (c >= 0 ? c : 0));
+        m |= m3 << (3 * q);
+    }
+    mask[row] = m;
+}
+
+extern "C" int linr_kmap_compress(const int32_t* nbr, int64_t nbr_ld, int64_t n, int32_t* lo, uint32_t* mask, int64_t ld,
+                                  void* stream) {
+    if (n < 0 || nbr_ld < n || ld < n) return LINR_EINVAL;
+    if (n == 0) return 0;
+    if (!nbr || !lo || !mask) return LINR_EINVAL;
+    kmap_compress_k<<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, (hipStream_t)stream>>>(nbr, nbr_ld, n, lo, mask, ld);
+    return linr_launch_rc();
+}
+
+// tile8t[g][t][u][j] = nbr[LINR_TAP(4 j + t)][8 g + u] (-1 for position 27, for j = 7 and beyond n): a lane (t, u) of the transposing
+// kernel reads its seven indices of group g as two 16-byte loads.  Gather instruction j fetches the taps at positions 4 j .. 4 j + 3
+// of the convolutions' slab-major tap sequence (common.h: LINR_TAP), i.e. neighbours that sit in the same few cache lines
+__global__ __launch_bounds__(LINR_BLOCK) void kmap_tile8t_k(const int32_t* __restrict__ nbr, int64_t ld, int64_t n, int64_t groups,
+                                                            int32_t* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
+    if (e >= groups * 256) return;
+    const int64_t g = e >> 8;
+    const int r = (int)(e & 255), t = r >> 6, u = (r >> 3) & 7, j = r & 7;
+    const int p = 4 * j + t;                 // position in the gather sequence; its tap: the convolutions' slab-major order
+    const int64_t row = 8 * g + u;
+    out[e] = (j < 7 && p < 27 && row < n) ? nbr[(int64_t)LINR_TAP(p) * ld + row] : -1;
+}
+
+extern "C" size_t linr_kmap_tile8t_bytes(int64_t n) {
+    if (n < 0) return 0;
+    return (size_t)((n + 7) / 8 + LINR_TILE8T_SPARE) * 256 * sizeof(int32_t);
+}
+
+extern "C" int linr_kmap_tile8t(const int32_t* nbr, int64_t ld, int64_t n, int32_t* tile8t, size_t tile8t_bytes, void* stream) {
+    if (n < 0 || ld < n) return LINR_EINVAL;
+    if (n == 0) return 0;
+    if (!nbr || !tile8t) return LINR_EINVAL;
+    if (tile8t_bytes < linr_kmap_tile8t_bytes(n)) return LINR_ENOSPC;
+    if (!linr_aligned16(tile8t)) return LINR_EALIGN;
+    const int64_t groups = (n + 7) / 8 + LINR_TILE8T_SPARE;      // spare all -1 groups: the kernel prefetches two strides ahead
+    kmap_tile8t_k<<<linr_grid(groups * 256, LINR_BLOCK), LINR_BLOCK, 0, (hipStream_t)stream>>>(nbr, ld, n, groups, tile8t);
     return linr_launch_rc();
 }

@@ -16,6 +16,7 @@
 // Encoder (all 8 stages, grouped launches) and decoder (stage by stage) run the same kernels with the same per-row
 // instruction sequence, so their probabilities are bit-identical and the 16-bit CDF quantisation cannot diverge.
 #include "bf16_common.h"
+#include "prof.h"
 #include <stdlib.h>
 
 #define TRY(e) do { int rc_ = (e); if (rc_) return rc_; } while (0)
@@ -92,7 +93,7 @@ template <class G, class... X>
 static int blaunch(const BCtx& c, const G* g, int ng, X... x) {
     BArgs a = base_args(c);
     TRY(bfill(a, g, ng, x...));
-    linr_poison_hook(c.s, 14);
+    linr_poison_hook(c.s, PK_BF16_INFER);
     bconv_k<G::MODE><<<dim3(linr_grid(c.R, LINR_BLOCK), ng), LINR_BLOCK, 0, c.s>>>(a);
     return linr_launch_rc();
 }
@@ -158,7 +159,7 @@ extern "C" int linr_net_forward_bf16(const linr_frame* f, const uint8_t* codes, 
         zero_pads16_k<<<a.pads.n, 64, 0, c.s>>>(a.mats, a.pads);
         BSce sa;
         linr_sce_table(f, L, sa);
-        linr_poison_hook(c.s, 14);
+        linr_poison_hook(c.s, PK_BF16_INFER);
         sce_bf16_k<<<linr_grid(c.R, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(a.PF, f->offset_feat, sa, c.R, a.X0);
         TRY(bblock(c, L.block_in, a.X0, 0, nullptr));                                   // O[0] = x_glob
     }

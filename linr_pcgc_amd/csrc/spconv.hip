@@ -450,7 +450,7 @@ extern "C" int linr_spconv_bwd_weight(const float* in, int32_t in_ld, const floa
         const int nb = wg_blocks(n);
         const int elems = (27 * cin + 1) * cout;
         // slab row: kernel [27][cin][cout], then the bias.  Rows with a zero pad row in front (LINR_PAD_ROW) take the executor's
-        // matrix-core kernel (csrc/fused.hip)
+        // matrix-core kernel (csrc/wgrad.hip)
         int rc;
         if ((flags & LINR_PAD_ROW) && (in_ld == 4 || in_ld == 8)) {
             const WgradGroup g = {in, gout, 0, 27 * cin * cout, 0};

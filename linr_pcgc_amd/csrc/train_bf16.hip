@@ -37,14 +37,12 @@
 #include "bf16_common.h"
 #include "head_bwd.h"
 #include "sce.h"
-#include "net_shared.h"
+#include "bwd_tail.h"
+#include "prof.h"
 #include <stdlib.h>
 #include <vector>
 
 #define TRY(e) do { int rc_ = (e); if (rc_) return rc_; } while (0)
-
-// profiling / poison classes of this executor (include/linr_hip.h: linr_prof_*)
-enum { TK_BWD88 = 17, TK_BWD_DUAL = 18, TK_BWD_C00 = 19, TK_FWD = 20, TK_HEAD_BWD = 21, TK_FIRST_WGRAD = 22, TK_MISC = 23 };
 
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -1143,7 +1141,7 @@ static int tlaunch(const TCtx& c, int image0, const G* g, int ng, X... x) {
     BArgs a = tbase(c);
     TRY(bfill(a, g, ng, x...));
     for (int i = 0; i < ng; ++i) a.wi[i] = image0 + (G::MODE < 2 ? 7 : 4) * i;
-    LinrProf ps(c.s, TK_FWD, ng);
+    ProfScope ps(c.s, TK_FWD, ng);
     bconv_k<G::MODE, 2, true><<<dim3(linr_grid(c.R, LINR_BLOCK), ng), LINR_BLOCK, 0, c.s>>>(a);
     return linr_launch_rc();
 }
@@ -1158,7 +1156,7 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
     const linr_frame* f = c.f;
     const int64_t nblk = linr_grid(c.R, LINR_BLOCK);
     {
-        LinrProf ps(c.s, TK_MISC, 1);
+        ProfScope ps(c.s, TK_MISC, 1);
         if (c.OCC == a.OCC) occ_bf16_k<<<linr_grid(c.R, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(f->occ, c.R, a.OCC);
         TPack tp;
         tp.conv0_w[0] = L.block_in.a_w; tp.conv0_w[1] = L.block_in.b_w;
@@ -1181,7 +1179,7 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
         BOcc7Group og;
         for (int g = 0; g < 7; ++g) og.A[g] = a.A[g + 1];
         bo_fill(o, og, L);
-        LinrProf ps(c.s, TK_FWD, 7);
+        ProfScope ps(c.s, TK_FWD, 7);
         const char* e16 = getenv("LINR_BOCC7_MFMA16");       // 0: bocc7_k (v_mfma_f32_4x4x4_16b_bf16); read per call: tests compare the two
         const int mfma16 = e16 ? atoi(e16) : 1;
         if (mfma16) {
@@ -1226,7 +1224,7 @@ static int bb_launch(TCtx& c, const G* g, int ng, int kind_prof, int* rows) {
     BbArgs a = BbArgs();
     a.P = c.P; a.lo = c.f->nbr_lo; a.mask = c.f->nbr_mask; a.ld = c.f->nbr_ld; a.n = c.R;
     a.big = c.A.BIG; a.block_stride = c.L.total;
-    LinrProf ps(c.s, kind_prof, ng);
+    ProfScope ps(c.s, kind_prof, ng);
     return bb_run<EPI>(a, g, ng, c.nb, rows, c.s);
 }
 
@@ -1244,7 +1242,7 @@ static int tbackward(TCtx& c, float gscale) {
         for (int k = 0; k < 8; ++k) hg[k] = {a.C[k], a.PR + (int64_t)k * c.R, c.f->occ + k, a.gC[k], L.h0_w[k], L.h0_b[k], L.h2_w[k], L.h2_b[k]};
         TRY(th_fill(h, hg, 8));
         h.active = hb_blocks(c.R, 8, tb_cus(), c.nb);
-        LinrProf ps(c.s, TK_HEAD_BWD, 8);
+        ProfScope ps(c.s, TK_HEAD_BWD, 8);
         thead_bwd_k<<<dim3(h.active, 8), HB_WAVES * 64, 0, c.s>>>(h);
         TRY(linr_launch_rc());
         c.note_short(L.h0_w[0], L.h2_b[7] + 1, h.active);          // the heads' parameters are one contiguous range
@@ -1259,7 +1257,7 @@ static int tbackward(TCtx& c, float gscale) {
     {   // prior_k = x_glob (+ outter block k): x_glob receives every gO
         TPtr8 src;
         for (int k = 0; k < 8; ++k) src.p[k] = a.gO[k];
-        LinrProf ps(c.s, TK_MISC, 1);
+        ProfScope ps(c.s, TK_MISC, 1);
         tsum8_k<<<linr_grid(c.R, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(src, c.R, a.gXG);
         TRY(linr_launch_rc());
     }
@@ -1297,7 +1295,7 @@ static int tbackward(TCtx& c, float gscale) {
         if (target > c.nb) target = c.nb;
         o.tiles_per_block = (int)((t64 + target - 1) / target);
         rows = (int)((t64 + o.tiles_per_block - 1) / o.tiles_per_block);
-        LinrProf ps(c.s, TK_FIRST_WGRAD, 7);
+        ProfScope ps(c.s, TK_FIRST_WGRAD, 7);
         static const bool big_lds = hipFuncSetAttribute((const void*)bocc_wgrad7_k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                         OW_WAVES * OW_SLOTS * BB_SLOT) == hipSuccess;
         if (!big_lds) return LINR_EINVAL;
@@ -1347,7 +1345,7 @@ extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void
     if (c.R == 0) return 0;
     TRY(tforward(c, nullptr, bits_acc));
     TRY(tbackward(c, gscale));
-    LinrProf ps(c.s, TK_MISC, 0);
+    ProfScope ps(c.s, TK_MISC, 0);
     return linr_adam_step_launch(c.L, params, c.A.GSUM, exp_avg, exp_avg_sq, lr, step, scale_steps_h, beta1, beta2, eps, weight_decay, c.s);
 }
 

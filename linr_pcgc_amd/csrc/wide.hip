@@ -12,6 +12,8 @@
 // the same in training, encoding and stage-by-stage decoding (wide_net.py runs the same launches in all three).
 #include "common.h"
 #include "conv_common.h"
+#include "bwd_tail.h"
+#include "prof.h"
 #include <stdlib.h>
 
 #ifndef LINR_CONV_BLOCK
@@ -351,7 +353,7 @@ static int spconv_wide_impl(int32_t bwd, const float* const* in_h, const int32_t
         }
     }
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 16);
+    linr_poison_hook(s, PK_WIDE);
     for (int p0 = 0; p0 < npb; p0 += 2) {
         const int pb = npb - p0 >= 2 ? 2 : 1;
         for (int q = 0; q < 2; ++q) {
@@ -397,7 +399,7 @@ extern "C" int linr_spconv_wide_pw(int32_t bwd, const float* const* in_h, const 
 
 // ---- weight gradient of a wide convolution -------------------------------------------------------------------------------------------
 // gW[k][ci][co] = sum_r in[nbr_k(r)][ci] gout[r][co] block pair by block pair (input block bi, gradient block bo) with the 8-wide
-// transposing kernel (csrc/fused.hip: spconv_wgrad_t_k), all pairs of the convolution as the groups of grouped launches (8 pairs per
+// transposing kernel (csrc/wgrad.hip: spconv_wgrad_t_k), all pairs of the convolution as the groups of grouped launches (8 pairs per
 // launch) into ONE slab, then one fixed-order reduction straight into the dense [27][cin][cout] kernel gradient and the bias gradient
 // (round 3: a launch, a reduction and two copies per pair).
 #define WW_PAIR 1736          // slab elements of a pair: [27][8][8] kernel block + 8 bias sums
@@ -441,7 +443,7 @@ __global__ __launch_bounds__(LINR_BLOCK) void wide_slab_reduce_k(const float* __
 }
 
 
-// One gather for ALL gradient blocks: spconv_wgrad_t_k<8, false> (csrc/fused.hip) with the transposed image of an input block's
+// One gather for ALL gradient blocks: spconv_wgrad_t_k<8, false> (csrc/wgrad.hip) with the transposed image of an input block's
 // gathered rows multiplied with the 8-row tiles of NGB gradient blocks (group = input block, blockIdx.y) - the gathers, index loads
 // and LDS transposes of a pair launch are paid once per input block instead of once per (input, gradient) pair; per accumulator the
 // same v_mfma_f32_4x4x1 sequence in the same row order and the same wave fold as the pair kernel, so the slab holds the same bits.
@@ -658,7 +660,7 @@ extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, con
     if (!in_h || !g_h || !nbr || !slab) return LINR_EINVAL;
     if (!linr_rows_fit32(n)) return LINR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 16);
+    linr_poison_hook(s, PK_WIDE);
     const int nbi = (cin + 7) / 8, nbo = cout / 8, npairs = nbi * nbo;
     if (n == 0) {
         if (!gW) return LINR_EINVAL;                     // deferred reductions (gW == NULL) need rows
@@ -724,7 +726,7 @@ extern "C" int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* c
     }
     a.slab = slab; a.block_stride = (int64_t)2 * npairs * WW_PAIR;
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 16);
+    linr_poison_hook(s, PK_WIDE);
     const dim3 grid(256, 2 * nb);
     if (nb == 1) wwgrad_k<1><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
     else wwgrad_k<2><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
@@ -852,7 +854,7 @@ extern "C" int linr_linear_wide(const float* const* in_h, int32_t cin, int32_t i
     }
     a.W = W; a.ws_ci = ws_ci; a.ws_co = ws_co; a.bias = (flags & LINR_NO_BIAS) ? nullptr : bias; a.flags = flags;
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 16);
+    linr_poison_hook(s, PK_WIDE);
     const unsigned grid = linr_grid(n, LINR_BLOCK);
     const bool com = (ws_ci == cout && ws_co == 1);
     if (!com && !(ws_ci == 1 && ws_co == cin)) return LINR_EINVAL;          // dense [cin][cout] or dense [cout][cin]
@@ -892,7 +894,7 @@ extern "C" int linr_linear_wgrad_wide(const float* const* in_h, int32_t cin, int
     for (int i = 0; i < ni; ++i) if (!in_h[i]) return LINR_EINVAL;
     for (int i = 0; i < no; ++i) if (!g_h[i]) return LINR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 16);
+    linr_poison_hook(s, PK_WIDE);
     const int nb = linr_lin_blocks(n);
     const int64_t stride = (int64_t)(cin + 2) * cout;                             // [cin + 1][cout] + a dump row for the duplicate bias sums
     WgradGroup pr[LINR_MAXG];
@@ -974,7 +976,7 @@ extern "C" int linr_wide_reduce_many(const linr_wide_reduce* items_h, int32_t co
         if (t.kind == 0 && t.cout % 8) return LINR_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 16);
+    linr_poison_hook(s, PK_WIDE);
     for (int i0 = 0; i0 < count; i0 += RD_MAX) {
         RdArgs A;
         A.n = count - i0 < RD_MAX ? count - i0 : RD_MAX;
@@ -1076,7 +1078,7 @@ extern "C" int linr_head_wide_fwd(const float* const* c_h, int32_t C, const floa
     a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.target = target; a.target_ld = target_ld; a.p = p;
     a.partial = want_bits ? (double*)ws : nullptr;
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 16);
+    linr_poison_hook(s, PK_WIDE);
     const unsigned nb = linr_grid(n, LINR_BLOCK);
     if (C == 16) whead_fwd_k<16><<<nb, LINR_BLOCK, 0, s>>>(a, n);
     else whead_fwd_k<32><<<nb, LINR_BLOCK, 0, s>>>(a, n);
@@ -1300,7 +1302,7 @@ extern "C" int linr_head_wide_bwd(const float* const* c_h, const float* const* p
     if (!c_h || !p_h || !target_h || !w1_h || !b1_h || !w2_h || !gc_h || !slab || !grads) return LINR_EINVAL;
     if (slab_bytes < linr_head_wide_bwd_slab_bytes(C, nstages)) return LINR_ENOSPC;
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 16);
+    linr_poison_hook(s, PK_WIDE);
     const int64_t total = (int64_t)nstages * (24 * C + 49);
     if (n == 0) return linr_hip_rc(hipMemsetAsync(grads, 0, (size_t)total * sizeof(float), s));
     WhbArgs A;
@@ -1352,7 +1354,7 @@ extern "C" int linr_sum_many(const float* const* src_h, int32_t count, int64_t n
         if (!a.src[k]) return LINR_EINVAL;
         if (!linr_aligned16(a.src[k])) return LINR_EALIGN;
     }
-    linr_poison_hook((hipStream_t)stream, 16);
+    linr_poison_hook((hipStream_t)stream, PK_WIDE);
     sum_many_k<<<linr_grid(n / 4, LINR_BLOCK), LINR_BLOCK, 0, (hipStream_t)stream>>>(a, n / 4, dst, accumulate ? 1 : 0);
     return linr_launch_rc();
 }

@@ -20,6 +20,7 @@
 //              bits partials).
 // Inference only: nothing is kept for a backward pass.
 #include "bf16_common.h"
+#include "prof.h"
 
 // ---- prologue ------------------------------------------------------------------------------------------------------------------
 // Image of a convolution (kernel [27][cin][co], ME layout): combos c = s * NC + cq * (co / 4) + oq (s = the step of the tap loop, tap
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(LINR_BLOCK, 2) void wconv16_k(WArgs a) {
 
 template <int NBI, int CO, int EPI>
 static int wlaunch(const WArgs& a, hipStream_t s) {
-    linr_poison_hook(s, 14);
+    linr_poison_hook(s, PK_BF16_INFER);
     wconv16_k<NBI, CO, EPI><<<linr_grid(a.n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(a);
     return linr_launch_rc();
 }
@@ -359,7 +360,7 @@ extern "C" int linr_sce_fwd_bf16(const float* pf, const linr_frame* f, uint16_t*
     if (!f->offset_feat) return LINR_EINVAL;
     if (!al16(x0_padded)) return LINR_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    linr_poison_hook(s, 14);
+    linr_poison_hook(s, PK_BF16_INFER);
     sce_bf16_k<<<linr_grid(f->rows, LINR_BLOCK), LINR_BLOCK, 0, s>>>(pf, f->offset_feat, sa, f->rows,
                                                                     reinterpret_cast<bf16_t*>(x0_padded) + 8);
     return linr_launch_rc();

@@ -6,7 +6,7 @@ set -e
 cd "$(dirname "$0")/../linr_pcgc_amd/csrc"
 mkdir -p ../../tools/_lab
 BASE="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -fvisibility=hidden -Wall"
-OBJS="_obj/kmap.o _obj/spconv.o _obj/linear.o _obj/loss_optim.o _obj/net.o _obj/fused.o _obj/occ_wgrad.o _obj/net_bf16.o _obj/train_bf16.o _obj/decode.o _obj/wide.o _obj/ac.o _obj/ply.o"
+OBJS=$(ls _obj/*.o | grep -v "/fused_bwd.o$")          # every object of the last csrc/build.sh but the file under test
 declare -a V=(
   "-mllvm -amdgpu-mfma-vgpr-form"
   ""
