@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 16
+#define LINR_ABI_VERSION 17
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -709,6 +709,43 @@ LINR_API int linr_ac_codes(const float* probs, int64_t probs_ld, const float* oc
  * Host pointers only; no GPU involved; thread-safe (linr_pcgc_amd/ply.py reads the frames of a GOP on a thread pool). */
 LINR_API int linr_ply_parse_ascii(const char* text_h, size_t len, int64_t n_rows, int32_t n_cols, int32_t cx, int32_t cy,
                          int32_t cz, int64_t* xyz_h, int64_t* rows_parsed_h);
+
+/* ---- frame input (device) --------------------------------------------------------------------------------------------
+ * The same bodies parsed on the DEVICE (csrc/ply_parse.hip), for callers that want the coordinates there anyway.
+ * linr_ply_parse_ascii_device: text_d / len are the bytes BEHIND "end_header\n" in device memory, text_d 16-byte aligned,
+ * len <= 2^31 - 1 (offsets are 32-bit).  The contract is linr_ply_parse_ascii's: n_rows vertices of n_cols (3..64) whitespace-separated
+ * numbers, one vertex per line, a line ended by '\n' only, blanks ' ' \t \r \f \v, whitespace-only lines between vertices tolerated,
+ * everything behind the n_rows-th non-empty line ignored, a last line without a newline complete.  No byte at or past text_d + len is
+ * read.  xyz_d [n_rows][3] int32 receives columns cx, cy, cz rounded to the nearest integer, ties to even.  status_d: 2 int64 in
+ * device memory, 8-byte aligned, set to {0, n_rows} in stream order before anything else and left as {flags, first_row}: flags == 0
+ * when every one of the first n_rows non-empty lines was handled on the device, else an OR of
+ *   LINR_PLY_TOKEN    a token is not [+-] digits [. digits] with 1..15 digits in all (the host parser takes such tokens to strtod:
+ *                     they may be valid);
+ *   LINR_PLY_COLUMNS  a line ended before n_cols tokens, or has a non-blank byte behind them;
+ *   LINR_PLY_SHORT    fewer than n_rows non-empty lines;
+ *   LINR_PLY_RANGE    a rounded value is outside int32 (linr_ply_gather_binary: or not finite);
+ * first_row is the smallest vertex index that raised a flag (LINR_PLY_SHORT: the number of non-empty lines found).  Rows without a flag
+ * are written correctly in every case, rows with one are unspecified: a caller that sees flags != 0 hands the same bytes to
+ * linr_ply_parse_ascii.  The device takes the host parser's fast path only and takes it exactly: mant / 10^f rounded in integers is what
+ * the host's correctly rounded double division followed by nearbyint gives for at most 15 digits.
+ * ws_d: linr_ply_parse_ws_bytes(len, n_rows) bytes (0 for len over the bound or n_rows < 0), 256-byte aligned, uninitialised.
+ * linr_ply_gather_binary: rec_d holds n_rows records of `stride` bytes (no alignment); field j of a record lies at byte off[j] and
+ * has type code type[j]: 0 i1, 1 u1, 2 i2, 3 u2, 4 i4, 5 u4, 6 f4, 7 f8 (off / type are HOST arrays), little endian or, with
+ * big_endian != 0, big endian.  Every value is converted exactly to double and rounded with rint; xyz_d and status_d as above.
+ * Both check their arguments before the first launch: LINR_EINVAL for n_rows < 0, a NULL pointer with n_rows > 0, n_cols outside
+ * 3..64, a column outside [0, n_cols), len over the bound, stride <= 0, a type code outside 0..7 or a field that does not lie inside
+ * the record; LINR_ENOSPC for a short workspace; LINR_EALIGN for a misaligned text_d, ws_d, xyz_d or status_d.  n_rows == 0 returns
+ * 0, launches nothing and leaves *status_d untouched.  Stream-ordered, nothing allocated, no LDS, no float atomics; the kernels belong to
+ * no linr_prof_* / linr_debug_poison class (all 24 are taken). */
+#define LINR_PLY_TOKEN   1
+#define LINR_PLY_COLUMNS 2
+#define LINR_PLY_SHORT   4
+#define LINR_PLY_RANGE   8
+LINR_API size_t linr_ply_parse_ws_bytes(size_t len, int64_t n_rows);
+LINR_API int    linr_ply_parse_ascii_device(const char* text_d, size_t len, int64_t n_rows, int32_t n_cols, int32_t cx, int32_t cy,
+                                   int32_t cz, int32_t* xyz_d, void* ws_d, size_t ws_bytes, int64_t* status_d, void* stream);
+LINR_API int    linr_ply_gather_binary(const uint8_t* rec_d, int64_t n_rows, int32_t stride, const int32_t off[3], const int32_t type[3],
+                              int32_t big_endian, int32_t* xyz_d, int64_t* status_d, void* stream);
 
 /* ---- frame output (device) -------------------------------------------------------------------------------------------
  * Body of an ASCII PLY formatted on the DEVICE (csrc/ply_format.hip): what write_ply_ascii (datautils/custom_dataset.py:37-58,

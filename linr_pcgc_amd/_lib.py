@@ -11,7 +11,8 @@ LIB_PATH = os.environ.get('LINR_HIP_LIB') or os.path.join(_HERE, 'liblinr_hip.so
 
 LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 16
 LINR_FRAME_OCC_PADDED = 1
-ABI_VERSION = 16
+LINR_PLY_TOKEN, LINR_PLY_COLUMNS, LINR_PLY_SHORT, LINR_PLY_RANGE = 1, 2, 4, 8
+ABI_VERSION = 17
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -184,6 +185,9 @@ _PROTOS = {
     'linr_ply_format_text_bytes': (c_size, [c_i64]),
     'linr_ply_format_ws_bytes': (c_size, [c_i64]),
     'linr_ply_format_ascii': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_size, c_ptr, c_size, c_ptr, c_ptr]),
+    'linr_ply_parse_ws_bytes': (c_size, [c_size, c_i64]),
+    'linr_ply_parse_ascii_device': (ctypes.c_int, [c_ptr, c_size, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_size, c_ptr, c_ptr]),
+    'linr_ply_gather_binary': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_ptr]),
 }
 
 EXPORTS = tuple(_PROTOS)

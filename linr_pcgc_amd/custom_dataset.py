@@ -86,10 +86,11 @@ def _read(path, ori_type):
 
 
 class MytestDataset:
-    """custom_dataset.py:123-152: frame idx as an int32 [P, 3] tensor sorted by the x-major key (sort_by_coord_sum_c)."""
+    """custom_dataset.py:123-152: frame idx as an int32 [P, 3] tensor sorted by the x-major key (sort_by_coord_sum_c).
+    device_parse=True: PLY bodies are parsed on the GPU (ply.read_points_device) instead of by the host parser; same tensors."""
 
-    def __init__(self, ori_dir, ori_type='npy'):
-        self.ori_type = ori_type
+    def __init__(self, ori_dir, ori_type='npy', device_parse=False):
+        self.ori_type, self.device_parse = ori_type, bool(device_parse)
         self.all_files_path = _list_frames(ori_dir, ori_type)
 
     def __getitem__(self, idx):
@@ -99,6 +100,8 @@ class MytestDataset:
         return len(self.all_files_path)
 
     def handle_data(self, file_path):
+        if self.device_parse and self.ori_type == 'ply':
+            return sort_by_coord_sum_c(ply.read_points_device(file_path, device).to(torch.int32))
         pts = torch.as_tensor(np.asarray(_read(file_path, self.ori_type)).astype(np.int32), device=device)
         return sort_by_coord_sum_c(pts)          # sorted, NOT de-duplicated, like the reference
 

@@ -43,7 +43,7 @@ def decode_one_gop(inargs):
 
 
 def main(argv=None):
-    """python -m linr_pcgc_amd.decoder --enc-dir OUT/result_enc --dec-dir OUT/dec [--ori-dir frames --ori-type ply] [--lockstep B]
+    """python -m linr_pcgc_amd.decoder --enc-dir OUT/result_enc --dec-dir OUT/dec [--ori-dir frames --ori-type ply --ply-parse device] [--lockstep B]
     The decoder as its own program (decoder.py:179-200): every GOP under --enc-dir from its files alone, frames written as
     frameXXXX.ply; with --ori-dir each one is also compared with the input.  The model's shape travels in side_info.json (the
     reference hard-codes it, decoder.py:189); for streams without it the scale count is read off the stream files and width /
@@ -59,6 +59,8 @@ def main(argv=None):
     ap.add_argument('--block-layers', type=int, default=1)
     ap.add_argument('--lockstep', type=int, default=0,
                     help='decode the frames of a GOP in groups of up to this many, all scales in lock step (codec.decode_gop lockstep=; 0: frame by frame)')
+    ap.add_argument('--ply-parse', '--ply_parse', dest='ply_parse', default='host', choices=['host', 'device'],
+                    help='with --ori-dir: the original PLY frames are parsed by the host parser (default) or on the GPU (ply.read_points_device)')
     args = ap.parse_args(argv)
     names = sorted((n for n in os.listdir(args.enc_dir) if n.startswith('gop_')), key=lambda n: gop_bounds(n)[0])
     if not names:
@@ -67,7 +69,7 @@ def main(argv=None):
     truth = None
     if args.ori_dir is not None:
         from .custom_dataset import MytestDataset
-        truth = MytestDataset(args.ori_dir, ori_type=args.ori_type)
+        truth = MytestDataset(args.ori_dir, ori_type=args.ori_type, device_parse=args.ply_parse == 'device')
     dev = 'cuda' if torch.cuda.is_available() else 'cpu'
     frames = 0
     with PlyWriter() as writer:          # closed - every file complete - before main returns or raises

@@ -56,6 +56,9 @@ def parse(argv=None):
     ap.add_argument('--device-codes', '--device_codes', dest='device_codes', action='store_true',
                     help="the range coder's 16-bit code values and symbol bits are computed on the GPU (linr_ac_codes): 17 bits per symbol "
                          'cross to the host instead of 40; the streams are byte for byte those of the default path')
+    ap.add_argument('--ply-parse', '--ply_parse', dest='ply_parse', default='host', choices=['host', 'device'],
+                    help='with --input-glob / --ori_dir: PLY frames are parsed by the host parser on a thread pool (default) or on the GPU '
+                         '(ply.read_many_device, on the staging stream); the encoded files are byte for byte the same')
     ap.add_argument('--decode', action='store_true', help='decode every GOP again and check it is lossless')
     ap.add_argument('--decode-lockstep', '--decode_lockstep', dest='decode_lockstep', type=int, default=0,
                     help='with --decode: decode the frames of a GOP in groups of up to this many, all scales in lock step '
@@ -108,9 +111,13 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
             ahead = {'pool': ThreadPoolExecutor(max_workers=1), 'futures': {}, 'stream': torch.cuda.Stream(),
                      'next': {tuple(groups[a]): groups[b] for a, b in zip(my_order, my_order[1:])}}
 
+    device_parse = getattr(args, 'ply_parse', 'host') == 'device'
+
     def load_group(group):
         if files is None:
             return [synthetic.sequence_frame_device(args.config, t, device) for t in group]
+        if device_parse:
+            return ply.read_many_device([files[t] for t in group], device)          # on the current stream: the staging stream when staged ahead
         return ply.read_many([files[t] for t in group])
 
     # main.py:73-78: the scale count of the whole sequence is fixed by its FIRST frame (dataset[0]) unless --scale_num gives it; every
@@ -119,7 +126,10 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
     seq_scale_num = getattr(args, 'scale_num', None)
     if seq_scale_num is None:
         from .module_utils import prepare_frame
-        first = ply.read_points(files[0]) if files is not None else synthetic.sequence_frame_device(args.config, 0, device)
+        if files is not None:
+            first = ply.read_points_device(files[0], device) if device_parse else ply.read_points(files[0])
+        else:
+            first = synthetic.sequence_frame_device(args.config, 0, device)
         seq_scale_num = prepare_frame(first, None, getattr(args, 'min_point_num', 64), device=device, with_offsets=False)['scale_num']
         del first
 
