@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 17
+#define LINR_ABI_VERSION 18
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -404,6 +404,33 @@ LINR_API int linr_net_train_step(const linr_frame* f, float* params, float* aren
                         float* exp_avg, float* exp_avg_sq, double lr, int64_t step, const int64_t* scale_steps_h,
                         double beta1, double beta2, double eps, double weight_decay, double* bits_acc, void* stream);
 
+/* ---- quantisation-aware overfit (opt-in) --------------------------------------------------------------------------
+ * The codec never codes geometry with the weights it trained: encode_one_gop quantises the flat parameter vector
+ * (quant_uniform2, model_compression/model_size_est.py:72-91) and codes every frame with the DE-QUANTISED model
+ * (encoder.py:101-103).  These entries let the overfit iteration (main.py:305-321) see that step.
+ *
+ * linr_params_fake_quant: qparams = the de-quantised image of params, bit for bit what quant_uniform2 followed by the decoder's
+ *   de-quantisation computes in fp32 on the CPU:  mn = min(params), mx = max(params), r = mx - mn, s = 2^bitdepth - 1,
+ *   q = rint(((p - mn) / r) * s) (round half to even), qparams = (q / s) * r + mn, each of the six operations rounded to fp32 on
+ *   its own.  params, qparams: device [n] floats, 16-byte aligned; codes: device [n] uint16 (8-byte aligned) that receive q, or
+ *   NULL; minmax: two device floats that receive mn and mx, or NULL; bitdepth 2..16.  ONE launch, no host synchronisation.
+ *   mx == mn: codes 0 and qparams = params (quant_uniform2 itself yields NaN there).  A NaN parameter takes no part in the minimum
+ *   and maximum, stays NaN in qparams and has code 0; of a negative and a positive zero the negative one is the smaller.  Codes
+ *   never leave [0, s].
+ * linr_params_fake_quant_host: the same arithmetic as a plain loop over HOST pointers (no GPU needed).
+ * linr_net_train_step_qat: linr_net_train_step whose forward and backward run at qparams = fake_quant(params) (written by the
+ *   call: a caller-owned device buffer of linr_param_count floats, 16-byte aligned, not params itself) while Adam - weight decay
+ *   included - updates the fp32 master `params` with that gradient (straight-through estimator): bits_acc receives the bits of the
+ *   weights the codec would code with.  One launch more than linr_net_train_step; the arena layout is the same. */
+LINR_API int linr_params_fake_quant(const float* params, int64_t n, int32_t bitdepth, float* qparams, uint16_t* codes, float* minmax,
+                                    void* stream);
+LINR_API int linr_params_fake_quant_host(const float* params, int64_t n, int32_t bitdepth, float* qparams, uint16_t* codes,
+                                         float* minmax);
+LINR_API int linr_net_train_step_qat(const linr_frame* f, float* params, float* arena, size_t arena_bytes, float gscale,
+                            float* exp_avg, float* exp_avg_sq, double lr, int64_t step, const int64_t* scale_steps_h,
+                            double beta1, double beta2, double eps, double weight_decay, double* bits_acc, float* qparams,
+                            int32_t bitdepth, void* stream);
+
 /* ---- bf16 / uint8-weight inference executor (BASELINE config[4]) ------------------------------------------------
  * The codec codes the geometry with the DE-QUANTISED model (encoder.py:101-103, decoder.py:87): w = q/255*(max-min)+min
  * for the uint8 codes q of quant_uniform2 (model_compression/model_size_est.py:72-91).  This entry takes the codes
@@ -481,6 +508,12 @@ LINR_API int linr_net_train_step_bf16(const linr_frame* f, float* params, void* 
                              float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
                              const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay,
                              double* bits_acc, void* stream);
+/* linr_net_train_step_bf16 at the fake-quantised weights (see linr_net_train_step_qat; model_size_est.py:72-91, encoder.py:101-103,
+ * main.py:305-321): every kernel of the step, the weight images rounded to bf16 included, reads qparams; Adam updates `params`. */
+LINR_API int linr_net_train_step_bf16_qat(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
+                                 float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
+                                 const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay,
+                                 double* bits_acc, float* qparams, int32_t bitdepth, void* stream);
 /* The backward of ONE convolution 8->8 of that executor as a stand-alone op (ME.MinkowskiConvolution's backward, models/resnet.py:15-51
  * under autograd): gin = bwd-data(gout; W) rounded to bf16 AND the kernel / bias gradient from one gather of gout.  gout / in / gin:
  * bf16 [n][8] whose row -1 exists (gout's must be zero); W fp32 [27][8][8] (rounded to bf16 in-kernel for backward-data);

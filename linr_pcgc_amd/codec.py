@@ -73,6 +73,10 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     side_info.update(model_shape(model))
     # informational (the decoder does not need it): which training executor produced the coded model
     side_info['train_precision'] = getattr(model, 'train_precision', 'f32')
+    # ... and, when the driver says so, how many of its last epochs were quantisation-aware (overfit_gop qat_epochs=): not counted
+    # in EXTRA_SIDE_BITS, ignored by the decoders
+    if getattr(model, 'qat_epochs', 0):
+        side_info['qat_epochs'] = int(model.qat_epochs)
     # Pipeline: the GPU forward + D2H of frame i+1 runs while host workers range-code earlier frames (the coder's C call
     # releases the GIL).  A frame has 8 x scales independent streams, but the 8 streams of its finest scale carry 73 % of the
     # symbols, so one frame keeps only ~8 threads busy: TWO frames are coded concurrently, each on half of the threads

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "layout.h"
+#include "fake_quant.h"
 #include <math.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -13,14 +14,10 @@ typedef unsigned short bf16_t;
 __device__ __forceinline__ bf16_t f2bf(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }     // RNE (v_cvt_pk_bf16_f32)
 __device__ __forceinline__ float bf2f(bf16_t b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
 
-// torch: recon = q / sym_max * ten_range + min_n, each step ONE fp32 rounding: hipcc contracts a * b + c into an fma by
-// default (-ffp-contract=fast-honor-pragmas), which changes the last bit where the sum cancels, so contraction is switched
-// off here; the division is IEEE (correctly rounded is hipcc's default for fp32 divide)
+// torch: recon = q / sym_max * ten_range + min_n, each step ONE fp32 rounding (no contraction, IEEE division): the expression the
+// quantisation-aware train steps evaluate their weights with, too (fake_quant.h)
 __device__ __forceinline__ float dequant_code(uint8_t code, float range, float minv) {
-#pragma clang fp contract(off)
-    const float t = (float)code / 255.0f;
-    const float u = t * range;
-    return u + minv;
+    return linr_fq_dequant((float)code, 255.0f, range, minv);
 }
 __device__ __forceinline__ float dequant(const uint8_t* __restrict__ codes, int64_t i, float range, float minv) {
     return dequant_code(codes[i], range, minv);

@@ -1333,20 +1333,45 @@ extern "C" int linr_net_backward_bf16(const linr_frame* f, const float* params, 
     return linr_axpy(c.A.GSUM, c.L.total, grads, 1, stream);
 }
 
-extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes,
-                                        const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr,
-                                        int64_t step, const int64_t* scale_steps_h, double beta1, double beta2, double eps,
-                                        double weight_decay, double* bits_acc, void* stream) {
+// One overfit iteration (csrc/net.hip: train_step, in this executor's arithmetic): with qparams != NULL every kernel - tpack_k's
+// weight images included - reads the fake-quantised image of the fp32 master, and Adam updates the master.
+static int ttrain_step(const linr_frame* f, float* params, float* qparams, int32_t bitdepth, void* arena, size_t arena_bytes,
+                       const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
+                       const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay, double* bits_acc,
+                       void* stream) {
     if (!exp_avg || !exp_avg_sq || !bits_acc || step < 1) return LINR_EINVAL;
     TCtx c;
     TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
+    if (qparams) TRY(linr_fake_quant_check(params, c.L.total, bitdepth, qparams, nullptr));
     TRY(linr_scale_steps_check(f, c.L, scale_steps_h));          // before anything is launched
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;
+    if (qparams) {
+        ProfScope ps(c.s, TK_MISC, 0);
+        TRY(linr_fake_quant_launch(params, c.L.total, bitdepth, qparams, nullptr, nullptr, c.s));
+        c.P = qparams;
+    }
     TRY(tforward(c, nullptr, bits_acc));
     TRY(tbackward(c, gscale));
     ProfScope ps(c.s, TK_MISC, 0);
     return linr_adam_step_launch(c.L, params, c.A.GSUM, exp_avg, exp_avg_sq, lr, step, scale_steps_h, beta1, beta2, eps, weight_decay, c.s);
+}
+
+extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes,
+                                        const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr,
+                                        int64_t step, const int64_t* scale_steps_h, double beta1, double beta2, double eps,
+                                        double weight_decay, double* bits_acc, void* stream) {
+    return ttrain_step(f, params, nullptr, 0, arena, arena_bytes, occ_bf16, gscale, exp_avg, exp_avg_sq, lr, step, scale_steps_h, beta1,
+                       beta2, eps, weight_decay, bits_acc, stream);
+}
+
+extern "C" int linr_net_train_step_bf16_qat(const linr_frame* f, float* params, void* arena, size_t arena_bytes,
+                                            const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr,
+                                            int64_t step, const int64_t* scale_steps_h, double beta1, double beta2, double eps,
+                                            double weight_decay, double* bits_acc, float* qparams, int32_t bitdepth, void* stream) {
+    if (!qparams || qparams == params) return LINR_EINVAL;
+    return ttrain_step(f, params, qparams, bitdepth, arena, arena_bytes, occ_bf16, gscale, exp_avg, exp_avg_sq, lr, step, scale_steps_h,
+                       beta1, beta2, eps, weight_decay, bits_acc, stream);
 }
 
 extern "C" int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* in, const int32_t* lo, const uint32_t* mask, int64_t ld,

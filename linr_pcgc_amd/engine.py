@@ -222,15 +222,36 @@ def net_backward(frame, flat_params, flat_grads, gscale, arena=None):
                                        flat_grads.data_ptr(), _stream()), 'linr_net_backward')
 
 
+def params_fake_quant(flat, bitdepth=8, codes=False):
+    """linr_params_fake_quant: the de-quantised image of the flat parameter vector `flat` (device float32), bit for bit what
+    model_codec.quant_uniform2 and the decoder's de-quantisation give on the CPU.  Returns (qparams, minmax float32[2]), with
+    codes=True (qparams, codes uint16, minmax); one launch, nothing synchronises with the host."""
+    flat = flat.contiguous()
+    q = torch.empty_like(flat)
+    c = torch.empty(flat.numel(), dtype=torch.uint16, device=flat.device) if codes else None
+    mm = torch.empty(2, dtype=torch.float32, device=flat.device)
+    check(_lib.lib().linr_params_fake_quant(flat.data_ptr(), flat.numel(), int(bitdepth), q.data_ptr(),
+                                            None if c is None else c.data_ptr(), mm.data_ptr(), _stream()), 'linr_params_fake_quant')
+    return (q, c, mm) if codes else (q, mm)
+
+
 def net_train_step(frame, flat_params, exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits,
-                   arena=None, scale_steps=None):
+                   arena=None, scale_steps=None, qparams=None, bitdepth=8):
     """linr_net_train_step: forward + backward + deterministic gradient reduction + fused Adam in one call.
     scale_steps: int64 numpy array [model_scale_num] of the per-scale context MLPs' 1-based step counts (torch.optim.Adam
-    semantics for scales a frame does not contain), or None = every parameter uses `step`."""
+    semantics for scales a frame does not contain), or None = every parameter uses `step`.
+    qparams (a float32 device buffer like flat_params): the quantisation-aware step linr_net_train_step_qat - the network is
+    evaluated at the `bitdepth`-bit fake-quantised weights, written into qparams, and Adam updates flat_params."""
     arena = frame.arena if arena is None else arena
+    steps = None if scale_steps is None else scale_steps.ctypes.data
+    if qparams is not None:
+        check(_lib.lib().linr_net_train_step_qat(frame.cref(), flat_params.data_ptr(), arena.data_ptr(), arena.numel(),
+                                                 float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step), steps,
+                                                 beta1, beta2, eps, weight_decay, bits.data_ptr(), qparams.data_ptr(), int(bitdepth),
+                                                 _stream()), 'linr_net_train_step_qat')
+        return
     check(_lib.lib().linr_net_train_step(frame.cref(), flat_params.data_ptr(), arena.data_ptr(), arena.numel(),
-                                         float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step),
-                                         None if scale_steps is None else scale_steps.ctypes.data,
+                                         float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step), steps,
                                          beta1, beta2, eps, weight_decay, bits.data_ptr(), _stream()),
           'linr_net_train_step')
 
@@ -251,11 +272,18 @@ def net_backward_bf16(frame, flat_params, flat_grads, gscale):
 
 
 def net_train_step_bf16(frame, flat_params, exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits,
-                        scale_steps=None):
-    """linr_net_train_step_bf16: net_train_step with bf16 feature / gradient rows, fp32 master parameters and accumulation."""
+                        scale_steps=None, qparams=None, bitdepth=8):
+    """linr_net_train_step_bf16: net_train_step with bf16 feature / gradient rows, fp32 master parameters and accumulation; with
+    qparams linr_net_train_step_bf16_qat (see net_train_step)."""
     base, nbytes = frame.train_bf16_arena()
+    steps = None if scale_steps is None else scale_steps.ctypes.data
+    if qparams is not None:
+        check(_lib.lib().linr_net_train_step_bf16_qat(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(),
+                                                      float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step),
+                                                      steps, beta1, beta2, eps, weight_decay, bits.data_ptr(), qparams.data_ptr(),
+                                                      int(bitdepth), _stream()), 'linr_net_train_step_bf16_qat')
+        return
     check(_lib.lib().linr_net_train_step_bf16(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(),
-                                              float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step),
-                                              None if scale_steps is None else scale_steps.ctypes.data,
+                                              float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step), steps,
                                               beta1, beta2, eps, weight_decay, bits.data_ptr(), _stream()),
           'linr_net_train_step_bf16')

@@ -204,6 +204,14 @@ class LINR_PCGC_Model(nn.Module):
         """The contiguous float32 buffer holding every parameter in parameters() order (what the model codec codes)."""
         return self._flat
 
+    def qat_parameters(self):
+        """The buffer the quantisation-aware train step writes the fake-quantised weights into (allocated on first use; it follows
+        the flat buffer when the model moves)."""
+        q = getattr(self, '_qat_flat', None)
+        if q is None or q.device != self._flat.device or q.numel() != self._flat.numel():
+            q = self._qat_flat = torch.empty_like(self._flat)
+        return q
+
     # ---- frames ----------------------------------------------------------------------------------------------------
     def make_frame(self, scales, validate=True, with_arena=True):
         """Batched multi-scale frame for the fast path.  scales: list of per-scale input dicts (see engine.Frame)."""
@@ -632,12 +640,19 @@ class FlatAdam:
         self.t = steps.pop() if steps else 0
 
 
-def train_step(model, opt, frame, point_num, out=None):
+def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
     """One iteration of main.py:305-321 on a batched frame: bits -> loss = bits/point_num -> backward -> Adam ->
     StepLR, as ONE C-ABI call (linr_net_train_step).  Returns the device-resident bits accumulator (float64[1]);
     nothing synchronises with the host.  `out`: a zeroed float64[1] device tensor to add the bits into (e.g. one slot of a
-    per-GOP vector that is cleared once per epoch) - saves the per-step allocation + fill."""
+    per-GOP vector that is cleared once per epoch) - saves the per-step allocation + fill.
+    qat_bitdepth > 0: the quantisation-aware step (linr_net_train_step_qat / _bf16_qat) - bits and gradient are those of the
+    weights the model codec would code with at that depth (quant_uniform2 and back), Adam updates the fp32 master."""
     bits = torch.zeros(1, dtype=torch.float64, device=frame.device) if out is None else out
+    qat = {}
+    if qat_bitdepth:
+        if model._wide is not None:
+            raise _lib.LinrError('quantisation-aware training exists for hidden_channel_conv=8 only')
+        qat = {'qparams': model.qat_parameters(), 'bitdepth': int(qat_bitdepth)}
     if model._wide is not None:          # hidden_channel_conv 16 / 32: the channel-blocked executor + the segment-wise Adam
         if model.train_precision != 'f32':
             raise _lib.LinrError('the bf16 training executor exists for hidden_channel_conv=8 only')
@@ -656,10 +671,10 @@ def train_step(model, opt, frame, point_num, out=None):
         if model.block_layers != 1:
             raise _lib.LinrError('the bf16 training executor supports block_layers=1 only')
         engine.net_train_step_bf16(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
-                                   opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale)
+                                   opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale, **qat)
     elif model.train_precision == 'f32':
         engine.net_train_step(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
-                              opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale)
+                              opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale, **qat)
     else:
         raise ValueError("train_precision must be 'f32' or 'bf16'")
     opt.t, opt.t_scale = t, t_scale              # committed only after the call returned without an error

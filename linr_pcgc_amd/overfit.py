@@ -141,13 +141,28 @@ class BestState:
         self.opt.t, self.opt.t_scale, self.opt.lr, self.opt.sched_steps = self.meta[0], self.meta[1].copy(), self.meta[2], self.meta[3]
 
 
-def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best', info=None):
+def qat_first_epoch(epochs, qat_epochs):
+    """The first quantisation-aware epoch of an overfit of `epochs` epochs whose last min(qat_epochs, epochs) are; `epochs` (no
+    such epoch) when qat_epochs is 0."""
+    if qat_epochs < 0:
+        raise ValueError('qat_epochs must be >= 0, got %d' % qat_epochs)
+    return max(0, int(epochs) - int(qat_epochs))
+
+
+def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best', info=None, qat_epochs=0, qat_bitdepth=8):
     """main.py:297-437: frames in fixed order, one optimiser + StepLR step per frame, lr clamp after each epoch.
     keep='best' (the reference's policy, main.py:413-426,440-451): model and optimiser are left in the state at the end of the epoch
     with the lowest mean loss; keep='last': in the state after the last epoch.  Returns the per-epoch mean loss (bits per point),
-    like the reference logs; `info` (a dict) receives 'coded_epoch' and 'coded_loss'."""
+    like the reference logs; `info` (a dict) receives 'coded_epoch' and 'coded_loss'.
+    qat_epochs > 0 (opt-in; 0 is the plain overfit, untouched): the last min(qat_epochs, epochs) epochs are quantisation-aware
+    (train_step qat_bitdepth=): their loss is the rate of the weights encode_gop will code with at `qat_bitdepth` bits.  With
+    keep='best' only those epochs compete - the loss of a plain epoch belongs to weights that are never coded.  The state left
+    behind is the fp32 master either way; `info` also receives 'qat_from', the first quantisation-aware epoch."""
     if keep not in ('best', 'last'):
         raise ValueError("keep must be 'best' or 'last'")
+    qat_from = qat_first_epoch(epochs, qat_epochs)
+    if qat_epochs and not 2 <= int(qat_bitdepth) <= 16:
+        raise ValueError('qat_bitdepth must be in 2..16, got %r' % (qat_bitdepth,))
     if getattr(model, 'train_precision', 'f32') == 'bf16':
         gop.share_train_bf16_arena()
     losses = []
@@ -158,12 +173,15 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
     for epoch in range(epochs):
         bits.zero_()
         for j, (f, pn) in enumerate(zip(gop.frames, gop.point_nums)):
-            train_step(model, opt, f, pn, out=bits[j:j + 1])
+            if epoch >= qat_from:
+                train_step(model, opt, f, pn, out=bits[j:j + 1], qat_bitdepth=qat_bitdepth)
+            else:
+                train_step(model, opt, f, pn, out=bits[j:j + 1])
         # the only host sync of the epoch.  Non-finite parameters make the epoch count as diverged (loss = inf): the loss itself
         # would not show them - BCELoss's clamp at -100 (models/model_core.py:76-81) turns a NaN probability into 100 nats
         val = (bits / pns).sum() / len(gop)
         loss_mean = float(torch.where(torch.isfinite(model.flat_parameters()).all(), val, torch.full_like(val, float('inf'))))
-        if best is not None:
+        if best is not None and (not qat_epochs or epoch >= qat_from):
             best.offer(epoch, loss_mean)
         opt.clamp_lr(min_lr)
         losses.append(loss_mean)
@@ -178,6 +196,8 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
     if info is not None:
         info['coded_epoch'] = best.epoch if best is not None else epochs - 1
         info['coded_loss'] = best.loss if best is not None else (losses[-1] if losses else None)
+        if qat_epochs:
+            info['qat_from'] = qat_from
     return losses
 
 

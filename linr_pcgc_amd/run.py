@@ -59,6 +59,11 @@ def parse(argv=None):
     ap.add_argument('--ply-parse', '--ply_parse', dest='ply_parse', default='host', choices=['host', 'device'],
                     help='with --input-glob / --ori_dir: PLY frames are parsed by the host parser on a thread pool (default) or on the GPU '
                          '(ply.read_many_device, on the staging stream); the encoded files are byte for byte the same')
+    ap.add_argument('--qat-epochs', '--qat_epochs', dest='qat_epochs', type=int, default=0,
+                    help='the last N epochs of every overfit (--first-epoch and --others-epoch alike) are quantisation-aware: the network is '
+                         'evaluated at the --model_bitdepth-bit weights the model codec will code with, the gradient goes straight through to '
+                         'the fp32 weights, and with --keep best only those epochs compete.  0 (default): the plain overfit.  '
+                         '--hidden-channel-conv 8 only; streams decode as ever')
     ap.add_argument('--decode', action='store_true', help='decode every GOP again and check it is lossless')
     ap.add_argument('--decode-lockstep', '--decode_lockstep', dest='decode_lockstep', type=int, default=0,
                     help='with --decode: decode the frames of a GOP in groups of up to this many, all scales in lock step '
@@ -68,7 +73,14 @@ def parse(argv=None):
                          'epoch of every GOP; results under <out>/output/<gop>/<epoch>/ and <out>/output/<gop>/result.json')
     ap.add_argument('--check-freq', '--check_freq', dest='check_freq', type=int, default=5, help='main.py --check_freq')
     ap.add_argument('--write-real-bitstream', action='store_true', help='main.py --write_real_bitstream: the mid-test also writes its bins at every 50th epoch')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.qat_epochs < 0:
+        ap.error('--qat-epochs must be >= 0')
+    if args.qat_epochs and args.hidden_channel_conv != 8:
+        ap.error('--qat-epochs: quantisation-aware training exists for --hidden-channel-conv 8 only')
+    if args.qat_epochs and not 2 <= args.model_bitdepth <= 16:
+        ap.error('--qat-epochs needs --model_bitdepth in 2..16')
+    return args
 
 
 def train_precision(args):
@@ -214,7 +226,13 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
             clock['mark'] = time.time()
 
         try:
-            losses = overfit.overfit_gop(model, opt, gop, epochs, args.min_lr, keep=getattr(args, 'keep', 'best'), info=info, on_epoch=on_epoch)
+            qat_epochs = int(getattr(args, 'qat_epochs', 0) or 0)
+            if qat_epochs:
+                model.qat_epochs = min(qat_epochs, epochs)           # informational, for side_info.json (codec.encode_gop)
+                losses = overfit.overfit_gop(model, opt, gop, epochs, args.min_lr, keep=getattr(args, 'keep', 'best'), info=info, on_epoch=on_epoch,
+                                             qat_epochs=qat_epochs, qat_bitdepth=getattr(args, 'model_bitdepth', 8))
+            else:
+                losses = overfit.overfit_gop(model, opt, gop, epochs, args.min_lr, keep=getattr(args, 'keep', 'best'), info=info, on_epoch=on_epoch)
         finally:
             log.close()
         torch.cuda.synchronize()
@@ -241,6 +259,8 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                   'coded_epoch': info['coded_epoch'], 'coded_loss': info['coded_loss'],
                   'bpp': enc['bpp'], 'points': enc['point_num'], 'lossless': ok, 'stage_s': stage_s, 'overfit_s': t1 - t0,
                   'encode_s': t2 - t1, 'decode_s': t3 - t2, 'seconds': stage_s + (t3 - t0), 'rank': rank}
+        if 'qat_from' in info:
+            result['qat_from'] = info['qat_from']
         if getattr(args, 'mid_test', False):
             result['mid_test'] = mid
         del gop
