@@ -136,3 +136,27 @@ def _relu_tie_slack(sd, scales, gscale=1.0, thresh=3e-7):
             for k, g in moved.items():
                 slack[k] += float((g - base[k]).abs().max())
     return slack
+
+
+# ---- per-entry rounding bounds (tests/test_gpu_wide.py, tests/test_gpu_multi_tile.py) --------------------------------------------
+# Op level at the multi-tile size: per-entry bounds against float64.  A relative-to-max bound loses its sharpness at 1e5 rows (one lost
+# 256-row tile moves a weight-gradient entry by ~1e-3 of its largest), so every entry gets the rounding bound of its own sum,
+#     |got - exact| <= C_ROUND * 2^-24 * (the same sum over the absolute values of its terms)
+# (forward: |x| (*) |W| + |b| + |res|; backward-data: |g| (*) |W|^T; weight gradients: sum over rows of |x| |g|), computed by the same
+# float64 oracle.  A recursive fp32 sum of m terms errs by at most ~m 2^-24 of that; the kernels' sums are blocked (depth < 200 at 157 k
+# rows) and rounding errors cancel, so C_ROUND = 64 is far above what any summation order gives in practice and far below what a skipped
+# tile or 8-row group costs (16 of a typical term per 256 rows, against 64 2^-24 157 k = 0.6 of one).  Measured on the MI355X: worst
+# entries at 0.12 of the bound (forward), 0.1 (backward-data), 1.4e-3 (weight gradients); a weight-gradient kernel that drops the last
+# 8-row group lands at 17-43 x.  Every output is pre-filled with NaN, so a tile that is never written fails instead of reading stale memory.
+C_ROUND = 64.0
+_U = 2.0 ** -24
+
+
+def _within_rounding(got, exact, absum, what):
+    got = got.double()
+    tol = C_ROUND * _U * absum
+    ratio = (got - exact).abs() / tol.clamp(min=1e-300)
+    assert bool(torch.isfinite(got).all()), '%s: %d entries never written (NaN)' % (what, int((~torch.isfinite(got)).sum()))
+    worst = float(ratio.max())
+    assert bool(((got - exact).abs() <= tol).all()), '%s: worst entry at %.3g x its bound' % (what, worst)
+    return worst

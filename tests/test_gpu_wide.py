@@ -11,7 +11,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import network as onet          # noqa: E402
 from oracle import octree as ooct           # noqa: E402
-from gpu_common import _close, _grads_close_per_tensor, _relu_tie_slack, _smallest_relu_input          # noqa: E402
+from gpu_common import C_ROUND, _U, _close, _grads_close_per_tensor, _relu_tie_slack, _smallest_relu_input, _within_rounding          # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -583,27 +583,7 @@ def test_wide_multi_tile_frame_matches_the_oracle(pkg, sphere9):
           % (frame.rows, worst[0], worst[1], time.perf_counter() - t0, torch.cuda.max_memory_allocated() / 2 ** 30))
 
 
-# Op level at the multi-tile size: per-entry bounds against float64.  A relative-to-max bound loses its sharpness at 1e5 rows (one lost
-# 256-row tile moves a weight-gradient entry by ~1e-3 of its largest), so every entry gets the rounding bound of its own sum,
-#     |got - exact| <= C_ROUND * 2^-24 * (the same sum over the absolute values of its terms)
-# (forward: |x| (*) |W| + |b| + |res|; backward-data: |g| (*) |W|^T; weight gradients: sum over rows of |x| |g|), computed by the same
-# float64 oracle.  A recursive fp32 sum of m terms errs by at most ~m 2^-24 of that; the kernels' sums are blocked (depth < 200 at 157 k
-# rows) and rounding errors cancel, so C_ROUND = 64 is far above what any summation order gives in practice and far below what a skipped
-# tile or 8-row group costs (16 of a typical term per 256 rows, against 64 2^-24 157 k = 0.6 of one).  Measured on the MI355X: worst
-# entries at 0.12 of the bound (forward), 0.1 (backward-data), 1.4e-3 (weight gradients); a weight-gradient kernel that drops the last
-# 8-row group lands at 17-43 x.  Every output is pre-filled with NaN, so a tile that is never written fails instead of reading stale memory.
-C_ROUND = 64.0
-_U = 2.0 ** -24
-
-
-def _within_rounding(got, exact, absum, what):
-    got = got.double()
-    tol = C_ROUND * _U * absum
-    ratio = (got - exact).abs() / tol.clamp(min=1e-300)
-    assert bool(torch.isfinite(got).all()), '%s: %d entries never written (NaN)' % (what, int((~torch.isfinite(got)).sum()))
-    worst = float(ratio.max())
-    assert bool(((got - exact).abs() <= tol).all()), '%s: worst entry at %.3g x its bound' % (what, worst)
-    return worst
+# Op level at the multi-tile size: per-entry rounding bounds against float64 (C_ROUND, _within_rounding: tests/gpu_common.py).
 
 
 def _nan_blocks(n, nb):
