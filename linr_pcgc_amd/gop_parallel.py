@@ -200,6 +200,99 @@ def run_sequence(groups, work_dir, first_fn, other_fn, rank=0, world=1, dist=Non
     return results
 
 
+class FinishPipeline:
+    """The second half of a GOP on ONE background thread while the caller runs the first half of the next one.
+
+    A GOP is two plain callables to this class: whatever the caller does itself (train: overfit the GOP) and
+    ``finish_fn(key, payload) -> result`` (code, write and check it), which runs on the worker.  ``hand_over(key, payload)`` first
+    waits for the finish in flight - so there is never more than one, and they start in hand-over order -, re-raises its exception
+    in the caller, and only then starts ``finish_fn(key, payload)``; ``drain()`` waits for the last one and returns
+    {key: result} of all of them; ``close()`` ends the worker thread (on every exit path: put it in a ``finally``).  After a
+    finish has raised nothing more is started: the same exception is raised again by every later call.
+    ``blocked_s`` is the time the caller spent waiting in here, ``blocked[key]`` the part of it spent waiting for key's finish.
+    The payload is referenced by the worker alone once it is handed over, so that ``finish_fn`` decides when it is released.
+    Knows nothing of torch: streams, devices and the lifetime of device memory are finish_fn's business."""
+
+    def __init__(self, finish_fn, thread_name='gop-finish'):
+        from concurrent.futures import ThreadPoolExecutor
+        self._finish_fn = finish_fn
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=thread_name)
+        self._pending = None                             # (key, future) of the finish in flight
+        self._error = None
+        self.results = {}
+        self.blocked = {}
+        self.blocked_s = 0.0
+
+    def _wait(self):
+        if self._error is not None:
+            raise self._error
+        if self._pending is None:
+            return
+        key, fut = self._pending
+        self._pending = None
+        t0 = time.time()
+        try:
+            self.results[key] = fut.result()
+        except BaseException as e:
+            self._error = e
+            raise
+        finally:
+            dt = time.time() - t0
+            self.blocked[key] = self.blocked.get(key, 0.0) + dt
+            self.blocked_s += dt
+
+    def hand_over(self, key, payload):
+        self._wait()
+        self._pending = (key, self._pool.submit(self._finish_fn, key, payload))
+
+    def drain(self):
+        self._wait()
+        return dict(self.results)
+
+    def close(self):
+        self._pool.shutdown(wait=True)
+
+
+def run_sequence_pipelined(groups, work_dir, train_first_fn, train_other_fn, finish_fn, rank=0, world=1, dist=None, prepare_fn=None,
+                           schedule='static', prepared=None, done_marker=True):
+    """run_sequence with every GOP split in two: this rank finishes GOP g (FinishPipeline, one background thread) while it
+    trains the next GOP it runs.  train_first_fn(group[, prepared]) -> (checkpoint, payload) and
+    train_other_fn(group, checkpoint[, prepared]) -> (placeholder, payload) run on the calling thread like first_fn / other_fn;
+    finish_fn(gop index, payload) -> result runs on the worker.  The checkpoint is returned - and written by run_sequence - as soon
+    as GOP 0 is TRAINED: the waiting ranks start while GOP 0 is still being coded, so nothing of a finish may be in it (it is
+    pickled; checkpoint['result'] is the placeholder of GOP 0).  After GOP g+1 is trained the caller waits for finish(g) - an
+    exception of it is raised there - and hands finish(g+1) over; the last finish is drained before the markers are written: a
+    failing finish leaves rank<N>_failed and never rank<N>_done, like a failing training (done_marker=False: rank<N>_done is the
+    caller's to write, as with run_sequence).  The worker is gone when this returns or raises.
+    Returns ({gop index: finish_fn's result} of this rank, the FinishPipeline with its blocked seconds)."""
+    pipe = FinishPipeline(finish_fn)
+    index = {tuple(g): i for i, g in enumerate(groups)}
+
+    def first_fn(group, *staged):
+        ckpt, payload = train_first_fn(group, *staged)
+        pipe.hand_over(index[tuple(group)], payload)
+        return ckpt
+
+    def other_fn(group, ckpt, *staged):
+        placeholder, payload = train_other_fn(group, ckpt, *staged)
+        pipe.hand_over(index[tuple(group)], payload)
+        return placeholder
+
+    try:
+        try:
+            results = run_sequence(groups, work_dir, first_fn, other_fn, rank, world, dist, prepare_fn=prepare_fn, schedule=schedule,
+                                   prepared=prepared, done_marker=False)
+            results.update(pipe.drain())                 # the placeholders become the full results
+        finally:
+            pipe.close()
+    except BaseException:
+        mark_failed(work_dir, rank)
+        raise
+    if done_marker:
+        mark_done(work_dir, rank)
+    return results, pipe
+
+
 def check_failures(work_dir):
     """Raises if any rank left a failure marker in work_dir - called before the final reductions so that the surviving ranks of
     a job without kill-on-failure supervision do not wait in a collective for a rank that is gone."""

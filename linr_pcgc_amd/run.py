@@ -68,6 +68,10 @@ def parse(argv=None):
     ap.add_argument('--decode-lockstep', '--decode_lockstep', dest='decode_lockstep', type=int, default=0,
                     help='with --decode: decode the frames of a GOP in groups of up to this many, all scales in lock step '
                          '(codec.decode_gop lockstep=; 0: frame by frame on 4 workers)')
+    ap.add_argument('--pipeline', action='store_true',
+                    help='code, write and check GOP g on a background thread with a HIP stream of its own while GOP g+1 overfits (at most one '
+                         'such finish in flight); the encoded files and the losses are those of the plain flow.  Up to three GOPs are resident '
+                         'in HBM at once: one finishing, one training, one staged ahead')
     ap.add_argument('--mid-test', action='store_true',
                     help='main.py --mid_test: measure the model through Test_one_gop (model.codec) at epochs 0..9 and every --check-freq-th '
                          'epoch of every GOP; results under <out>/output/<gop>/<epoch>/ and <out>/output/<gop>/result.json')
@@ -101,6 +105,13 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
     region starts behind a barrier with all inputs resident (bench.py's contract); otherwise GOPs are staged as they are
     claimed (ranks >= 1 stage their first GOP while rank 0 runs GOP 0).  decode_frames: None = all frames of a GOP when
     args.decode, or an int = the first n frames of each GOP.
+    args.pipeline (opt-in, read with getattr: callers that build their own namespace are untouched): every GOP is split into
+    train_gop and finish_gop, and finish_gop(g) - encode, write, decode check - runs on one background thread and HIP stream while this
+    thread stages and trains its next GOP (gop_parallel.run_sequence_pipelined); files and losses are those of the plain flow.  Every
+    result then has 'finish_wait_s' (what this thread waited for that GOP's finish) and the summary 'pipeline',
+    'gpu_train_fraction' (sum of overfit_s over the sum of the ranks' walls) and 'finish_wait_s'.  'phase_b_efficiency' then counts
+    as busy only what THIS thread spent - stage, overfit and the blocked waits - because encode_s and decode_s overlap the next
+    GOP's overfit_s: it stays <= 1.
     Returns (summary dict on every rank, {gop index: result} of this rank)."""
     groups = gop_parallel.split_gops(args.frames, args.gop)
     device = 'cuda'
@@ -173,7 +184,13 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                 ahead['futures'][tuple(nxt)] = ahead['pool'].submit(build_gop_ahead, nxt)
         return gop, time.time() - t0
 
-    def run_gop(group, epochs, ckpt, staged):
+    pipeline = bool(getattr(args, 'pipeline', False))
+
+    def gen_shell(gop):
+        return overfit.gen_model(gop.scale_num, device, block_layers=getattr(args, 'block_layers', 1), hidden=getattr(args, 'hidden_channel_conv', 8))
+
+    def train_gop(group, epochs, ckpt, staged):
+        """The first half of a GOP: stage (or take what was staged), overfit, synchronise.  Returns what finish_gop needs."""
         gop, stage_s = staged if staged is not None else stage(group)
         t0 = time.time()
         model = overfit.gen_model(gop.scale_num, device, seed=args.seed, block_layers=getattr(args, 'block_layers', 1), hidden=getattr(args, 'hidden_channel_conv', 8))
@@ -235,36 +252,69 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                 losses = overfit.overfit_gop(model, opt, gop, epochs, args.min_lr, keep=getattr(args, 'keep', 'best'), info=info, on_epoch=on_epoch)
         finally:
             log.close()
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                 # overfit_s ends here, and the model is complete before another stream reads it
         t1 = time.time()
-        enc = codec.encode_gop(model, overfit.gen_model(gop.scale_num, device, block_layers=getattr(args, 'block_layers', 1), hidden=getattr(args, 'hidden_channel_conv', 8)), gop,
-                               getattr(args, 'model_bitdepth', 8), precision=getattr(args, 'precision', 'f32'),
-                               device_codes=getattr(args, 'device_codes', False))
-        res_dir = os.path.join(args.out, 'result_enc', gop_parallel.gop_name(group))
-        codec.write_gop(enc, res_dir)
-        torch.cuda.synchronize()
-        t2 = time.time()
-        ok = None
-        if args.decode:
-            todo = list(range(len(group))) if decode_frames is None else list(range(min(decode_frames, len(group))))
-            lockstep = int(getattr(args, 'decode_lockstep', 0) or 0)
-            dec = codec.decode_gop(overfit.gen_model(gop.scale_num, device, block_layers=getattr(args, 'block_layers', 1), hidden=getattr(args, 'hidden_channel_conv', 8)),
-                                   codec.read_gop(res_dir), device, frames=todo, **({'lockstep': lockstep} if lockstep > 0 else {'workers': 4}))
-            ok = all(torch.equal(d, torch.as_tensor(gop.infos[i]['ori']).cuda() +
-                                 torch.tensor(gop.coord_mins[i], device='cuda', dtype=torch.int32))
-                     for d, i in zip(dec, todo))
-        torch.cuda.synchronize()
-        t3 = time.time()
-        result = {'gop': gop_parallel.gop_name(group), 'frames': len(group), 'epochs': epochs, 'loss': losses,
-                  'coded_epoch': info['coded_epoch'], 'coded_loss': info['coded_loss'],
-                  'bpp': enc['bpp'], 'points': enc['point_num'], 'lossless': ok, 'stage_s': stage_s, 'overfit_s': t1 - t0,
-                  'encode_s': t2 - t1, 'decode_s': t3 - t2, 'seconds': stage_s + (t3 - t0), 'rank': rank}
-        if 'qat_from' in info:
-            result['qat_from'] = info['qat_from']
-        if getattr(args, 'mid_test', False):
-            result['mid_test'] = mid
-        del gop
-        return model, opt, losses, result, info
+        half = {'group': group, 'epochs': epochs, 'gop': gop, 'model': model, 'opt': opt, 'losses': losses, 'info': info, 'mid': mid,
+                'stage_s': stage_s, 'overfit_s': t1 - t0, 'shells': None, 'ready': None}
+        if pipeline:
+            # the shells the codec and the decode check fill are built HERE, in the order of the plain flow: torch initialises them from
+            # the process-wide generator, and a draw from the finish thread between the next GOP's manual_seed and its model's
+            # initialisation would change that model
+            half['shells'] = [gen_shell(gop)] + ([gen_shell(gop)] if args.decode else [])
+            half['ready'] = torch.cuda.Event()
+            half['ready'].record()               # the finish stream waits for this, not for whatever this stream is given later
+        return half
+
+    def finish_gop(half, stream=None):
+        """The second half: encode_gop -> write_gop -> the optional decode check -> the result dict.  stream=None: on the caller's
+        stream with device-wide synchronisation (the plain flow).  Otherwise (the --pipeline worker thread) everything runs under
+        `stream`, the clocks stop at ITS synchronisation, and it is synchronised once more before the GOP and the model are let go:
+        they were allocated on the training stream and must not return to the allocator while this stream may still read them."""
+        group, gop, model, info = half['group'], half['gop'], half['model'], half['info']
+        sync = torch.cuda.synchronize if stream is None else stream.synchronize
+        shells = list(half['shells']) if half['shells'] is not None else None
+        shell = (lambda: shells.pop(0)) if shells is not None else (lambda: gen_shell(gop))
+        try:
+            t1 = time.time()
+            enc = codec.encode_gop(model, shell(), gop,
+                                   getattr(args, 'model_bitdepth', 8), precision=getattr(args, 'precision', 'f32'),
+                                   device_codes=getattr(args, 'device_codes', False))
+            res_dir = os.path.join(args.out, 'result_enc', gop_parallel.gop_name(group))
+            codec.write_gop(enc, res_dir)
+            sync()
+            t2 = time.time()
+            ok = None
+            if args.decode:
+                todo = list(range(len(group))) if decode_frames is None else list(range(min(decode_frames, len(group))))
+                lockstep = int(getattr(args, 'decode_lockstep', 0) or 0)
+                dec = codec.decode_gop(shell(),
+                                       codec.read_gop(res_dir), device, frames=todo, **({'lockstep': lockstep} if lockstep > 0 else {'workers': 4}))
+                ok = all(torch.equal(d, torch.as_tensor(gop.infos[i]['ori']).cuda() +
+                                     torch.tensor(gop.coord_mins[i], device='cuda', dtype=torch.int32))
+                         for d, i in zip(dec, todo))
+                del dec
+            sync()
+            t3 = time.time()
+            stage_s, overfit_s = half['stage_s'], half['overfit_s']
+            result = {'gop': gop_parallel.gop_name(group), 'frames': len(group), 'epochs': half['epochs'], 'loss': half['losses'],
+                      'coded_epoch': info['coded_epoch'], 'coded_loss': info['coded_loss'],
+                      'bpp': enc['bpp'], 'points': enc['point_num'], 'lossless': ok, 'stage_s': stage_s, 'overfit_s': overfit_s,
+                      'encode_s': t2 - t1, 'decode_s': t3 - t2, 'seconds': stage_s + overfit_s + (t3 - t1), 'rank': rank}
+            if 'qat_from' in info:
+                result['qat_from'] = info['qat_from']
+            if getattr(args, 'mid_test', False):
+                result['mid_test'] = half['mid']
+            return result
+        finally:
+            if stream is not None:
+                stream.synchronize()
+            half.clear()
+            del gop, model, shells
+
+    def run_gop(group, epochs, ckpt, staged):
+        half = train_gop(group, epochs, ckpt, staged)
+        model, opt, losses, info = half['model'], half['opt'], half['losses'], half['info']
+        return model, opt, losses, finish_gop(half), info
 
     def first_fn(group, staged=None):
         model, opt, losses, result, info = run_gop(group, args.first_epoch, None, staged)
@@ -274,6 +324,33 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
 
     def other_fn(group, ckpt, staged=None):
         return run_gop(group, args.others_epoch, ckpt, staged)[3]
+
+    # --pipeline: finish_gop(g) on ONE worker thread with a stream of its own while this thread stages and trains the next GOP
+    # (gop_parallel.run_sequence_pipelined has the hand-over rules).  The second job is mostly host work - range coding, files, the
+    # decode check's range decoding - beside about 0.7 ms per frame of codec forward: it hides under the training kernels.
+    finish_stream = None
+
+    def placeholder(half):
+        """The training half of a GOP's result: what GOP 0's checkpoint carries, and what stands in `results` until the finish is in."""
+        return {'gop': gop_parallel.gop_name(half['group']), 'frames': len(half['group']), 'epochs': half['epochs'], 'loss': half['losses'],
+                'coded_epoch': half['info']['coded_epoch'], 'coded_loss': half['info']['coded_loss'], 'stage_s': half['stage_s'],
+                'overfit_s': half['overfit_s'], 'rank': rank}
+
+    def train_first(group, staged=None):
+        half = train_gop(group, args.first_epoch, None, staged)
+        ck = overfit.checkpoint(half['model'], half['opt'], half['info']['coded_epoch'], half['info']['coded_loss'], getattr(args, 'model_bitdepth', 8))
+        ck['result'] = placeholder(half)
+        return ck, half
+
+    def train_other(group, ckpt, staged=None):
+        half = train_gop(group, args.others_epoch, ckpt, staged)
+        return placeholder(half), half
+
+    def finish_in_background(g, half):
+        torch.cuda.set_device(dev_index)       # a new thread starts on device 0, whatever the rank's device is
+        with torch.cuda.stream(finish_stream):
+            finish_stream.wait_event(half['ready'])
+            return finish_gop(half, finish_stream)
 
     prepared = {}
     t_stage0 = time.time()
@@ -289,8 +366,16 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
     work_dir = os.path.join(args.out, 'output')
     try:
         try:
-            results = gop_parallel.run_sequence(groups, work_dir, first_fn, other_fn, rank, world, dist,
-                                                prepare_fn=stage, schedule=schedule, prepared=prepared, done_marker=False)
+            if pipeline:
+                finish_stream = torch.cuda.Stream()      # default priority: the lowest one was measured and is no better (profiles/gop_pipeline.txt)
+                # the last finish is drained in there: its exception raises here, in front of the done marker
+                results, pipe = gop_parallel.run_sequence_pipelined(groups, work_dir, train_first, train_other, finish_in_background, rank, world,
+                                                                    dist, prepare_fn=stage, schedule=schedule, prepared=prepared, done_marker=False)
+                for g, r in results.items():
+                    r['finish_wait_s'] = pipe.blocked.get(g, 0.0)
+            else:
+                results = gop_parallel.run_sequence(groups, work_dir, first_fn, other_fn, rank, world, dist,
+                                                    prepare_fn=stage, schedule=schedule, prepared=prepared, done_marker=False)
         finally:
             if ahead is not None:
                 ahead['pool'].shutdown(wait=True)
@@ -305,10 +390,19 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
     wall = gop_parallel.max_over_ranks(my_wall, dist, 'cuda')
     # phase A = rank 0's GOP 0; phase B = the rest of the wall.  Phase-B efficiency = busy GPU-seconds of the GOPs >= 1
     # over (ranks x phase-B wall): what SURVEY.md section 8e asks to be reported next to the whole-sequence wall.
-    timed = lambda r: r['overfit_s'] + r['encode_s'] + r['decode_s'] + (0.0 if stage_all else r['stage_s'])
+    if pipeline:
+        # Under overlap encode_s and decode_s run beside the next GOP's overfit_s: counting them as busy would exceed the wall.  Busy
+        # is what the MAIN thread spent: stage, overfit and its blocked waits for a finish (all of which fall into phase B: the first
+        # one is the wait for GOP 0's finish after GOP 1 is trained), so phase_b_efficiency stays <= 1; phase A is GOP 0 up to its
+        # checkpoint.
+        timed = lambda r: r['overfit_s'] + (0.0 if stage_all else r['stage_s'])
+        waits = sum(r['finish_wait_s'] for r in results.values())
+    else:
+        timed = lambda r: r['overfit_s'] + r['encode_s'] + r['decode_s'] + (0.0 if stage_all else r['stage_s'])
+        waits = 0.0
     phase_a = timed(results[0]) if 0 in results else 0.0
     phase_a = gop_parallel.max_over_ranks(phase_a, dist, 'cuda')
-    busy_b = gop_parallel.sum_over_ranks(sum(timed(r) for g, r in results.items() if g != 0), dist, 'cuda')
+    busy_b = gop_parallel.sum_over_ranks(sum(timed(r) for g, r in results.items() if g != 0) + waits, dist, 'cuda')
     bits = gop_parallel.sum_over_ranks(sum(r['bpp']['bpp_all'] * r['points'] for r in results.values()), dist, 'cuda')
     points = gop_parallel.sum_over_ranks(sum(r['points'] for r in results.values()), dist, 'cuda')
     lossless = gop_parallel.sum_over_ranks(sum(0 if (r['lossless'] in (True, None)) else 1 for r in results.values()), dist, 'cuda') == 0
@@ -319,6 +413,11 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                'ideal_speedup_bound': round(gop_parallel.ideal_speedup(groups, world), 3),
                'bits_per_point': round(bits / max(points, 1.0), 5), 'lossless': bool(lossless) if args.decode else None,
                'inputs_resident_before_t0': bool(stage_all), 'staging_s_this_rank': round(stage_all_s, 2)}
+    if pipeline:
+        train_s = gop_parallel.sum_over_ranks(sum(r['overfit_s'] for r in results.values()), dist, 'cuda')
+        walls = gop_parallel.sum_over_ranks(my_wall, dist, 'cuda')
+        summary.update({'pipeline': True, 'gpu_train_fraction': round(train_s / max(walls, 1e-9), 4),
+                        'finish_wait_s': round(gop_parallel.sum_over_ranks(waits, dist, 'cuda'), 4)})
     return summary, results
 
 
