@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 18
+#define LINR_ABI_VERSION 19
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -732,6 +732,34 @@ LINR_API int linr_ac_encode_binary_codes_batch(const uint16_t* const* c1_h, cons
 LINR_API size_t linr_ac_codes_sym_words(int64_t n);
 LINR_API int linr_ac_codes(const float* probs, int64_t probs_ld, const float* occ, int32_t occ_ld, int64_t n, uint16_t* c1,
                   int64_t c1_ld, uint32_t* sym, int64_t sym_ld, void* stream);
+
+/* ---- range coder on the DEVICE (csrc/ac_device.hip, body: csrc/rc_body.h) ------------------------------------------------
+ * linr_ac_encode_binary_codes for many independent streams in one call, a wave per stream: only stream bytes and lengths have to
+ * cross to the host.  The bytes are the host coder's bytes.  Stream i codes n symbols whose code values start at element c1_off of
+ * c1_dev (uint16) and whose symbol bits start at bit 0 of word sym_off of sym_dev (bit j & 31 of word sym_off + (j >> 5), ceil(n / 32)
+ * words are read), into out_dev + out_off (a multiple of 4), at most cap bytes: no byte at or behind out_off + cap is written. */
+typedef struct linr_rc_stream {
+    int64_t c1_off, sym_off, n, out_off, cap;
+} linr_rc_stream;
+/* Workspace of linr_rc_encode_codes for n_streams streams whose caps sum to total_cap: the device copy of the table, the scan's
+ * input and temporary storage.  0 for negative arguments. */
+LINR_API size_t linr_rc_encode_ws_bytes(int32_t n_streams, int64_t total_cap);
+/* Three launches on `stream`: rc_encode_k (len_dev[i] = length of stream i in bytes, or LINR_ENOSPC when it needs more than its
+ * cap - the other streams of the call are unaffected), an exclusive scan of the lengths (a negative one counts as 0) into
+ * offsets_dev [n_streams + 1] int64, and rc_pack_k, which gathers the streams into payload_dev: stream i is
+ * payload[offsets[i] .. offsets[i + 1]).  A host then needs two small reads: the offsets, then payload[:offsets[n_streams]].
+ * streams_host is a HOST array; it is checked completely before the first launch and may be freed when the call returns.
+ * LINR_EINVAL, nothing launched: a NULL pointer (with n_streams > 0), n_streams < 0, a stream with n < 0, cap < 0, negative
+ * offsets, n >= 2^27 - 1, out_off not a multiple of 4, an out region that ends behind out_bytes or overlaps another stream's,
+ * payload_bytes below the sum of the caps, ws_bytes below linr_rc_encode_ws_bytes(n_streams, sum of caps).
+ * LINR_EALIGN: out_dev or ws not 8-byte aligned.  n_streams == 0 returns 0 and launches nothing.
+ * The kernels use no LDS and no atomics and belong to no linr_prof_* / linr_debug_poison class (all 24 are taken). */
+LINR_API int linr_rc_encode_codes(const uint16_t* c1_dev, const uint32_t* sym_dev, const linr_rc_stream* streams_host, int32_t n_streams,
+                         uint8_t* out_dev, int64_t out_bytes, int64_t* len_dev, uint8_t* payload_dev, int64_t payload_bytes,
+                         int64_t* offsets_dev, void* ws, size_t ws_bytes, void* stream);
+/* The same body run for ONE stream on the CPU (all pointers HOST pointers; its staging is a 64-word array standing in for the
+ * lanes): arguments and return value as linr_ac_encode_binary_codes.  What the device coder is tested with where there is no GPU. */
+LINR_API int64_t linr_rc_encode_codes_host(const uint16_t* c1_h, const uint32_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap);
 
 /* ---- frame input (host) ----------------------------------------------------------------------------------------------
  * Body of an ASCII PLY (datautils/custom_dataset.py:9-14 read_ply_o3d - open3d's C++ reader - followed by :263-269, which keeps

@@ -15,7 +15,7 @@ import torch
 
 from .function_utils import pack_bitstream, unpack_bitstream
 from .model_codec import Model_Estimate
-from .model_core import codes_word_off, encode_streams, encode_streams_codes
+from .model_core import DeviceCoderSet, codes_word_off, encode_streams, encode_streams_codes
 from .module_utils import octree_level_obj, qscTensor, unique_sorted  # noqa: F401
 
 # The probabilities the range coder sees must be reproduced BIT FOR BIT by the decoder, so the fp32 evaluation order of the
@@ -53,13 +53,89 @@ def model_shape(model):
     return {'scale_num': int(model.scale_num), 'block_layers': int(model.block_layers), 'hidden_channel_conv': int(model.hidden)}
 
 
-def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32', device_codes=False):
+def _code_frames_device(coded_model, gop, coder_group):
+    """The frames' streams from the device range coder (linr_rc_encode_codes), coder_group frames per call.  The forwards stay on the
+    caller's stream and write their code values and symbol planes (model.frame_codes) into group-wide buffers; the group is coded on a
+    second stream behind an event, so group g is coded under the forwards of group g + 1.  Two buffer sets alternate: the forwards
+    of group g + 2 wait (on the device) for the coding of group g, and the host has read group g's payload before that set is
+    launched again.  Returns (per frame the per-scale pack_bitstream containers, per frame the bits estimate on the device)."""
+    frames = gop.frames
+    dev = frames[0].device
+    groups = [frames[i:i + coder_group] for i in range(0, len(frames), coder_group)]
+    plans = []                       # per group: per frame (c1 base, rows, word base, words), the stream table, sizes
+    for group in groups:
+        cb = wb = 0
+        parts, desc = [], []
+        for f in group:
+            woff = codes_word_off(f.row_off)
+            rows, words = f.rows, int(woff[-1])
+            parts.append((cb, rows, wb, words))
+            for i in range(f.n_scales):
+                a, n = int(f.row_off[i]), int(f.row_off[i + 1] - f.row_off[i])
+                desc += [(cb + k * rows + a, wb + k * words + int(woff[i]), n) for k in range(8)]
+            cb, wb = cb + 8 * rows, wb + 8 * words
+        plans.append((parts, np.asarray(desc, dtype=np.int64).reshape(-1, 3), cb, wb))
+    n_sets = min(2, len(groups))
+    max_c1, max_w = max(1, max(p[2] for p in plans)), max(1, max(p[3] for p in plans))
+    max_n, max_cap = max(len(p[1]) for p in plans), max(DeviceCoderSet.table(p[1])[1] for p in plans)
+    sets = [(torch.empty(max_c1, dtype=torch.uint16, device=dev), torch.empty(max_w, dtype=torch.uint32, device=dev),
+             DeviceCoderSet(max_n, max_cap, dev)) for _ in range(n_sets)]
+    main = torch.cuda.current_stream()
+    coder_stream = torch.cuda.Stream(device=dev)
+    streams, bits_dev = [None] * len(groups), []
+    for g, (group, (parts, desc, _, _)) in enumerate(zip(groups, plans)):
+        c1, sym, coder = sets[g % n_sets]
+        if g >= n_sets:
+            main.wait_event(coder.coded)                     # group g - 2 has read c1 / sym
+        for f, (cb, rows, wb, words) in zip(group, parts):
+            _, _, bits = coded_model.frame_codes(f, out=(c1[cb:cb + 8 * rows].view(8, rows), sym[wb:wb + 8 * words].view(8, words)))
+            bits_dev.append(bits)
+        ready = torch.cuda.Event()
+        ready.record(main)
+        if g >= n_sets:
+            streams[g - n_sets] = coder.collect() if len(plans[g - n_sets][1]) else []   # ... and its payload is on the host before the set is coded into again
+        if len(desc):
+            with torch.cuda.stream(coder_stream):
+                coder_stream.wait_event(ready)
+                coder.launch(c1, sym, desc)
+    for g in range(max(0, len(groups) - n_sets), len(groups)):
+        streams[g] = sets[g % n_sets][2].collect() if len(plans[g][1]) else []
+    frames_bytes = []
+    for group, got in zip(groups, streams):
+        at = 0
+        for f in group:
+            frames_bytes.append([pack_bitstream(got[at + 8 * i:at + 8 * i + 8]) for i in range(f.n_scales)])
+            at += 8 * f.n_scales
+    return frames_bytes, bits_dev
+
+
+def _gop_result(gop, comp, side_info, frames_bytes, bits_dev):
+    bits_est = float(torch.stack(bits_dev).sum())
+    low = enc_all_frame_low_xyz(gop)
+    points = sum(gop.point_nums)
+    occ_bits = 8 * sum(len(b) for fb in frames_bytes for b in fb)
+    return {'frames': frames_bytes, 'model_bin': comp['final_bytes'], 'side_info': side_info, 'low_enc_bytes': low,
+            'point_num': points, 'bits_est': bits_est,
+            # the five one-byte side-info fields this codec adds (arith_version, precision, scale_num, block_layers,
+            # hidden_channel_conv: EXTRA_SIDE_BITS = 40) are counted with the model
+            'bpp': {'point_bpp': occ_bits / points, 'model_bpp': (comp['bit_real'] + EXTRA_SIDE_BITS) / points,
+                    'xyzlow_bpp': len(low) * 8 / points,
+                    'bpp_all': (occ_bits + comp['bit_real'] + EXTRA_SIDE_BITS + len(low) * 8) / points}}       # test_utils.py:146-157
+
+
+def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32', device_codes=False, device_coder=False,
+               coder_group=8):
     """encoder.encode_one_gop: quantise the model, then per frame ONE forward over all scales and 8 x scales
     independent arithmetic-coded streams (thread pool).  precision='bf16': the forward runs on the bf16 / uint8-weight
     executor (BASELINE config[4]); the choice is recorded in side_info so that the decoder reproduces it.
     device_codes=True: the coder's inputs are prepared on the GPU (model.frame_codes): 16-bit code values and one symbol bit cross to
     the host per symbol instead of an fp32 probability and a byte, and the coder threads read the code values instead of computing
-    them.  The streams are byte for byte those of the default path, so nothing about it is recorded."""
+    them.  The streams are byte for byte those of the default path, so nothing about it is recorded.
+    device_coder=True (implies device codes): the range coder itself runs on the GPU, coder_group (1..64) frames per call
+    (_code_frames_device); only stream bytes and lengths cross to the host and no coder thread is started.  Again the same bytes,
+    again nothing recorded."""
+    if device_coder and not 1 <= int(coder_group) <= 64:
+        raise ValueError('coder_group must be in 1..64, got %r' % (coder_group,))
     if n_threads is None:
         n_threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else 8))
     comp = Model_Estimate().compress_model(model, bitdepth, True, model_ori)
@@ -77,6 +153,9 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     # in EXTRA_SIDE_BITS, ignored by the decoders
     if getattr(model, 'qat_epochs', 0):
         side_info['qat_epochs'] = int(model.qat_epochs)
+    if device_coder:
+        frames_bytes, bits_dev = _code_frames_device(coded_model, gop, int(coder_group))
+        return _gop_result(gop, comp, side_info, frames_bytes, bits_dev)
     # Pipeline: the GPU forward + D2H of frame i+1 runs while host workers range-code earlier frames (the coder's C call
     # releases the GIL).  A frame has 8 x scales independent streams, but the 8 streams of its finest scale carry 73 % of the
     # symbols, so one frame keeps only ~8 threads busy: TWO frames are coded concurrently, each on half of the threads
@@ -148,17 +227,7 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
         while pending:
             hand_over(pending.pop(0), coder)
         frames_bytes = [j.result() for j in jobs]
-    bits_est = float(torch.stack(bits_dev).sum())
-    low = enc_all_frame_low_xyz(gop)
-    points = sum(gop.point_nums)
-    occ_bits = 8 * sum(len(b) for fb in frames_bytes for b in fb)
-    return {'frames': frames_bytes, 'model_bin': comp['final_bytes'], 'side_info': side_info, 'low_enc_bytes': low,
-            'point_num': points, 'bits_est': bits_est,
-            # the five one-byte side-info fields this codec adds (arith_version, precision, scale_num, block_layers,
-            # hidden_channel_conv: EXTRA_SIDE_BITS = 40) are counted with the model
-            'bpp': {'point_bpp': occ_bits / points, 'model_bpp': (comp['bit_real'] + EXTRA_SIDE_BITS) / points,
-                    'xyzlow_bpp': len(low) * 8 / points,
-                    'bpp_all': (occ_bits + comp['bit_real'] + EXTRA_SIDE_BITS + len(low) * 8) / points}}       # test_utils.py:146-157
+    return _gop_result(gop, comp, side_info, frames_bytes, bits_dev)
 
 
 def decode_one_frame(model, frame_enc_bytes, xyz_low):

@@ -1,0 +1,174 @@
+// The range coder on the device: linr_ac_encode_binary_codes for many streams at once, a wave per stream.  A stream is serial by its
+// format, the streams of a group of frames (8 stages x scales x frames) are independent and outnumber the SIMDs of the device, so a
+// group is coded in about the time of its longest stream and only stream bytes and lengths cross to the host.  The coder itself is
+// csrc/rc_body.h, the same text that linr_rc_encode_codes_host runs on the CPU; this file adds where a wave takes its symbols from
+// and where its finished words go.
+#include "common.h"
+#include "rc_body.h"
+#include <hipcub/hipcub.hpp>
+#include <algorithm>
+#include <vector>
+
+namespace {
+
+// Symbols of a wave: per chunk of 64, lane l holds c1[base + l] (one coalesced 128-byte load) and the chunk's two symbol words
+// are loaded uniformly.  chunk(base) makes the chunk loaded one call earlier current and issues the loads of the one behind it,
+// so they are under way while the current chunk is walked.  The walk reads symbol i's code value with a readlane: i, and with it
+// everything the coder computes from it, is uniform.
+struct RcWaveSrc {
+    const uint16_t* c; const uint32_t* w; int64_t n; int lane;
+    uint32_t cur = 0, nxt = 0;             // per lane
+    uint64_t bits = 0, nbits = 0;          // uniform
+    __device__ inline void load(int64_t base) {
+        nxt = 0; nbits = 0;
+        if (base < n) {
+            if (base + lane < n) nxt = c[base + lane];
+            const int64_t i = base >> 5;
+            nbits = w[i];
+            if (base + 32 < n) nbits |= (uint64_t)w[i + 1] << 32;
+        }
+    }
+    __device__ inline void chunk(int64_t base) {
+        cur = nxt; bits = nbits;
+        load(base + RC_CHUNK);
+    }
+    __device__ inline uint32_t c1(int i) const { return (uint32_t)__builtin_amdgcn_readlane((int)cur, i); }
+    __device__ inline uint32_t mask(int i) const { return 0u - (uint32_t)((bits >> i) & 1u); }
+};
+
+// Finished words of a wave: lane j holds word j of the current 64-word block, a full block leaves as one coalesced
+// 256-byte store, the last one lane-masked with its 1..3 odd bytes from lane 0.  pos, k and over are uniform.  Nothing is stored
+// at or behind out + cap: a block that would cross it raises `over` instead (the stream needs more than its cap then, whatever follows).
+struct RcWaveOut {
+    uint8_t* out; int64_t cap; int lane;
+    uint32_t stage = 0;                    // per lane
+    int k = 0; int64_t pos = 0; bool over = false;
+    __device__ inline bool full() const { return over; }
+    __device__ inline void word(uint32_t v) {
+        stage = lane == k ? v : stage;          // (this compiler has no writelane builtin; a compare and a select per finished word)
+        if (++k == RC_STAGE_WORDS) {
+            if (!over && pos + 4 * RC_STAGE_WORDS <= cap) reinterpret_cast<uint32_t*>(out + pos)[lane] = stage; else over = true;
+            pos += 4 * RC_STAGE_WORDS;
+            k = 0;
+        }
+    }
+    __device__ inline void tail(uint32_t v, int nbytes) {
+        if (over || pos + 4 * k + nbytes > cap) { over = true; return; }
+        if (lane < k) reinterpret_cast<uint32_t*>(out + pos)[lane] = stage;
+        if (lane < nbytes) out[pos + 4 * k + lane] = (uint8_t)(v >> (8 * lane));
+    }
+};
+
+// One wave per stream, block = one wave, blockIdx.x = stream.  No LDS, no atomics; len[stream] has one writer.
+__global__ __launch_bounds__(LINR_WAVE) void rc_encode_k(const uint16_t* __restrict__ c1, const uint32_t* __restrict__ sym,
+                                                         const linr_rc_stream* __restrict__ tab, uint8_t* __restrict__ out,
+                                                         int64_t* __restrict__ len) {
+    const linr_rc_stream d = tab[blockIdx.x];
+    const int lane = threadIdx.x;
+    RcWaveSrc src{c1 + d.c1_off, sym + d.sym_off, d.n, lane};
+    RcWaveOut o{out + d.out_off, d.cap, lane};
+    src.load(0);
+    // vmcnt(0) here, once: the first chunk has arrived before the loop, so inside it the compiler needs no wait between issuing the
+    // next chunk's load and walking the current one (without this it placed a vmcnt(0) there, for the first pass's sake)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    const int64_t bytes = rc_encode(src, d.n, o);
+    if (lane == 0) len[blockIdx.x] = o.over ? (int64_t)LINR_ENOSPC : bytes;
+}
+
+// The table reaches the device as kernel arguments, RC_TAB_BATCH descriptors per launch: the runtime copies them when the launch is
+// queued, so the caller's array is free when the entry returns, and nothing waits for the stream (a copy from pageable memory may).
+#define RC_TAB_BATCH 96                     // 96 x 40 bytes = 3840 of the 4096 bytes of kernel arguments
+struct RcTabBatch { linr_rc_stream d[RC_TAB_BATCH]; };
+__global__ __launch_bounds__(LINR_BLOCK) void rc_table_k(RcTabBatch b, int32_t count, linr_rc_stream* __restrict__ tab) {
+    const int t = blockIdx.x * LINR_BLOCK + threadIdx.x;          // one 8-byte field each
+    if (t < count * 5) reinterpret_cast<int64_t*>(tab)[t] = reinterpret_cast<const int64_t*>(b.d)[t];
+}
+
+// the scan's input: a stream without space counts as empty; one more element so that the scan's last output is the total
+__global__ void rc_count_k(const int64_t* __restrict__ len, int32_t n_streams, int64_t* __restrict__ cnt) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= n_streams) cnt[i] = (i < n_streams && len[i] > 0) ? len[i] : 0;
+}
+
+// One block per stream: its len bytes to payload + offsets[stream].  offsets[i] + len <= sum of the caps <= payload_bytes.
+__global__ __launch_bounds__(LINR_BLOCK) void rc_pack_k(const uint8_t* __restrict__ out, const linr_rc_stream* __restrict__ tab,
+                                                        const int64_t* __restrict__ len, const int64_t* __restrict__ offsets,
+                                                        uint8_t* __restrict__ payload) {
+    const int64_t m = len[blockIdx.x];
+    const uint8_t* src = out + tab[blockIdx.x].out_off;
+    uint8_t* dst = payload + offsets[blockIdx.x];
+    for (int64_t b = threadIdx.x; b < m; b += LINR_BLOCK) dst[b] = src[b];
+}
+
+struct RcWs { size_t tab, cnt, cub, cub_bytes, total; };
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+RcWs rc_ws(int32_t n_streams) {
+    RcWs w;
+    w.cub_bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, w.cub_bytes, (const int64_t*)nullptr, (int64_t*)nullptr, n_streams + 1);
+    w.tab = 0;
+    w.cnt = up256(sizeof(linr_rc_stream) * (size_t)n_streams);
+    w.cub = w.cnt + up256(sizeof(int64_t) * ((size_t)n_streams + 1));
+    w.total = w.cub + up256(w.cub_bytes);
+    return w;
+}
+
+}  // namespace
+
+extern "C" size_t linr_rc_encode_ws_bytes(int32_t n_streams, int64_t total_cap) {
+    if (n_streams < 0 || total_cap < 0) return 0;
+    return rc_ws(n_streams).total;
+}
+
+extern "C" int linr_rc_encode_codes(const uint16_t* c1_dev, const uint32_t* sym_dev, const linr_rc_stream* streams_host, int32_t n_streams,
+                                    uint8_t* out_dev, int64_t out_bytes, int64_t* len_dev, uint8_t* payload_dev, int64_t payload_bytes,
+                                    int64_t* offsets_dev, void* ws, size_t ws_bytes, void* stream) {
+    if (n_streams < 0 || out_bytes < 0 || payload_bytes < 0) return LINR_EINVAL;
+    if (n_streams == 0) return 0;
+    if (!c1_dev || !sym_dev || !streams_host || !out_dev || !len_dev || !payload_dev || !offsets_dev || !ws) return LINR_EINVAL;
+    int64_t total_cap = 0;
+    std::vector<std::pair<int64_t, int64_t>> regions;
+    regions.reserve((size_t)n_streams);
+    for (int32_t i = 0; i < n_streams; ++i) {
+        const linr_rc_stream& d = streams_host[i];
+        if (d.n < 0 || d.cap < 0 || d.c1_off < 0 || d.sym_off < 0 || d.out_off < 0 || !linr_rows_fit32(d.n)) return LINR_EINVAL;
+        if ((d.out_off & 3) || d.out_off > out_bytes || d.cap > out_bytes - d.out_off) return LINR_EINVAL;
+        total_cap += d.cap;
+        if (total_cap > payload_bytes) return LINR_EINVAL;
+        if (d.cap > 0) regions.emplace_back(d.out_off, d.out_off + d.cap);
+    }
+    std::sort(regions.begin(), regions.end());
+    for (size_t i = 1; i < regions.size(); ++i)
+        if (regions[i].first < regions[i - 1].second) return LINR_EINVAL;
+    const RcWs w = rc_ws(n_streams);
+    if (ws_bytes < w.total) return LINR_EINVAL;
+    if (((uintptr_t)out_dev & 7) || ((uintptr_t)ws & 7)) return LINR_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)ws;
+    linr_rc_stream* tab = (linr_rc_stream*)(base + w.tab);
+    int64_t* cnt = (int64_t*)(base + w.cnt);
+    int rc;
+    for (int32_t i = 0; i < n_streams; i += RC_TAB_BATCH) {
+        RcTabBatch b;
+        const int32_t m = std::min<int32_t>(RC_TAB_BATCH, n_streams - i);
+        std::copy(streams_host + i, streams_host + i + m, b.d);
+        std::fill(b.d + m, b.d + RC_TAB_BATCH, linr_rc_stream{0, 0, 0, 0, 0});
+        rc_table_k<<<dim3(linr_grid(5 * RC_TAB_BATCH, LINR_BLOCK)), dim3(LINR_BLOCK), 0, s>>>(b, m, tab + i);
+        if ((rc = linr_launch_rc())) return rc;
+    }
+    rc_encode_k<<<dim3((unsigned)n_streams), dim3(LINR_WAVE), 0, s>>>(c1_dev, sym_dev, tab, out_dev, len_dev);
+    if ((rc = linr_launch_rc())) return rc;
+    rc_count_k<<<dim3(linr_grid((int64_t)n_streams + 1, LINR_BLOCK)), dim3(LINR_BLOCK), 0, s>>>(len_dev, n_streams, cnt);
+    if ((rc = linr_launch_rc())) return rc;
+    size_t cb = w.cub_bytes;
+    if ((rc = linr_hip_rc(hipcub::DeviceScan::ExclusiveSum(base + w.cub, cb, cnt, offsets_dev, n_streams + 1, s)))) return rc;
+    rc_pack_k<<<dim3((unsigned)n_streams), dim3(LINR_BLOCK), 0, s>>>(out_dev, tab, len_dev, offsets_dev, payload_dev);
+    return linr_launch_rc();
+}
+
+extern "C" int64_t linr_rc_encode_codes_host(const uint16_t* c1_h, const uint32_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap) {
+    if (n < 0 || cap < 0 || (n > 0 && (!c1_h || !sym_h)) || (cap > 0 && !out_h)) return LINR_EINVAL;
+    return rc_encode_host(c1_h, sym_h, n, out_h, cap);
+}

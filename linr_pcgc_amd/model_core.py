@@ -274,16 +274,23 @@ class LINR_PCGC_Model(nn.Module):
         return probs, bits
 
     @torch.no_grad()
-    def frame_codes(self, frame, precision=None):
+    def frame_codes(self, frame, precision=None, out=None):
         """frame_probs, then the range coder's inputs on the GPU (linr_ac_codes, csrc/ac_codes.hip) on the current stream:
         c1 uint16 [8, rows], the code value of every probability; sym uint32 [8, words], the occupancy as bit planes; bits float64[1].
         The coder cuts a frame into per-scale streams and the scales' row offsets are no multiples of 32, so every scale gets words of
-        its own: scale i's symbols are bits 0 .. n_i - 1 of the words from codes_word_off(frame.row_off)[i] on (one launch per scale)."""
+        its own: scale i's symbols are bits 0 .. n_i - 1 of the words from codes_word_off(frame.row_off)[i] on (one launch per scale).
+        out=(c1, sym): contiguous tensors of those shapes and types to write into (a frame's part of a group-wide buffer)."""
         probs, bits = self.frame_probs(frame, precision)
         woff = codes_word_off(frame.row_off)
         rows, words = frame.rows, int(woff[-1])
-        c1 = torch.empty((8, rows), dtype=torch.uint16, device=frame.device)
-        sym = torch.empty((8, words), dtype=torch.uint32, device=frame.device)
+        if out is None:
+            c1 = torch.empty((8, rows), dtype=torch.uint16, device=frame.device)
+            sym = torch.empty((8, words), dtype=torch.uint32, device=frame.device)
+        else:
+            c1, sym = out
+            if (c1.dtype, tuple(c1.shape), sym.dtype, tuple(sym.shape)) != (torch.uint16, (8, rows), torch.uint32, (8, words)) or \
+                    not (c1.is_contiguous() and sym.is_contiguous()):
+                raise ValueError('frame_codes: out must be contiguous uint16 [8, %d] and uint32 [8, %d]' % (rows, words))
         L, st = _lib.lib(), _lib.current_stream_handle()
         for i in range(frame.n_scales):
             a, n = int(frame.row_off[i]), int(frame.row_off[i + 1] - frame.row_off[i])
@@ -489,6 +496,84 @@ def encode_streams_codes(c1s, syms, ns, n_threads=8):
     _lib.check(_lib.lib().linr_ac_encode_binary_codes_batch(arr_c, arr_s, arr_n, n, arr_o, arr_cap, arr_l, n_threads),
                'linr_ac_encode_binary_codes_batch')
     return [outs[i][:arr_l[i]].tobytes() for i in range(n)]
+
+
+class DeviceCoderSet:
+    """One buffer set of the device range coder (linr_rc_encode_codes, csrc/ac_device.hip): stream regions, lengths, the dense payload
+    and its offsets on the device, pinned copies of the last two, and a stream of its own for the two small reads a call needs, so
+    that reading one set never queues behind the coding of another.  launch() on the current stream, collect() anywhere later."""
+
+    def __init__(self, n_streams, total_cap, device):
+        L = _lib.lib()
+        self.n_max, self.cap_max = int(n_streams), max(8, int(total_cap))
+        self.out = torch.empty(self.cap_max, dtype=torch.uint8, device=device)
+        self.payload = torch.empty(self.cap_max, dtype=torch.uint8, device=device)
+        self.len = torch.empty(self.n_max, dtype=torch.int64, device=device)
+        self.offsets = torch.empty(self.n_max + 1, dtype=torch.int64, device=device)
+        self.ws = _lib.scratch(L.linr_rc_encode_ws_bytes(self.n_max, self.cap_max), device)
+        self.offsets_pin = torch.empty(self.n_max + 1, dtype=torch.int64, pin_memory=True)
+        self.payload_pin = torch.empty(self.cap_max, dtype=torch.uint8, pin_memory=True)
+        self.read_stream = torch.cuda.Stream(device=device)
+        self.coded, self.read = torch.cuda.Event(), torch.cuda.Event()
+        self.n = 0
+
+    @staticmethod
+    def table(descriptors):
+        """int64 [n, 5] rows {c1 offset, symbol word offset, n, out offset, cap} from rows {c1 offset, symbol word offset, n}: cap is the
+        host path's 2 n + 64, the regions follow each other on 4-byte boundaries.  Returns (table, bytes of all regions)."""
+        d = np.asarray(descriptors, dtype=np.int64).reshape(-1, 3)
+        tab = np.empty((len(d), 5), dtype=np.int64)
+        tab[:, :3] = d
+        tab[:, 4] = 2 * d[:, 2] + 64
+        ends = np.cumsum((tab[:, 4] + 3) & ~3)
+        tab[:, 3] = ends - ((tab[:, 4] + 3) & ~3)
+        return tab, int(ends[-1]) if len(d) else 0
+
+    def launch(self, c1, sym, descriptors):
+        """Codes the streams {c1 element offset, symbol word offset, n} of c1 (uint16) / sym (uint32) on the current stream."""
+        tab, total = self.table(descriptors)
+        n = len(tab)
+        if n == 0 or n > self.n_max or total > self.cap_max:
+            raise ValueError('DeviceCoderSet: %d streams / %d bytes in a set made for %d / %d' % (n, total, self.n_max, self.cap_max))
+        if c1.dtype != torch.uint16 or sym.dtype != torch.uint32 or not (c1.is_contiguous() and sym.is_contiguous()):
+            raise ValueError('DeviceCoderSet: c1 must be contiguous uint16, sym contiguous uint32')
+        if (tab[:, :3] < 0).any() or (tab[:, 0] + tab[:, 2] > c1.numel()).any() or (tab[:, 1] + (tab[:, 2] + 31) // 32 > sym.numel()).any():
+            raise ValueError('DeviceCoderSet: a stream reads outside c1 or sym')
+        _lib.check(_lib.lib().linr_rc_encode_codes(c1.data_ptr(), sym.data_ptr(), tab.ctypes.data, n, self.out.data_ptr(), self.out.numel(),
+                                                   self.len.data_ptr(), self.payload.data_ptr(), self.payload.numel(), self.offsets.data_ptr(),
+                                                   self.ws.data_ptr(), self.ws.numel(), _lib.current_stream_handle()), 'linr_rc_encode_codes')
+        self.coded.record(torch.cuda.current_stream())
+        with torch.cuda.stream(self.read_stream):
+            self.read_stream.wait_event(self.coded)
+            self.offsets_pin[:n + 1].copy_(self.offsets[:n + 1], non_blocking=True)
+            self.read.record(self.read_stream)
+        self.n = n
+
+    def collect(self):
+        """The streams of the last launch as a list of bytes: waits for it, reads payload[:total]."""
+        n = self.n
+        self.read.synchronize()
+        offs = self.offsets_pin[:n + 1].numpy().copy()
+        total = int(offs[-1])
+        if (np.diff(offs) < 1).any() or total > self.cap_max:          # every stream has at least one byte; LINR_ENOSPC counts 0
+            raise _lib.LinrError('linr_rc_encode_codes: a stream did not fit its region')
+        with torch.cuda.stream(self.read_stream):
+            self.payload_pin[:total].copy_(self.payload[:total], non_blocking=True)
+        self.read_stream.synchronize()
+        data = self.payload_pin[:total].numpy().tobytes()
+        return [data[int(offs[i]):int(offs[i + 1])] for i in range(n)]
+
+
+def encode_streams_device(c1, sym, descriptors):
+    """encode_streams_codes on the GPU (linr_rc_encode_codes): c1 uint16 and sym uint32 device tensors, descriptors rows of
+    {c1 element offset, symbol word offset, n}; stream i's symbols are bits 0 .. n - 1 from its word offset on.  Returns the streams
+    as a list of bytes, byte for byte what the host coder gives."""
+    d = np.asarray(descriptors, dtype=np.int64).reshape(-1, 3)
+    if len(d) == 0:
+        return []
+    coder = DeviceCoderSet(len(d), DeviceCoderSet.table(d)[1], c1.device)
+    coder.launch(c1.reshape(-1), sym.reshape(-1), d)
+    return coder.collect()
 
 
 class FlatAdam:

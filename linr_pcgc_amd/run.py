@@ -56,6 +56,12 @@ def parse(argv=None):
     ap.add_argument('--device-codes', '--device_codes', dest='device_codes', action='store_true',
                     help="the range coder's 16-bit code values and symbol bits are computed on the GPU (linr_ac_codes): 17 bits per symbol "
                          'cross to the host instead of 40; the streams are byte for byte those of the default path')
+    ap.add_argument('--device-coder', '--device_coder', dest='device_coder', action='store_true',
+                    help='the range coder itself runs on the GPU (linr_rc_encode_codes, a wave per stream, --coder-group frames per call): only '
+                         'stream bytes and lengths cross to the host and no coder thread is started; implies --device-codes; the streams are '
+                         'byte for byte those of the default path')
+    ap.add_argument('--coder-group', '--coder_group', dest='coder_group', type=int, default=8,
+                    help='with --device-coder: frames coded per call (1..64)')
     ap.add_argument('--ply-parse', '--ply_parse', dest='ply_parse', default='host', choices=['host', 'device'],
                     help='with --input-glob / --ori_dir: PLY frames are parsed by the host parser on a thread pool (default) or on the GPU '
                          '(ply.read_many_device, on the staging stream); the encoded files are byte for byte the same')
@@ -278,7 +284,8 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
             t1 = time.time()
             enc = codec.encode_gop(model, shell(), gop,
                                    getattr(args, 'model_bitdepth', 8), precision=getattr(args, 'precision', 'f32'),
-                                   device_codes=getattr(args, 'device_codes', False))
+                                   device_codes=getattr(args, 'device_codes', False),
+                                   device_coder=getattr(args, 'device_coder', False), coder_group=getattr(args, 'coder_group', 8))
             res_dir = os.path.join(args.out, 'result_enc', gop_parallel.gop_name(group))
             codec.write_gop(enc, res_dir)
             sync()
