@@ -735,7 +735,7 @@ LINR_API int linr_ac_codes(const float* probs, int64_t probs_ld, const float* oc
 
 /* ---- range coder on the DEVICE (csrc/ac_device.hip, body: csrc/rc_body.h) ------------------------------------------------
  * linr_ac_encode_binary_codes for many independent streams in one call, a wave per stream: only stream bytes and lengths have to
- * cross to the host.  The bytes are the host coder's bytes.  Stream i codes n symbols whose code values start at element c1_off of
+ * cross to the host.  The bytes are the host coder's bytes: both run the one body of csrc/rc_body.h.  Stream i codes n symbols whose code values start at element c1_off of
  * c1_dev (uint16) and whose symbol bits start at bit 0 of word sym_off of sym_dev (bit j & 31 of word sym_off + (j >> 5), ceil(n / 32)
  * words are read), into out_dev + out_off (a multiple of 4), at most cap bytes: no byte at or behind out_off + cap is written. */
 typedef struct linr_rc_stream {
@@ -757,9 +757,6 @@ LINR_API size_t linr_rc_encode_ws_bytes(int32_t n_streams, int64_t total_cap);
 LINR_API int linr_rc_encode_codes(const uint16_t* c1_dev, const uint32_t* sym_dev, const linr_rc_stream* streams_host, int32_t n_streams,
                          uint8_t* out_dev, int64_t out_bytes, int64_t* len_dev, uint8_t* payload_dev, int64_t payload_bytes,
                          int64_t* offsets_dev, void* ws, size_t ws_bytes, void* stream);
-/* The same body run for ONE stream on the CPU (all pointers HOST pointers; its staging is a 64-word array standing in for the
- * lanes): arguments and return value as linr_ac_encode_binary_codes.  What the device coder is tested with where there is no GPU. */
-LINR_API int64_t linr_rc_encode_codes_host(const uint16_t* c1_h, const uint32_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap);
 
 /* ---- frame input (host) ----------------------------------------------------------------------------------------------
  * Body of an ASCII PLY (datautils/custom_dataset.py:9-14 read_ply_o3d - open3d's C++ reader - followed by :263-269, which keeps

@@ -189,7 +189,6 @@ _PROTOS = {
     'linr_ac_codes': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     'linr_rc_encode_ws_bytes': (c_size, [c_i32, c_i64]),
     'linr_rc_encode_codes': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    'linr_rc_encode_codes_host': (c_i64, [c_ptr, c_ptr, c_i64, c_ptr, c_i64]),
     'linr_ply_format_text_bytes': (c_size, [c_i64]),
     'linr_ply_format_ws_bytes': (c_size, [c_i64]),
     'linr_ply_format_ascii': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_size, c_ptr, c_size, c_ptr, c_ptr]),
@@ -235,8 +234,7 @@ class _Poisoned:
     """LINR_DEBUG_POISON=1 (test aid, tools/README.md): every GPU entry point is called with the LDS and vector registers of all
     CUs freshly filled with a NaN pattern (linr_debug_poison_now in front of it, linr_debug_poison(all classes) for the launches
     inside the executors).  The test suite must pass unchanged under it: no kernel may read on-chip state it did not write."""
-    _HOST = ('linr_ac_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host',
-             'linr_rc_encode_codes_host')
+    _HOST = ('linr_ac_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host')
 
     def __init__(self, handle):
         self._h = handle

@@ -123,6 +123,13 @@ def _gop_result(gop, comp, side_info, frames_bytes, bits_dev):
                     'bpp_all': (occ_bits + comp['bit_real'] + EXTRA_SIDE_BITS + len(low) * 8) / points}}       # test_utils.py:146-157
 
 
+def _coder_threads(n_threads):
+    """The host threads of the range coders: as asked, by default the cores this process may use, at most 16."""
+    if n_threads is not None:
+        return n_threads
+    return max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else 8))
+
+
 def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32', device_codes=False, device_coder=False,
                coder_group=8):
     """encoder.encode_one_gop: quantise the model, then per frame ONE forward over all scales and 8 x scales
@@ -136,8 +143,7 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     again nothing recorded."""
     if device_coder and not 1 <= int(coder_group) <= 64:
         raise ValueError('coder_group must be in 1..64, got %r' % (coder_group,))
-    if n_threads is None:
-        n_threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else 8))
+    n_threads = _coder_threads(n_threads)
     comp = Model_Estimate().compress_model(model, bitdepth, True, model_ori)
     coded_model = comp['new_model']                      # the de-quantised model is what codes the geometry
     coded_model.inference_precision = precision
@@ -363,8 +369,7 @@ def _map_on_streams(fn, items, workers):
 
 
 def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads):
-    if n_threads is None:
-        n_threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else 8))
+    n_threads = _coder_threads(n_threads)
     groups = lockstep_groups(todo, {i: len(enc['frames'][i]) for i in set(todo)}, lockstep)
     workers = max(1, min(int(workers), len(groups)))
     per_group = max(1, n_threads // workers)

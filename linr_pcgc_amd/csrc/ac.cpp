@@ -18,6 +18,7 @@
 #include <emmintrin.h>
 #endif
 #include "../../include/linr_hip.h"
+#include "rc_body.h"
 
 namespace {
 
@@ -130,28 +131,9 @@ inline uint32_t binary_c1(float p) {
 // (high = low - 1 + span is unchanged), symbol 0: high = low + t - 1.  Renormalisation shifts all leading bits on which
 // low and high agree at once (torchac emits them one by one; the first one is followed by the pending complement bits),
 // c1 is computed for a block of symbols at a time (vectorisable, off the serial dependency chain), and the symbol
-// selects are branch-free (the symbol is the one thing the branch predictor cannot know).
+// selects are branch-free (the symbol is the one thing the branch predictor cannot know).  The encoder's body is csrc/rc_body.h,
+// which the device coder runs too; this file feeds it and keeps the decoder.
 namespace {
-
-struct BitSinkFast {
-    uint8_t* out; int64_t cap; int64_t len = 0; uint64_t acc = 0; int nacc = 0;       // nacc < 8 between calls
-    BitSinkFast(uint8_t* o, int64_t c) : out(o), cap(c) {}
-    inline void put_bits(uint32_t v, int n) {             // n in 0..32, v < 2^n
-        acc = (acc << n) | v;
-        nacc += n;
-        while (nacc >= 8) {
-            nacc -= 8;
-            if (len < cap) out[len] = (uint8_t)(acc >> nacc);
-            ++len;
-        }
-    }
-    inline void put_run(uint32_t bit, uint64_t count) {
-        const uint32_t word = bit ? 0xFFFFFFFFu : 0u;
-        while (count >= 32) { put_bits(word, 32); count -= 32; }
-        if (count) put_bits(word >> (32 - (int)count), (int)count);
-    }
-    inline void finish() { if (nacc) put_bits(0, 8 - nacc); }
-};
 
 constexpr int AC_CHUNK = 256;
 
@@ -169,7 +151,7 @@ inline void c1_block(const float* p, int n, uint32_t* c1) {
     for (; i < n; ++i) c1[i] = binary_c1(p[i]);
 }
 
-// Where the serial loops take their code values and symbols from.  A source hands out the code values of symbols
+// Where the decoder's serial loop takes its code values from.  A source hands out the code values of symbols
 // [base, base + m), m <= AC_CHUNK: from probabilities they are computed into a block (c1_block), ready-made ones (csrc/ac_codes.hip
 // computes them on the device) are read in place.
 struct CodesFromProbs {
@@ -180,76 +162,36 @@ struct CodesReady {
     const uint16_t* c;
     inline const uint16_t* block(int64_t base, int) const { return c + base; }
 };
-struct SymBytes {            // one byte per symbol, non-zero = 1
-    const uint8_t* s;
-    inline uint32_t mask(int64_t i) const { return s[i] ? 0xFFFFFFFFu : 0u; }
-};
-struct SymBits {             // bit i & 31 of word i >> 5
-    const uint32_t* w;
-    inline uint32_t mask(int64_t i) const { return 0u - ((w[i >> 5] >> (i & 31)) & 1u); }
+
+// The encoder's Src (csrc/rc_body.h) over probabilities and one byte per symbol (non-zero = 1): a chunk's code values from c1_block
+struct RcProbSrc {
+    const float* p; const uint8_t* s; int64_t n;
+    uint32_t c[RC_CHUNK]; int64_t base = 0;
+    inline void chunk(int64_t b) {
+        base = b;
+        c1_block(p + b, (int)(n - b < RC_CHUNK ? n - b : RC_CHUNK), c);
+    }
+    inline uint32_t c1(int i) const { return c[i]; }
+    inline uint32_t mask(int i) const { return s[base + i] ? 0xFFFFFFFFu : 0u; }
 };
 
-template <class Codes, class Syms>
-inline int64_t encode_binary_body(Codes codes, Syms syms, int64_t n, uint8_t* out_h, int64_t cap) {
-    BitSinkFast sink(out_h, cap);
-    uint32_t low = 0, high = 0xFFFFFFFFu;
-    uint64_t pending = 0;
-    for (int64_t base = 0; base < n; base += AC_CHUNK) {
-        const int m = (int)(n - base < AC_CHUNK ? n - base : AC_CHUNK);
-        const auto* c1 = codes.block(base, m);
-        for (int i = 0; i < m; ++i) {
-            const uint64_t span = (uint64_t)high - (uint64_t)low + 1;
-            const uint32_t t = (uint32_t)((span * c1[i]) >> 16);
-            const uint32_t one = syms.mask(base + i);
-            const uint32_t lt = low + t;
-            high = (high & one) | ((lt - 1u) & ~one);
-            low = (lt & one) | (low & ~one);
-            for (;;) {
-                const uint32_t diff = low ^ high;
-                if (diff < 0x80000000u) {
-                    int k = diff ? __builtin_clz(diff) : 31;            // leading bits shared by low and high (>= 1)
-                    if (k > 31) k = 31;
-                    const uint32_t first = low >> 31;
-                    if (pending) {
-                        sink.put_bits(first, 1);
-                        sink.put_run(first ^ 1u, pending);
-                        pending = 0;
-                        if (k > 1) sink.put_bits((low << 1) >> (33 - k), k - 1);
-                    } else {
-                        sink.put_bits(low >> (32 - k), k);
-                    }
-                    low <<= k;
-                    high = (high << k) | ((1u << k) - 1u);
-                } else if (low >= 0x40000000u && high < 0xC0000000u) {
-                    ++pending;
-                    low = (low << 1) & 0x7FFFFFFFu;
-                    high = (high << 1) | 0x80000001u;
-                } else {
-                    break;
-                }
-            }
-        }
-    }
-    ++pending;
-    const uint32_t last = low < 0x40000000u ? 0u : 1u;
-    sink.put_bits(last, 1);
-    sink.put_run(last ^ 1u, pending);
-    sink.finish();
-    return sink.len <= cap ? sink.len : (int64_t)LINR_ENOSPC;
+template <class Src>
+inline int64_t encode_binary(Src src, int64_t n, uint8_t* out_h, int64_t cap) {
+    RcHostOut o(out_h, cap);
+    const int64_t len = rc_encode(src, n, o);
+    return o.over ? (int64_t)LINR_ENOSPC : len;
 }
 
 }  // namespace
 
 extern "C" int64_t linr_ac_encode_binary(const float* prob_h, const uint8_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap) {
     if (n < 0 || cap < 0 || (n > 0 && (!prob_h || !sym_h)) || (cap > 0 && !out_h)) return LINR_EINVAL;
-    CodesFromProbs codes;
-    codes.p = prob_h;
-    return encode_binary_body(codes, SymBytes{sym_h}, n, out_h, cap);
+    return encode_binary(RcProbSrc{prob_h, sym_h, n}, n, out_h, cap);
 }
 
 extern "C" int64_t linr_ac_encode_binary_codes(const uint16_t* c1_h, const uint32_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap) {
     if (n < 0 || cap < 0 || (n > 0 && (!c1_h || !sym_h)) || (cap > 0 && !out_h)) return LINR_EINVAL;
-    return encode_binary_body(CodesReady{c1_h}, SymBits{sym_h}, n, out_h, cap);
+    return encode_binary(RcHostSrc{c1_h, sym_h, n}, n, out_h, cap);
 }
 
 namespace {
@@ -380,10 +322,10 @@ extern "C" int linr_ac_decode_cdf16(const uint16_t* cdf_h, int32_t lp, int32_t c
 
 namespace {
 
-// n_streams independent streams on a pool of threads that take them in order; one(i) codes stream i and returns its length
+// n_streams independent streams on up to n_threads threads that take them in order, the caller among them; one(i) codes stream i
+// and returns its code.  Returns the first non-zero code; every thread has joined on return.
 template <class One>
-inline int encode_batch(int32_t n_streams, int32_t n_threads, int64_t* out_len, One one) {
-    if (n_threads < 1) n_threads = 1;
+inline int run_batch(int32_t n_streams, int32_t n_threads, One one) {
     if (n_threads > n_streams) n_threads = n_streams;
     std::atomic<int> next(0);
     std::atomic<int> err(0);
@@ -391,19 +333,22 @@ inline int encode_batch(int32_t n_streams, int32_t n_threads, int64_t* out_len, 
         for (;;) {
             const int i = next.fetch_add(1);
             if (i >= n_streams) return;
-            const int64_t r = one(i);
-            out_len[i] = r;
-            if (r < 0) err.store((int)r);
+            const int r = one(i);
+            int none = 0;
+            if (r != 0) err.compare_exchange_strong(none, r);
         }
     };
-    if (n_threads <= 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < n_threads; ++t) pool.emplace_back(work);
-        for (auto& t : pool) t.join();
-    }
+    std::vector<std::thread> pool;
+    for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
     return err.load();
+}
+
+// the encoders' one(i): the length of stream i to out_len[i]; a negative one is the stream's code
+template <class One>
+inline int encode_batch(int32_t n_streams, int32_t n_threads, int64_t* out_len, One one) {
+    return run_batch(n_streams, n_threads, [&](int i) { return (out_len[i] = one(i)) < 0 ? (int)out_len[i] : 0; });
 }
 
 }  // namespace
@@ -419,28 +364,8 @@ extern "C" int linr_ac_encode_binary_batch(const float* const* prob_h, const uin
 extern "C" int linr_ac_decode_binary_batch(const float* const* prob_h, const int64_t* n, const uint8_t* const* in_h,
                                            const int64_t* in_len, int32_t n_streams, uint8_t* const* sym_h, int32_t n_threads) {
     if (n_streams < 0 || (n_streams > 0 && (!prob_h || !n || !in_h || !in_len || !sym_h))) return LINR_EINVAL;
-    if (n_threads < 1) n_threads = 1;
-    if (n_threads > n_streams) n_threads = n_streams;
-    std::atomic<int> next(0);
-    std::atomic<int> err(0);
-    auto work = [&]() {
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n_streams) return;
-            const int r = linr_ac_decode_binary(prob_h[i], n[i], in_h[i], in_len[i], sym_h[i]);
-            int none = 0;
-            if (r != 0) err.compare_exchange_strong(none, r);          // the first non-zero code wins
-        }
-    };
-    if (n_threads <= 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
-        work();                                                        // the caller is one of the workers
-        for (auto& t : pool) t.join();
-    }
-    return err.load();
+    return run_batch(n_streams, n_threads,
+                     [&](int i) { return linr_ac_decode_binary(prob_h[i], n[i], in_h[i], in_len[i], sym_h[i]); });
 }
 
 extern "C" int linr_ac_encode_binary_codes_batch(const uint16_t* const* c1_h, const uint32_t* const* sym_h, const int64_t* n,

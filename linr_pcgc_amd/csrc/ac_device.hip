@@ -1,7 +1,7 @@
 // The range coder on the device: linr_ac_encode_binary_codes for many streams at once, a wave per stream.  A stream is serial by its
 // format, the streams of a group of frames (8 stages x scales x frames) are independent and outnumber the SIMDs of the device, so a
 // group is coded in about the time of its longest stream and only stream bytes and lengths cross to the host.  The coder itself is
-// csrc/rc_body.h, the same text that linr_rc_encode_codes_host runs on the CPU; this file adds where a wave takes its symbols from
+// csrc/rc_body.h, the same text that linr_ac_encode_binary_codes runs on the CPU; this file adds where a wave takes its symbols from
 // and where its finished words go.
 #include "common.h"
 #include "rc_body.h"
@@ -166,9 +166,4 @@ extern "C" int linr_rc_encode_codes(const uint16_t* c1_dev, const uint32_t* sym_
     if ((rc = linr_hip_rc(hipcub::DeviceScan::ExclusiveSum(base + w.cub, cb, cnt, offsets_dev, n_streams + 1, s)))) return rc;
     rc_pack_k<<<dim3((unsigned)n_streams), dim3(LINR_BLOCK), 0, s>>>(out_dev, tab, len_dev, offsets_dev, payload_dev);
     return linr_launch_rc();
-}
-
-extern "C" int64_t linr_rc_encode_codes_host(const uint16_t* c1_h, const uint32_t* sym_h, int64_t n, uint8_t* out_h, int64_t cap) {
-    if (n < 0 || cap < 0 || (n > 0 && (!c1_h || !sym_h)) || (cap > 0 && !out_h)) return LINR_EINVAL;
-    return rc_encode_host(c1_h, sym_h, n, out_h, cap);
 }

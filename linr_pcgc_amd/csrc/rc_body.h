@@ -1,6 +1,6 @@
-// The binary range coder's body, once, for the host and for the device (csrc/ac_device.hip): everything that decides a byte of a
-// stream.  It is encode_binary_body of csrc/ac.cpp (the comparand: linr_ac_encode_binary_codes) restated so that it compiles for both
-// sides and holds its whole state in a handful of integers that a wave can keep uniform:
+// The binary range encoder's body, once, for the host (csrc/ac.cpp: linr_ac_encode_binary, linr_ac_encode_binary_codes) and for the
+// device (csrc/ac_device.hip: rc_encode_k): everything that decides a byte of a stream.  It compiles for both sides and holds its
+// whole state in a handful of integers that a wave can keep uniform:
 //   interval update   t = (span * c1) >> 16;  symbol 1: low += t;  symbol 0: high = low + t - 1      (branch-free select)
 //   renormalisation   all leading bits on which low and high agree at once (clz), the first of them followed by the pending
 //                     complements; the straddle case low >= 0x40000000 && high < 0xC0000000 adds one pending bit per step, and
@@ -27,6 +27,15 @@
 #define RC_CHUNK 64              // symbols per chunk: one wave's load of code values, two symbol words
 #define RC_STAGE_WORDS 64        // finished words staged before they leave: one per lane, 256 bytes
 #define RC_RENORM_CAP 34
+// Host only: a symbol that shifts nothing leaves rc_symbol after one test (most symbols of a trained model), and one that takes no
+// straddle step skips that step's arithmetic: predicted branches keep both off the chain low, high -> next symbol
+// (profiles/host_coder_one_body.txt).  On the device the early exit was measured and was not faster (profiles/device_coder_ab.txt),
+// so the kernel's code stays as it is.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RC_QUIET_EXIT 0
+#else
+#define RC_QUIET_EXIT 1
+#endif
 
 struct RcState {
     uint32_t low, high;
@@ -67,6 +76,12 @@ RC_HD void rc_symbol(RcState& s, Out& out, uint32_t c1, uint32_t one) {         
     const uint32_t lt = s.low + t;
     uint32_t high = (s.high & one) | ((lt - 1u) & ~one);
     uint32_t low = (lt & one) | (s.low & ~one);
+    // the top bits differ and the interval does not straddle the middle as 01.. / 10..: nothing to shift (the test of
+    // decode_binary_body in csrc/ac.cpp; as two branches it measured faster here than as that one)
+    if (RC_QUIET_EXIT && (int32_t)(low ^ high) < 0 && !((low & ~high) & 0x40000000u)) {
+        s.low = low; s.high = high;
+        return;
+    }
     for (int pass = 0; pass < RC_RENORM_CAP; ++pass) {
         const uint32_t diff = low ^ high;
         if (diff < 0x80000000u) {
@@ -85,6 +100,7 @@ RC_HD void rc_symbol(RcState& s, Out& out, uint32_t c1, uint32_t one) {         
             high = (high << k) | ((1u << k) - 1u);
             if (diff == 0) continue;                          // low == high: the new top bits may agree again
         }
+        if (RC_QUIET_EXIT && !((low & ~high) & 0x40000000u)) break;          // host: no straddle step to take
         // The top bits differ now (low 0.., high 1..) and do so after every straddle step, so no bit can be shared again and
         // the steps can be taken at once: one per leading position below the top with low 1 and high 0 (none: j = 0).
         const int j = __builtin_clz(~((low & ~high) << 1));          // 0..31; bit 0 of the argument is set
@@ -123,9 +139,11 @@ RC_HD int64_t rc_encode(Src& src, int64_t n, Out& out) {
     return rc_finish(s, out);
 }
 
-// ---- the host's Src and Out: what linr_rc_encode_codes_host and tools/ac_device_emul.cpp run -------------------------------
+// ---- the host's Src and Out (csrc/ac.cpp) ------------------------------------------------------------------------------------
 #include <string.h>
 
+// Code values and symbol bit planes, read in place.  (The source of linr_ac_encode_binary, probabilities and symbol bytes, stands
+// in csrc/ac.cpp beside c1_block, which it shares with the decoder.)
 struct RcHostSrc {
     const uint16_t* c; const uint32_t* w; int64_t n;
     uint64_t bits = 0; int64_t base = 0;
@@ -139,7 +157,8 @@ struct RcHostSrc {
     inline uint32_t mask(int i) const { return 0u - (uint32_t)((bits >> i) & 1u); }
 };
 
-// A 64-word array stands in for the lanes' staging registers; a block leaves whole, the last one cut to the stream's length.
+// Finished words are staged in a 64-word array, as in the lanes' registers on the device; a block leaves whole, the last one cut
+// to the stream's length.  Nothing is stored at or behind out + cap: a block that would cross it raises `over` instead.
 struct RcHostOut {
     uint8_t* out; int64_t cap;
     uint32_t stage[RC_STAGE_WORDS]; int k = 0; int64_t pos = 0; bool over = false;
@@ -159,11 +178,3 @@ struct RcHostOut {
         if (nbytes) memcpy(out + pos + 4 * k, &v, (size_t)nbytes);          // little-endian host: the first nbytes stream bytes
     }
 };
-
-// One stream on the CPU; the return convention of linr_ac_encode_binary_codes (arguments already checked).
-inline int64_t rc_encode_host(const uint16_t* c1, const uint32_t* sym, int64_t n, uint8_t* out, int64_t cap) {
-    RcHostSrc src{c1, sym, n};
-    RcHostOut o(out, cap);
-    const int64_t len = rc_encode(src, n, o);
-    return o.over ? (int64_t)-2 /* LINR_ENOSPC */ : len;
-}

@@ -1,12 +1,13 @@
-"""CPU: the device range coder's body (csrc/rc_body.h) run for one stream on the host (linr_rc_encode_codes_host: a 64-word array
-stands in for the lanes' staging registers) against the host coder linr_ac_encode_binary_codes, itself pinned to the oracle's coder
-in tests/test_cpu_host.py.  Bytes and lengths, all exact."""
+"""CPU: the range encoder's one body (csrc/rc_body.h), which the device coder runs a wave per stream, run for one stream on the host
+(linr_ac_encode_binary_codes: a 64-word array stands in for the lanes' staging registers) against the library's bit-at-a-time coder
+(linr_ac_encode_cdf16 on the rows [0, c1, 0], lp = 3, unshared), which shares no code with it; tests/test_cpu_host.py pins the body
+to the oracle's coder.  Bytes and lengths, all exact."""
 import os
 
 import numpy as np
 import pytest
 
-# each side of the 32-symbol word, the 64-symbol chunk and the host coder's AC_CHUNK = 256; one long stream
+# each side of the 32-symbol word, the 64-symbol chunk and 256 (the host decoder's AC_CHUNK); one long stream
 NS = (0, 1, 2, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1000, 70001)
 REGIMES = ('uniform', 'quiet', 'loud', 'half')
 
@@ -54,9 +55,22 @@ def encode(fn, c1, s, cap=None):
     return r, out[:max(r, 0)].tobytes()
 
 
+def encode_cdf16(lib, c1, s, cap=None):
+    """The same stream through linr_ac_encode_cdf16, one row [0, c1, 0] per symbol: the return convention of encode()."""
+    n = len(c1)
+    rows = np.zeros((n, 3), dtype=np.uint16)
+    rows[:, 1] = c1
+    sym = (np.asarray(s) != 0).astype(np.int16)
+    cap = 2 * n + 64 if cap is None else cap
+    out = np.full(cap + GUARD, 0xA5, dtype=np.uint8)
+    r = lib.linr_ac_encode_cdf16(rows.ctypes.data if n else None, 3, 0, sym.ctypes.data if n else None, n, out.ctypes.data, cap)
+    assert (out[cap:] == 0xA5).all(), 'bytes behind cap were written'
+    return r, out[:max(r, 0)].tobytes()
+
+
 def same(lib, c1, s, what):
-    want = encode(lib.linr_ac_encode_binary_codes, c1, s)
-    got = encode(lib.linr_rc_encode_codes_host, c1, s)
+    want = encode_cdf16(lib, c1, s)
+    got = encode(lib.linr_ac_encode_binary_codes, c1, s)
     assert want[0] >= 1
     assert got[0] == want[0], (what, got[0], want[0])
     assert got[1] == want[1], what
@@ -146,23 +160,11 @@ def test_small_cap_is_enospc_and_guard_bytes_stay(lib, regime):
     for n in (0, 1, 33, 257, 1000):
         c1, s = draw(regime, n, 77 + n)
         want, data = same(lib, c1, s, (regime, n))
-        r, got = encode(lib.linr_rc_encode_codes_host, c1, s, cap=want)              # exactly enough
+        r, got = encode(lib.linr_ac_encode_binary_codes, c1, s, cap=want)            # exactly enough
         assert (r, got) == (want, data)
         for cap in (want - 1, 0):
-            assert encode(lib.linr_rc_encode_codes_host, c1, s, cap=cap)[0] == -2, (regime, n, cap)
-            assert encode(lib.linr_ac_encode_binary_codes, c1, s, cap=cap)[0] == -2
-
-
-def test_bad_arguments_are_einval(lib):
-    c1, s = draw('uniform', 40, 5)
-    w = pack_symbols(s)
-    out = np.zeros(200, dtype=np.uint8)
-    f = lib.linr_rc_encode_codes_host
-    assert f(None, w.ctypes.data, 40, out.ctypes.data, 200) == -1
-    assert f(c1.ctypes.data, None, 40, out.ctypes.data, 200) == -1
-    assert f(c1.ctypes.data, w.ctypes.data, -1, out.ctypes.data, 200) == -1
-    assert f(c1.ctypes.data, w.ctypes.data, 40, out.ctypes.data, -1) == -1
-    assert f(c1.ctypes.data, w.ctypes.data, 40, None, 200) == -1
+            assert encode(lib.linr_ac_encode_binary_codes, c1, s, cap=cap)[0] == -2, (regime, n, cap)
+            assert encode_cdf16(lib, c1, s, cap=cap)[0] == -2
 
 
 def test_device_entry_checks_its_table_before_any_launch(lib):

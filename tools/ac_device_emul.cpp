@@ -1,14 +1,15 @@
-// The device range coder's body (csrc/rc_body.h) run on the HOST through the code path of linr_rc_encode_codes_host (rc_encode_host:
-// the 64-word staging array stands in for the lanes) against linr_ac_encode_binary_codes, under AddressSanitizer + UBSan; no GPU is
-// involved and nothing is launched.
+// The range encoder's one body (csrc/rc_body.h: what the device coder runs a wave per stream) run on the HOST through both of its host
+// sources - linr_ac_encode_binary_codes (code values + symbol bit planes) and linr_ac_encode_binary (probabilities + symbol bytes; the
+// 64-word staging array of their sink stands in for the lanes) - against the bit-at-a-time coder linr_ac_encode_cdf16 (rows [0, c1, 0],
+// lp = 3, unshared), which shares no code with the body, under AddressSanitizer + UBSan; no GPU is involved and nothing is launched.
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined tools/ac_device_emul.cpp \
 //       linr_pcgc_amd/csrc/ac.cpp -lpthread -o a.out && ./a.out 300000
-// Every stream is coded into a heap buffer of exactly cap bytes (a store at or behind out + cap aborts), its code values and symbol
-// words sit in buffers of exactly n and ceil(n / 32) elements.  Inputs: <count> random streams (lengths around the 32-symbol word, the
-// 64-symbol chunk and the 64-word staging block; code values uniform, tiny with either symbol dominant, 32768 alternating), each also
-// with cap = the host's length (fits exactly), one byte less and 0 (LINR_ENOSPC); and greedy prefixes that drive `pending` past the
-// 32- and 64-bit pieces of the run writer, resolved by bit 0, by bit 1 and by the end of the stream.
-#include "../linr_pcgc_amd/csrc/rc_body.h"
+// Every stream is coded into a heap buffer of exactly cap bytes (a store at or behind out + cap aborts), its code values, symbol
+// words, probabilities and symbol bytes sit in buffers of exactly n, ceil(n / 32), n and n elements.  The probability of a symbol is
+// 1 - (c1 - 1) / 65534, which the library's rounding takes back to c1.  Inputs: <count> random streams (lengths around the 32-symbol
+// word, the 64-symbol chunk and the 64-word staging block; code values uniform, tiny with either symbol dominant, 32768 alternating),
+// each also with cap = the stream's length (fits exactly), one byte less and 0 (LINR_ENOSPC); and greedy prefixes that drive `pending`
+// past the 32- and 64-bit pieces of the run writer, resolved by bit 0, by bit 1 and by the end of the stream.
 #include "../include/linr_hip.h"
 #include <cstdio>
 #include <cstdlib>
@@ -19,41 +20,50 @@
 static std::mt19937_64 rng(20240607);
 static long checked = 0;
 
-static std::vector<uint32_t> pack(const std::vector<uint8_t>& s) {
-    std::vector<uint32_t> w((s.size() + 31) / 32, 0u);
-    for (size_t i = 0; i < s.size(); ++i) w[i >> 5] |= (uint32_t)(s[i] & 1) << (i & 31);
-    return w;
-}
-
 static void fail(const char* what, size_t n, long a, long b) {
     fprintf(stderr, "FAIL %s: n = %zu, body %ld, comparand %ld\n", what, n, a, b);
     exit(1);
 }
 
-// both coders on one stream in exact-size buffers; returns the comparand's length
+template <class T>
+static T* exact(size_t n) { return (T*)malloc(n ? n * sizeof(T) : 1); }
+
+// the three coders on one stream in exact-size buffers; returns the comparand's length
 static int64_t compare(const std::vector<uint16_t>& c1v, const std::vector<uint8_t>& s, int64_t cap) {
-    const size_t n = c1v.size();
-    const std::vector<uint32_t> wv = pack(s);
-    uint16_t* c1 = (uint16_t*)malloc(n ? 2 * n : 1);
-    uint32_t* w = (uint32_t*)malloc(wv.size() ? 4 * wv.size() : 1);
-    if (n) memcpy(c1, c1v.data(), 2 * n);
-    if (!wv.empty()) memcpy(w, wv.data(), 4 * wv.size());
-    uint8_t* a = (uint8_t*)malloc(cap ? cap : 1);
-    uint8_t* b = (uint8_t*)malloc(cap ? cap : 1);
-    memset(a, 0xA5, cap ? cap : 1);
-    memset(b, 0xA5, cap ? cap : 1);
-    const int64_t ra = rc_encode_host(c1, w, (int64_t)n, a, cap);
-    const int64_t rb = linr_ac_encode_binary_codes(c1, w, (int64_t)n, b, cap);
-    if (ra != rb) fail("length", n, (long)ra, (long)rb);
-    if (rb > 0 && memcmp(a, b, (size_t)rb)) fail("bytes", n, (long)ra, (long)rb);
-    free(a); free(b); free(c1); free(w);
+    const size_t n = c1v.size(), nw = (n + 31) / 32;
+    uint16_t* c1 = exact<uint16_t>(n);
+    uint32_t* w = exact<uint32_t>(nw);
+    float* p = exact<float>(n);
+    uint8_t* sb = exact<uint8_t>(n);
+    uint16_t* rows = exact<uint16_t>(3 * n);
+    int16_t* sym = exact<int16_t>(n);
+    memset(w, 0, nw * 4);
+    for (size_t i = 0; i < n; ++i) {
+        c1[i] = c1v[i];
+        w[i >> 5] |= (uint32_t)(s[i] & 1) << (i & 31);
+        p[i] = 1.0f - (float)(c1v[i] - 1) / 65534.0f;
+        sb[i] = s[i];
+        rows[3 * i] = 0; rows[3 * i + 1] = c1v[i]; rows[3 * i + 2] = 0;
+        sym[i] = s[i] & 1;
+    }
+    uint8_t* out[3];
+    for (auto& o : out) { o = exact<uint8_t>((size_t)cap); memset(o, 0xA5, cap ? (size_t)cap : 1); }
+    const int64_t want = linr_ac_encode_cdf16(rows, 3, 0, sym, (int64_t)n, out[0], cap);
+    const int64_t got[2] = {linr_ac_encode_binary_codes(c1, w, (int64_t)n, out[1], cap),
+                            linr_ac_encode_binary(p, sb, (int64_t)n, out[2], cap)};
+    for (int k = 0; k < 2; ++k) {
+        if (got[k] != want) fail(k ? "length, probabilities" : "length, code values", n, (long)got[k], (long)want);
+        if (want > 0 && memcmp(out[k + 1], out[0], (size_t)want)) fail(k ? "bytes, probabilities" : "bytes, code values", n, (long)got[k], (long)want);
+    }
+    for (auto& o : out) free(o);
+    free(c1); free(w); free(p); free(sb); free(rows); free(sym);
     ++checked;
-    return rb;
+    return want;
 }
 
 static void all_caps(const std::vector<uint16_t>& c1, const std::vector<uint8_t>& s) {
     const int64_t len = compare(c1, s, 2 * (int64_t)c1.size() + 64);
-    if (len < 1) fail("host length", c1.size(), 0, (long)len);
+    if (len < 1) fail("comparand length", c1.size(), 0, (long)len);
     if (compare(c1, s, len) != len) fail("exact cap", c1.size(), 0, (long)len);
     if (compare(c1, s, len - 1) != LINR_ENOSPC) fail("cap - 1", c1.size(), 0, (long)len);
     if (compare(c1, s, 0) != LINR_ENOSPC) fail("cap 0", c1.size(), 0, (long)len);
