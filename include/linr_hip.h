@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 19
+#define LINR_ABI_VERSION 20
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -418,6 +418,18 @@ LINR_API int linr_net_train_step(const linr_frame* f, float* params, float* aren
  *   and maximum, stays NaN in qparams and has code 0; of a negative and a positive zero the negative one is the smaller.  Codes
  *   never leave [0, s].
  * linr_params_fake_quant_host: the same arithmetic as a plain loop over HOST pointers (no GPU needed).
+ * linr_params_fake_quant_ranges: the same quantiser under K GIVEN ranges instead of the vector's own minimum and maximum (the
+ *   encoder's range search, codec.encode_gop qrange_search=).  ranges_h: HOST [K][2] floats (lo, hi), lo <= hi, K in 1..16; they
+ *   travel as a kernel argument, nothing is allocated.  For candidate k:  p' = p < lo ? lo : (p > hi ? hi : p)  (a NaN passes),
+ *   then the arithmetic above with mn = lo, r = hi - lo (hi == lo: code 0 and p').  Outputs are rows of `stride` elements
+ *   (stride >= n, a multiple of 4; the elements behind n are not touched): qparams device [K][stride] floats (16-byte aligned),
+ *   codes device [K][stride] uint16 (8-byte aligned) or NULL, stats device int64 [K][4] (8-byte aligned) or NULL =
+ *   {parameters below lo, parameters above hi, sum of the codes q, sum of |q - mu|} with mu = rint((float)sum_q / (float)n) as
+ *   the model codec computes it: exact integers from which the host forms the codec's Laplace size estimate without reading a
+ *   code back.  For (lo, hi) = (minimum, maximum) of params row k is bit for bit what linr_params_fake_quant writes.  ONE launch
+ *   of K workgroups, no host synchronisation, no atomics; n == 0 launches nothing.  A bad K, stride, bound pair (lo > hi or NaN),
+ *   pointer or alignment is refused before the launch.
+ * linr_params_fake_quant_ranges_host: the same as a plain loop over HOST pointers (no GPU needed; no alignment asked).
  * linr_net_train_step_qat: linr_net_train_step whose forward and backward run at qparams = fake_quant(params) (written by the
  *   call: a caller-owned device buffer of linr_param_count floats, 16-byte aligned, not params itself) while Adam - weight decay
  *   included - updates the fp32 master `params` with that gradient (straight-through estimator): bits_acc receives the bits of the
@@ -426,6 +438,10 @@ LINR_API int linr_params_fake_quant(const float* params, int64_t n, int32_t bitd
                                     void* stream);
 LINR_API int linr_params_fake_quant_host(const float* params, int64_t n, int32_t bitdepth, float* qparams, uint16_t* codes,
                                          float* minmax);
+LINR_API int linr_params_fake_quant_ranges(const float* params, int64_t n, int32_t bitdepth, const float* ranges_h, int32_t K,
+                                           int64_t stride, float* qparams, uint16_t* codes, int64_t* stats, void* stream);
+LINR_API int linr_params_fake_quant_ranges_host(const float* params, int64_t n, int32_t bitdepth, const float* ranges_h, int32_t K,
+                                                int64_t stride, float* qparams, uint16_t* codes, int64_t* stats);
 LINR_API int linr_net_train_step_qat(const linr_frame* f, float* params, float* arena, size_t arena_bytes, float gscale,
                             float* exp_avg, float* exp_avg_sq, double lr, int64_t step, const int64_t* scale_steps_h,
                             double beta1, double beta2, double eps, double weight_decay, double* bits_acc, float* qparams,

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('LINR_HIP_LIB') or os.path.join(_HERE, 'liblinr_hip.so
 LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 16
 LINR_FRAME_OCC_PADDED = 1
 LINR_PLY_TOKEN, LINR_PLY_COLUMNS, LINR_PLY_SHORT, LINR_PLY_RANGE = 1, 2, 4, 8
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -197,6 +197,8 @@ _PROTOS = {
     'linr_ply_gather_binary': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_ptr]),
     'linr_params_fake_quant': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     'linr_params_fake_quant_host': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
+    'linr_params_fake_quant_ranges': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'linr_params_fake_quant_ranges_host': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_ptr]),
     'linr_net_train_step_qat': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_f32, c_ptr, c_ptr, c_f64,
                                                c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr, c_i32, c_ptr]),
     'linr_net_train_step_bf16_qat': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr, c_f64,
@@ -234,7 +236,8 @@ class _Poisoned:
     """LINR_DEBUG_POISON=1 (test aid, tools/README.md): every GPU entry point is called with the LDS and vector registers of all
     CUs freshly filled with a NaN pattern (linr_debug_poison_now in front of it, linr_debug_poison(all classes) for the launches
     inside the executors).  The test suite must pass unchanged under it: no kernel may read on-chip state it did not write."""
-    _HOST = ('linr_ac_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host')
+    _HOST = ('linr_ac_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host',
+             'linr_params_fake_quant_ranges_host')
 
     def __init__(self, handle):
         self._h = handle

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .function_utils import pack_bitstream, unpack_bitstream
-from .model_codec import Model_Estimate
+from .model_codec import Model_Estimate, candidate_ranges, laplace_bits_est
 from .model_core import DeviceCoderSet, codes_word_off, encode_streams, encode_streams_codes
 from .module_utils import octree_level_obj, qscTensor, unique_sorted  # noqa: F401
 
@@ -109,12 +109,14 @@ def _code_frames_device(coded_model, gop, coder_group):
     return frames_bytes, bits_dev
 
 
-def _gop_result(gop, comp, side_info, frames_bytes, bits_dev):
+def _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found=None):
     bits_est = float(torch.stack(bits_dev).sum())
     low = enc_all_frame_low_xyz(gop)
     points = sum(gop.point_nums)
     occ_bits = 8 * sum(len(b) for fb in frames_bytes for b in fb)
-    return {'frames': frames_bytes, 'model_bin': comp['final_bytes'], 'side_info': side_info, 'low_enc_bytes': low,
+    extra = {} if found is None else {'qrange': {'trims': found['trims'], 'objective_bits': found['objective_bits'],
+                                                 'chosen': found['trims'][found['chosen']], 'search_s': found['search_s']}}
+    return {**extra, 'frames': frames_bytes, 'model_bin': comp['final_bytes'], 'side_info': side_info, 'low_enc_bytes': low,
             'point_num': points, 'bits_est': bits_est,
             # the five one-byte side-info fields this codec adds (arith_version, precision, scale_num, block_layers,
             # hidden_channel_conv: EXTRA_SIDE_BITS = 40) are counted with the model
@@ -130,8 +132,59 @@ def _coder_threads(n_threads):
     return max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else 8))
 
 
+def qrange_eval_frames(n_frames, want):
+    """The frames the range search evaluates: `want` of a GOP's n_frames, evenly spaced (the middles of `want` equal stretches); 0 or a
+    value >= n_frames: all of them."""
+    want = int(want)
+    if want <= 0 or want >= n_frames:
+        return list(range(n_frames))
+    return [(2 * i + 1) * n_frames // (2 * want) for i in range(want)]
+
+
+def search_qrange(model, model_ori, gop, bitdepth=8, precision='f32', trims=None, eval_frames=4, frame_bits=None):
+    """The encoder's rate-checked quantiser range (encode_gop qrange_search=True).  The model codec quantises with ONE step for the
+    whole parameter vector, (max - min) / (2^bitdepth - 1), so a single outlier weight widens it for every other weight.  A decoder
+    reads the range from side_info.json (min_param / max_param) and never checks that it is the vector's own, so the encoder may
+    write a narrower one and let the few weights outside it saturate.  Whether that pays is not predictable - the outlier may
+    matter to the network - so it is measured: every candidate (model_codec.candidate_ranges: `trims` weights cut at either end;
+    trim 0, today's range, is always the first) is quantised by one call of linr_params_fake_quant_ranges for all of them, filled
+    into `model_ori` through Model_Estimate._fill, and asked for its bits on the evaluated frames (qrange_eval_frames) by the
+    codec's own forward (frame_probs: any precision, any width).  Objective of candidate j:
+        model_bits_est_j + (frames / evaluated frames) * sum of the evaluated frames' bits
+    (model_codec.laplace_bits_est from the kernel's integer stats).  The smallest wins, a tie goes to the smaller trim, so on the
+    frames it evaluates the choice is never worse than trim 0.  On the caller's stream, no draw from torch's generator.
+    gop: an overfit.Gop, or - with frame_bits(candidate model, i) -> device float64[1], the bits of frame i - any sequence of frames
+    (encoder.encode_one_gop's per-scale inputs).  Returns
+    {'trims', 'ranges', 'objective_bits', 'chosen' (an index into trims), 'frames', 'search_s'}; `model_ori` is left filled with
+    the last candidate."""
+    import time
+    from . import engine
+    t0 = time.time()
+    flat = model.flat_parameters().detach()
+    kept, ranges = candidate_ranges(flat.to('cpu', torch.float32), trims)
+    with_codes = bitdepth == 8                               # what _fill hands to the executors that run from codes
+    q, codes, stats = engine.params_fake_quant_ranges(flat, ranges, bitdepth, codes=with_codes)
+    n = flat.numel()                                         # (the rows are padded to the kernel's stride)
+    codes_h = codes.cpu().numpy()[:, :n] if with_codes else None
+    frames = gop.frames if frame_bits is None else gop
+    if frame_bits is None:
+        frame_bits = lambda cand, i: cand.frame_probs(frames[i])[1]
+    todo = qrange_eval_frames(len(frames), eval_frames)
+    bits = []
+    for j, (lo, hi) in enumerate(ranges):
+        cand = Model_Estimate._fill(model_ori, q[j, :n], None if codes_h is None else codes_h[j], lo, hi, bitdepth)
+        cand.inference_precision = precision
+        bits.append(torch.stack([frame_bits(cand, i) for i in todo]).sum())
+    bits = torch.stack(bits).cpu().tolist()
+    stats = stats.cpu().tolist()
+    up = len(frames) / len(todo)
+    objective = [laplace_bits_est(n, st[3], bitdepth) + up * b for st, b in zip(stats, bits)]
+    chosen = min(range(len(objective)), key=lambda j: (objective[j], j))
+    return {'trims': kept, 'ranges': ranges, 'objective_bits': objective, 'chosen': chosen, 'frames': todo, 'search_s': time.time() - t0}
+
+
 def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32', device_codes=False, device_coder=False,
-               coder_group=8):
+               coder_group=8, qrange_search=False, qrange_trims=None, qrange_frames=4):
     """encoder.encode_one_gop: quantise the model, then per frame ONE forward over all scales and 8 x scales
     independent arithmetic-coded streams (thread pool).  precision='bf16': the forward runs on the bf16 / uint8-weight
     executor (BASELINE config[4]); the choice is recorded in side_info so that the decoder reproduces it.
@@ -140,11 +193,19 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     them.  The streams are byte for byte those of the default path, so nothing about it is recorded.
     device_coder=True (implies device codes): the range coder itself runs on the GPU, coder_group (1..64) frames per call
     (_code_frames_device); only stream bytes and lengths cross to the host and no coder thread is started.  Again the same bytes,
-    again nothing recorded."""
+    again nothing recorded.
+    qrange_search=True (opt-in): the quantiser's range is chosen by search_qrange among the candidates of qrange_trims (default
+    model_codec.DEFAULT_QRANGE_TRIMS) on qrange_frames evaluated frames (0: all); the winner goes through the model codec
+    (compress_model(qrange=)) and everything behind it is unchanged: min_param / max_param carry the range, every decoder decodes the
+    stream.  The result then has 'qrange' = {'trims', 'objective_bits', 'chosen' (the chosen trim), 'search_s'}, and - when there was
+    more than the plain range to choose from - side_info the informational 'qrange_trim' and 'qrange_candidates'."""
     if device_coder and not 1 <= int(coder_group) <= 64:
         raise ValueError('coder_group must be in 1..64, got %r' % (coder_group,))
     n_threads = _coder_threads(n_threads)
-    comp = Model_Estimate().compress_model(model, bitdepth, True, model_ori)
+    found = search_qrange(model, model_ori, gop, bitdepth, precision, qrange_trims, qrange_frames) if qrange_search else None
+    # trim 0 is the vector's own (min, max): today's call, to the letter
+    qrange = found['ranges'][found['chosen']] if found is not None and found['chosen'] else None
+    comp = Model_Estimate().compress_model(model, bitdepth, True, model_ori, **({} if qrange is None else {'qrange': qrange}))
     coded_model = comp['new_model']                      # the de-quantised model is what codes the geometry
     coded_model.inference_precision = precision
     side_info = {'mu': comp['mu'], 'b': comp['b'], 'min_param': comp['min_param'], 'max_param': comp['max_param'],
@@ -159,9 +220,14 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     # in EXTRA_SIDE_BITS, ignored by the decoders
     if getattr(model, 'qat_epochs', 0):
         side_info['qat_epochs'] = int(model.qat_epochs)
+    # ... and which quantiser range the search chose among how many: not counted, ignored by the decoders (min_param / max_param are
+    # the range).  A search with nothing but the plain range to choose from records nothing: its files are the plain files.
+    if found is not None and len(found['trims']) > 1:
+        side_info['qrange_trim'] = int(found['trims'][found['chosen']])
+        side_info['qrange_candidates'] = len(found['trims'])
     if device_coder:
         frames_bytes, bits_dev = _code_frames_device(coded_model, gop, int(coder_group))
-        return _gop_result(gop, comp, side_info, frames_bytes, bits_dev)
+        return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found)
     # Pipeline: the GPU forward + D2H of frame i+1 runs while host workers range-code earlier frames (the coder's C call
     # releases the GIL).  A frame has 8 x scales independent streams, but the 8 streams of its finest scale carry 73 % of the
     # symbols, so one frame keeps only ~8 threads busy: TWO frames are coded concurrently, each on half of the threads
@@ -233,7 +299,7 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
         while pending:
             hand_over(pending.pop(0), coder)
         frames_bytes = [j.result() for j in jobs]
-    return _gop_result(gop, comp, side_info, frames_bytes, bits_dev)
+    return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found)
 
 
 def decode_one_frame(model, frame_enc_bytes, xyz_low):

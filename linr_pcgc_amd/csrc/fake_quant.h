@@ -48,6 +48,16 @@ __host__ __device__ __forceinline__ float linr_fq_element(float p, float sym_max
 __host__ __device__ __forceinline__ float linr_fq_min(float a, float b) { return (b < a || (b == a && __builtin_signbit(b))) ? b : a; }
 __host__ __device__ __forceinline__ float linr_fq_max(float a, float b) { return (b > a || (b == a && !__builtin_signbit(b))) ? b : a; }
 
+// Candidate ranges (linr_params_fake_quant_ranges): a parameter clamped into [lo, hi]; a NaN passes through
+#define LINR_FQ_MAX_RANGES 16
+__host__ __device__ __forceinline__ float linr_fq_clamp(float p, float lo, float hi) { return p < lo ? lo : (p > hi ? hi : p); }
+
+// mu of the model codec's Laplace model from the exact sum of the codes: torch.round(codes.mean()) in fp32 - the sum as one float
+// (exact below 2^24, which 8-bit codes of up to 65,793 parameters are), one division, round half to even
+__host__ __device__ __forceinline__ long long linr_fq_mean_level(unsigned long long sum_q, int64_t n) {
+    return (long long)rintf((float)sum_q / (float)n);
+}
+
 // the one launch behind linr_params_fake_quant, after its argument checks (csrc/fake_quant.hip); the executors wrap it in their
 // own profiler class
 __attribute__((visibility("hidden")))

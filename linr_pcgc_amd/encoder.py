@@ -23,7 +23,8 @@ def gop_bounds(gop_name):
 
 
 def encode(enc_args):
-    """encoder.py:20-54.  enc_args: 'outputdir' (holds <gop>/model.pth), 'gop_names', 'Gen_Model', 'dataset', 'encode_dir'."""
+    """encoder.py:20-54.  enc_args: 'outputdir' (holds <gop>/model.pth), 'gop_names', 'Gen_Model', 'dataset', 'encode_dir'; optional
+    'qrange_search' (default off), 'qrange_trims', 'qrange_frames': the rate-checked quantiser range of codec.encode_gop."""
     os.makedirs(enc_args['encode_dir'], exist_ok=True)
     for gop_name in enc_args['gop_names']:
         first, last = gop_bounds(gop_name)
@@ -31,7 +32,8 @@ def encode(enc_args):
         encode_one_gop({'Gen_Model': enc_args['Gen_Model'], 'frame_num': last - first + 1,
                         'model_path': os.path.join(enc_args['outputdir'], gop_name, 'model.pth'),
                         'result_dir': os.path.join(enc_args['encode_dir'], gop_name), 'reading_data': reading,
-                        'low_enc_bytes': enc_all_frame_low_xyz(reading, last - first + 1)})
+                        'low_enc_bytes': enc_all_frame_low_xyz(reading, last - first + 1),
+                        **{k: enc_args[k] for k in ('qrange_search', 'qrange_trims', 'qrange_frames') if k in enc_args}})
 
 
 def encode_one_frame(model, all_inargs, ori=None):
@@ -63,12 +65,31 @@ def encode_one_gop(inargs):
     os.makedirs(bins_dir, exist_ok=True)
     with open(os.path.join(bins_dir, 'low_enc_bytes.bin'), 'wb') as f:
         f.write(low)
-    packed = Model_Estimate().compress_model(trained, bitdepth, True, gen())
+    qrange, found = None, None
+    if inargs.get('qrange_search', False):
+        # the rate-checked quantiser range of codec.encode_gop (codec.search_qrange), on this road's per-scale inputs
+        reading = [inargs['reading_data'][i] for i in range(inargs['frame_num'])]
+
+        def frame_bits(cand, i):
+            per_scale = []
+            for sc in reading[i]['all_input_info']:
+                putin = dict(sc)
+                putin['coord'], putin['offset_tensor'] = sc['xyzqsc_t'].get_coord(), sc['xyzqsc_t'].get_offset_tensor()
+                per_scale.append(cand.frame_probs(cand._scale_frame(putin))[1])
+            return torch.stack(per_scale).sum(0)
+
+        found = codec.search_qrange(trained, gen(), reading, bitdepth, 'f32', inargs.get('qrange_trims'), inargs.get('qrange_frames', 4),
+                                    frame_bits=frame_bits)
+        qrange = found['ranges'][found['chosen']] if found['chosen'] else None
+    packed = Model_Estimate().compress_model(trained, bitdepth, True, gen(), **({} if qrange is None else {'qrange': qrange}))
     with open(os.path.join(bins_dir, 'model.bin'), 'wb') as f:
         f.write(packed['final_bytes'])
     side_info = {'mu': packed['mu'], 'b': packed['b'], 'min_param': packed['min_param'], 'max_param': packed['max_param'],
                  'enc_mode': packed['enc_mode'], 'bitdepth': bitdepth, 'arith_version': codec.ARITH_VERSION}
     side_info.update(codec.model_shape(trained))
+    if found is not None and len(found['trims']) > 1:
+        side_info['qrange_trim'] = int(found['trims'][found['chosen']])
+        side_info['qrange_candidates'] = len(found['trims'])
     with open(os.path.join(result_dir, 'side_info.json'), 'w') as f:
         json.dump(side_info, f, indent=4)
     model = packed['new_model']

@@ -235,6 +235,26 @@ def params_fake_quant(flat, bitdepth=8, codes=False):
     return (q, c, mm) if codes else (q, mm)
 
 
+def params_fake_quant_ranges(flat, ranges, bitdepth=8, codes=True):
+    """linr_params_fake_quant_ranges: `flat` (device float32 [n]) quantised under each of the K candidate ranges [(lo, hi)] in one
+    launch.  Returns (qparams float32 [K, stride], codes uint16 [K, stride] or None, stats int64 [K, 4] on the device:
+    n_below_lo, n_above_hi, sum_q, sum |q - mu|); stride = n rounded up to a multiple of 4, the first n elements of a row count and the
+    rest is never written.  Nothing synchronises with the host."""
+    if not flat.is_cuda:
+        raise _lib.LinrError('params_fake_quant_ranges: the parameters must be on the GPU')
+    flat = flat.contiguous()
+    n, K = flat.numel(), len(ranges)
+    stride = (n + 3) & ~3
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.float32).reshape(K, 2))
+    q = torch.empty((K, stride), dtype=torch.float32, device=flat.device)
+    c = torch.empty((K, stride), dtype=torch.uint16, device=flat.device) if codes else None
+    st = torch.empty((K, 4), dtype=torch.int64, device=flat.device)
+    check(_lib.lib().linr_params_fake_quant_ranges(flat.data_ptr(), n, int(bitdepth), r.ctypes.data, K, stride, q.data_ptr(),
+                                                   None if c is None else c.data_ptr(), st.data_ptr(), _stream()),
+          'linr_params_fake_quant_ranges')
+    return q, c, st
+
+
 def net_train_step(frame, flat_params, exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits,
                    arena=None, scale_steps=None, qparams=None, bitdepth=8):
     """linr_net_train_step: forward + backward + deterministic gradient reduction + fused Adam in one call.

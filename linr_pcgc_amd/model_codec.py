@@ -15,8 +15,22 @@ import torch
 from . import _lib
 
 
-def quant_uniform2(param_lst, bitdepth=8):
-    min_n, max_n = param_lst.min(), param_lst.max()
+DEFAULT_QRANGE_TRIMS = (0, 1, 2, 4, 8, 16, 32, 64)
+MAX_QRANGE_CANDIDATES = 16          # LINR_FQ_MAX_RANGES of csrc/fake_quant.h: what one call of linr_params_fake_quant_ranges takes
+
+
+def quant_uniform2(param_lst, bitdepth=8, qrange=None):
+    """qrange=(lo, hi) (opt-in; None = the reference's quantiser, below): the parameters are clamped into it and quantised with lo and
+    hi in the place of their minimum and maximum, so the few outside it saturate to code 0 / 2^bitdepth - 1.  A decoder is told (lo, hi) as
+    min_param / max_param and de-quantises as ever."""
+    if qrange is None:
+        min_n, max_n = param_lst.min(), param_lst.max()
+    else:
+        min_n = torch.tensor(float(qrange[0]), dtype=param_lst.dtype)
+        max_n = torch.tensor(float(qrange[1]), dtype=param_lst.dtype)
+        if not bool(min_n <= max_n):
+            raise ValueError('qrange needs lo <= hi, got %r' % (tuple(qrange),))
+        param_lst = torch.where(param_lst < min_n, min_n, torch.where(param_lst > max_n, max_n, param_lst))     # a NaN passes
     ten_range = max_n - min_n
     sym_max = float(np.ceil(2 ** bitdepth) - 1)
     new_p = torch.round((param_lst - min_n) / ten_range * sym_max)
@@ -54,11 +68,57 @@ def _ac_decode(cdf_u16, data, n):
     return out
 
 
-def compress_params(params, bitdepth=8):
-    """compress_model (model_size_est.py:390-521) on a flat float32 parameter vector (any device)."""
+def candidate_ranges(flat, trims=None):
+    """The candidate quantiser ranges of the encoder's range search (codec.encode_gop qrange_search=): for every t of `trims` (default
+    DEFAULT_QRANGE_TRIMS) lo = the (t+1)-th smallest and hi = the (t+1)-th largest parameter of `flat` (a CPU float32 vector), so t
+    parameters at either end saturate.  t = 0, the true (min, max) and today's range, is always the first candidate whether `trims`
+    names it or not; a trim that yields a range already listed (equal parameters at the ends), or that would trim half of the vector
+    or more, is dropped.  Returns (trims kept, [(lo, hi)]), at most MAX_QRANGE_CANDIDATES of them, in ascending trim order."""
+    v = np.sort(np.asarray(flat.detach().to('cpu', torch.float32).numpy() if torch.is_tensor(flat) else flat, dtype=np.float32).reshape(-1))
+    v = v[~np.isnan(v)]
+    if v.size == 0:
+        raise ValueError('no parameter to take a range from')
+    want = sorted({int(t) for t in (DEFAULT_QRANGE_TRIMS if trims is None else trims)} | {0})
+    if want[0] < 0:
+        raise ValueError('trims must be >= 0, got %r' % (trims,))
+    kept, ranges = [], []
+    for t in want:
+        if t and 2 * t >= v.size:
+            continue
+        r = (float(v[t]), float(v[v.size - 1 - t]))
+        if r not in ranges:
+            kept.append(t)
+            ranges.append(r)
+    if len(kept) > MAX_QRANGE_CANDIDATES:
+        raise ValueError('at most %d candidate ranges, got %d' % (MAX_QRANGE_CANDIDATES, len(kept)))
+    return kept, ranges
+
+
+def laplace_bits_est(n, sum_abs_dev, bitdepth=8):
+    """The size ESTIMATE of the coded model in bits, as Model_Estimate.estibits forms it, from integers alone: n codes whose deviations
+    from mu = round(mean) sum to sum_abs_dev (the `stats` of linr_params_fake_quant_ranges).  b = round(sum_abs_dev / n) in fp32 like
+    compress_params; bits = sum_abs_dev / b * log2(e) + n * log2(2 b) + 2 * bitdepth in float64; the raw bound bitdepth * n stands in
+    where the Laplace figure passes it or does not exist (b == 0: all codes within half a step of mu).  The zlib bound, which needs
+    the codes, is left out: an estimate for comparing candidates, not the coded size."""
+    n, sum_abs_dev = int(n), int(sum_abs_dev)
+    b = float(np.rint(np.float32(sum_abs_dev) / np.float32(n)))
+    side = 2 + 2 * 32
+    if b > 0:
+        bits = sum_abs_dev / b * float(np.log2(np.e)) + n * float(np.log2(2 * b)) + 2 * bitdepth
+        if bits <= bitdepth * n:
+            return bits + side
+    return float(bitdepth * n + side)
+
+
+def compress_params(params, bitdepth=8, qrange=None):
+    """compress_model (model_size_est.py:390-521) on a flat float32 parameter vector (any device).  qrange=(lo, hi): quant_uniform2's
+    opt-in clipped range; min_param / max_param of the result are then lo / hi."""
     params = params.detach().to('cpu', torch.float32)
-    min_param, max_param = params.min(), params.max()
-    quant_ret, recon_ret = quant_uniform2(params, bitdepth)
+    if qrange is None:
+        min_param, max_param = params.min(), params.max()
+    else:
+        min_param, max_param = (torch.tensor(float(x), dtype=torch.float32) for x in qrange)
+    quant_ret, recon_ret = quant_uniform2(params, bitdepth, qrange)
     mu = torch.round(quant_ret.mean())
     b = torch.round((quant_ret - mu).abs().mean())
     like = torch.exp(-torch.abs(quant_ret - mu) / b) / (2 * b)
@@ -141,8 +201,8 @@ class Model_Estimate:
         return model
 
     @torch.no_grad()
-    def compress_model(self, model, bitdepth=8, derive_new_model=False, model_ori=None):
-        out = compress_params(model.flat_parameters(), bitdepth)
+    def compress_model(self, model, bitdepth=8, derive_new_model=False, model_ori=None, qrange=None):
+        out = compress_params(model.flat_parameters(), bitdepth, qrange)
         out['new_model'] = None
         if derive_new_model and model_ori is not None:
             out['new_model'] = self._fill(model_ori, out['recon_ret'], out['symbols'], out['min_param'], out['max_param'], bitdepth)

@@ -70,6 +70,16 @@ def parse(argv=None):
                          'evaluated at the --model_bitdepth-bit weights the model codec will code with, the gradient goes straight through to '
                          'the fp32 weights, and with --keep best only those epochs compete.  0 (default): the plain overfit.  '
                          '--hidden-channel-conv 8 only; streams decode as ever')
+    ap.add_argument('--qrange-search', '--qrange_search', dest='qrange_search', action='store_true',
+                    help="the encoder chooses the weight quantiser's range by measured rate (codec.search_qrange): candidate ranges that let "
+                         'the --qrange-trims smallest and largest weights saturate are each quantised and asked for their bits on '
+                         '--qrange-frames frames of the GOP, model size included; the plain range is always a candidate.  The range travels as '
+                         "side_info.json's min_param / max_param: streams decode as ever.  With --qat-epochs the aware epochs keep training at "
+                         'the unclipped quantiser')
+    ap.add_argument('--qrange-trims', '--qrange_trims', dest='qrange_trims', default=None,
+                    help='with --qrange-search: comma-separated trims, e.g. 0,1,2,4 (default 0,1,2,4,8,16,32,64; 0 is always tried)')
+    ap.add_argument('--qrange-frames', '--qrange_frames', dest='qrange_frames', type=int, default=4,
+                    help='with --qrange-search: frames of a GOP, evenly spaced, on which every candidate is measured (0: all)')
     ap.add_argument('--decode', action='store_true', help='decode every GOP again and check it is lossless')
     ap.add_argument('--decode-lockstep', '--decode_lockstep', dest='decode_lockstep', type=int, default=0,
                     help='with --decode: decode the frames of a GOP in groups of up to this many, all scales in lock step '
@@ -90,6 +100,15 @@ def parse(argv=None):
         ap.error('--qat-epochs: quantisation-aware training exists for --hidden-channel-conv 8 only')
     if args.qat_epochs and not 2 <= args.model_bitdepth <= 16:
         ap.error('--qat-epochs needs --model_bitdepth in 2..16')
+    if args.qrange_trims is not None:
+        try:
+            args.qrange_trims = tuple(int(t) for t in args.qrange_trims.split(','))
+        except ValueError:
+            ap.error('--qrange-trims: comma-separated integers, got %r' % (args.qrange_trims,))
+        if min(args.qrange_trims) < 0:
+            ap.error('--qrange-trims must be >= 0')
+    if args.qrange_frames < 0:
+        ap.error('--qrange-frames must be >= 0')
     return args
 
 
@@ -285,7 +304,9 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
             enc = codec.encode_gop(model, shell(), gop,
                                    getattr(args, 'model_bitdepth', 8), precision=getattr(args, 'precision', 'f32'),
                                    device_codes=getattr(args, 'device_codes', False),
-                                   device_coder=getattr(args, 'device_coder', False), coder_group=getattr(args, 'coder_group', 8))
+                                   device_coder=getattr(args, 'device_coder', False), coder_group=getattr(args, 'coder_group', 8),
+                                   **({'qrange_search': True, 'qrange_trims': getattr(args, 'qrange_trims', None),
+                                       'qrange_frames': getattr(args, 'qrange_frames', 4)} if getattr(args, 'qrange_search', False) else {}))
             res_dir = os.path.join(args.out, 'result_enc', gop_parallel.gop_name(group))
             codec.write_gop(enc, res_dir)
             sync()
@@ -309,6 +330,8 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                       'encode_s': t2 - t1, 'decode_s': t3 - t2, 'seconds': stage_s + overfit_s + (t3 - t1), 'rank': rank}
             if 'qat_from' in info:
                 result['qat_from'] = info['qat_from']
+            if 'qrange' in enc:
+                result['qrange'] = enc['qrange']
             if getattr(args, 'mid_test', False):
                 result['mid_test'] = half['mid']
             return result
