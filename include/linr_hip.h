@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 20
+#define LINR_ABI_VERSION 21
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -611,6 +611,22 @@ LINR_API int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_of
                             float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
                             void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap,
                             int64_t* child_off_h, int32_t n_threads, void* stream);
+/* Both scale entries for CHUNKED stage streams (linr_stream_split_chunks below; side_info.json's stream_chunk): with chunk_symbols = S
+ * a stream of n > S symbols is a header and k = ceil(n / S) chunks, and every chunk joins its stage's linr_ac_decode_binary_batch call
+ * as an entry of its own - chunk j decodes rows [j S, min((j + 1) S, n)) of its frame - on up to n_threads host threads (at most one
+ * per 65,536 symbols of the stage: the batch starts its threads anew in every call), which the per-frame entry therefore takes, too.  Every stream's header is parsed and checked before the first launch: LINR_EINVAL for a
+ * truncated length, one of more than 5 bytes, lengths that exceed the stream, or an S that is no multiple of 64 in 64..2^24.
+ * chunk_symbols 0: the entries above (which are these with 0, the per-frame one with one thread).  Everything else as there. */
+LINR_API int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                              int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                              const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                              float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
+                              int64_t chunk_symbols, int32_t n_threads, void* stream);
+LINR_API int linr_decode_scale_batch_chunked(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                    int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                    float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                                    void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
+                                    int64_t child_cap, int64_t* child_off_h, int32_t n_threads, int64_t chunk_symbols, void* stream);
 
 /* ---- the executor's fused layers as stand-alone ops ------------------------------------------------------------
  * What linr_net_forward / _backward launch for one layer, callable (and testable) on its own.  All of them work on the
@@ -736,6 +752,17 @@ LINR_API int     linr_ac_decode_binary_codes(const uint16_t* c1_h, int64_t n, co
 LINR_API int linr_ac_encode_binary_codes_batch(const uint16_t* const* c1_h, const uint32_t* const* sym_h, const int64_t* n,
                                       int32_t n_streams, uint8_t* const* out_h, const int64_t* cap,
                                       int64_t* out_len, int32_t n_threads);
+/* Chunked stage streams (opt-in; side_info.json's stream_chunk = S, a multiple of 64 in 64..2^24): a stage stream of n symbols has
+ * k = max(1, ceil(n / S)) chunks, chunk j being exactly the stream of symbols [j S, min((j + 1) S, n)) on their own.  k == 1: the
+ * stream is that chunk, i.e. the unchunked stream.  k > 1: the byte lengths of chunks 0 .. k - 2 as unsigned LEB128 of at most 5
+ * bytes each, then the chunks; the last chunk takes the bytes that remain (a decoder knows n and S, so there is no count field).
+ * linr_stream_chunk_count: k (1 for S == 0, "not chunked"), LINR_EINVAL for n < 0 or a bad S.
+ * linr_stream_split_chunks: chunk_h[j] / chunk_len[j], j < k, point into in_h; returns k.  LINR_EINVAL for a truncated length, a
+ * length of more than 5 bytes, lengths that together exceed the bytes present, or bad arguments; LINR_ENOSPC for max_chunks < k.  No
+ * byte at or behind in_h + in_len is read, and a refused stream writes nothing to chunk_h / chunk_len. */
+LINR_API int64_t linr_stream_chunk_count(int64_t n, int64_t chunk_symbols);
+LINR_API int64_t linr_stream_split_chunks(const uint8_t* in_h, int64_t in_len, int64_t n, int64_t chunk_symbols,
+                                 const uint8_t** chunk_h, int64_t* chunk_len, int64_t max_chunks);
 /* Those inputs computed on the DEVICE (csrc/ac_codes.hip), one launch on `stream`: what BinaryArithmeticCoding.encode
  * (models/module_utils.py:8-40) derives from the probabilities and occupancy of CNP.encode (models/upsample.py:224-239) on the
  * host.  probs [8][probs_ld] fp32 in [0, 1] (plane k = stage k, as linr_net_forward writes them), occ [n][occ_ld] fp32, 0 or
@@ -773,6 +800,21 @@ LINR_API size_t linr_rc_encode_ws_bytes(int32_t n_streams, int64_t total_cap);
 LINR_API int linr_rc_encode_codes(const uint16_t* c1_dev, const uint32_t* sym_dev, const linr_rc_stream* streams_host, int32_t n_streams,
                          uint8_t* out_dev, int64_t out_bytes, int64_t* len_dev, uint8_t* payload_dev, int64_t payload_bytes,
                          int64_t* offsets_dev, void* ws, size_t ws_bytes, void* stream);
+/* linr_rc_encode_codes for chunked stage streams, a wave per CHUNK: with chunk_symbols = S stream i has k_i =
+ * linr_stream_chunk_count(n, S) chunks, and payload[offsets[i] .. offsets[i + 1]) receives its final bytes - the LEB128 lengths of
+ * chunks 0 .. k_i - 2 and the chunks, or the lone chunk - byte for byte what the host coder's chunks joined give.  The table stays
+ * per stream and is checked as above; the chunks' descriptors are derived on the device from it and from the host's prefix sum of
+ * the k_i.  Chunk j of a stream with k > 1 owns the 2 n_j + 64 bytes at out_off + j (2 S + 64), so such a stream needs
+ * cap >= 2 n + 64 k (LINR_EINVAL otherwise); a stream of one chunk keeps its own cap.  len_dev[i] is the final length, or LINR_ENOSPC
+ * when one of its chunks needed more than its region (then it counts 0 in the offsets).  payload_bytes must reach the sum of the caps
+ * + 5 (chunks - streams), ws_bytes linr_rc_encode_chunked_ws_bytes(n_streams, chunks) (0 for n_chunks < n_streams or >= 2^31 - 1);
+ * ws 16-byte aligned.  Launches: the two uploads, the chunk table, rc_encode_k unchanged, a scan over the chunks, one over the
+ * streams, the pack.  No LDS, no atomics, no floating point.  chunk_symbols == 0 IS linr_rc_encode_codes. */
+LINR_API size_t linr_rc_encode_chunked_ws_bytes(int32_t n_streams, int64_t n_chunks);
+LINR_API int linr_rc_encode_codes_chunked(const uint16_t* c1_dev, const uint32_t* sym_dev, const linr_rc_stream* streams_host,
+                                 int32_t n_streams, int64_t chunk_symbols, uint8_t* out_dev, int64_t out_bytes, int64_t* len_dev,
+                                 uint8_t* payload_dev, int64_t payload_bytes, int64_t* offsets_dev, void* ws, size_t ws_bytes,
+                                 void* stream);
 
 /* ---- frame input (host) ----------------------------------------------------------------------------------------------
  * Body of an ASCII PLY (datautils/custom_dataset.py:9-14 read_ply_o3d - open3d's C++ reader - followed by :263-269, which keeps

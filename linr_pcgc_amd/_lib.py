@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('LINR_HIP_LIB') or os.path.join(_HERE, 'liblinr_hip.so
 LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 16
 LINR_FRAME_OCC_PADDED = 1
 LINR_PLY_TOKEN, LINR_PLY_COLUMNS, LINR_PLY_SHORT, LINR_PLY_RANGE = 1, 2, 4, 8
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -177,7 +177,13 @@ _PROTOS = {
     'linr_decode_scale_batch_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32]),
     'linr_decode_scale_batch': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
                                                c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_ptr]),
+    'linr_decode_scale_chunked': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
+                                                 c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr]),
+    'linr_decode_scale_batch_chunked': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr,
+                                                       c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr]),
     'linr_ac_decode_binary_batch': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i32]),
+    'linr_stream_chunk_count': (c_i64, [c_i64, c_i64]),
+    'linr_stream_split_chunks': (c_i64, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64]),
     'linr_ac_encode_cdf16': (c_i64, [c_ptr, c_i32, c_i32, c_ptr, c_i64, c_ptr, c_i64]),
     'linr_ac_decode_cdf16': (ctypes.c_int, [c_ptr, c_i32, c_i32, c_i64, c_ptr, c_i64, c_ptr]),
     'linr_ply_parse_ascii': (ctypes.c_int, [c_ptr, c_size, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr]),
@@ -189,6 +195,9 @@ _PROTOS = {
     'linr_ac_codes': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     'linr_rc_encode_ws_bytes': (c_size, [c_i32, c_i64]),
     'linr_rc_encode_codes': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    'linr_rc_encode_chunked_ws_bytes': (c_size, [c_i32, c_i64]),
+    'linr_rc_encode_codes_chunked': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i32, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_size,
+                                                    c_ptr]),
     'linr_ply_format_text_bytes': (c_size, [c_i64]),
     'linr_ply_format_ws_bytes': (c_size, [c_i64]),
     'linr_ply_format_ascii': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_size, c_ptr, c_size, c_ptr, c_ptr]),
@@ -236,7 +245,7 @@ class _Poisoned:
     """LINR_DEBUG_POISON=1 (test aid, tools/README.md): every GPU entry point is called with the LDS and vector registers of all
     CUs freshly filled with a NaN pattern (linr_debug_poison_now in front of it, linr_debug_poison(all classes) for the launches
     inside the executors).  The test suite must pass unchanged under it: no kernel may read on-chip state it did not write."""
-    _HOST = ('linr_ac_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host',
+    _HOST = ('linr_ac_', 'linr_stream_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host',
              'linr_params_fake_quant_ranges_host')
 
     def __init__(self, handle):

@@ -17,6 +17,7 @@ from .function_utils import pack_bitstream, unpack_bitstream
 from .model_codec import Model_Estimate, candidate_ranges, laplace_bits_est
 from .model_core import DeviceCoderSet, codes_word_off, encode_streams, encode_streams_codes
 from .module_utils import octree_level_obj, qscTensor, unique_sorted  # noqa: F401
+from .stream_chunks import SIDE_BITS as STREAM_CHUNK_SIDE_BITS, check_chunk
 
 # The probabilities the range coder sees must be reproduced BIT FOR BIT by the decoder, so the fp32 evaluation order of the
 # network is part of the stream format.  ARITH_VERSION names it: 1 = taps in ascending index order (rounds 1 and 2 up to the
@@ -53,12 +54,13 @@ def model_shape(model):
     return {'scale_num': int(model.scale_num), 'block_layers': int(model.block_layers), 'hidden_channel_conv': int(model.hidden)}
 
 
-def _code_frames_device(coded_model, gop, coder_group):
+def _code_frames_device(coded_model, gop, coder_group, chunk=0):
     """The frames' streams from the device range coder (linr_rc_encode_codes), coder_group frames per call.  The forwards stay on the
     caller's stream and write their code values and symbol planes (model.frame_codes) into group-wide buffers; the group is coded on a
     second stream behind an event, so group g is coded under the forwards of group g + 1.  Two buffer sets alternate: the forwards
     of group g + 2 wait (on the device) for the coding of group g, and the host has read group g's payload before that set is
-    launched again.  Returns (per frame the per-scale pack_bitstream containers, per frame the bits estimate on the device)."""
+    launched again.  chunk = S > 0: the chunked entry, a wave per chunk (DeviceCoderSet(chunk=)); the table stays per stream.
+    Returns (per frame the per-scale pack_bitstream containers, per frame the bits estimate on the device)."""
     frames = gop.frames
     dev = frames[0].device
     groups = [frames[i:i + coder_group] for i in range(0, len(frames), coder_group)]
@@ -77,9 +79,10 @@ def _code_frames_device(coded_model, gop, coder_group):
         plans.append((parts, np.asarray(desc, dtype=np.int64).reshape(-1, 3), cb, wb))
     n_sets = min(2, len(groups))
     max_c1, max_w = max(1, max(p[2] for p in plans)), max(1, max(p[3] for p in plans))
-    max_n, max_cap = max(len(p[1]) for p in plans), max(DeviceCoderSet.table(p[1])[1] for p in plans)
+    max_n, max_cap = max(len(p[1]) for p in plans), max(DeviceCoderSet.table(p[1], chunk)[1] for p in plans)
+    max_chunks = max(DeviceCoderSet.chunks(p[1], chunk) for p in plans)
     sets = [(torch.empty(max_c1, dtype=torch.uint16, device=dev), torch.empty(max_w, dtype=torch.uint32, device=dev),
-             DeviceCoderSet(max_n, max_cap, dev)) for _ in range(n_sets)]
+             DeviceCoderSet(max_n, max_cap, dev, chunk, max_chunks)) for _ in range(n_sets)]
     main = torch.cuda.current_stream()
     coder_stream = torch.cuda.Stream(device=dev)
     streams, bits_dev = [None] * len(groups), []
@@ -114,15 +117,17 @@ def _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found=None):
     low = enc_all_frame_low_xyz(gop)
     points = sum(gop.point_nums)
     occ_bits = 8 * sum(len(b) for fb in frames_bytes for b in fb)
+    # ... and the stream_chunk field, when the GOP has one, as 32 bits
+    side_bits = EXTRA_SIDE_BITS + (STREAM_CHUNK_SIDE_BITS if side_info.get('stream_chunk') else 0)
     extra = {} if found is None else {'qrange': {'trims': found['trims'], 'objective_bits': found['objective_bits'],
                                                  'chosen': found['trims'][found['chosen']], 'search_s': found['search_s']}}
     return {**extra, 'frames': frames_bytes, 'model_bin': comp['final_bytes'], 'side_info': side_info, 'low_enc_bytes': low,
             'point_num': points, 'bits_est': bits_est,
             # the five one-byte side-info fields this codec adds (arith_version, precision, scale_num, block_layers,
             # hidden_channel_conv: EXTRA_SIDE_BITS = 40) are counted with the model
-            'bpp': {'point_bpp': occ_bits / points, 'model_bpp': (comp['bit_real'] + EXTRA_SIDE_BITS) / points,
+            'bpp': {'point_bpp': occ_bits / points, 'model_bpp': (comp['bit_real'] + side_bits) / points,
                     'xyzlow_bpp': len(low) * 8 / points,
-                    'bpp_all': (occ_bits + comp['bit_real'] + EXTRA_SIDE_BITS + len(low) * 8) / points}}       # test_utils.py:146-157
+                    'bpp_all': (occ_bits + comp['bit_real'] + side_bits + len(low) * 8) / points}}       # test_utils.py:146-157
 
 
 def _coder_threads(n_threads):
@@ -184,7 +189,7 @@ def search_qrange(model, model_ori, gop, bitdepth=8, precision='f32', trims=None
 
 
 def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32', device_codes=False, device_coder=False,
-               coder_group=8, qrange_search=False, qrange_trims=None, qrange_frames=4):
+               coder_group=8, qrange_search=False, qrange_trims=None, qrange_frames=4, stream_chunk=0):
     """encoder.encode_one_gop: quantise the model, then per frame ONE forward over all scales and 8 x scales
     independent arithmetic-coded streams (thread pool).  precision='bf16': the forward runs on the bf16 / uint8-weight
     executor (BASELINE config[4]); the choice is recorded in side_info so that the decoder reproduces it.
@@ -198,9 +203,17 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     model_codec.DEFAULT_QRANGE_TRIMS) on qrange_frames evaluated frames (0: all); the winner goes through the model codec
     (compress_model(qrange=)) and everything behind it is unchanged: min_param / max_param carry the range, every decoder decodes the
     stream.  The result then has 'qrange' = {'trims', 'objective_bits', 'chosen' (the chosen trim), 'search_s'}, and - when there was
-    more than the plain range to choose from - side_info the informational 'qrange_trim' and 'qrange_candidates'."""
+    more than the plain range to choose from - side_info the informational 'qrange_trim' and 'qrange_candidates'.
+    stream_chunk=S > 0 (opt-in; a multiple of 64 in 64..2^24; stream_chunks.py has the format): every stage stream of more than S
+    symbols is cut into chunks of S symbols that are coded - and later decoded - independently, on the coder threads or a wave each,
+    at a few bytes per chunk.  The decoder needs S: side_info gets 'stream_chunk', counted as 32 bits in model_bpp / bpp_all, and a
+    build that does not know the field cannot decode such a GOP.  The three coder paths write the same bytes at the same S; a GOP
+    whose streams all have at most S symbols differs from the plain one in that field only.  hidden_channel_conv 8 only."""
     if device_coder and not 1 <= int(coder_group) <= 64:
         raise ValueError('coder_group must be in 1..64, got %r' % (coder_group,))
+    stream_chunk = check_chunk(stream_chunk)
+    if stream_chunk and getattr(model, '_wide', None) is not None:
+        raise ValueError('stream_chunk needs hidden_channel_conv 8: the widths 16 and 32 decode stage-wise in Python, without chunks')
     n_threads = _coder_threads(n_threads)
     found = search_qrange(model, model_ori, gop, bitdepth, precision, qrange_trims, qrange_frames) if qrange_search else None
     # trim 0 is the vector's own (min, max): today's call, to the letter
@@ -214,6 +227,8 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
         side_info['precision'] = precision
     side_info['arith_version'] = ARITH_VERSION
     side_info.update(model_shape(model))
+    if stream_chunk:
+        side_info['stream_chunk'] = stream_chunk
     # informational (the decoder does not need it): which training executor produced the coded model
     side_info['train_precision'] = getattr(model, 'train_precision', 'f32')
     # ... and, when the driver says so, how many of its last epochs were quantisation-aware (overfit_gop qat_epochs=): not counted
@@ -226,7 +241,7 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
         side_info['qrange_trim'] = int(found['trims'][found['chosen']])
         side_info['qrange_candidates'] = len(found['trims'])
     if device_coder:
-        frames_bytes, bits_dev = _code_frames_device(coded_model, gop, int(coder_group))
+        frames_bytes, bits_dev = _code_frames_device(coded_model, gop, int(coder_group), stream_chunk)
         return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found)
     # Pipeline: the GPU forward + D2H of frame i+1 runs while host workers range-code earlier frames (the coder's C call
     # releases the GIL).  A frame has 8 x scales independent streams, but the 8 streams of its finest scale carry 73 % of the
@@ -247,7 +262,7 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
                 ps.append(p_host[k, a:b])
                 ss.append(occ_host[k, sa:sb])
                 ns.append(b - a)
-        streams = encode_streams_codes(ps, ss, ns, per_job) if device_codes else encode_streams(ps, ss, per_job)
+        streams = encode_streams_codes(ps, ss, ns, per_job, stream_chunk) if device_codes else encode_streams(ps, ss, per_job, stream_chunk)
         return [pack_bitstream(streams[8 * i:8 * i + 8]) for i in range(n_scales)]
 
     # Device side: forward of frame i+1 on the caller's stream while a copy stream moves the probabilities (fp32) and the
@@ -302,18 +317,21 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found)
 
 
-def decode_one_frame(model, frame_enc_bytes, xyz_low):
+def decode_one_frame(model, frame_enc_bytes, xyz_low, chunk=0, n_threads=1):
     """decoder.decode_one_frame (decoder.py:153-176): coarse to fine, 8 AC-decoded stages per scale.  A scale is ONE call into the
     library (model.decode_scale -> linr_decode_scale: kernel map, the 7-neighbour occupancy read off it instead of
     qscTensor.set_offset_tensor's searches, the 8 stage forwards with their host round trips, upper_layer), so the Python side of a
-    frame is seven buffer allocations."""
+    frame is seven buffer allocations.  chunk = S > 0: the stage streams are chunked (side_info's stream_chunk) and a stage's chunks are
+    decoded on n_threads host threads."""
     if getattr(model, '_wide', None) is not None:          # hidden_channel_conv 16 / 32: no single-call decoder scale
+        if chunk:
+            raise ValueError('chunked stage streams decode with hidden_channel_conv 8 only')
         return decode_one_frame_stagewise(model, frame_enc_bytes, xyz_low)
     lowx = unique_sorted(xyz_low)
     bits = max(1, int(xyz_low.max()).bit_length()) if xyz_low.numel() else 1       # coordinates of the coarsest level
     for s_idx in range(len(frame_enc_bytes) - 1, -1, -1):
         bits = min(bits + 1, 21)
-        lowx = model.decode_scale(lowx, s_idx, frame_enc_bytes[s_idx], bits)
+        lowx = model.decode_scale(lowx, s_idx, frame_enc_bytes[s_idx], bits, chunk, n_threads)
     return {'dec_coord': lowx}
 
 
@@ -332,20 +350,21 @@ LOCKSTEP_MAX_FRAMES = 64                  # LINR_DECODE_MAX_FRAMES of include/li
 LOCKSTEP_MAX_ROWS = (1 << 26) - 64        # rows of one lock-step call: the compressed kernel map's 32-bit bound (linr_cmap_fits32)
 
 
-def _lockstep_scale(model, lows, s_idx, encs, n_threads):
+def _lockstep_scale(model, lows, s_idx, encs, n_threads, chunk=0):
     """One scale of a lock-step group; a group whose levels together pass the row bound of one call is halved."""
     if len(lows) > 1 and sum(int(c.shape[0]) for c in lows) > LOCKSTEP_MAX_ROWS:
         h = len(lows) // 2
-        return _lockstep_scale(model, lows[:h], s_idx, encs[:h], n_threads) + _lockstep_scale(model, lows[h:], s_idx, encs[h:], n_threads)
-    return model.decode_scale_batch(lows, s_idx, encs, n_threads)
+        return (_lockstep_scale(model, lows[:h], s_idx, encs[:h], n_threads, chunk) +
+                _lockstep_scale(model, lows[h:], s_idx, encs[h:], n_threads, chunk))
+    return model.decode_scale_batch(lows, s_idx, encs, n_threads, chunk)
 
 
-def decode_frames_lockstep(model, frames_enc_bytes, xyz_lows, n_threads=8):
+def decode_frames_lockstep(model, frames_enc_bytes, xyz_lows, n_threads=8, chunk=0):
     """decode_one_frame for a group of frames with the same number of scales, in lock step: coarse to fine, every scale of the whole
     group is ONE call into the library (model.decode_scale_batch -> linr_decode_scale_batch).  Returns the frames' coordinates."""
     lows = [unique_sorted(x) for x in xyz_lows]
     for s_idx in range(len(frames_enc_bytes[0]) - 1, -1, -1):
-        lows = _lockstep_scale(model, lows, s_idx, [f[s_idx] for f in frames_enc_bytes], n_threads)
+        lows = _lockstep_scale(model, lows, s_idx, [f[s_idx] for f in frames_enc_bytes], n_threads, chunk)
     return lows
 
 
@@ -368,6 +387,10 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
     flight, each on its own stream.  Models of hidden_channel_conv 16 / 32 ignore it.  The streams are the same either way.
     `timing` (a dict) receives 'setup_s': the once-per-GOP part (model.bin -> parameters, the coarsest coordinates), and with
     lockstep 'lockstep_ws_bytes': the largest device workspace of a lock-step call.
+    side_info's 'stream_chunk' = S (absent or 0: nothing changes): the stage streams are chunked (stream_chunks.py) and a stage's
+    chunks are range-decoded in parallel - with lockstep on the group's threads as ever, and per frame on n_threads threads, too
+    (default: the cores this process may use, at most 16, divided by `workers`).  A stream whose chunk header does not hold raises
+    LinrError.
     Frames are independent once the model is known; with workers > 1 they are decoded by a host thread pool, each
     thread on its own HIP stream (a frame's own chain - 56 stage forwards with a serial range decode in between - cannot
     be parallelised, but the range decoding of one frame overlaps the stage forwards and copies of the others; the
@@ -388,6 +411,9 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
     side['final_bytes'] = enc['model_bin']
     model, _ = Model_Estimate().decompress_model(model_ori, side)
     model.inference_precision = side.get('precision', 'f32')
+    chunk = check_chunk(side.get('stream_chunk', 0))
+    if chunk and getattr(model, '_wide', None) is not None:
+        raise ValueError('chunked stage streams decode with hidden_channel_conv 8 only')
     lows, mins = dec_all_frame_low_xyz(enc['low_enc_bytes'])
     todo = list(range(len(enc['frames'])) if frames is None else frames)
     if timing is not None:
@@ -395,16 +421,18 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
             torch.cuda.synchronize()
         timing['setup_s'] = time.time() - t_setup
 
+    per_frame = max(1, _coder_threads(n_threads) // max(1, int(workers))) if chunk else 1
+
     def one(i):
         xyz_low = torch.tensor(lows[i].astype(np.int32), device=device)
-        dec = decode_one_frame(model, list(enc['frames'][i]), xyz_low)['dec_coord']
+        dec = decode_one_frame(model, list(enc['frames'][i]), xyz_low, chunk, per_frame)['dec_coord']
         return dec + torch.tensor(mins[i], device=device, dtype=torch.int32)
 
     if getattr(model, '_wide', None) is not None:
         workers = 1          # the channel-blocked executor keeps per-call state on the model: frames one after the other
         lockstep = 0
     if lockstep and lockstep > 0 and todo:
-        out = _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, min(int(lockstep), LOCKSTEP_MAX_FRAMES), n_threads)
+        out = _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, min(int(lockstep), LOCKSTEP_MAX_FRAMES), n_threads, chunk)
         if timing is not None:
             timing['lockstep_ws_bytes'] = int(getattr(model, '_lockstep_ws_peak', 0))          # the largest workspace of a call
         return out
@@ -434,7 +462,7 @@ def _map_on_streams(fn, items, workers):
         return list(pool.map(job, items))
 
 
-def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads):
+def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads, chunk=0):
     n_threads = _coder_threads(n_threads)
     groups = lockstep_groups(todo, {i: len(enc['frames'][i]) for i in set(todo)}, lockstep)
     workers = max(1, min(int(workers), len(groups)))
@@ -442,7 +470,7 @@ def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep
 
     def one(group):
         xyz_lows = [torch.tensor(lows[i].astype(np.int32), device=device) for i in group]
-        dec = decode_frames_lockstep(model, [list(enc['frames'][i]) for i in group], xyz_lows, per_group)
+        dec = decode_frames_lockstep(model, [list(enc['frames'][i]) for i in group], xyz_lows, per_group, chunk)
         return [d + torch.tensor(mins[i], device=device, dtype=torch.int32) for i, d in zip(group, dec)]
 
     return [x for out in _map_on_streams(one, groups, workers) for x in out]

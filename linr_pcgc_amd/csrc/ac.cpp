@@ -375,3 +375,53 @@ extern "C" int linr_ac_encode_binary_codes_batch(const uint16_t* const* c1_h, co
     return encode_batch(n_streams, n_threads, out_len,
                         [&](int i) { return linr_ac_encode_binary_codes(c1_h[i], sym_h[i], n[i], out_h[i], cap[i]); });
 }
+
+// ---- chunked stage streams -----------------------------------------------------------------------------------------------------
+// A stage stream of n symbols coded with chunk size S (a multiple of 64 in 64..2^24) has k = max(1, ceil(n / S)) chunks, each the
+// stream of its own symbols [j S, min((j + 1) S, n)).  k == 1: the stream is that one chunk.  k > 1: the byte lengths of chunks
+// 0 .. k - 2 as unsigned LEB128 (at most 5 bytes each), then the chunks; the last one takes the bytes that remain.
+extern "C" int64_t linr_stream_chunk_count(int64_t n, int64_t chunk_symbols) {
+    if (n < 0 || chunk_symbols < 0) return LINR_EINVAL;
+    if (chunk_symbols == 0) return 1;
+    if (chunk_symbols % 64 != 0 || chunk_symbols > ((int64_t)1 << 24)) return LINR_EINVAL;
+    return n <= chunk_symbols ? 1 : (n + chunk_symbols - 1) / chunk_symbols;
+}
+
+extern "C" int64_t linr_stream_split_chunks(const uint8_t* in_h, int64_t in_len, int64_t n, int64_t chunk_symbols,
+                                            const uint8_t** chunk_h, int64_t* chunk_len, int64_t max_chunks) {
+    const int64_t k = linr_stream_chunk_count(n, chunk_symbols);
+    if (k < 0) return k;
+    if (in_len < 0 || (in_len > 0 && !in_h) || !chunk_h || !chunk_len) return LINR_EINVAL;
+    if (k > max_chunks) return LINR_ENOSPC;
+    // first the whole header, reading no byte at or behind in_h + in_len; only a header that holds writes anything
+    int64_t pos = 0, sum = 0;
+    for (int64_t j = 0; j + 1 < k; ++j) {
+        uint64_t v = 0;
+        for (int b = 0;; ++b) {
+            if (b == 5 || pos >= in_len) return LINR_EINVAL;          // a varint of more than 5 bytes; a truncated one
+            const uint8_t byte = in_h[pos++];
+            v |= (uint64_t)(byte & 0x7Fu) << (7 * b);
+            if (!(byte & 0x80u)) break;
+        }
+        sum += (int64_t)v;                                            // v < 2^35, k < 2^58: no overflow
+        if (sum > in_len) return LINR_EINVAL;
+    }
+    if (sum > in_len - pos) return LINR_EINVAL;                       // lengths that exceed the bytes present
+    const int64_t header = pos;
+    int64_t at = header;
+    pos = 0;
+    for (int64_t j = 0; j + 1 < k; ++j) {
+        uint64_t v = 0;
+        for (int b = 0;; ++b) {
+            const uint8_t byte = in_h[pos++];
+            v |= (uint64_t)(byte & 0x7Fu) << (7 * b);
+            if (!(byte & 0x80u)) break;
+        }
+        chunk_h[j] = in_h + at;
+        chunk_len[j] = (int64_t)v;
+        at += (int64_t)v;
+    }
+    chunk_h[k - 1] = in_len > 0 ? in_h + at : in_h;
+    chunk_len[k - 1] = in_len - at;
+    return k;
+}

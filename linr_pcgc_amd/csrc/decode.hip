@@ -11,6 +11,7 @@
 #include "layout.h"
 #include "prof.h"
 #include <hipcub/hipcub.hpp>
+#include <vector>
 
 #define TRY(e) do { int rc_ = (e); if (rc_) return rc_; } while (0)
 
@@ -154,36 +155,84 @@ __global__ __launch_bounds__(LINR_BLOCK) void keys_to_coord_k(const uint64_t* __
     xyz[3 * i + 2] = (int32_t)(k & msk);
 }
 
+// The range decoders of the 8 stages: entry e of stage k decodes n[e] symbols from in[e] / len[e] against p[e] into s[e], the
+// entries [first[k], first[k + 1]).  Without chunks (chunk_symbols 0) an entry is a segment's whole stream k; with them a stream of
+// more than chunk_symbols symbols is cut by the checked parser (linr_stream_split_chunks) and every chunk is an entry of its own, its
+// rows those behind the chunks in front of it.  An empty segment is left out with its streams unread.
+#define RC_THREAD_SYMBOLS 65536
+struct StagePlan {
+    std::vector<const float*> p;
+    std::vector<uint8_t*> s;
+    std::vector<const uint8_t*> in;
+    std::vector<int64_t> n, len;
+    int64_t first[9];
+    int64_t symbols[8];             // of stage k
+    bool chunked;
+};
+
+int plan_stages(const int64_t* seg_off_h, int n_seg, const uint8_t* const* streams_h, const int64_t* stream_len_h, int64_t chunk_symbols,
+                const float* p_pinned, uint8_t* s_pinned, StagePlan& plan) {
+    std::vector<const uint8_t*> cp;
+    std::vector<int64_t> cl;
+    plan.chunked = chunk_symbols > 0;
+    for (int k = 0; k < 8; ++k) {
+        plan.first[k] = (int64_t)plan.n.size();
+        plan.symbols[k] = 0;
+        for (int i = 0; i < n_seg; ++i) {
+            const int64_t r0 = seg_off_h[i], n = seg_off_h[i + 1] - r0;
+            if (n <= 0) continue;
+            const int64_t nc = linr_stream_chunk_count(n, chunk_symbols);
+            if (nc < 0) return (int)nc;
+            cp.resize((size_t)nc);
+            cl.resize((size_t)nc);
+            const int64_t got = linr_stream_split_chunks(streams_h[i * 8 + k], stream_len_h[i * 8 + k], n, chunk_symbols, cp.data(),
+                                                         cl.data(), nc);
+            if (got < 0) return (int)got;
+            plan.symbols[k] += n;
+            for (int64_t j = 0; j < nc; ++j) {
+                const int64_t a = j * chunk_symbols;              // (one chunk: a = 0 whatever chunk_symbols is)
+                plan.p.push_back(p_pinned + r0 + a);
+                plan.s.push_back(s_pinned + r0 + a);
+                plan.n.push_back(nc == 1 ? n : (n - a < chunk_symbols ? n - a : chunk_symbols));
+                plan.in.push_back(cp[(size_t)j]);
+                plan.len.push_back(cl[(size_t)j]);
+            }
+        }
+    }
+    plan.first[8] = (int64_t)plan.n.size();
+    return 0;
+}
+
 // The 8 decode stages of the frame object f, whose rows are n_seg segments (seg_off_h, HOST) with 8 streams each.  The stage's forward
-// checks f (linr_frame_layout) before seg_off_h is read, so that may be f's own row_off_h.  An empty segment is left out with its
-// streams unread.  The range decoders return the first failing segment's code (in order on this thread with n_threads 1); they
-// decode the segments behind it, too, but those bytes stay in s_pinned: the call returns before anything more is launched.
+// checks f (linr_frame_layout) before seg_off_h is read, so that may be f's own row_off_h: a caller that has checked its segments
+// itself hands in the plan it made of them (`ready`), otherwise the plan is made behind the first forward.  The range decoders return
+// the first failing entry's code (in order on this thread with n_threads 1); they decode the entries behind it, too, but those bytes
+// stay in s_pinned: the call returns before anything more is launched.
 int decode_stages(const linr_frame* f, const float* params, const uint8_t* codes, float min_param, float max_param, void* arena,
                   size_t arena_bytes, const int64_t* seg_off_h, int n_seg, const uint8_t* const* streams_h,
                   const int64_t* stream_len_h, float* probs, float* p_pinned, uint8_t* s_pinned, uint8_t* s_dev, int n_threads,
-                  hipStream_t s) {
+                  const StagePlan* ready, hipStream_t s) {
     const int64_t R = f->rows;
     if (R == 0) return 0;
     float* occ = const_cast<float*>(f->occ);
-    static_assert(LINR_DECODE_MAX_FRAMES >= MAX_SCALES, "the per-segment arrays also hold a frame's scales");
-    const float* p_h[LINR_DECODE_MAX_FRAMES];
-    uint8_t* s_h[LINR_DECODE_MAX_FRAMES];
-    const uint8_t* in_h[LINR_DECODE_MAX_FRAMES];
-    int64_t n_h[LINR_DECODE_MAX_FRAMES], len_h[LINR_DECODE_MAX_FRAMES];
+    StagePlan own;
     for (int k = 0; k < 8; ++k) {
         if (codes) TRY(linr_net_forward_bf16(f, codes, min_param, max_param, arena, arena_bytes, k, k + 1, probs, nullptr, s));
         else TRY(linr_net_forward(f, params, (float*)arena, arena_bytes, k, k + 1, probs, nullptr, s));
         TRY(linr_hip_rc(hipMemcpyAsync(p_pinned, probs + (int64_t)k * R, (size_t)R * sizeof(float), hipMemcpyDeviceToHost, s)));
         TRY(linr_hip_rc(hipStreamSynchronize(s)));
-        int m = 0;
-        for (int i = 0; i < n_seg; ++i) {
-            const int64_t r0 = seg_off_h[i], n = seg_off_h[i + 1] - r0;
-            if (n <= 0) continue;
-            p_h[m] = p_pinned + r0; s_h[m] = s_pinned + r0; n_h[m] = n;
-            in_h[m] = streams_h[i * 8 + k]; len_h[m] = stream_len_h[i * 8 + k];
-            ++m;
+        if (!ready) {
+            TRY(plan_stages(seg_off_h, n_seg, streams_h, stream_len_h, 0, p_pinned, s_pinned, own));
+            ready = &own;
         }
-        TRY(linr_ac_decode_binary_batch(p_h, n_h, in_h, len_h, m, s_h, n_threads));
+        const int64_t e = ready->first[k];
+        // The batch entry starts its threads anew in every call, at some tens of microseconds each, so chunks get a thread per
+        // RC_THREAD_SYMBOLS symbols of the stage (about 0.2 ms of decoding), not one per chunk: small scales stay on this thread.
+        // (Without chunks the caller's count holds, as ever.)
+        int threads = n_threads;
+        if (ready->chunked && threads > 1 + ready->symbols[k] / RC_THREAD_SYMBOLS) threads = (int)(1 + ready->symbols[k] / RC_THREAD_SYMBOLS);
+        TRY(linr_ac_decode_binary_batch(ready->p.data() + e, ready->n.data() + e, ready->in.data() + e, ready->len.data() + e,
+                                        (int32_t)(ready->first[k + 1] - e), ready->s.data() + e, threads));
         TRY(linr_hip_rc(hipMemcpyAsync(s_dev, s_pinned, (size_t)R, hipMemcpyHostToDevice, s)));
         occ_col_from_u8_k<<<linr_grid(R, LINR_BLOCK), LINR_BLOCK, 0, s>>>(s_dev, R, occ + k);
         TRY(linr_launch_rc());
@@ -200,7 +249,7 @@ extern "C" int linr_net_decode_stages(const linr_frame* f, const float* params, 
     if (!f || !arena || !streams_h || !stream_len_h || !probs || !p_pinned || !s_pinned || !s_dev || !f->occ) return LINR_EINVAL;
     if (!codes && !params) return LINR_EINVAL;
     return decode_stages(f, params, codes, min_param, max_param, arena, arena_bytes, f->row_off_h, f->n_scales, streams_h, stream_len_h,
-                         probs, p_pinned, s_pinned, s_dev, 1, (hipStream_t)stream);
+                         probs, p_pinned, s_pinned, s_dev, 1, nullptr, (hipStream_t)stream);
 }
 
 // The same for a frame of ONE scale whose rows are the levels of n_seg frames back to back (linr_decode_scale_batch): a stage is one
@@ -217,7 +266,7 @@ extern "C" int linr_net_decode_stages_segments(const linr_frame* f, const float*
     for (int i = 0; i < n_seg; ++i)
         if (seg_off_h[i + 1] < seg_off_h[i]) return LINR_EINVAL;
     return decode_stages(f, params, codes, min_param, max_param, arena, arena_bytes, seg_off_h, n_seg, streams_h, stream_len_h, probs,
-                         p_pinned, s_pinned, s_dev, n_threads, (hipStream_t)stream);
+                         p_pinned, s_pinned, s_dev, n_threads, nullptr, (hipStream_t)stream);
 }
 
 extern "C" size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16) {
@@ -225,11 +274,11 @@ extern "C" size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, in
     return layout(n, block_layers, bf16 ? 1 : 0, false).total + 256;
 }
 
-extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
-                                 int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
-                                 const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
-                                 float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
-                                 void* stream) {
+extern "C" int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                                         int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                                         const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                                         float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
+                                         int64_t chunk_symbols, int32_t n_threads, void* stream) {
     if (n < 0 || !child_n_h || child_bits < 1 || child_bits > 21 || block_layers < 1) return LINR_EINVAL;
     *child_n_h = 0;
     if (n == 0) return 0;
@@ -242,9 +291,12 @@ extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
     ScaleFrame sf;
+    sf.row_off[0] = 0; sf.row_off[1] = n;
+    StagePlan plan;                 // a malformed chunk header is refused here, in front of the first launch
+    TRY(plan_stages(sf.row_off, 1, streams_h, stream_len_h, chunk_symbols, p_pinned, s_pinned, plan));
     TRY(scale_prologue(coord, n, nullptr, 0, scale_idx, model_scale_num, block_layers, base, w, sf, s));
     TRY(decode_stages(&sf.f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, sf.row_off, 1, streams_h, stream_len_h,
-                      (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), 1, s));
+                      (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, &plan, s));
     // upper_layer: children of the occupied octants, sorted x-major
     const float* occ = sf.f.occ;
     char* cbase = base + w.child;
@@ -268,6 +320,15 @@ extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_
     }
     *child_n_h = total;
     return linr_launch_rc();
+}
+
+extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                                 int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                                 const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                                 float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
+                                 void* stream) {
+    return linr_decode_scale_chunked(coord, n, scale_idx, model_scale_num, block_layers, child_bits, params, codes, min_param, max_param,
+                                     streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap, child_n_h, 0, 1, stream);
 }
 
 // ---- the same for the frames of a GOP in lock step: one scale of n_frames frames per call, children without a sort ------------------
@@ -428,11 +489,12 @@ extern "C" size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_fr
     return layout(n_total, block_layers, bf16 ? 1 : 0, true).total + 256;
 }
 
-extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
-                                       int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
-                                       float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
-                                       void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
-                                       int64_t child_cap, int64_t* child_off_h, int32_t n_threads, void* stream) {
+extern "C" int linr_decode_scale_batch_chunked(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                               int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                               float min_param, float max_param, const uint8_t* const* streams_h,
+                                               const int64_t* stream_len_h, void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned,
+                                               int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h, int32_t n_threads,
+                                               int64_t chunk_symbols, void* stream) {
     LinrSegTab tab;
     int64_t n = 0;
     int rc = linr_seg_tab(seg_off_h, n_frames, &tab, &n);
@@ -449,10 +511,22 @@ extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
     ScaleFrame sf;
+    StagePlan plan;                 // a malformed chunk header is refused here, in front of the first launch
+    TRY(plan_stages(seg_off_h, n_frames, streams_h, stream_len_h, chunk_symbols, p_pinned, s_pinned, plan));
     TRY(scale_prologue(coord, n, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, base, w, sf, s));
     TRY(decode_stages(&sf.f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, seg_off_h, n_frames, streams_h,
-                      stream_len_h, (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, s));
+                      stream_len_h, (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, &plan, s));
     return children_segments(coord, sf.f.occ, tab, n, n_frames, child_xyz, child_cap, child_off_h, base + w.child, w.scan, s);
+}
+
+extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                       int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                       float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                                       void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
+                                       int64_t child_cap, int64_t* child_off_h, int32_t n_threads, void* stream) {
+    return linr_decode_scale_batch_chunked(coord, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, params, codes, min_param,
+                                           max_param, streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap,
+                                           child_off_h, n_threads, 0, stream);
 }
 
 // ---- sorted unique coordinate list, optionally of the parents (coords >> shift); one octree level as one call ------------------------

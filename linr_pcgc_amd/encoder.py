@@ -15,6 +15,7 @@ from .custom_dataset import Read_Data_with_cache
 from .model_codec import Model_Estimate
 from .test_utils import enc_all_frame_low_xyz, write_bin_file
 from . import codec
+from .stream_chunks import SIDE_BITS, check_chunk
 
 
 def gop_bounds(gop_name):
@@ -24,7 +25,8 @@ def gop_bounds(gop_name):
 
 def encode(enc_args):
     """encoder.py:20-54.  enc_args: 'outputdir' (holds <gop>/model.pth), 'gop_names', 'Gen_Model', 'dataset', 'encode_dir'; optional
-    'qrange_search' (default off), 'qrange_trims', 'qrange_frames': the rate-checked quantiser range of codec.encode_gop."""
+    'qrange_search' (default off), 'qrange_trims', 'qrange_frames': the rate-checked quantiser range of codec.encode_gop; optional
+    'stream_chunk' (default 0 = off): its chunked stage streams."""
     os.makedirs(enc_args['encode_dir'], exist_ok=True)
     for gop_name in enc_args['gop_names']:
         first, last = gop_bounds(gop_name)
@@ -33,16 +35,18 @@ def encode(enc_args):
                         'model_path': os.path.join(enc_args['outputdir'], gop_name, 'model.pth'),
                         'result_dir': os.path.join(enc_args['encode_dir'], gop_name), 'reading_data': reading,
                         'low_enc_bytes': enc_all_frame_low_xyz(reading, last - first + 1),
-                        **{k: enc_args[k] for k in ('qrange_search', 'qrange_trims', 'qrange_frames') if k in enc_args}})
+                        **{k: enc_args[k] for k in ('qrange_search', 'qrange_trims', 'qrange_frames', 'stream_chunk') if k in enc_args}})
 
 
-def encode_one_frame(model, all_inargs, ori=None):
-    """encoder.py:158-176: model.encode on every scale of a frame."""
+def encode_one_frame(model, all_inargs, ori=None, stream_chunk=0):
+    """encoder.py:158-176: model.encode on every scale of a frame (stream_chunk: codec.encode_gop's, handed to model.encode)."""
     all_bit, all_bytes = 0, []
     for inargs in all_inargs:
         putin = dict(inargs)
         qsc = inargs['xyzqsc_t']
         putin['coord'], putin['offset_tensor'] = qsc.get_coord(), qsc.get_offset_tensor()
+        if stream_chunk:
+            putin['stream_chunk'] = stream_chunk
         ret = model.encode(putin)
         all_bit += ret['bits']
         all_bytes.append(ret['enc_bytes'])
@@ -51,14 +55,18 @@ def encode_one_frame(model, all_inargs, ori=None):
 
 def encode_one_gop(inargs):
     """encoder.py:57-156.  Returns {'bpp_all', 'point_bpp', 'model_bpp', 'xyzlow_bpp'} (test_utils.py:146-157's accounting; the
-    two extra side-info fields of this codec counted with the model)."""
+    two extra side-info fields of this codec counted with the model).  inargs['stream_chunk'] = S > 0: the chunked stage streams of
+    codec.encode_gop (side_info's 'stream_chunk', 32 bits more with the model; hidden_channel_conv 8 only)."""
     low = inargs.get('low_enc_bytes')
     if low is None:
         raise ValueError('low_enc_bytes is None')
+    stream_chunk = check_chunk(inargs.get('stream_chunk', 0))
     gen = inargs['Gen_Model']
     ckpt = torch.load(inargs['model_path'], map_location='cpu', weights_only=False)
     trained = gen()
     trained.load_state_dict(ckpt['model'])
+    if stream_chunk and getattr(trained, '_wide', None) is not None:
+        raise ValueError('stream_chunk needs hidden_channel_conv 8: the widths 16 and 32 decode stage-wise in Python, without chunks')
     bitdepth = ckpt.get('bitdepth') or 8
     result_dir = inargs['result_dir']
     bins_dir = os.path.join(result_dir, 'bins')
@@ -87,6 +95,8 @@ def encode_one_gop(inargs):
     side_info = {'mu': packed['mu'], 'b': packed['b'], 'min_param': packed['min_param'], 'max_param': packed['max_param'],
                  'enc_mode': packed['enc_mode'], 'bitdepth': bitdepth, 'arith_version': codec.ARITH_VERSION}
     side_info.update(codec.model_shape(trained))
+    if stream_chunk:
+        side_info['stream_chunk'] = stream_chunk
     if found is not None and len(found['trims']) > 1:
         side_info['qrange_trim'] = int(found['trims'][found['chosen']])
         side_info['qrange_candidates'] = len(found['trims'])
@@ -96,10 +106,10 @@ def encode_one_gop(inargs):
     bits, points = 0, 0
     for frame_idx in range(inargs['frame_num']):
         frame = inargs['reading_data'][frame_idx]
-        out = encode_one_frame(model, frame['all_input_info'], frame.get('ori'))
+        out = encode_one_frame(model, frame['all_input_info'], frame.get('ori'), stream_chunk)
         write_bin_file(frame_idx, out['all_bytes'], bins_dir)
         bits += out['all_bit']
         points += frame['point_num']
-    model_bits = packed['bit_real'] + codec.EXTRA_SIDE_BITS
+    model_bits = packed['bit_real'] + codec.EXTRA_SIDE_BITS + (SIDE_BITS if stream_chunk else 0)
     return {'point_bpp': bits / points, 'model_bpp': model_bits / points, 'xyzlow_bpp': len(low) * 8 / points,
             'bpp_all': (bits + model_bits + len(low) * 8) / points}

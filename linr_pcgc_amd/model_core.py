@@ -21,6 +21,7 @@ from torch import nn
 from . import _lib, engine, ops
 from .function_utils import pack_bitstream, unpack_bitstream
 from .module_utils import BinaryArithmeticCoding, PointwiseMLP
+from .stream_chunks import check_chunk, chunk_count, chunk_entries, join_chunks
 from .upsample import CNP
 
 
@@ -324,8 +325,11 @@ class LINR_PCGC_Model(nn.Module):
         probs, _ = self.frame_probs(frame)
         p_host = probs.cpu().numpy()
         occ_host = frame.occ.t().contiguous().cpu().numpy().astype(np.uint8)
-        streams = encode_streams([p_host[k] for k in range(8)], [occ_host[k] for k in range(8)])
-        if DBG:
+        chunk = check_chunk(in_args.get('stream_chunk', 0))          # opt-in chunked stage streams (stream_chunks); width 8 only
+        if chunk and self._wide is not None:
+            raise ValueError('stream_chunk needs hidden_channel_conv 8: the widths 16 and 32 decode stage-wise in Python, without chunks')
+        streams = encode_streams([p_host[k] for k in range(8)], [occ_host[k] for k in range(8)], chunk=chunk)
+        if DBG and not chunk:
             bac = BinaryArithmeticCoding()
             for k in range(8):
                 assert (bac.decode(p_host[k], streams[k]).numpy() == occ_host[k]).all()
@@ -362,10 +366,12 @@ class LINR_PCGC_Model(nn.Module):
                 child.data_ptr(), 8 * n), need, (child, ws, bufs)
 
     @torch.no_grad()
-    def decode_scale(self, coord, scale_idx, enc_bytes, child_bits):
+    def decode_scale(self, coord, scale_idx, enc_bytes, child_bits, chunk=0, n_threads=1):
         """One scale of decoder.decode_one_frame (decoder.py:153-176) as ONE C call that does not hold the GIL
         (linr_decode_scale): kernel map of `coord` (int32 [n,3] on the GPU, sorted x-major), the 8 decode stages against the
-        packed stream `enc_bytes`, octree_level.upper_layer.  Returns the next finer level's coordinates (int32 [m,3])."""
+        packed stream `enc_bytes`, octree_level.upper_layer.  Returns the next finer level's coordinates (int32 [m,3]).
+        chunk = S > 0: the stage streams are chunked (stream_chunks) and a stage's chunks are decoded on `n_threads` host threads
+        (linr_decode_scale_chunked)."""
         L = _lib.lib()
         n = int(coord.shape[0])
         if n == 0:
@@ -373,16 +379,22 @@ class LINR_PCGC_Model(nn.Module):
         coord = coord.contiguous()
         shared, _, keep = self._decode_scale_args(L.linr_decode_scale_ws_bytes, (n,), coord, unpack_bitstream(enc_bytes))
         m = ctypes.c_int64(0)
-        _lib.check(L.linr_decode_scale(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits), *shared,
-                                       ctypes.byref(m), torch.cuda.current_stream().cuda_stream), 'linr_decode_scale')
+        if chunk:
+            _lib.check(L.linr_decode_scale_chunked(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits),
+                                                   *shared, ctypes.byref(m), int(chunk), int(n_threads),
+                                                   torch.cuda.current_stream().cuda_stream), 'linr_decode_scale_chunked')
+        else:
+            _lib.check(L.linr_decode_scale(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits), *shared,
+                                           ctypes.byref(m), torch.cuda.current_stream().cuda_stream), 'linr_decode_scale')
         return keep[0][:m.value]
 
     @torch.no_grad()
-    def decode_scale_batch(self, coords_list, scale_idx, enc_bytes_list, n_threads=8):
+    def decode_scale_batch(self, coords_list, scale_idx, enc_bytes_list, n_threads=8, chunk=0):
         """decode_scale for several frames in lock step as ONE C call (linr_decode_scale_batch): the frames' levels `coords_list`
         (int32 [n_i,3] on the GPU, each sorted x-major) are one row space whose kernel map never links two frames, every decode stage
         is one launch set and one copy each way for all of them, their range decoders run on `n_threads` host threads, and the
-        children come from prefix sums instead of a sort.  Returns the list of the next finer levels' coordinates (int32 [m_i,3])."""
+        children come from prefix sums instead of a sort.  Returns the list of the next finer levels' coordinates (int32 [m_i,3]).
+        chunk = S > 0: the stage streams are chunked (stream_chunks; linr_decode_scale_batch_chunked)."""
         L = _lib.lib()
         nf = len(coords_list)
         if nf < 1 or nf > 64 or len(enc_bytes_list) != nf:
@@ -400,9 +412,14 @@ class LINR_PCGC_Model(nn.Module):
         if need == 0:
             raise ValueError('%d rows in one decode group: the bound is 2^26 - 64' % n)
         off = (ctypes.c_int64 * (nf + 1))()
-        _lib.check(L.linr_decode_scale_batch(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num, self.block_layers,
-                                             *shared, off, int(n_threads), torch.cuda.current_stream().cuda_stream),
-                   'linr_decode_scale_batch')
+        if chunk:
+            _lib.check(L.linr_decode_scale_batch_chunked(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num,
+                                                         self.block_layers, *shared, off, int(n_threads), int(chunk),
+                                                         torch.cuda.current_stream().cuda_stream), 'linr_decode_scale_batch_chunked')
+        else:
+            _lib.check(L.linr_decode_scale_batch(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num, self.block_layers,
+                                                 *shared, off, int(n_threads), torch.cuda.current_stream().cuda_stream),
+                       'linr_decode_scale_batch')
         self._lockstep_ws_peak = max(getattr(self, '_lockstep_ws_peak', 0), int(need))
         return [keep[0][off[i]:off[i + 1]] for i in range(nf)]
 
@@ -452,21 +469,74 @@ class LINR_PCGC_Model(nn.Module):
         return [frame.occ[:, k:k + 1].clone() for k in range(8)]
 
 
-def encode_streams(probs, symbols, n_threads=8):
-    """Codes independent binary streams on a host thread pool (linr_ac_encode_binary_batch)."""
-    n = len(probs)
+def _code_entries(ns, chunk, in_a, in_b, entry, n_threads, what):
+    """The streams of ns[i] symbols through a batch entry of the host coder (`entry`), every chunk (stream_chunks; chunk 0: every
+    stream) as an entry of its own.  in_a / in_b = (the streams' input arrays, bytes per 64 symbols): a chunk starts at a multiple
+    of 64 symbols, so its inputs start that many bytes into them.  The chunks are handed over longest first - the full chunks of the
+    finest scales, then the tails and the coarse scales - and the coder threads take them in that order, so all chunks of a frame
+    balance across them.  The tables are built with numpy: this runs under the GIL, beside the thread that launches the forwards.
+    Returns the streams, chunks joined."""
+    ns = np.asarray(ns, dtype=np.int64).reshape(-1)
+    k = np.maximum(1, -(-ns // chunk)) if chunk else np.ones(len(ns), dtype=np.int64)
+    first = np.zeros(len(ns) + 1, dtype=np.int64)
+    first[1:] = np.cumsum(k)
+    n = int(first[-1])
+    stream = np.repeat(np.arange(len(ns)), k)
+    start = (np.arange(n) - first[stream]) * chunk
+    m = np.minimum(ns[stream] - start, chunk) if chunk else ns.copy()
+    order = np.argsort(-m, kind='stable') if chunk else np.arange(n)          # stable: equal lengths keep the order of the streams
+    cap = 2 * m + 64
+    off = np.cumsum(cap) - cap
+    out = np.empty(int(cap.sum()), dtype=np.uint8)
+    blocks = start[order] // 64
+    ptr = [np.asarray([x.ctypes.data for x in arrays], dtype=np.int64)[stream[order]] + per64 * blocks for arrays, per64 in (in_a, in_b)]
+    arr_o = out.ctypes.data + off[order]
+    arr_n, arr_c = np.ascontiguousarray(m[order]), np.ascontiguousarray(cap[order])
+    arr_l = np.empty(n, dtype=np.int64)
+    _lib.check(entry(ptr[0].ctypes.data, ptr[1].ctypes.data, arr_n.ctypes.data, n, arr_o.ctypes.data, arr_c.ctypes.data, arr_l.ctypes.data,
+                     n_threads), what)
+    lens = np.empty(n, dtype=np.int64)
+    lens[order] = arr_l
+    view, off, lens, first = memoryview(out), off.tolist(), lens.tolist(), first.tolist()
+    return [join_chunks([view[off[e]:off[e] + lens[e]] for e in range(first[i], first[i + 1])]) for i in range(len(ns))]
+
+
+def encode_streams(probs, symbols, n_threads=8, chunk=0):
+    """Codes independent binary streams on a host thread pool (linr_ac_encode_binary_batch).  chunk = S > 0 (stream_chunks): a stream
+    of more than S symbols is coded as chunks of S symbols, each an entry of the batch, and comes back as header + chunks."""
+    chunk = check_chunk(chunk)
     probs = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in probs]
     symbols = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1) for s in symbols]
-    outs = [np.empty(2 * p.size + 64, dtype=np.uint8) for p in probs]
-    arr_p = (ctypes.c_void_p * n)(*[p.ctypes.data for p in probs])
-    arr_s = (ctypes.c_void_p * n)(*[s.ctypes.data for s in symbols])
-    arr_o = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
-    arr_n = (ctypes.c_int64 * n)(*[p.size for p in probs])
-    arr_c = (ctypes.c_int64 * n)(*[o.size for o in outs])
-    arr_l = (ctypes.c_int64 * n)()
-    _lib.check(_lib.lib().linr_ac_encode_binary_batch(arr_p, arr_s, arr_n, n, arr_o, arr_c, arr_l, n_threads),
-               'linr_ac_encode_binary_batch')
-    return [outs[i][:arr_l[i]].tobytes() for i in range(n)]
+    return _code_entries([p.size for p in probs], chunk, (probs, 256), (symbols, 64), _lib.lib().linr_ac_encode_binary_batch, n_threads,
+                         'linr_ac_encode_binary_batch')
+
+
+def decode_streams(probs, streams, n_threads=8, chunk=0):
+    """The twin of encode_streams: stream i decoded against probs[i] (float32 [n_i]) into uint8 [n_i], on a host thread pool
+    (linr_ac_decode_binary_batch).  chunk = S > 0: the streams are cut by the checked parser (linr_stream_split_chunks: a header that
+    does not hold raises LinrError, nothing is decoded) and every chunk is an entry of the batch, as in the decoder's scale entries."""
+    chunk = check_chunk(chunk)
+    L = _lib.lib()
+    probs = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in probs]
+    bufs = [np.frombuffer(b, dtype=np.uint8) for b in streams]
+    syms = [np.empty(p.size, dtype=np.uint8) for p in probs]
+    ks = [chunk_count(p.size, chunk) for p in probs]
+    n = sum(ks)
+    arr_in, arr_len = (ctypes.c_void_p * n)(), (ctypes.c_int64 * n)()
+    at = 0
+    for p, b, k in zip(probs, bufs, ks):
+        got = L.linr_stream_split_chunks(b.ctypes.data if b.size else None, int(b.size), p.size, chunk,
+                                         ctypes.byref(arr_in, at * ctypes.sizeof(ctypes.c_void_p)),
+                                         ctypes.byref(arr_len, at * ctypes.sizeof(ctypes.c_int64)), k)
+        if got != k:
+            _lib.check(int(got), 'linr_stream_split_chunks')
+        at += k
+    entries = chunk_entries([p.size for p in probs], chunk)
+    arr_p = (ctypes.c_void_p * n)(*[probs[i].ctypes.data + 4 * a for i, a, _ in entries])
+    arr_s = (ctypes.c_void_p * n)(*[syms[i].ctypes.data + a for i, a, _ in entries])
+    arr_n = (ctypes.c_int64 * n)(*[e[2] for e in entries])
+    _lib.check(L.linr_ac_decode_binary_batch(arr_p, arr_n, arr_in, arr_len, n, arr_s, n_threads), 'linr_ac_decode_binary_batch')
+    return syms
 
 
 def codes_word_off(row_off):
@@ -477,71 +547,88 @@ def codes_word_off(row_off):
     return off
 
 
-def encode_streams_codes(c1s, syms, ns, n_threads=8):
+def encode_streams_codes(c1s, syms, ns, n_threads=8, chunk=0):
     """encode_streams from code values and symbol bit planes (linr_ac_encode_binary_codes_batch): stream i has ns[i] symbols,
-    c1s[i] uint16 [>= ns[i]], syms[i] uint32 [>= ceil(ns[i] / 32)], bit j & 31 of word j >> 5 = symbol j."""
-    n = len(c1s)
+    c1s[i] uint16 [>= ns[i]], syms[i] uint32 [>= ceil(ns[i] / 32)], bit j & 31 of word j >> 5 = symbol j.  chunk = S > 0: chunk j of a
+    stream reads its code values from j S and its symbol words from j S / 32 on (S is a multiple of 64)."""
+    chunk = check_chunk(chunk)
     ns = [int(v) for v in ns]
     c1s = [np.ascontiguousarray(c, dtype=np.uint16).reshape(-1) for c in c1s]
     syms = [np.ascontiguousarray(w, dtype=np.uint32).reshape(-1) for w in syms]
     if any(c.size < m or w.size < (m + 31) // 32 for c, w, m in zip(c1s, syms, ns)):
         raise ValueError('a stream has fewer code values or symbol words than symbols')
-    outs = [np.empty(2 * m + 64, dtype=np.uint8) for m in ns]
-    arr_c = (ctypes.c_void_p * n)(*[c.ctypes.data for c in c1s])
-    arr_s = (ctypes.c_void_p * n)(*[w.ctypes.data for w in syms])
-    arr_o = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
-    arr_n = (ctypes.c_int64 * n)(*ns)
-    arr_cap = (ctypes.c_int64 * n)(*[o.size for o in outs])
-    arr_l = (ctypes.c_int64 * n)()
-    _lib.check(_lib.lib().linr_ac_encode_binary_codes_batch(arr_c, arr_s, arr_n, n, arr_o, arr_cap, arr_l, n_threads),
-               'linr_ac_encode_binary_codes_batch')
-    return [outs[i][:arr_l[i]].tobytes() for i in range(n)]
+
+    return _code_entries(ns, chunk, (c1s, 128), (syms, 8), _lib.lib().linr_ac_encode_binary_codes_batch, n_threads,
+                         'linr_ac_encode_binary_codes_batch')
 
 
 class DeviceCoderSet:
     """One buffer set of the device range coder (linr_rc_encode_codes, csrc/ac_device.hip): stream regions, lengths, the dense payload
     and its offsets on the device, pinned copies of the last two, and a stream of its own for the two small reads a call needs, so
-    that reading one set never queues behind the coding of another.  launch() on the current stream, collect() anywhere later."""
+    that reading one set never queues behind the coding of another.  launch() on the current stream, collect() anywhere later.
+    chunk = S > 0 (stream_chunks): linr_rc_encode_codes_chunked, a wave per chunk; total_cap and n_chunks are then those of
+    table(descriptors, S) and chunks(descriptors, S)."""
 
-    def __init__(self, n_streams, total_cap, device):
+    def __init__(self, n_streams, total_cap, device, chunk=0, n_chunks=0):
         L = _lib.lib()
+        self.chunk = check_chunk(chunk)
         self.n_max, self.cap_max = int(n_streams), max(8, int(total_cap))
+        self.chunks_max = max(int(n_chunks), self.n_max) if self.chunk else 0
+        # the final bytes of a chunked stream: at most its region and a header of 5 bytes per further chunk
+        self.payload_max = self.cap_max + 5 * max(0, self.chunks_max - self.n_max)
         self.out = torch.empty(self.cap_max, dtype=torch.uint8, device=device)
-        self.payload = torch.empty(self.cap_max, dtype=torch.uint8, device=device)
+        self.payload = torch.empty(self.payload_max, dtype=torch.uint8, device=device)
         self.len = torch.empty(self.n_max, dtype=torch.int64, device=device)
         self.offsets = torch.empty(self.n_max + 1, dtype=torch.int64, device=device)
-        self.ws = _lib.scratch(L.linr_rc_encode_ws_bytes(self.n_max, self.cap_max), device)
+        self.ws = _lib.scratch(L.linr_rc_encode_chunked_ws_bytes(self.n_max, self.chunks_max) if self.chunk else
+                               L.linr_rc_encode_ws_bytes(self.n_max, self.cap_max), device)
         self.offsets_pin = torch.empty(self.n_max + 1, dtype=torch.int64, pin_memory=True)
-        self.payload_pin = torch.empty(self.cap_max, dtype=torch.uint8, pin_memory=True)
+        self.payload_pin = torch.empty(self.payload_max, dtype=torch.uint8, pin_memory=True)
         self.read_stream = torch.cuda.Stream(device=device)
         self.coded, self.read = torch.cuda.Event(), torch.cuda.Event()
         self.n = 0
 
     @staticmethod
-    def table(descriptors):
+    def chunks(descriptors, chunk=0):
+        """The chunks of all streams of rows {c1 offset, symbol word offset, n} together."""
+        return sum(chunk_count(int(n), chunk) for n in np.asarray(descriptors, dtype=np.int64).reshape(-1, 3)[:, 2])
+
+    @staticmethod
+    def table(descriptors, chunk=0):
         """int64 [n, 5] rows {c1 offset, symbol word offset, n, out offset, cap} from rows {c1 offset, symbol word offset, n}: cap is the
-        host path's 2 n + 64, the regions follow each other on 4-byte boundaries.  Returns (table, bytes of all regions)."""
+        host path's 2 n + 64 - with chunk = S > 0 that of every chunk, 2 n + 64 k together -, the regions follow each other on 4-byte
+        boundaries.  Returns (table, bytes of all regions)."""
         d = np.asarray(descriptors, dtype=np.int64).reshape(-1, 3)
         tab = np.empty((len(d), 5), dtype=np.int64)
         tab[:, :3] = d
-        tab[:, 4] = 2 * d[:, 2] + 64
+        k = np.maximum(1, -(-d[:, 2] // chunk)) if chunk else 1
+        tab[:, 4] = 2 * d[:, 2] + 64 * k
         ends = np.cumsum((tab[:, 4] + 3) & ~3)
         tab[:, 3] = ends - ((tab[:, 4] + 3) & ~3)
         return tab, int(ends[-1]) if len(d) else 0
 
     def launch(self, c1, sym, descriptors):
         """Codes the streams {c1 element offset, symbol word offset, n} of c1 (uint16) / sym (uint32) on the current stream."""
-        tab, total = self.table(descriptors)
+        tab, total = self.table(descriptors, self.chunk)
         n = len(tab)
         if n == 0 or n > self.n_max or total > self.cap_max:
             raise ValueError('DeviceCoderSet: %d streams / %d bytes in a set made for %d / %d' % (n, total, self.n_max, self.cap_max))
+        if self.chunk and self.chunks(descriptors, self.chunk) > self.chunks_max:
+            raise ValueError('DeviceCoderSet: more chunks than the set was made for (%d)' % self.chunks_max)
         if c1.dtype != torch.uint16 or sym.dtype != torch.uint32 or not (c1.is_contiguous() and sym.is_contiguous()):
             raise ValueError('DeviceCoderSet: c1 must be contiguous uint16, sym contiguous uint32')
         if (tab[:, :3] < 0).any() or (tab[:, 0] + tab[:, 2] > c1.numel()).any() or (tab[:, 1] + (tab[:, 2] + 31) // 32 > sym.numel()).any():
             raise ValueError('DeviceCoderSet: a stream reads outside c1 or sym')
-        _lib.check(_lib.lib().linr_rc_encode_codes(c1.data_ptr(), sym.data_ptr(), tab.ctypes.data, n, self.out.data_ptr(), self.out.numel(),
-                                                   self.len.data_ptr(), self.payload.data_ptr(), self.payload.numel(), self.offsets.data_ptr(),
-                                                   self.ws.data_ptr(), self.ws.numel(), _lib.current_stream_handle()), 'linr_rc_encode_codes')
+        L = _lib.lib()
+        if self.chunk:
+            _lib.check(L.linr_rc_encode_codes_chunked(c1.data_ptr(), sym.data_ptr(), tab.ctypes.data, n, self.chunk, self.out.data_ptr(),
+                                                      self.out.numel(), self.len.data_ptr(), self.payload.data_ptr(), self.payload.numel(),
+                                                      self.offsets.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                                      _lib.current_stream_handle()), 'linr_rc_encode_codes_chunked')
+        else:
+            _lib.check(L.linr_rc_encode_codes(c1.data_ptr(), sym.data_ptr(), tab.ctypes.data, n, self.out.data_ptr(), self.out.numel(),
+                                              self.len.data_ptr(), self.payload.data_ptr(), self.payload.numel(), self.offsets.data_ptr(),
+                                              self.ws.data_ptr(), self.ws.numel(), _lib.current_stream_handle()), 'linr_rc_encode_codes')
         self.coded.record(torch.cuda.current_stream())
         with torch.cuda.stream(self.read_stream):
             self.read_stream.wait_event(self.coded)
@@ -555,7 +642,7 @@ class DeviceCoderSet:
         self.read.synchronize()
         offs = self.offsets_pin[:n + 1].numpy().copy()
         total = int(offs[-1])
-        if (np.diff(offs) < 1).any() or total > self.cap_max:          # every stream has at least one byte; LINR_ENOSPC counts 0
+        if (np.diff(offs) < 1).any() or total > self.payload_max:          # every stream has at least one byte; LINR_ENOSPC counts 0
             raise _lib.LinrError('linr_rc_encode_codes: a stream did not fit its region')
         with torch.cuda.stream(self.read_stream):
             self.payload_pin[:total].copy_(self.payload[:total], non_blocking=True)
@@ -564,14 +651,14 @@ class DeviceCoderSet:
         return [data[int(offs[i]):int(offs[i + 1])] for i in range(n)]
 
 
-def encode_streams_device(c1, sym, descriptors):
-    """encode_streams_codes on the GPU (linr_rc_encode_codes): c1 uint16 and sym uint32 device tensors, descriptors rows of
-    {c1 element offset, symbol word offset, n}; stream i's symbols are bits 0 .. n - 1 from its word offset on.  Returns the streams
-    as a list of bytes, byte for byte what the host coder gives."""
+def encode_streams_device(c1, sym, descriptors, chunk=0):
+    """encode_streams_codes on the GPU (linr_rc_encode_codes; with chunk = S > 0 linr_rc_encode_codes_chunked): c1 uint16 and sym
+    uint32 device tensors, descriptors rows of {c1 element offset, symbol word offset, n}; stream i's symbols are bits 0 .. n - 1 from
+    its word offset on.  Returns the streams as a list of bytes, byte for byte what the host coder gives."""
     d = np.asarray(descriptors, dtype=np.int64).reshape(-1, 3)
     if len(d) == 0:
         return []
-    coder = DeviceCoderSet(len(d), DeviceCoderSet.table(d)[1], c1.device)
+    coder = DeviceCoderSet(len(d), DeviceCoderSet.table(d, chunk)[1], c1.device, chunk, DeviceCoderSet.chunks(d, chunk))
     coder.launch(c1.reshape(-1), sym.reshape(-1), d)
     return coder.collect()
 

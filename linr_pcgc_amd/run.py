@@ -62,6 +62,11 @@ def parse(argv=None):
                          'byte for byte those of the default path')
     ap.add_argument('--coder-group', '--coder_group', dest='coder_group', type=int, default=8,
                     help='with --device-coder: frames coded per call (1..64)')
+    ap.add_argument('--stream-chunk', '--stream_chunk', dest='stream_chunk', type=int, default=0,
+                    help='cut every stage stream into chunks of this many symbols (a multiple of 64 in 64..2^24; 0 = off) that are range-coded '
+                         'and -decoded independently, on the coder threads or a wave each (codec.encode_gop stream_chunk=): a few bytes per '
+                         'chunk; travels as stream_chunk in side_info.json, which builds before this option cannot read; '
+                         '--hidden-channel-conv 8 only')
     ap.add_argument('--ply-parse', '--ply_parse', dest='ply_parse', default='host', choices=['host', 'device'],
                     help='with --input-glob / --ori_dir: PLY frames are parsed by the host parser on a thread pool (default) or on the GPU '
                          '(ply.read_many_device, on the staging stream); the encoded files are byte for byte the same')
@@ -109,6 +114,10 @@ def parse(argv=None):
             ap.error('--qrange-trims must be >= 0')
     if args.qrange_frames < 0:
         ap.error('--qrange-frames must be >= 0')
+    if args.stream_chunk and (args.stream_chunk % 64 or not 64 <= args.stream_chunk <= 1 << 24):
+        ap.error('--stream-chunk must be 0 or a multiple of 64 in 64..2^24')
+    if args.stream_chunk and args.hidden_channel_conv != 8:
+        ap.error('--stream-chunk: chunked stage streams exist for --hidden-channel-conv 8 only')
     return args
 
 
@@ -305,6 +314,7 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                                    getattr(args, 'model_bitdepth', 8), precision=getattr(args, 'precision', 'f32'),
                                    device_codes=getattr(args, 'device_codes', False),
                                    device_coder=getattr(args, 'device_coder', False), coder_group=getattr(args, 'coder_group', 8),
+                                   **({'stream_chunk': args.stream_chunk} if getattr(args, 'stream_chunk', 0) else {}),
                                    **({'qrange_search': True, 'qrange_trims': getattr(args, 'qrange_trims', None),
                                        'qrange_frames': getattr(args, 'qrange_frames', 4)} if getattr(args, 'qrange_search', False) else {}))
             res_dir = os.path.join(args.out, 'result_enc', gop_parallel.gop_name(group))
