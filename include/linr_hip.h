@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 21
+#define LINR_ABI_VERSION 22
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -628,6 +628,30 @@ LINR_API int linr_decode_scale_batch_chunked(const int32_t* coord, const int64_t
                                     void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
                                     int64_t child_cap, int64_t* child_off_h, int32_t n_threads, int64_t chunk_symbols, void* stream);
 
+/* Both scale entries with the range decoders on the DEVICE (opt-in; linr_rc_decode_probs below): the arguments of
+ * linr_decode_scale_chunked / linr_decode_scale_batch_chunked without p_pinned, s_pinned and n_threads; chunk_symbols 0 means plain
+ * streams.  plan_stages and with it linr_stream_split_chunks run as there (a malformed chunk header is LINR_EINVAL in front of the first
+ * launch); the bytes of the scale's 8 streams of every frame are uploaded once (stream order, from a staging copy the call owns: the
+ * caller's stream arrays are free on return), and stage k is the stage's forward followed by rc_decode_k over the stage's entries,
+ * which write column k of the occupancy - no copy down, no host thread, and ONE synchronisation per scale, where the call reads the
+ * child count.  The decoded geometry is that of the host path on every stream (the decoders agree on any bytes).  Workspace: the
+ * layout of the entries above plus a region for the stream bytes (stream_bytes_total = the sum of the 8 (x n_frames) stream lengths,
+ * padded to 256 bytes plus one 256-byte window) and one for the table (n_entries = the chunks of all 8 stages: the sum over frames
+ * and stages of linr_stream_chunk_count(rows of the frame, chunk_symbols), empty frames excluded; more is allowed): LINR_ENOSPC when
+ * ws_bytes is below what the call needs.  The new launches belong to poison class 15 like the rest of a scale. */
+LINR_API size_t linr_decode_scale_device_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total, int64_t n_entries);
+LINR_API int linr_decode_scale_device(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                             int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                             const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                             int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h, int64_t chunk_symbols, void* stream);
+LINR_API size_t linr_decode_scale_batch_device_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
+                                               int64_t stream_bytes_total, int64_t n_entries);
+LINR_API int linr_decode_scale_batch_device(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                   int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                   float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                                   void* ws, size_t ws_bytes, int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h,
+                                   int64_t chunk_symbols, void* stream);
+
 /* ---- the executor's fused layers as stand-alone ops ------------------------------------------------------------
  * What linr_net_forward / _backward launch for one layer, callable (and testable) on its own.  All of them work on the
  * compressed kernel map (linr_kmap_compress) and follow the LINR_PAD_ROW contract: every matrix that a kernel GATHERS
@@ -752,6 +776,11 @@ LINR_API int     linr_ac_decode_binary_codes(const uint16_t* c1_h, int64_t n, co
 LINR_API int linr_ac_encode_binary_codes_batch(const uint16_t* const* c1_h, const uint32_t* const* sym_h, const int64_t* n,
                                       int32_t n_streams, uint8_t* const* out_h, const int64_t* cap,
                                       int64_t* out_len, int32_t n_threads);
+/* linr_ac_decode_binary through the DEVICE decoder's body (csrc/rc_dec_body.h, what rc_decode_k below runs a wave per entry) on the
+ * CPU: 64-symbol chunks of code values, the stream through aligned 64-word windows with the funnel shift and the masked last word,
+ * exactly as the wave walks them.  Same arguments, same symbols on ANY bytes (both decoders read zeros at and behind in_h + in_len;
+ * no byte there is read); it shares no text with linr_ac_decode_binary, which is its reference (tests/test_rc_decode_host.py). */
+LINR_API int     linr_ac_decode_binary_twin(const float* prob_h, int64_t n, const uint8_t* in_h, int64_t in_len, uint8_t* sym_h);
 /* Chunked stage streams (opt-in; side_info.json's stream_chunk = S, a multiple of 64 in 64..2^24): a stage stream of n symbols has
  * k = max(1, ceil(n / S)) chunks, chunk j being exactly the stream of symbols [j S, min((j + 1) S, n)) on their own.  k == 1: the
  * stream is that chunk, i.e. the unchunked stream.  k > 1: the byte lengths of chunks 0 .. k - 2 as unsigned LEB128 of at most 5
@@ -815,6 +844,31 @@ LINR_API int linr_rc_encode_codes_chunked(const uint16_t* c1_dev, const uint32_t
                                  int32_t n_streams, int64_t chunk_symbols, uint8_t* out_dev, int64_t out_bytes, int64_t* len_dev,
                                  uint8_t* payload_dev, int64_t payload_bytes, int64_t* offsets_dev, void* ws, size_t ws_bytes,
                                  void* stream);
+
+/* ---- range DECODER on the DEVICE (csrc/ac_device_dec.hip, body: csrc/rc_dec_body.h) ---------------------------------------
+ * linr_ac_decode_binary for many independent entries in one launch, a wave per entry, from probabilities that never leave the device:
+ * entry i decodes n symbols against probs_dev[p_off .. p_off + n) (fp32 in [0, 1]; the code value is computed as linr_ac_codes
+ * computes it) from the bytes [in_off, in_off + in_len) of bytes_dev - in_off has NO alignment; whatever follows the entry's last
+ * byte reads as zeros, as the host decoder reads past a stream's end - and writes symbol j as 0.0f / 1.0f to
+ * occ_col_dev[(out_row + j) * occ_ld] (a column of an occupancy matrix: pass occ + k and occ_ld = 8) and, with sym_dev != NULL, as a
+ * byte to sym_dev[out_row + j].  Nothing else is written.  An entry is a whole stream or one chunk of a chunked stream. */
+typedef struct linr_rc_dec_entry {
+    int64_t p_off, n, in_off, in_len, out_row;
+} linr_rc_dec_entry;
+/* Workspace of linr_rc_decode_probs: the device copy of the table.  0 for a negative count. */
+LINR_API size_t linr_rc_decode_ws_bytes(int32_t n_entries);
+/* The table's upload (kernel arguments: entries_host is a HOST array and free on return) and rc_decode_k, on `stream`; no
+ * synchronisation.  The whole table is checked before the first launch - LINR_EINVAL, nothing written: a NULL pointer (sym_dev may be
+ * NULL; bytes_dev too when bytes_len is 0), n_entries < 0, occ_ld < 1, a negative field, p_off + n > n_probs, in_off + in_len >
+ * bytes_len, out_row + n > n_rows, two entries whose row ranges [out_row, out_row + n) overlap, ws_bytes below
+ * linr_rc_decode_ws_bytes(n_entries).  LINR_EALIGN: probs_dev, occ_col_dev or bytes_dev not 4-byte aligned, ws not 8-byte aligned.
+ * bytes_dev is read in aligned 32-bit words: it must be readable up to bytes_len rounded up to a multiple of 4, and no address at or
+ * behind that is formed (a 256-byte aligned buffer makes every window one full-line load).  n_entries == 0 returns 0 and launches
+ * nothing.  The kernel uses no LDS, no atomics and no scratch, and belongs to no linr_prof_* class; on its own it belongs to no
+ * linr_debug_poison class either (inside the decoder scales below it sits behind class 15). */
+LINR_API int linr_rc_decode_probs(const float* probs_dev, int64_t n_probs, const uint8_t* bytes_dev, int64_t bytes_len,
+                         const linr_rc_dec_entry* entries_host, int32_t n_entries, float* occ_col_dev, int64_t occ_ld, int64_t n_rows,
+                         uint8_t* sym_dev, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- frame input (host) ----------------------------------------------------------------------------------------------
  * Body of an ASCII PLY (datautils/custom_dataset.py:9-14 read_ply_o3d - open3d's C++ reader - followed by :263-269, which keeps

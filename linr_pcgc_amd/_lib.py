@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('LINR_HIP_LIB') or os.path.join(_HERE, 'liblinr_hip.so
 LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 16
 LINR_FRAME_OCC_PADDED = 1
 LINR_PLY_TOKEN, LINR_PLY_COLUMNS, LINR_PLY_SHORT, LINR_PLY_RANGE = 1, 2, 4, 8
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -41,6 +41,11 @@ class LinrFrame(ctypes.Structure):
 class LinrInceptionParams(ctypes.Structure):
     """struct linr_inception_params (include/linr_hip.h)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ('w00', 'b00', 'w01', 'b01', 'w10', 'b10', 'w11', 'b11', 'w12', 'b12')]
+
+
+class LinrRcDecEntry(ctypes.Structure):
+    """struct linr_rc_dec_entry (include/linr_hip.h): one entry of linr_rc_decode_probs; five int64, so an int64 [n, 5] array is a table."""
+    _fields_ = [(n, c_i64) for n in ('p_off', 'n', 'in_off', 'in_len', 'out_row')]
 
 
 class LinrRcStream(ctypes.Structure):
@@ -181,6 +186,15 @@ _PROTOS = {
                                                  c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr]),
     'linr_decode_scale_batch_chunked': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr,
                                                        c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr]),
+    'linr_decode_scale_device_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i64, c_i64]),
+    'linr_decode_scale_device': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
+                                                c_size, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    'linr_decode_scale_batch_device_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32, c_i64, c_i64]),
+    'linr_decode_scale_batch_device': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr,
+                                                      c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    'linr_ac_decode_binary_twin': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    'linr_rc_decode_ws_bytes': (c_size, [c_i32]),
+    'linr_rc_decode_probs': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i32, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
     'linr_ac_decode_binary_batch': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i32]),
     'linr_stream_chunk_count': (c_i64, [c_i64, c_i64]),
     'linr_stream_split_chunks': (c_i64, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64]),

@@ -317,21 +317,24 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found)
 
 
-def decode_one_frame(model, frame_enc_bytes, xyz_low, chunk=0, n_threads=1):
+def decode_one_frame(model, frame_enc_bytes, xyz_low, chunk=0, n_threads=1, device_decoder=False):
     """decoder.decode_one_frame (decoder.py:153-176): coarse to fine, 8 AC-decoded stages per scale.  A scale is ONE call into the
     library (model.decode_scale -> linr_decode_scale: kernel map, the 7-neighbour occupancy read off it instead of
     qscTensor.set_offset_tensor's searches, the 8 stage forwards with their host round trips, upper_layer), so the Python side of a
     frame is seven buffer allocations.  chunk = S > 0: the stage streams are chunked (side_info's stream_chunk) and a stage's chunks are
-    decoded on n_threads host threads."""
+    decoded on n_threads host threads.  device_decoder=True: the range decoders run on the GPU (model.decode_scale(device_decoder=True)
+    -> linr_decode_scale_device), no host round trip per stage; n_threads is ignored."""
     if getattr(model, '_wide', None) is not None:          # hidden_channel_conv 16 / 32: no single-call decoder scale
         if chunk:
             raise ValueError('chunked stage streams decode with hidden_channel_conv 8 only')
+        if device_decoder:
+            raise ValueError('the device decoder needs hidden_channel_conv 8: the widths 16 and 32 decode stage-wise in Python')
         return decode_one_frame_stagewise(model, frame_enc_bytes, xyz_low)
     lowx = unique_sorted(xyz_low)
     bits = max(1, int(xyz_low.max()).bit_length()) if xyz_low.numel() else 1       # coordinates of the coarsest level
     for s_idx in range(len(frame_enc_bytes) - 1, -1, -1):
         bits = min(bits + 1, 21)
-        lowx = model.decode_scale(lowx, s_idx, frame_enc_bytes[s_idx], bits, chunk, n_threads)
+        lowx = model.decode_scale(lowx, s_idx, frame_enc_bytes[s_idx], bits, chunk, n_threads, device_decoder)
     return {'dec_coord': lowx}
 
 
@@ -350,21 +353,24 @@ LOCKSTEP_MAX_FRAMES = 64                  # LINR_DECODE_MAX_FRAMES of include/li
 LOCKSTEP_MAX_ROWS = (1 << 26) - 64        # rows of one lock-step call: the compressed kernel map's 32-bit bound (linr_cmap_fits32)
 
 
-def _lockstep_scale(model, lows, s_idx, encs, n_threads, chunk=0):
+def _lockstep_scale(model, lows, s_idx, encs, n_threads, chunk=0, device_decoder=False):
     """One scale of a lock-step group; a group whose levels together pass the row bound of one call is halved."""
     if len(lows) > 1 and sum(int(c.shape[0]) for c in lows) > LOCKSTEP_MAX_ROWS:
         h = len(lows) // 2
-        return (_lockstep_scale(model, lows[:h], s_idx, encs[:h], n_threads, chunk) +
-                _lockstep_scale(model, lows[h:], s_idx, encs[h:], n_threads, chunk))
-    return model.decode_scale_batch(lows, s_idx, encs, n_threads, chunk)
+        return (_lockstep_scale(model, lows[:h], s_idx, encs[:h], n_threads, chunk, device_decoder) +
+                _lockstep_scale(model, lows[h:], s_idx, encs[h:], n_threads, chunk, device_decoder))
+    return model.decode_scale_batch(lows, s_idx, encs, n_threads, chunk, device_decoder)
 
 
-def decode_frames_lockstep(model, frames_enc_bytes, xyz_lows, n_threads=8, chunk=0):
+def decode_frames_lockstep(model, frames_enc_bytes, xyz_lows, n_threads=8, chunk=0, device_decoder=False):
     """decode_one_frame for a group of frames with the same number of scales, in lock step: coarse to fine, every scale of the whole
-    group is ONE call into the library (model.decode_scale_batch -> linr_decode_scale_batch).  Returns the frames' coordinates."""
+    group is ONE call into the library (model.decode_scale_batch -> linr_decode_scale_batch; with device_decoder
+    linr_decode_scale_batch_device, the group's range decoders on the GPU).  Returns the frames' coordinates."""
+    if device_decoder and getattr(model, '_wide', None) is not None:
+        raise ValueError('the device decoder needs hidden_channel_conv 8')
     lows = [unique_sorted(x) for x in xyz_lows]
     for s_idx in range(len(frames_enc_bytes[0]) - 1, -1, -1):
-        lows = _lockstep_scale(model, lows, s_idx, [f[s_idx] for f in frames_enc_bytes], n_threads, chunk)
+        lows = _lockstep_scale(model, lows, s_idx, [f[s_idx] for f in frames_enc_bytes], n_threads, chunk, device_decoder)
     return lows
 
 
@@ -379,7 +385,7 @@ def lockstep_groups(todo, n_scales, lockstep):
     return groups
 
 
-def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=None, lockstep=0, n_threads=None):
+def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=None, lockstep=0, n_threads=None, device_decoder=False):
     """decoder.decode_one_gop: rebuild the model from model.bin, then every frame from its streams alone.
     lockstep=B > 0 (opt-in; 0 = the per-frame path below, untouched): the requested frames are decoded in groups of up to B
     consecutive entries, the scales of a group from coarsest to finest in lock step (decode_frames_lockstep), the group's range
@@ -391,6 +397,11 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
     chunks are range-decoded in parallel - with lockstep on the group's threads as ever, and per frame on n_threads threads, too
     (default: the cores this process may use, at most 16, divided by `workers`).  A stream whose chunk header does not hold raises
     LinrError.
+    device_decoder=True (opt-in; hidden_channel_conv 8 only, ValueError otherwise): the range decoders of every scale run on the GPU,
+    a wave per stream or chunk, from the probabilities where the stage forward left them (linr_decode_scale_device /
+    linr_decode_scale_batch_device): no host coder threads (n_threads is ignored) and one synchronisation per scale instead of one
+    per stage.  It reads the same streams and side_info.json and decodes the same geometry; it composes with workers, lockstep and
+    stream_chunk.
     Frames are independent once the model is known; with workers > 1 they are decoded by a host thread pool, each
     thread on its own HIP stream (a frame's own chain - 56 stage forwards with a serial range decode in between - cannot
     be parallelised, but the range decoding of one frame overlaps the stage forwards and copies of the others; the
@@ -414,6 +425,9 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
     chunk = check_chunk(side.get('stream_chunk', 0))
     if chunk and getattr(model, '_wide', None) is not None:
         raise ValueError('chunked stage streams decode with hidden_channel_conv 8 only')
+    device_decoder = bool(device_decoder)
+    if device_decoder and getattr(model, '_wide', None) is not None:
+        raise ValueError('the device decoder needs hidden_channel_conv 8: the widths 16 and 32 decode stage-wise in Python')
     lows, mins = dec_all_frame_low_xyz(enc['low_enc_bytes'])
     todo = list(range(len(enc['frames'])) if frames is None else frames)
     if timing is not None:
@@ -425,14 +439,15 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
 
     def one(i):
         xyz_low = torch.tensor(lows[i].astype(np.int32), device=device)
-        dec = decode_one_frame(model, list(enc['frames'][i]), xyz_low, chunk, per_frame)['dec_coord']
+        dec = decode_one_frame(model, list(enc['frames'][i]), xyz_low, chunk, per_frame, device_decoder)['dec_coord']
         return dec + torch.tensor(mins[i], device=device, dtype=torch.int32)
 
     if getattr(model, '_wide', None) is not None:
         workers = 1          # the channel-blocked executor keeps per-call state on the model: frames one after the other
         lockstep = 0
     if lockstep and lockstep > 0 and todo:
-        out = _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, min(int(lockstep), LOCKSTEP_MAX_FRAMES), n_threads, chunk)
+        out = _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, min(int(lockstep), LOCKSTEP_MAX_FRAMES), n_threads, chunk,
+                                   device_decoder)
         if timing is not None:
             timing['lockstep_ws_bytes'] = int(getattr(model, '_lockstep_ws_peak', 0))          # the largest workspace of a call
         return out
@@ -462,7 +477,7 @@ def _map_on_streams(fn, items, workers):
         return list(pool.map(job, items))
 
 
-def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads, chunk=0):
+def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads, chunk=0, device_decoder=False):
     n_threads = _coder_threads(n_threads)
     groups = lockstep_groups(todo, {i: len(enc['frames'][i]) for i in set(todo)}, lockstep)
     workers = max(1, min(int(workers), len(groups)))
@@ -470,7 +485,7 @@ def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep
 
     def one(group):
         xyz_lows = [torch.tensor(lows[i].astype(np.int32), device=device) for i in group]
-        dec = decode_frames_lockstep(model, [list(enc['frames'][i]) for i in group], xyz_lows, per_group, chunk)
+        dec = decode_frames_lockstep(model, [list(enc['frames'][i]) for i in group], xyz_lows, per_group, chunk, device_decoder)
         return [d + torch.tensor(mins[i], device=device, dtype=torch.int32) for i, d in zip(group, dec)]
 
     return [x for out in _map_on_streams(one, groups, workers) for x in out]

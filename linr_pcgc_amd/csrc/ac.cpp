@@ -19,6 +19,7 @@
 #endif
 #include "../../include/linr_hip.h"
 #include "rc_body.h"
+#include "rc_dec_body.h"
 
 namespace {
 
@@ -281,6 +282,31 @@ extern "C" int linr_ac_decode_binary(const float* prob_h, int64_t n, const uint8
 extern "C" int linr_ac_decode_binary_codes(const uint16_t* c1_h, int64_t n, const uint8_t* in_h, int64_t in_len, uint8_t* sym_h) {
     if (n < 0 || in_len < 0 || (n > 0 && (!c1_h || !sym_h)) || (in_len > 0 && !in_h)) return LINR_EINVAL;
     decode_binary_body(CodesReady{c1_h}, n, in_h, in_len, sym_h);
+    return 0;
+}
+
+// ---- the device decoder's body on the host ------------------------------------------------------------------------------------------
+// csrc/rc_dec_body.h - what rc_decode_k of csrc/ac_device_dec.hip runs a wave per entry - for one stream on the CPU: 64-symbol chunks
+// of code values from c1_block, the stream through 64-word windows (RcWinIn over RcHostFetch), one byte per symbol out.
+// decode_binary_body above shares no text with that body and is its reference: both give the same symbols on ANY bytes.
+namespace {
+
+struct RcDecProbSrc {
+    const float* p; int64_t n;
+    uint32_t c[RC_CHUNK];
+    inline void chunk(int64_t b) { c1_block(p + b, (int)(n - b < RC_CHUNK ? n - b : RC_CHUNK), c); }
+    inline uint32_t c1(int i) const { return c[i]; }
+};
+
+}  // namespace
+
+extern "C" int linr_ac_decode_binary_twin(const float* prob_h, int64_t n, const uint8_t* in_h, int64_t in_len, uint8_t* sym_h) {
+    if (n < 0 || in_len < 0 || (n > 0 && (!prob_h || !sym_h)) || (in_len > 0 && !in_h)) return LINR_EINVAL;
+    RcDecProbSrc src{prob_h, n, {}};
+    RcWinIn<RcHostFetch> in{RcHostFetch(in_h)};
+    in.open(0, in_len);
+    RcDecHostOut out{sym_h};
+    rc_decode(src, n, in, out);
     return 0;
 }
 

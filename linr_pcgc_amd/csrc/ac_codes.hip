@@ -4,6 +4,7 @@
 // [8][rows] uint16 code values and 8 bit planes: 17 bits per symbol cross to the host instead of 40, and the coder threads
 // read c1 instead of computing it (linr_ac_encode_binary_codes).
 #include "common.h"
+#include "rc_c1.h"
 
 namespace {
 
@@ -19,9 +20,7 @@ __global__ __launch_bounds__(512) void ac_codes_k(const float* __restrict__ prob
     bool bit = false;
     if (i < n) {
         const float p = probs[k * probs_ld + i];
-        // two separately rounded fp32 operations, as the host computes them: a contracted fma(-p, 65534, 65534) rounds once
-        const int scaled = __float2int_rn(__fmul_rn(__fsub_rn(1.0f, p), 65534.0f));
-        c1[k * c1_ld + i] = (uint16_t)(((uint32_t)scaled + 1u) & 0xFFFFu);
+        c1[k * c1_ld + i] = (uint16_t)linr_c1_from_p(p);          // (csrc/rc_c1.h: the range decoder's kernel computes the same)
         bit = occ[i * occ_ld + k] != 0.0f;
     }
     const unsigned long long b = __ballot(bit);          // lanes past n vote 0: the pad bits of the last word

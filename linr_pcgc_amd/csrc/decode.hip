@@ -1,5 +1,6 @@
 // The staged decoder.  The 8 decode stages of a frame object (decode_stages: stage forward, D2H, range decoders, H2D, occupancy
-// column; exported as linr_net_decode_stages for a frame's scales and as linr_net_decode_stages_segments for one scale of several
+// column - or, in its device mode, stage forward and rc_decode_k of csrc/ac_device_dec.hip, with no host round trip; exported as
+// linr_net_decode_stages for a frame's scales and as linr_net_decode_stages_segments for one scale of several
 // frames), and one scale of the decoder as ONE call (decoder.decode_one_frame's loop body, decoder.py:153-176): the kernel map of
 // the coarser level's coordinates, the 7-neighbour features read off it, the 8 stages and the next level's coordinates
 // (octree_level.upper_layer, models/module_utils.py:117-127: the children 2 p + (dx, dy, dz) of every occupied octant, sorted
@@ -10,6 +11,7 @@
 #include "common.h"
 #include "layout.h"
 #include "prof.h"
+#include "ac_device_dec.h"
 #include <hipcub/hipcub.hpp>
 #include <vector>
 
@@ -57,13 +59,16 @@ SortWs sort_layout(int64_t n) {
 // or by scan (linr_decode_scale_batch), whichever layout() was asked for: `is_scan` says which member is set
 struct ScaleWs {
     size_t nbr, lo, mask, feat, occ, probs, sdev, kws, child, arena, total;
+    size_t sbytes, tab;             // device decoders only (behind everything else): the scale's stream bytes, the entry table
     int64_t ld;
     size_t arena_bytes;
     bool is_scan;
     union { SortWs sort; ChildWs scan; };
 };
 
-ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan) {
+// stream_bytes >= 0: with the device decoders' two regions - the stream bytes padded to 256 bytes plus one 256-byte window, so that
+// every aligned window a wave could ask for lies inside, and n_entries table entries
+ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan, int64_t stream_bytes = -1, int64_t n_entries = 0) {
     ScaleWs w;
     w.ld = (n + 63) / 64 * 64;
     size_t cur = 0;
@@ -81,6 +86,11 @@ ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan) {
     w.child = take(scan ? w.scan.total : w.sort.total);
     w.arena_bytes = bf16 ? linr_net_bf16_arena_bytes(n, block_layers) : linr_net_arena_bytes(n, block_layers);
     w.arena = take(w.arena_bytes);
+    w.sbytes = w.tab = cur;
+    if (stream_bytes >= 0) {
+        w.sbytes = take(up256((size_t)stream_bytes) + 256);
+        w.tab = take(sizeof(linr_rc_dec_entry) * (size_t)n_entries);
+    }
     w.total = cur;
     return w;
 }
@@ -165,6 +175,8 @@ struct StagePlan {
     std::vector<uint8_t*> s;
     std::vector<const uint8_t*> in;
     std::vector<int64_t> n, len;
+    std::vector<int64_t> row;       // the entry's first row
+    std::vector<int32_t> stream;    // the stream it lies in: 8 * segment + stage
     int64_t first[9];
     int64_t symbols[8];             // of stage k
     bool chunked;
@@ -191,8 +203,12 @@ int plan_stages(const int64_t* seg_off_h, int n_seg, const uint8_t* const* strea
             plan.symbols[k] += n;
             for (int64_t j = 0; j < nc; ++j) {
                 const int64_t a = j * chunk_symbols;              // (one chunk: a = 0 whatever chunk_symbols is)
-                plan.p.push_back(p_pinned + r0 + a);
-                plan.s.push_back(s_pinned + r0 + a);
+                if (p_pinned) {                                   // (the device decoders address rows, not host buffers)
+                    plan.p.push_back(p_pinned + r0 + a);
+                    plan.s.push_back(s_pinned + r0 + a);
+                }
+                plan.row.push_back(r0 + a);
+                plan.stream.push_back((int32_t)(i * 8 + k));
                 plan.n.push_back(nc == 1 ? n : (n - a < chunk_symbols ? n - a : chunk_symbols));
                 plan.in.push_back(cp[(size_t)j]);
                 plan.len.push_back(cl[(size_t)j]);
@@ -208,10 +224,15 @@ int plan_stages(const int64_t* seg_off_h, int n_seg, const uint8_t* const* strea
 // itself hands in the plan it made of them (`ready`), otherwise the plan is made behind the first forward.  The range decoders return
 // the first failing entry's code (in order on this thread with n_threads 1); they decode the entries behind it, too, but those bytes
 // stay in s_pinned: the call returns before anything more is launched.
+// Device mode (dev != NULL, with `ready`): the entries of `ready` are in dev->tab and their bytes in dev->bytes on the device, and
+// stage k is the forward followed by rc_decode_k over the stage's entries, which write column k of the occupancy from the
+// probabilities where the forward left them: no copy, no host thread and NO synchronisation - the caller's child count is the one.
+struct DeviceStages { const uint8_t* bytes; const linr_rc_dec_entry* tab; };
+
 int decode_stages(const linr_frame* f, const float* params, const uint8_t* codes, float min_param, float max_param, void* arena,
                   size_t arena_bytes, const int64_t* seg_off_h, int n_seg, const uint8_t* const* streams_h,
                   const int64_t* stream_len_h, float* probs, float* p_pinned, uint8_t* s_pinned, uint8_t* s_dev, int n_threads,
-                  const StagePlan* ready, hipStream_t s) {
+                  const StagePlan* ready, hipStream_t s, const DeviceStages* dev = nullptr) {
     const int64_t R = f->rows;
     if (R == 0) return 0;
     float* occ = const_cast<float*>(f->occ);
@@ -219,6 +240,12 @@ int decode_stages(const linr_frame* f, const float* params, const uint8_t* codes
     for (int k = 0; k < 8; ++k) {
         if (codes) TRY(linr_net_forward_bf16(f, codes, min_param, max_param, arena, arena_bytes, k, k + 1, probs, nullptr, s));
         else TRY(linr_net_forward(f, params, (float*)arena, arena_bytes, k, k + 1, probs, nullptr, s));
+        if (dev) {
+            linr_poison_hook(s, PK_DECODE);
+            TRY(linr_rc_dec_launch(probs + (int64_t)k * R, dev->bytes, dev->tab + ready->first[k], (int32_t)(ready->first[k + 1] - ready->first[k]),
+                                   occ + k, 8, nullptr, s));
+            continue;
+        }
         TRY(linr_hip_rc(hipMemcpyAsync(p_pinned, probs + (int64_t)k * R, (size_t)R * sizeof(float), hipMemcpyDeviceToHost, s)));
         TRY(linr_hip_rc(hipStreamSynchronize(s)));
         if (!ready) {
@@ -237,8 +264,47 @@ int decode_stages(const linr_frame* f, const float* params, const uint8_t* codes
         occ_col_from_u8_k<<<linr_grid(R, LINR_BLOCK), LINR_BLOCK, 0, s>>>(s_dev, R, occ + k);
         TRY(linr_launch_rc());
     }
+    if (dev) return 0;
     return linr_hip_rc(hipStreamSynchronize(s));       // s_pinned / p_pinned may be reused by the caller right away
 }
+
+// The device decoders' side of a scale: the bytes of the plan's streams back to back in stream order, every entry of the
+// plan as a table entry over them, checked stage by stage as linr_rc_decode_probs checks its table.  Host work only.
+struct DevicePlan {
+    std::vector<uint8_t> bytes;
+    std::vector<linr_rc_dec_entry> ent;
+};
+
+int plan_device(const StagePlan& plan, int n_seg, const int64_t* seg_off_h, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                int64_t rows, DevicePlan& d) {
+    std::vector<int64_t> off((size_t)n_seg * 8 + 1, 0);
+    for (int i = 0; i < n_seg; ++i)
+        for (int k = 0; k < 8; ++k) {
+            const size_t x = (size_t)i * 8 + k;
+            const bool live = seg_off_h[i + 1] > seg_off_h[i];          // an empty segment's streams stay unread
+            if (live && (stream_len_h[x] < 0 || (stream_len_h[x] > 0 && !streams_h[x]))) return LINR_EINVAL;
+            off[x + 1] = off[x] + (live ? stream_len_h[x] : 0);
+        }
+    d.bytes.resize((size_t)off.back());
+    for (size_t x = 0; x + 1 < off.size(); ++x)
+        if (off[x + 1] > off[x]) memcpy(d.bytes.data() + off[x], streams_h[x], (size_t)(off[x + 1] - off[x]));
+    d.ent.resize(plan.n.size());
+    for (size_t e = 0; e < plan.n.size(); ++e) {
+        const size_t x = (size_t)plan.stream[e];
+        const int64_t in_off = off[x] + (plan.len[e] > 0 ? plan.in[e] - streams_h[x] : 0);
+        d.ent[e] = linr_rc_dec_entry{plan.row[e], plan.n[e], in_off, plan.len[e], plan.row[e]};
+    }
+    if (plan.n.size() >= (size_t)INT32_MAX) return LINR_EINVAL;
+    for (int k = 0; k < 8; ++k)
+        TRY(linr_rc_dec_check(d.ent.data() + plan.first[k], (int32_t)(plan.first[k + 1] - plan.first[k]), rows, off.back(), rows));
+    return 0;
+}
+
+// a stream synchronised when the scope is left early: the staging copy of the stream bytes must outlive its upload
+struct SyncOnExit {
+    hipStream_t s; bool armed;
+    ~SyncOnExit() { if (armed) (void)hipStreamSynchronize(s); }
+};
 
 }  // namespace
 
@@ -274,19 +340,42 @@ extern "C" size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, in
     return layout(n, block_layers, bf16 ? 1 : 0, false).total + 256;
 }
 
-extern "C" int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
-                                         int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
-                                         const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
-                                         float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
-                                         int64_t chunk_symbols, int32_t n_threads, void* stream) {
+namespace {
+
+// The device decoders of a scale in front of its stages: the plan's bytes and table into the workspace (laid out for exactly them:
+// LINR_ENOSPC when ws_bytes does not reach).  `keep` owns the staging copy; `guard` synchronises if the scale is left early.
+int stage_device(const StagePlan& plan, int n_seg, const int64_t* seg_off_h, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                 int64_t rows, int block_layers, int bf16, bool scan, size_t ws_bytes, char* base, DevicePlan& keep, ScaleWs& w,
+                 DeviceStages& dev) {
+    TRY(plan_device(plan, n_seg, seg_off_h, streams_h, stream_len_h, rows, keep));
+    w = layout(rows, block_layers, bf16, scan, (int64_t)keep.bytes.size(), (int64_t)keep.ent.size());
+    if (ws_bytes < w.total) return LINR_ENOSPC;
+    dev.bytes = (const uint8_t*)(base + w.sbytes);
+    dev.tab = (const linr_rc_dec_entry*)(base + w.tab);
+    return 0;
+}
+
+int upload_device(const DevicePlan& keep, const DeviceStages& dev, hipStream_t s) {
+    linr_poison_hook(s, PK_DECODE);
+    if (!keep.bytes.empty())
+        TRY(linr_hip_rc(hipMemcpyAsync(const_cast<uint8_t*>(dev.bytes), keep.bytes.data(), keep.bytes.size(), hipMemcpyHostToDevice, s)));
+    return linr_rc_dec_upload(keep.ent.data(), (int32_t)keep.ent.size(), const_cast<linr_rc_dec_entry*>(dev.tab), s);
+}
+
+// linr_decode_scale_chunked and linr_decode_scale_device: `device` picks the decoders (then p_pinned, s_pinned and n_threads are unused)
+int decode_scale_any(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers, int32_t child_bits,
+                     const float* params, const uint8_t* codes, float min_param, float max_param, const uint8_t* const* streams_h,
+                     const int64_t* stream_len_h, void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
+                     int64_t child_cap, int64_t* child_n_h, int64_t chunk_symbols, int32_t n_threads, bool device, void* stream) {
     if (n < 0 || !child_n_h || child_bits < 1 || child_bits > 21 || block_layers < 1) return LINR_EINVAL;
     *child_n_h = 0;
     if (n == 0) return 0;
-    if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !p_pinned || !s_pinned || !child_xyz) return LINR_EINVAL;
+    if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !child_xyz) return LINR_EINVAL;
+    if (!device && (!p_pinned || !s_pinned)) return LINR_EINVAL;
     // (one row looser than linr_rows_fit32, which the executor's frame check then applies to the frame built below)
     if (child_cap < 0 || n >= ((int64_t)1 << 27)) return LINR_EINVAL;
     if (((uintptr_t)ws) & 255u) return LINR_EALIGN;
-    const ScaleWs w = layout(n, block_layers, codes ? 1 : 0, false);
+    ScaleWs w = layout(n, block_layers, codes ? 1 : 0, false);
     if (ws_bytes < w.total) return LINR_ENOSPC;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
@@ -294,9 +383,17 @@ extern "C" int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_
     sf.row_off[0] = 0; sf.row_off[1] = n;
     StagePlan plan;                 // a malformed chunk header is refused here, in front of the first launch
     TRY(plan_stages(sf.row_off, 1, streams_h, stream_len_h, chunk_symbols, p_pinned, s_pinned, plan));
+    DevicePlan keep;
+    DeviceStages dev{nullptr, nullptr};
+    SyncOnExit guard{s, false};
+    if (device) {
+        TRY(stage_device(plan, 1, sf.row_off, streams_h, stream_len_h, n, block_layers, codes ? 1 : 0, false, ws_bytes, base, keep, w, dev));
+        guard.armed = true;
+        TRY(upload_device(keep, dev, s));
+    }
     TRY(scale_prologue(coord, n, nullptr, 0, scale_idx, model_scale_num, block_layers, base, w, sf, s));
     TRY(decode_stages(&sf.f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, sf.row_off, 1, streams_h, stream_len_h,
-                      (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, &plan, s));
+                      (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, &plan, s, device ? &dev : nullptr));
     // upper_layer: children of the occupied octants, sorted x-major
     const float* occ = sf.f.occ;
     char* cbase = base + w.child;
@@ -312,6 +409,7 @@ extern "C" int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_
     TRY(linr_hip_rc(hipMemcpyAsync(&total, pos + n, sizeof(int32_t), hipMemcpyDeviceToHost, s)));
     child_keys_k<<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(coord, occ, pos, n, child_bits, keys0);
     TRY(linr_hip_rc(hipStreamSynchronize(s)));                  // `total` is on the host now
+    guard.armed = false;
     if (total > child_cap) return LINR_ENOSPC;
     if (total > 0) {
         cb = w.sort.cub_bytes;
@@ -320,6 +418,32 @@ extern "C" int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_
     }
     *child_n_h = total;
     return linr_launch_rc();
+}
+
+}  // namespace
+
+extern "C" int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                                         int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                                         const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                                         float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
+                                         int64_t chunk_symbols, int32_t n_threads, void* stream) {
+    return decode_scale_any(coord, n, scale_idx, model_scale_num, block_layers, child_bits, params, codes, min_param, max_param, streams_h,
+                            stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap, child_n_h, chunk_symbols, n_threads, false,
+                            stream);
+}
+
+extern "C" size_t linr_decode_scale_device_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total,
+                                                    int64_t n_entries) {
+    if (n < 0 || block_layers < 1 || stream_bytes_total < 0 || n_entries < 0) return 0;
+    return layout(n, block_layers, bf16 ? 1 : 0, false, stream_bytes_total, n_entries).total + 256;
+}
+
+extern "C" int linr_decode_scale_device(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                                        int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                                        const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                                        int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h, int64_t chunk_symbols, void* stream) {
+    return decode_scale_any(coord, n, scale_idx, model_scale_num, block_layers, child_bits, params, codes, min_param, max_param, streams_h,
+                            stream_len_h, ws, ws_bytes, nullptr, nullptr, child_xyz, child_cap, child_n_h, chunk_symbols, 1, true, stream);
 }
 
 extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
@@ -489,12 +613,14 @@ extern "C" size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_fr
     return layout(n_total, block_layers, bf16 ? 1 : 0, true).total + 256;
 }
 
-extern "C" int linr_decode_scale_batch_chunked(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
-                                               int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
-                                               float min_param, float max_param, const uint8_t* const* streams_h,
-                                               const int64_t* stream_len_h, void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned,
-                                               int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h, int32_t n_threads,
-                                               int64_t chunk_symbols, void* stream) {
+namespace {
+
+// linr_decode_scale_batch_chunked and linr_decode_scale_batch_device, as decode_scale_any
+int decode_scale_batch_any(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx, int32_t model_scale_num,
+                           int32_t block_layers, const float* params, const uint8_t* codes, float min_param, float max_param,
+                           const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes, float* p_pinned,
+                           uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h, int32_t n_threads,
+                           int64_t chunk_symbols, bool device, void* stream) {
     LinrSegTab tab;
     int64_t n = 0;
     int rc = linr_seg_tab(seg_off_h, n_frames, &tab, &n);
@@ -504,19 +630,60 @@ extern "C" int linr_decode_scale_batch_chunked(const int32_t* coord, const int64
     if (!linr_cmap_fits32(ld) || !linr_rows_fit32(n)) return LINR_EINVAL;
     for (int i = 0; i <= n_frames; ++i) child_off_h[i] = 0;
     if (n == 0) return 0;
-    if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !p_pinned || !s_pinned || !child_xyz) return LINR_EINVAL;
+    if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !child_xyz) return LINR_EINVAL;
+    if (!device && (!p_pinned || !s_pinned)) return LINR_EINVAL;
     if (((uintptr_t)ws) & 255u) return LINR_EALIGN;
-    const ScaleWs w = layout(n, block_layers, codes ? 1 : 0, true);
+    ScaleWs w = layout(n, block_layers, codes ? 1 : 0, true);
     if (ws_bytes < w.total) return LINR_ENOSPC;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
     ScaleFrame sf;
     StagePlan plan;                 // a malformed chunk header is refused here, in front of the first launch
     TRY(plan_stages(seg_off_h, n_frames, streams_h, stream_len_h, chunk_symbols, p_pinned, s_pinned, plan));
+    DevicePlan keep;
+    DeviceStages dev{nullptr, nullptr};
+    SyncOnExit guard{s, false};
+    if (device) {
+        TRY(stage_device(plan, n_frames, seg_off_h, streams_h, stream_len_h, n, block_layers, codes ? 1 : 0, true, ws_bytes, base, keep, w, dev));
+        guard.armed = true;
+        TRY(upload_device(keep, dev, s));
+    }
     TRY(scale_prologue(coord, n, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, base, w, sf, s));
     TRY(decode_stages(&sf.f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, seg_off_h, n_frames, streams_h,
-                      stream_len_h, (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, &plan, s));
+                      stream_len_h, (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, &plan, s,
+                      device ? &dev : nullptr));
+    // (children_segments synchronises when it succeeds; the guard covers the ways out in front of that)
     return children_segments(coord, sf.f.occ, tab, n, n_frames, child_xyz, child_cap, child_off_h, base + w.child, w.scan, s);
+}
+
+}  // namespace
+
+extern "C" int linr_decode_scale_batch_chunked(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                               int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                               float min_param, float max_param, const uint8_t* const* streams_h,
+                                               const int64_t* stream_len_h, void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned,
+                                               int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h, int32_t n_threads,
+                                               int64_t chunk_symbols, void* stream) {
+    return decode_scale_batch_any(coord, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, params, codes, min_param, max_param,
+                                  streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap, child_off_h, n_threads,
+                                  chunk_symbols, false, stream);
+}
+
+extern "C" size_t linr_decode_scale_batch_device_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
+                                                          int64_t stream_bytes_total, int64_t n_entries) {
+    if (n_total < 0 || n_total >= ((int64_t)1 << 26) || n_frames < 1 || n_frames > LINR_DECODE_MAX_FRAMES || block_layers < 1) return 0;
+    if (stream_bytes_total < 0 || n_entries < 0) return 0;
+    return layout(n_total, block_layers, bf16 ? 1 : 0, true, stream_bytes_total, n_entries).total + 256;
+}
+
+extern "C" int linr_decode_scale_batch_device(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                              int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                              float min_param, float max_param, const uint8_t* const* streams_h,
+                                              const int64_t* stream_len_h, void* ws, size_t ws_bytes, int32_t* child_xyz, int64_t child_cap,
+                                              int64_t* child_off_h, int64_t chunk_symbols, void* stream) {
+    return decode_scale_batch_any(coord, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, params, codes, min_param, max_param,
+                                  streams_h, stream_len_h, ws, ws_bytes, nullptr, nullptr, child_xyz, child_cap, child_off_h, 1, chunk_symbols,
+                                  true, stream);
 }
 
 extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,

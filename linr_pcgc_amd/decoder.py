@@ -15,14 +15,15 @@ from .encoder import gop_bounds
 
 def decode(inargs):
     """decoder.py:16-48.  inargs: 'gop_names', 'result_enc_dir', 'result_dec_dir', 'Gen_Model', 'dataset' (a MytestDataset: the
-    sorted voxel list of every frame), 'write_flag'."""
+    sorted voxel list of every frame), 'write_flag'; optional 'device_decoder' (True: the range decoders run on the GPU,
+    codec.decode_gop device_decoder=)."""
     os.makedirs(inargs['result_dec_dir'], exist_ok=True)
     for gop_name in inargs['gop_names']:
         first, last = gop_bounds(gop_name)
         decode_one_gop({'gop_bound': [first, last], 'frame_num': last - first + 1, 'result_enc_dir': inargs['result_enc_dir'],
                         'result_dec_dir': inargs['result_dec_dir'], 'Gen_Model': inargs['Gen_Model'], 'gop_name': gop_name,
                         'reading_data': Read_Data_with_cache(inargs['dataset'], list(range(first, last + 1))),
-                        'write_flag': inargs['write_flag']})
+                        'write_flag': inargs['write_flag'], 'device_decoder': bool(inargs.get('device_decoder', False))})
 
 
 def decode_one_gop(inargs):
@@ -30,7 +31,8 @@ def decode_one_gop(inargs):
     AssertionError on the first frame that differs from the data set's."""
     enc = codec.read_gop(os.path.join(inargs['result_enc_dir'], inargs['gop_name']))
     dev = 'cuda' if torch.cuda.is_available() else 'cpu'
-    decoded = codec.decode_gop(inargs['Gen_Model'](), enc, dev, frames=list(range(inargs['frame_num'])), workers=1)
+    extra = {'device_decoder': True} if inargs.get('device_decoder', False) else {}
+    decoded = codec.decode_gop(inargs['Gen_Model'](), enc, dev, frames=list(range(inargs['frame_num'])), workers=1, **extra)
     with PlyWriter() as writer:          # formatted on the GPU, written by the writer's thread; closed before this returns or raises
         for frame_idx, dec in enumerate(decoded):
             truth = inargs['reading_data'][frame_idx]
@@ -42,14 +44,9 @@ def decode_one_gop(inargs):
     return decoded
 
 
-def main(argv=None):
-    """python -m linr_pcgc_amd.decoder --enc-dir OUT/result_enc --dec-dir OUT/dec [--ori-dir frames --ori-type ply --ply-parse device] [--lockstep B]
-    The decoder as its own program (decoder.py:179-200): every GOP under --enc-dir from its files alone, frames written as
-    frameXXXX.ply; with --ori-dir each one is also compared with the input.  The model's shape travels in side_info.json (the
-    reference hard-codes it, decoder.py:189); for streams without it the scale count is read off the stream files and width /
-    block_layers are flags."""
+def parser():
+    """The command line of main()."""
     import argparse
-    from .model_core import LINR_PCGC_Model
     ap = argparse.ArgumentParser('linr_pcgc_amd.decoder')
     ap.add_argument('--enc-dir', required=True)
     ap.add_argument('--dec-dir', required=True)
@@ -59,9 +56,23 @@ def main(argv=None):
     ap.add_argument('--block-layers', type=int, default=1)
     ap.add_argument('--lockstep', type=int, default=0,
                     help='decode the frames of a GOP in groups of up to this many, all scales in lock step (codec.decode_gop lockstep=; 0: frame by frame)')
+    ap.add_argument('--device-decoder', '--device_decoder', dest='device_decoder', action='store_true',
+                    help='range-decode on the GPU, a wave per stream or chunk, without host coder threads (codec.decode_gop device_decoder=; '
+                         'hidden_channel_conv 8 only); the files read are the same')
     ap.add_argument('--ply-parse', '--ply_parse', dest='ply_parse', default='host', choices=['host', 'device'],
                     help='with --ori-dir: the original PLY frames are parsed by the host parser (default) or on the GPU (ply.read_points_device)')
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    """python -m linr_pcgc_amd.decoder --enc-dir OUT/result_enc --dec-dir OUT/dec [--ori-dir frames --ori-type ply --ply-parse device] [--lockstep B]
+    [--device-decoder]
+    The decoder as its own program (decoder.py:179-200): every GOP under --enc-dir from its files alone, frames written as
+    frameXXXX.ply; with --ori-dir each one is also compared with the input.  The model's shape travels in side_info.json (the
+    reference hard-codes it, decoder.py:189); for streams without it the scale count is read off the stream files and width /
+    block_layers are flags."""
+    from .model_core import LINR_PCGC_Model
+    args = parser().parse_args(argv)
     names = sorted((n for n in os.listdir(args.enc_dir) if n.startswith('gop_')), key=lambda n: gop_bounds(n)[0])
     if not names:
         raise ValueError('no gop_* directory under %s' % args.enc_dir)
@@ -71,6 +82,7 @@ def main(argv=None):
         from .custom_dataset import MytestDataset
         truth = MytestDataset(args.ori_dir, ori_type=args.ori_type, device_parse=args.ply_parse == 'device')
     dev = 'cuda' if torch.cuda.is_available() else 'cpu'
+    extra = {'device_decoder': True} if args.device_decoder else {}
     frames = 0
     with PlyWriter() as writer:          # closed - every file complete - before main returns or raises
         for name in names:
@@ -82,9 +94,9 @@ def main(argv=None):
                      'block_layers': int(side.get('block_layers', args.block_layers)), 'outstage': 8, 'instage': 1}
             gen = lambda: LINR_PCGC_Model(shape).to(dev)
             if args.lockstep > 0:
-                decoded = codec.decode_gop(gen(), enc, dev, lockstep=args.lockstep)
+                decoded = codec.decode_gop(gen(), enc, dev, lockstep=args.lockstep, **extra)
             else:
-                decoded = codec.decode_gop(gen(), enc, dev, workers=1 if shape['hidden_channel_conv'] != 8 else 4)
+                decoded = codec.decode_gop(gen(), enc, dev, workers=1 if shape['hidden_channel_conv'] != 8 else 4, **extra)
             if len(decoded) != last - first + 1:
                 raise ValueError('%s holds %d frames, its name says %d' % (name, len(decoded), last - first + 1))
             for i, dec in enumerate(decoded):

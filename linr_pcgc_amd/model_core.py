@@ -346,37 +346,51 @@ class LINR_PCGC_Model(nn.Module):
         frame = self.make_frame([s], with_arena=self._precision(None) == 'f32')
         return self.decode_frame(frame, [streams])
 
-    def _decode_scale_args(self, size_fn, size_args, coord, streams):
+    def _decode_scale_args(self, size_fn, size_args, coord, streams, device_entries=None):
         """What decode_scale and decode_scale_batch hand their C entry alike, in the entries' order: (params, codes, lo, hi, stream
         pointers, stream lengths, aligned workspace, its bytes, pinned probabilities, pinned symbols, child buffer, its rows), the
         workspace bytes (size_fn(*size_args, block_layers, bf16); 0: the entry refuses the size, nothing else is returned) and the
-        objects that own that memory, child buffer first: keep them until the call has returned."""
+        objects that own that memory, child buffer first: keep them until the call has returned.
+        device_entries = the table entries of the scale: the device decoders' entries, whose size_fn also takes the streams' bytes
+        together and that count, and which take no pinned buffers."""
         n = int(coord.shape[0])
         ptrs, lens, bufs = engine.stream_arrays(streams)
         bf16 = self._precision(None) == 'bf16'
-        need = size_fn(*size_args, self.block_layers, 1 if bf16 else 0)
+        extra = () if device_entries is None else (sum(len(b) for b in streams), int(device_entries))
+        need = size_fn(*size_args, self.block_layers, 1 if bf16 else 0, *extra)
         if need == 0:
             return None, 0, None
         ws = _lib.scratch(need + 256, coord.device)
         child = torch.empty((8 * n, 3), dtype=torch.int32, device=coord.device)
-        p_host, s_host = self._host_buffers(n)
+        pinned = tuple(b.data_ptr() for b in self._host_buffers(n)) if device_entries is None else ()
         codes, lo, hi, params = (self._qcodes.data_ptr(), float(self._qrange[0]), float(self._qrange[1]), None) if bf16 else \
             (None, 0.0, 0.0, self._flat.data_ptr())
-        return (params, codes, lo, hi, ptrs, lens, (ws.data_ptr() + 255) & ~255, need, p_host.data_ptr(), s_host.data_ptr(),
+        return (params, codes, lo, hi, ptrs, lens, (ws.data_ptr() + 255) & ~255, need, *pinned,
                 child.data_ptr(), 8 * n), need, (child, ws, bufs)
 
     @torch.no_grad()
-    def decode_scale(self, coord, scale_idx, enc_bytes, child_bits, chunk=0, n_threads=1):
+    def decode_scale(self, coord, scale_idx, enc_bytes, child_bits, chunk=0, n_threads=1, device_decoder=False):
         """One scale of decoder.decode_one_frame (decoder.py:153-176) as ONE C call that does not hold the GIL
         (linr_decode_scale): kernel map of `coord` (int32 [n,3] on the GPU, sorted x-major), the 8 decode stages against the
         packed stream `enc_bytes`, octree_level.upper_layer.  Returns the next finer level's coordinates (int32 [m,3]).
         chunk = S > 0: the stage streams are chunked (stream_chunks) and a stage's chunks are decoded on `n_threads` host threads
-        (linr_decode_scale_chunked)."""
+        (linr_decode_scale_chunked).
+        device_decoder=True (opt-in): the range decoders run on the GPU, a wave per stream or chunk, from the probabilities where the
+        stage forward left them (linr_decode_scale_device): no host round trip per stage, one synchronisation per scale; n_threads is
+        ignored.  The streams and the result are the same."""
         L = _lib.lib()
         n = int(coord.shape[0])
         if n == 0:
             return coord.new_zeros((0, 3))
         coord = coord.contiguous()
+        if device_decoder:
+            shared, _, keep = self._decode_scale_args(L.linr_decode_scale_device_ws_bytes, (n,), coord, unpack_bitstream(enc_bytes),
+                                                      8 * chunk_count(n, int(chunk)))
+            m = ctypes.c_int64(0)
+            _lib.check(L.linr_decode_scale_device(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits),
+                                                  *shared, ctypes.byref(m), int(chunk), torch.cuda.current_stream().cuda_stream),
+                       'linr_decode_scale_device')
+            return keep[0][:m.value]
         shared, _, keep = self._decode_scale_args(L.linr_decode_scale_ws_bytes, (n,), coord, unpack_bitstream(enc_bytes))
         m = ctypes.c_int64(0)
         if chunk:
@@ -389,12 +403,14 @@ class LINR_PCGC_Model(nn.Module):
         return keep[0][:m.value]
 
     @torch.no_grad()
-    def decode_scale_batch(self, coords_list, scale_idx, enc_bytes_list, n_threads=8, chunk=0):
+    def decode_scale_batch(self, coords_list, scale_idx, enc_bytes_list, n_threads=8, chunk=0, device_decoder=False):
         """decode_scale for several frames in lock step as ONE C call (linr_decode_scale_batch): the frames' levels `coords_list`
         (int32 [n_i,3] on the GPU, each sorted x-major) are one row space whose kernel map never links two frames, every decode stage
         is one launch set and one copy each way for all of them, their range decoders run on `n_threads` host threads, and the
         children come from prefix sums instead of a sort.  Returns the list of the next finer levels' coordinates (int32 [m_i,3]).
-        chunk = S > 0: the stage streams are chunked (stream_chunks; linr_decode_scale_batch_chunked)."""
+        chunk = S > 0: the stage streams are chunked (stream_chunks; linr_decode_scale_batch_chunked).
+        device_decoder=True (opt-in): as in decode_scale - every stream or chunk of the group's frames a wave of one launch per stage
+        (linr_decode_scale_batch_device); n_threads is ignored."""
         L = _lib.lib()
         nf = len(coords_list)
         if nf < 1 or nf > 64 or len(enc_bytes_list) != nf:
@@ -408,11 +424,17 @@ class LINR_PCGC_Model(nn.Module):
         streams = [b for e in enc_bytes_list for b in unpack_bitstream(e)]
         if len(streams) != 8 * nf:
             raise ValueError('every frame needs the 8 stage streams of the scale')
-        shared, need, keep = self._decode_scale_args(L.linr_decode_scale_batch_ws_bytes, (n, nf), coord, streams)
+        entries = 8 * sum(chunk_count(int(c.shape[0]), int(chunk)) for c in coords_list if c.shape[0]) if device_decoder else None
+        size_fn = L.linr_decode_scale_batch_device_ws_bytes if device_decoder else L.linr_decode_scale_batch_ws_bytes
+        shared, need, keep = self._decode_scale_args(size_fn, (n, nf), coord, streams, entries)
         if need == 0:
             raise ValueError('%d rows in one decode group: the bound is 2^26 - 64' % n)
         off = (ctypes.c_int64 * (nf + 1))()
-        if chunk:
+        if device_decoder:
+            _lib.check(L.linr_decode_scale_batch_device(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num,
+                                                        self.block_layers, *shared, off, int(chunk),
+                                                        torch.cuda.current_stream().cuda_stream), 'linr_decode_scale_batch_device')
+        elif chunk:
             _lib.check(L.linr_decode_scale_batch_chunked(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num,
                                                          self.block_layers, *shared, off, int(n_threads), int(chunk),
                                                          torch.cuda.current_stream().cuda_stream), 'linr_decode_scale_batch_chunked')
@@ -661,6 +683,27 @@ def encode_streams_device(c1, sym, descriptors, chunk=0):
     coder = DeviceCoderSet(len(d), DeviceCoderSet.table(d, chunk)[1], c1.device, chunk, DeviceCoderSet.chunks(d, chunk))
     coder.launch(c1.reshape(-1), sym.reshape(-1), d)
     return coder.collect()
+
+
+def rc_decode_probs(probs, data, entries, occ, column, sym=None):
+    """The range decoder on the GPU, a wave per entry (linr_rc_decode_probs): probs a float32 device tensor of probabilities, data a
+    uint8 device tensor of stream bytes (padded to a multiple of 4), entries rows of {probability offset, n, byte offset, byte length,
+    first row}; entry i's decoded symbols go to occ[first row .. first row + n, column] (occ: float32 [rows, ld] on the device) as 0.0 /
+    1.0 and, with sym (uint8 [rows]), there as bytes.  Nothing else is written; the call does not synchronise."""
+    L = _lib.lib()
+    tab = np.ascontiguousarray(np.asarray(entries, dtype=np.int64).reshape(-1, 5))
+    if occ.dim() != 2 or occ.dtype != torch.float32 or not occ.is_contiguous() or not 0 <= int(column) < occ.shape[1]:
+        raise ValueError('occ is a contiguous float32 [rows, ld] tensor and column one of its columns')
+    if data.dtype != torch.uint8 or probs.dtype != torch.float32 or (sym is not None and (sym.dtype != torch.uint8 or sym.numel() < occ.shape[0])):
+        raise ValueError('probs float32, data uint8, sym uint8 [rows]')
+    if data.numel() % 4:
+        raise ValueError('the byte buffer is read in 32-bit words: pad it to a multiple of 4 bytes')
+    need = int(L.linr_rc_decode_ws_bytes(len(tab)))
+    ws = _lib.scratch(need + 8, occ.device)
+    _lib.check(L.linr_rc_decode_probs(probs.data_ptr(), probs.numel(), data.data_ptr(), data.numel(), tab.ctypes.data, len(tab),
+                                      occ.data_ptr() + 4 * int(column), int(occ.shape[1]), int(occ.shape[0]),
+                                      None if sym is None else sym.data_ptr(), ws.data_ptr(), need, _lib.current_stream_handle()),
+               'linr_rc_decode_probs')          # (ws may go: the caching allocator hands it out again in stream order only)
 
 
 class FlatAdam:

@@ -89,6 +89,10 @@ def parse(argv=None):
     ap.add_argument('--decode-lockstep', '--decode_lockstep', dest='decode_lockstep', type=int, default=0,
                     help='with --decode: decode the frames of a GOP in groups of up to this many, all scales in lock step '
                          '(codec.decode_gop lockstep=; 0: frame by frame on 4 workers)')
+    ap.add_argument('--device-decoder', '--device_decoder', dest='device_decoder', action='store_true',
+                    help='with --decode: the range decoders of the check run on the GPU, a wave per stream or chunk (codec.decode_gop '
+                         'device_decoder=): no host coder threads and one synchronisation per scale instead of one per stage; the streams and '
+                         'side_info.json are untouched.  --hidden-channel-conv 8 only')
     ap.add_argument('--pipeline', action='store_true',
                     help='code, write and check GOP g on a background thread with a HIP stream of its own while GOP g+1 overfits (at most one '
                          'such finish in flight); the encoded files and the losses are those of the plain flow.  Up to three GOPs are resident '
@@ -118,6 +122,8 @@ def parse(argv=None):
         ap.error('--stream-chunk must be 0 or a multiple of 64 in 64..2^24')
     if args.stream_chunk and args.hidden_channel_conv != 8:
         ap.error('--stream-chunk: chunked stage streams exist for --hidden-channel-conv 8 only')
+    if args.device_decoder and args.hidden_channel_conv != 8:
+        ap.error('--device-decoder: the device range decoder exists for --hidden-channel-conv 8 only')
     return args
 
 
@@ -326,7 +332,8 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                 todo = list(range(len(group))) if decode_frames is None else list(range(min(decode_frames, len(group))))
                 lockstep = int(getattr(args, 'decode_lockstep', 0) or 0)
                 dec = codec.decode_gop(shell(),
-                                       codec.read_gop(res_dir), device, frames=todo, **({'lockstep': lockstep} if lockstep > 0 else {'workers': 4}))
+                                       codec.read_gop(res_dir), device, frames=todo, **({'lockstep': lockstep} if lockstep > 0 else {'workers': 4}),
+                                       **({'device_decoder': True} if getattr(args, 'device_decoder', False) else {}))
                 ok = all(torch.equal(d, torch.as_tensor(gop.infos[i]['ori']).cuda() +
                                      torch.tensor(gop.coord_mins[i], device='cuda', dtype=torch.int32))
                          for d, i in zip(dec, todo))
