@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 22
+#define LINR_ABI_VERSION 23
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -549,7 +549,7 @@ LINR_API int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* in
  * bytes of page-locked host memory; s_dev [rows] bytes of device scratch.  codes == NULL: fp32 executor with `params`;
  * otherwise the bf16 / uint8-weight executor with codes, min_param, max_param (then `arena` is a linr_net_bf16_arena_bytes one).
  * A scale without rows is skipped, its streams unread.  A stream the range decoder refuses ends the call with the code of the first
- * such scale, before anything more is launched.  (csrc/decode.hip: decode_stages, the loop linr_net_decode_stages_segments shares.) */
+ * such scale, before anything more is launched.  (csrc/decode.hip: decode_stages, the loop the decoder scales below share.) */
 LINR_API int linr_net_decode_stages(const linr_frame* f, const float* params, const uint8_t* codes, float min_param,
                            float max_param, void* arena, size_t arena_bytes, const uint8_t* const* streams_h,
                            const int64_t* stream_len_h, float* probs, float* p_pinned, uint8_t* s_pinned, uint8_t* s_dev,
@@ -559,98 +559,76 @@ LINR_API int linr_net_decode_stages(const linr_frame* f, const float* params, co
  * level's coordinates, the 7-neighbour features read off it (instead of qscTensor.set_offset_tensor's 7 searches), the 8 decode
  * stages of linr_net_decode_stages, and octree_level.upper_layer (models/module_utils.py:117-127): the coordinates of the next finer
  * level = children 2 p + (dx, dy, dz) of every decoded octant 4 dx + 2 dy + dz, sorted x-major (radix sort of child_bits-bit-per-
- * axis keys).  coord: DEVICE int32 [n][3], sorted x-major, unique; streams_h / stream_len_h: the 8 stage streams of this scale
- * (HOST); ws: DEVICE workspace of linr_decode_scale_ws_bytes(n, block_layers, codes != NULL) bytes, 256-byte aligned; p_pinned /
- * s_pinned: pinned HOST buffers of n floats / n bytes; child_xyz: DEVICE int32 [child_cap][3] (8 n is always enough); *child_n_h
- * receives the number of children.  params (fp32 executor) or codes + min / max (bf16 / uint8-weight executor).  Synchronises the
- * stream.  Between two scales the caller only allocates the next workspace. */
-LINR_API size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16);
+ * axis keys).  coord: DEVICE int32 [n][3], sorted x-major, unique, n < 2^27; streams_h / stream_len_h: the 8 stage streams of this
+ * scale (HOST); ws: DEVICE workspace of linr_decode_scale_ws_bytes bytes, 256-byte aligned; p_pinned / s_pinned: pinned HOST
+ * buffers of n floats / n bytes; child_xyz: DEVICE int32 [child_cap][3] (8 n is always enough); *child_n_h receives the number of
+ * children.  params (fp32 executor) or codes + min / max (bf16 / uint8-weight executor).  Synchronises the stream.  Between two
+ * scales the caller only allocates the next workspace.  Arguments are checked before the first launch: LINR_EINVAL, then
+ * LINR_EALIGN, then LINR_ENOSPC (short ws; more than child_cap children: after the stages, nothing is written past the cap);
+ * n = 0 returns 0 with *child_n_h = 0 whatever the pointers are.
+ *
+ * linr_decode_scale_batch, the lock-step GOP decoder: the same for n_frames frames (1..LINR_DECODE_MAX_FRAMES) per call, with
+ * N = seg_off_h[n_frames] rows (N < 2^26) and without a sort.  A row's arithmetic depends neither on the tiling nor on the rows
+ * that share its launch, so the frames' levels, back to back, are one row space with one scale index as long as the kernel map
+ * never links two frames (linr_kmap_build_segments); a stage then costs one launch set, one copy each way and n_frames range
+ * decoders.  streams_h / stream_len_h: HOST [n_frames][8] (an empty frame's are not read); p_pinned / s_pinned: N floats / N bytes;
+ * child_xyz: [child_cap][3] (8 N is always enough), frames back to back; child_off_h: HOST [n_frames + 1], the frames' child
+ * offsets, zeroed before the pointer checks.  Everything else as above.  Both entries share everything between their argument
+ * checks and the child expansion (csrc/decode.hip: scale_middle); they differ in the kernel-map call and the child expansion.
+ * Their kernels belong to poison class 15 and to no linr_prof_* class.
+ *
+ * linr_children_segments, the batch entry's child expansion on its own: coords int32 [N,3] and occ fp32 [N][8] (0 / non-zero,
+ * octant 4 dx + 2 dy + dz) of n_seg frames back to back, every frame sorted x-major, seg_off_h (HOST) [n_seg + 1] from 0 to N,
+ * N < 2^26.  Writes the children 2 p + (dx, dy, dz) of every occupied octant to child_xyz [child_cap][3], x-major sorted within a
+ * frame, frames back to back, and child_off_h (HOST) [n_seg + 1].  The parents are sorted already, so a child's position is a
+ * closed form of four prefix sums over the rows (counts of the (dx, dy) pairs) and of the bounds of the row's (frame, x) and
+ * (frame, x, y) runs: one scan, one scatter, no sort, no atomics.  LINR_ENOSPC when there are more than child_cap children (nothing
+ * is written past the cap).  ws: linr_children_segments_ws_bytes(N) bytes, 256-byte aligned.  Synchronises the stream (one host
+ * read of the n_seg + 1 offsets).
+ *
+ * Options of a scale (opts == NULL: {0, 1, 0}):
+ * chunk_symbols = S > 0: CHUNKED stage streams (linr_stream_split_chunks below; side_info.json's stream_chunk).  A stream of n > S
+ *   symbols is a header and k = ceil(n / S) chunks, and every chunk is decoded as an entry of its own: chunk j gives rows
+ *   [j S, min((j + 1) S, n)) of its frame.  Every stream's header is parsed and checked before the first launch: LINR_EINVAL for a
+ *   truncated length, one of more than 5 bytes, lengths that exceed the stream, or an S that is no multiple of 64 in 64..2^24.
+ * n_threads: the host threads of a stage's range decoders (linr_ac_decode_binary_batch): at most one per entry of the stage - so a
+ *   frame's plain stream is decoded on the calling thread - and with chunks at most one per 65,536 symbols of the stage, because
+ *   the threads are started anew in every call.
+ * device != 0 (opt-in): the range decoders on the DEVICE (linr_rc_decode_probs below).  The bytes of the scale's 8 streams of every
+ *   frame are uploaded once (stream order, from a staging copy the call owns: the caller's stream arrays are free on return), and
+ *   stage k is the stage's forward followed by rc_decode_k over the stage's entries, which write column k of the occupancy - no
+ *   copy down, no host thread, and ONE synchronisation per scale, where the call reads the child count.  p_pinned, s_pinned and
+ *   n_threads are unused.  The decoded geometry is that of the host path on every stream (the decoders agree on any bytes).
+ *
+ * Workspace (linr_decode_scale_ws_bytes / linr_decode_scale_batch_ws_bytes; bf16 = codes != NULL): stream_bytes_total = -1 is the
+ * host decoders' layout (n_entries is ignored).  stream_bytes_total >= 0 is the device decoders': the same plus a region for the
+ * stream bytes (stream_bytes_total = the sum of the 8 (x n_frames) stream lengths; padded to 256 bytes, at least 256, plus one
+ * 256-byte window: the device layout is the host layout plus 512 bytes or more)
+ * and one for the table (n_entries = the chunks of all 8 stages: the sum over frames and stages of linr_stream_chunk_count(rows of
+ * the frame, chunk_symbols), empty frames excluded; more is allowed); a device scale whose ws_bytes is below what its plan needs is
+ * LINR_ENOSPC.  0 for any other negative stream_bytes_total, a negative n_entries of the device layout, or rows / frames out of
+ * range. */
+typedef struct linr_decode_opts {
+    int64_t chunk_symbols;   /* 0: plain stage streams; S: chunked (multiple of 64 in 64..2^24) */
+    int32_t n_threads;       /* host range decoders of a stage; ignored when device != 0 */
+    int32_t device;          /* 0: host range decoders (p_pinned / s_pinned required); 1: rc_decode_k, pinned buffers unused, may be NULL */
+} linr_decode_opts;
+LINR_API size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total, int64_t n_entries);
 LINR_API int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
                       int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
                       const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
                       float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
-                      void* stream);
-
-/* The lock-step GOP decoder: ONE scale of n_frames frames per call (decoder.decode_one_frame's loop body, decoder.py:153-176, for
- * every frame of a group at once; octree_level.upper_layer, models/module_utils.py:117-127, without a sort).  A row's arithmetic
- * depends neither on the tiling nor on the rows that share its launch, so the frames' levels, back to back, are one row space with
- * one scale index as long as the kernel map never links two frames (linr_kmap_build_segments); a stage then costs one launch set,
- * one copy each way and n_frames range decoders on host threads.
- *
- * linr_children_segments: coords int32 [N,3] and occ fp32 [N][8] (0 / non-zero, octant 4 dx + 2 dy + dz) of n_seg frames back to
- * back, every frame sorted x-major, seg_off_h (HOST) [n_seg + 1] from 0 to N, N < 2^26.  Writes the children 2 p + (dx, dy, dz) of
- * every occupied octant to child_xyz [child_cap][3], x-major sorted within a frame, frames back to back, and child_off_h (HOST)
- * [n_seg + 1].  The parents are sorted already, so a child's position is a closed form of four prefix sums over the rows (counts of
- * the (dx, dy) pairs) and of the bounds of the row's (frame, x) and (frame, x, y) runs: one scan, one scatter, no sort, no atomics.
- * LINR_ENOSPC when there are more than child_cap children (nothing is written past the cap).  ws: linr_children_segments_ws_bytes(N)
- * bytes, 256-byte aligned.  Synchronises the stream (one host read of the n_seg + 1 offsets).
- *
- * linr_net_decode_stages_segments: linr_net_decode_stages for a frame object of ONE scale whose rows are n_seg segments (seg_off_h),
- * each with its own 8 stage streams (streams_h / stream_len_h [n_seg][8]); the n_seg range decoders of a stage run on up to
- * n_threads host threads (linr_ac_decode_binary_batch).  The same loop (csrc/decode.hip: decode_stages) with the segments in the place
- * of the frame's scales: an empty segment is skipped, its streams unread.
- *
- * linr_decode_scale_batch: linr_decode_scale for n_frames frames (1..LINR_DECODE_MAX_FRAMES) with N = seg_off_h[n_frames] rows
- * (N < 2^26): segmented kernel map, its compressed form and offset features, the 8 stages in lock step, the children.  streams_h /
- * stream_len_h: HOST [n_frames][8]; p_pinned / s_pinned: pinned HOST buffers of N floats / N bytes; child_xyz: DEVICE int32
- * [child_cap][3] (8 N is always enough); child_off_h: HOST [n_frames + 1].  ws: linr_decode_scale_batch_ws_bytes(N, n_frames,
- * block_layers, codes != NULL) bytes, 256-byte aligned.  Arguments are checked before the first launch: LINR_EINVAL, LINR_ENOSPC
- * (short ws), LINR_EALIGN as linr_decode_scale.  Both scale entries share their workspace layout, everything in front of the stages and
- * the stage loop (csrc/decode.hip: layout, scale_prologue, decode_stages); they differ in the kernel-map call and the child expansion.
- * Their kernels belong to poison class 15 and to no linr_prof_* class. */
-LINR_API size_t linr_children_segments_ws_bytes(int64_t n);
-LINR_API int linr_children_segments(const int32_t* coords, const float* occ, const int64_t* seg_off_h, int32_t n_seg, int32_t* child_xyz,
-                           int64_t child_cap, int64_t* child_off_h, void* ws, size_t ws_bytes, void* stream);
-LINR_API int linr_net_decode_stages_segments(const linr_frame* f, const float* params, const uint8_t* codes, float min_param,
-                                    float max_param, void* arena, size_t arena_bytes, const int64_t* seg_off_h, int32_t n_seg,
-                                    const uint8_t* const* streams_h, const int64_t* stream_len_h, float* probs, float* p_pinned,
-                                    uint8_t* s_pinned, uint8_t* s_dev, int32_t n_threads, void* stream);
-LINR_API size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16);
+                      const linr_decode_opts* opts, void* stream);
+LINR_API size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
+                                        int64_t stream_bytes_total, int64_t n_entries);
 LINR_API int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
                             int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
                             float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
                             void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap,
-                            int64_t* child_off_h, int32_t n_threads, void* stream);
-/* Both scale entries for CHUNKED stage streams (linr_stream_split_chunks below; side_info.json's stream_chunk): with chunk_symbols = S
- * a stream of n > S symbols is a header and k = ceil(n / S) chunks, and every chunk joins its stage's linr_ac_decode_binary_batch call
- * as an entry of its own - chunk j decodes rows [j S, min((j + 1) S, n)) of its frame - on up to n_threads host threads (at most one
- * per 65,536 symbols of the stage: the batch starts its threads anew in every call), which the per-frame entry therefore takes, too.  Every stream's header is parsed and checked before the first launch: LINR_EINVAL for a
- * truncated length, one of more than 5 bytes, lengths that exceed the stream, or an S that is no multiple of 64 in 64..2^24.
- * chunk_symbols 0: the entries above (which are these with 0, the per-frame one with one thread).  Everything else as there. */
-LINR_API int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
-                              int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
-                              const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
-                              float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
-                              int64_t chunk_symbols, int32_t n_threads, void* stream);
-LINR_API int linr_decode_scale_batch_chunked(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
-                                    int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
-                                    float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
-                                    void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
-                                    int64_t child_cap, int64_t* child_off_h, int32_t n_threads, int64_t chunk_symbols, void* stream);
-
-/* Both scale entries with the range decoders on the DEVICE (opt-in; linr_rc_decode_probs below): the arguments of
- * linr_decode_scale_chunked / linr_decode_scale_batch_chunked without p_pinned, s_pinned and n_threads; chunk_symbols 0 means plain
- * streams.  plan_stages and with it linr_stream_split_chunks run as there (a malformed chunk header is LINR_EINVAL in front of the first
- * launch); the bytes of the scale's 8 streams of every frame are uploaded once (stream order, from a staging copy the call owns: the
- * caller's stream arrays are free on return), and stage k is the stage's forward followed by rc_decode_k over the stage's entries,
- * which write column k of the occupancy - no copy down, no host thread, and ONE synchronisation per scale, where the call reads the
- * child count.  The decoded geometry is that of the host path on every stream (the decoders agree on any bytes).  Workspace: the
- * layout of the entries above plus a region for the stream bytes (stream_bytes_total = the sum of the 8 (x n_frames) stream lengths,
- * padded to 256 bytes plus one 256-byte window) and one for the table (n_entries = the chunks of all 8 stages: the sum over frames
- * and stages of linr_stream_chunk_count(rows of the frame, chunk_symbols), empty frames excluded; more is allowed): LINR_ENOSPC when
- * ws_bytes is below what the call needs.  The new launches belong to poison class 15 like the rest of a scale. */
-LINR_API size_t linr_decode_scale_device_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total, int64_t n_entries);
-LINR_API int linr_decode_scale_device(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
-                             int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
-                             const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
-                             int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h, int64_t chunk_symbols, void* stream);
-LINR_API size_t linr_decode_scale_batch_device_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
-                                               int64_t stream_bytes_total, int64_t n_entries);
-LINR_API int linr_decode_scale_batch_device(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
-                                   int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
-                                   float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
-                                   void* ws, size_t ws_bytes, int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h,
-                                   int64_t chunk_symbols, void* stream);
+                            int64_t* child_off_h, const linr_decode_opts* opts, void* stream);
+LINR_API size_t linr_children_segments_ws_bytes(int64_t n);
+LINR_API int linr_children_segments(const int32_t* coords, const float* occ, const int64_t* seg_off_h, int32_t n_seg, int32_t* child_xyz,
+                           int64_t child_cap, int64_t* child_off_h, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- the executor's fused layers as stand-alone ops ------------------------------------------------------------
  * What linr_net_forward / _backward launch for one layer, callable (and testable) on its own.  All of them work on the

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('LINR_HIP_LIB') or os.path.join(_HERE, 'liblinr_hip.so
 LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 16
 LINR_FRAME_OCC_PADDED = 1
 LINR_PLY_TOKEN, LINR_PLY_COLUMNS, LINR_PLY_SHORT, LINR_PLY_RANGE = 1, 2, 4, 8
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -51,6 +51,11 @@ class LinrRcDecEntry(ctypes.Structure):
 class LinrRcStream(ctypes.Structure):
     """struct linr_rc_stream (include/linr_hip.h): one stream of linr_rc_encode_codes; five int64, so an int64 [n, 5] array is a table."""
     _fields_ = [(n, c_i64) for n in ('c1_off', 'sym_off', 'n', 'out_off', 'cap')]
+
+
+class LinrDecodeOpts(ctypes.Structure):
+    """struct linr_decode_opts (include/linr_hip.h): the options of a decoder scale; NULL in its place means (0, 1, 0)."""
+    _fields_ = [('chunk_symbols', c_i64), ('n_threads', c_i32), ('device', c_i32)]
 
 
 _PROTOS = {
@@ -171,27 +176,15 @@ _PROTOS = {
     'linr_ac_decode_binary': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     'linr_net_decode_stages': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_size, c_ptr, c_ptr, c_ptr,
                                               c_ptr, c_ptr, c_ptr, c_ptr]),
-    'linr_decode_scale_ws_bytes': (c_size, [c_i64, c_i32, c_i32]),
+    'linr_decode_scale_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i64, c_i64]),
     'linr_decode_scale': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_size,
-                                         c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+                                         c_ptr, c_ptr, c_ptr, c_i64, c_ptr, ctypes.POINTER(LinrDecodeOpts), c_ptr]),
     'linr_kmap_build_segments': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_size, c_ptr]),
     'linr_children_segments_ws_bytes': (c_size, [c_i64]),
     'linr_children_segments': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    'linr_net_decode_stages_segments': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_size, c_ptr, c_i32,
-                                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr]),
-    'linr_decode_scale_batch_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    'linr_decode_scale_batch_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32, c_i64, c_i64]),
     'linr_decode_scale_batch': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
-                                               c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_ptr]),
-    'linr_decode_scale_chunked': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
-                                                 c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr]),
-    'linr_decode_scale_batch_chunked': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr,
-                                                       c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr]),
-    'linr_decode_scale_device_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i64, c_i64]),
-    'linr_decode_scale_device': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
-                                                c_size, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    'linr_decode_scale_batch_device_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32, c_i64, c_i64]),
-    'linr_decode_scale_batch_device': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr,
-                                                      c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+                                               c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, ctypes.POINTER(LinrDecodeOpts), c_ptr]),
     'linr_ac_decode_binary_twin': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     'linr_rc_decode_ws_bytes': (c_size, [c_i32]),
     'linr_rc_decode_probs': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i32, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),

@@ -323,7 +323,7 @@ def decode_one_frame(model, frame_enc_bytes, xyz_low, chunk=0, n_threads=1, devi
     qscTensor.set_offset_tensor's searches, the 8 stage forwards with their host round trips, upper_layer), so the Python side of a
     frame is seven buffer allocations.  chunk = S > 0: the stage streams are chunked (side_info's stream_chunk) and a stage's chunks are
     decoded on n_threads host threads.  device_decoder=True: the range decoders run on the GPU (model.decode_scale(device_decoder=True)
-    -> linr_decode_scale_device), no host round trip per stage; n_threads is ignored."""
+    -> linr_decode_opts.device), no host round trip per stage; n_threads is ignored."""
     if getattr(model, '_wide', None) is not None:          # hidden_channel_conv 16 / 32: no single-call decoder scale
         if chunk:
             raise ValueError('chunked stage streams decode with hidden_channel_conv 8 only')
@@ -365,7 +365,7 @@ def _lockstep_scale(model, lows, s_idx, encs, n_threads, chunk=0, device_decoder
 def decode_frames_lockstep(model, frames_enc_bytes, xyz_lows, n_threads=8, chunk=0, device_decoder=False):
     """decode_one_frame for a group of frames with the same number of scales, in lock step: coarse to fine, every scale of the whole
     group is ONE call into the library (model.decode_scale_batch -> linr_decode_scale_batch; with device_decoder
-    linr_decode_scale_batch_device, the group's range decoders on the GPU).  Returns the frames' coordinates."""
+    linr_decode_opts.device, the group's range decoders on the GPU).  Returns the frames' coordinates."""
     if device_decoder and getattr(model, '_wide', None) is not None:
         raise ValueError('the device decoder needs hidden_channel_conv 8')
     lows = [unique_sorted(x) for x in xyz_lows]
@@ -398,8 +398,8 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
     (default: the cores this process may use, at most 16, divided by `workers`).  A stream whose chunk header does not hold raises
     LinrError.
     device_decoder=True (opt-in; hidden_channel_conv 8 only, ValueError otherwise): the range decoders of every scale run on the GPU,
-    a wave per stream or chunk, from the probabilities where the stage forward left them (linr_decode_scale_device /
-    linr_decode_scale_batch_device): no host coder threads (n_threads is ignored) and one synchronisation per scale instead of one
+    a wave per stream or chunk, from the probabilities where the stage forward left them (linr_decode_opts.device of
+    linr_decode_scale / linr_decode_scale_batch): no host coder threads (n_threads is ignored) and one synchronisation per scale instead of one
     per stage.  It reads the same streams and side_info.json and decodes the same geometry; it composes with workers, lockstep and
     stream_chunk.
     Frames are independent once the model is known; with workers > 1 they are decoded by a host thread pool, each

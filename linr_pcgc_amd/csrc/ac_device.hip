@@ -115,6 +115,37 @@ RcWs rc_ws(int32_t n_streams) {
     return w;
 }
 
+// What both entries ask of the host's table: every stream's descriptor within its bounds and its region inside out_dev, and no two
+// regions overlapping.
+int rc_check_streams(const linr_rc_stream* streams_host, int32_t n_streams, int64_t out_bytes) {
+    std::vector<std::pair<int64_t, int64_t>> regions;
+    regions.reserve((size_t)n_streams);
+    for (int32_t i = 0; i < n_streams; ++i) {
+        const linr_rc_stream& d = streams_host[i];
+        if (d.n < 0 || d.cap < 0 || d.c1_off < 0 || d.sym_off < 0 || d.out_off < 0 || !linr_rows_fit32(d.n)) return LINR_EINVAL;
+        if ((d.out_off & 3) || d.out_off > out_bytes || d.cap > out_bytes - d.out_off) return LINR_EINVAL;
+        if (d.cap > 0) regions.emplace_back(d.out_off, d.out_off + d.cap);
+    }
+    std::sort(regions.begin(), regions.end());
+    for (size_t i = 1; i < regions.size(); ++i)
+        if (regions[i].first < regions[i - 1].second) return LINR_EINVAL;
+    return 0;
+}
+
+// the host's table to `tab` on the device (rc_table_k)
+int rc_upload_table(const linr_rc_stream* streams_host, int32_t n_streams, linr_rc_stream* tab, hipStream_t s) {
+    for (int32_t i = 0; i < n_streams; i += RC_TAB_BATCH) {
+        RcTabBatch b;
+        const int32_t m = std::min<int32_t>(RC_TAB_BATCH, n_streams - i);
+        std::copy(streams_host + i, streams_host + i + m, b.d);
+        std::fill(b.d + m, b.d + RC_TAB_BATCH, linr_rc_stream{0, 0, 0, 0, 0});
+        rc_table_k<<<dim3(linr_grid(5 * RC_TAB_BATCH, LINR_BLOCK)), dim3(LINR_BLOCK), 0, s>>>(b, m, tab + i);
+        const int rc = linr_launch_rc();
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" size_t linr_rc_encode_ws_bytes(int32_t n_streams, int64_t total_cap) {
@@ -128,20 +159,13 @@ extern "C" int linr_rc_encode_codes(const uint16_t* c1_dev, const uint32_t* sym_
     if (n_streams < 0 || out_bytes < 0 || payload_bytes < 0) return LINR_EINVAL;
     if (n_streams == 0) return 0;
     if (!c1_dev || !sym_dev || !streams_host || !out_dev || !len_dev || !payload_dev || !offsets_dev || !ws) return LINR_EINVAL;
+    int rc = rc_check_streams(streams_host, n_streams, out_bytes);
+    if (rc) return rc;
     int64_t total_cap = 0;
-    std::vector<std::pair<int64_t, int64_t>> regions;
-    regions.reserve((size_t)n_streams);
     for (int32_t i = 0; i < n_streams; ++i) {
-        const linr_rc_stream& d = streams_host[i];
-        if (d.n < 0 || d.cap < 0 || d.c1_off < 0 || d.sym_off < 0 || d.out_off < 0 || !linr_rows_fit32(d.n)) return LINR_EINVAL;
-        if ((d.out_off & 3) || d.out_off > out_bytes || d.cap > out_bytes - d.out_off) return LINR_EINVAL;
-        total_cap += d.cap;
+        total_cap += streams_host[i].cap;
         if (total_cap > payload_bytes) return LINR_EINVAL;
-        if (d.cap > 0) regions.emplace_back(d.out_off, d.out_off + d.cap);
     }
-    std::sort(regions.begin(), regions.end());
-    for (size_t i = 1; i < regions.size(); ++i)
-        if (regions[i].first < regions[i - 1].second) return LINR_EINVAL;
     const RcWs w = rc_ws(n_streams);
     if (ws_bytes < w.total) return LINR_EINVAL;
     if (((uintptr_t)out_dev & 7) || ((uintptr_t)ws & 7)) return LINR_EALIGN;
@@ -149,15 +173,7 @@ extern "C" int linr_rc_encode_codes(const uint16_t* c1_dev, const uint32_t* sym_
     char* base = (char*)ws;
     linr_rc_stream* tab = (linr_rc_stream*)(base + w.tab);
     int64_t* cnt = (int64_t*)(base + w.cnt);
-    int rc;
-    for (int32_t i = 0; i < n_streams; i += RC_TAB_BATCH) {
-        RcTabBatch b;
-        const int32_t m = std::min<int32_t>(RC_TAB_BATCH, n_streams - i);
-        std::copy(streams_host + i, streams_host + i + m, b.d);
-        std::fill(b.d + m, b.d + RC_TAB_BATCH, linr_rc_stream{0, 0, 0, 0, 0});
-        rc_table_k<<<dim3(linr_grid(5 * RC_TAB_BATCH, LINR_BLOCK)), dim3(LINR_BLOCK), 0, s>>>(b, m, tab + i);
-        if ((rc = linr_launch_rc())) return rc;
-    }
+    if ((rc = rc_upload_table(streams_host, n_streams, tab, s))) return rc;
     rc_encode_k<<<dim3((unsigned)n_streams), dim3(LINR_WAVE), 0, s>>>(c1_dev, sym_dev, tab, out_dev, len_dev);
     if ((rc = linr_launch_rc())) return rc;
     rc_count_k<<<dim3(linr_grid((int64_t)n_streams + 1, LINR_BLOCK)), dim3(LINR_BLOCK), 0, s>>>(len_dev, n_streams, cnt);
@@ -314,26 +330,20 @@ extern "C" int linr_rc_encode_codes_chunked(const uint16_t* c1_dev, const uint32
     if (n_streams == 0) return 0;
     if (!c1_dev || !sym_dev || !streams_host || !out_dev || !len_dev || !payload_dev || !offsets_dev || !ws) return LINR_EINVAL;
     const int64_t S = chunk_symbols;
+    int rc = rc_check_streams(streams_host, n_streams, out_bytes);
+    if (rc) return rc;
     int64_t total_cap = 0, n_chunks = 0;
-    std::vector<std::pair<int64_t, int64_t>> regions;
     std::vector<int32_t> first((size_t)n_streams + 1);
-    regions.reserve((size_t)n_streams);
     for (int32_t i = 0; i < n_streams; ++i) {
         const linr_rc_stream& d = streams_host[i];
-        if (d.n < 0 || d.cap < 0 || d.c1_off < 0 || d.sym_off < 0 || d.out_off < 0 || !linr_rows_fit32(d.n)) return LINR_EINVAL;
-        if ((d.out_off & 3) || d.out_off > out_bytes || d.cap > out_bytes - d.out_off) return LINR_EINVAL;
         const int64_t k = linr_stream_chunk_count(d.n, S);
         if (k > 1 && d.cap < 2 * d.n + 64 * k) return LINR_EINVAL;          // the chunks' regions, 2 n_c + 64 each, lie inside the stream's
         first[(size_t)i] = (int32_t)n_chunks;
         n_chunks += k;
         total_cap += d.cap + 5 * (k - 1);                                    // the final bytes: at most the regions and a full header
         if (total_cap > payload_bytes || n_chunks >= INT32_MAX) return LINR_EINVAL;
-        if (d.cap > 0) regions.emplace_back(d.out_off, d.out_off + d.cap);
     }
     first[(size_t)n_streams] = (int32_t)n_chunks;
-    std::sort(regions.begin(), regions.end());
-    for (size_t i = 1; i < regions.size(); ++i)
-        if (regions[i].first < regions[i - 1].second) return LINR_EINVAL;
     const RcChunkWs w = rc_chunk_ws(n_streams, n_chunks);
     if (ws_bytes < w.total) return LINR_EINVAL;
     if (((uintptr_t)out_dev & 7) || ((uintptr_t)ws & 15)) return LINR_EALIGN;
@@ -347,15 +357,7 @@ extern "C" int linr_rc_encode_codes_chunked(const uint16_t* c1_dev, const uint32
     int64_t* cnt = (int64_t*)(base + w.cnt);
     RcSum* val = (RcSum*)(base + w.val);
     RcSum* pre = (RcSum*)(base + w.pre);
-    int rc;
-    for (int32_t i = 0; i < n_streams; i += RC_TAB_BATCH) {
-        RcTabBatch b;
-        const int32_t m = std::min<int32_t>(RC_TAB_BATCH, n_streams - i);
-        std::copy(streams_host + i, streams_host + i + m, b.d);
-        std::fill(b.d + m, b.d + RC_TAB_BATCH, linr_rc_stream{0, 0, 0, 0, 0});
-        rc_table_k<<<dim3(linr_grid(5 * RC_TAB_BATCH, LINR_BLOCK)), dim3(LINR_BLOCK), 0, s>>>(b, m, tab + i);
-        if ((rc = linr_launch_rc())) return rc;
-    }
+    if ((rc = rc_upload_table(streams_host, n_streams, tab, s))) return rc;
     for (int32_t i = 0; i <= n_streams; i += RC_FIRST_BATCH) {
         RcFirstBatch b;
         const int32_t m = std::min<int32_t>(RC_FIRST_BATCH, n_streams + 1 - i);

@@ -1,13 +1,13 @@
 // The staged decoder.  The 8 decode stages of a frame object (decode_stages: stage forward, D2H, range decoders, H2D, occupancy
 // column - or, in its device mode, stage forward and rc_decode_k of csrc/ac_device_dec.hip, with no host round trip; exported as
-// linr_net_decode_stages for a frame's scales and as linr_net_decode_stages_segments for one scale of several
-// frames), and one scale of the decoder as ONE call (decoder.decode_one_frame's loop body, decoder.py:153-176): the kernel map of
+// linr_net_decode_stages for a frame's scales), and one scale of the decoder as ONE call (decoder.decode_one_frame's loop body, decoder.py:153-176): the kernel map of
 // the coarser level's coordinates, the 7-neighbour features read off it, the 8 stages and the next level's coordinates
 // (octree_level.upper_layer, models/module_utils.py:117-127: the children 2 p + (dx, dy, dz) of every occupied octant, sorted
 // x-major).  Between two scales the caller only allocates the next workspace, so a frame's decode holds the Python GIL for a few
 // hundred microseconds instead of ~7 ms.  linr_decode_scale does it for one frame and linr_decode_scale_batch for the frames of a GOP
-// in lock step; they share the workspace layout (layout), everything in front of the stages (scale_prologue) and the stage loop, and
-// differ in the kernel map (one list / segments) and in the child expansion (radix sort / prefix sums).
+// in lock step; they share everything between their argument checks and the child expansion (scale_middle: the workspace layout, the
+// stage plan, the device decoders' upload, scale_prologue, decode_stages) and differ in the kernel map (one list / segments) and in the
+// child expansion (radix sort / prefix sums).  linr_decode_opts picks chunked streams, the host threads and the device decoders.
 #include "common.h"
 #include "layout.h"
 #include "prof.h"
@@ -66,8 +66,9 @@ struct ScaleWs {
     union { SortWs sort; ChildWs scan; };
 };
 
-// stream_bytes >= 0: with the device decoders' two regions - the stream bytes padded to 256 bytes plus one 256-byte window, so that
-// every aligned window a wave could ask for lies inside, and n_entries table entries
+// stream_bytes >= 0: with the device decoders' two regions - the stream bytes padded to 256 bytes (at least one such block, so this
+// layout is the host decoders' plus 512 bytes or more) plus one 256-byte window, so that every aligned window a wave could ask for
+// lies inside, and n_entries table entries
 ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan, int64_t stream_bytes = -1, int64_t n_entries = 0) {
     ScaleWs w;
     w.ld = (n + 63) / 64 * 64;
@@ -88,7 +89,7 @@ ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan, int64_t stream_
     w.arena = take(w.arena_bytes);
     w.sbytes = w.tab = cur;
     if (stream_bytes >= 0) {
-        w.sbytes = take(up256((size_t)stream_bytes) + 256);
+        w.sbytes = take(up256((size_t)(stream_bytes > 0 ? stream_bytes : 1)) + 256);
         w.tab = take(sizeof(linr_rc_dec_entry) * (size_t)n_entries);
     }
     w.total = cur;
@@ -318,42 +319,7 @@ extern "C" int linr_net_decode_stages(const linr_frame* f, const float* params, 
                          probs, p_pinned, s_pinned, s_dev, 1, nullptr, (hipStream_t)stream);
 }
 
-// The same for a frame of ONE scale whose rows are the levels of n_seg frames back to back (linr_decode_scale_batch): a stage is one
-// forward, one copy each way and n_seg range decoders on host threads.
-extern "C" int linr_net_decode_stages_segments(const linr_frame* f, const float* params, const uint8_t* codes, float min_param,
-                                               float max_param, void* arena, size_t arena_bytes, const int64_t* seg_off_h,
-                                               int32_t n_seg, const uint8_t* const* streams_h, const int64_t* stream_len_h,
-                                               float* probs, float* p_pinned, uint8_t* s_pinned, uint8_t* s_dev, int32_t n_threads,
-                                               void* stream) {
-    if (!f || !arena || !seg_off_h || !streams_h || !stream_len_h || !probs || !p_pinned || !s_pinned || !s_dev || !f->occ) return LINR_EINVAL;
-    if (!codes && !params) return LINR_EINVAL;
-    if (n_seg < 1 || n_seg > LINR_DECODE_MAX_FRAMES || f->n_scales != 1) return LINR_EINVAL;
-    if (seg_off_h[0] != 0 || seg_off_h[n_seg] != f->rows) return LINR_EINVAL;
-    for (int i = 0; i < n_seg; ++i)
-        if (seg_off_h[i + 1] < seg_off_h[i]) return LINR_EINVAL;
-    return decode_stages(f, params, codes, min_param, max_param, arena, arena_bytes, seg_off_h, n_seg, streams_h, stream_len_h, probs,
-                         p_pinned, s_pinned, s_dev, n_threads, nullptr, (hipStream_t)stream);
-}
-
-extern "C" size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16) {
-    if (n < 0 || block_layers < 1) return 0;
-    return layout(n, block_layers, bf16 ? 1 : 0, false).total + 256;
-}
-
 namespace {
-
-// The device decoders of a scale in front of its stages: the plan's bytes and table into the workspace (laid out for exactly them:
-// LINR_ENOSPC when ws_bytes does not reach).  `keep` owns the staging copy; `guard` synchronises if the scale is left early.
-int stage_device(const StagePlan& plan, int n_seg, const int64_t* seg_off_h, const uint8_t* const* streams_h, const int64_t* stream_len_h,
-                 int64_t rows, int block_layers, int bf16, bool scan, size_t ws_bytes, char* base, DevicePlan& keep, ScaleWs& w,
-                 DeviceStages& dev) {
-    TRY(plan_device(plan, n_seg, seg_off_h, streams_h, stream_len_h, rows, keep));
-    w = layout(rows, block_layers, bf16, scan, (int64_t)keep.bytes.size(), (int64_t)keep.ent.size());
-    if (ws_bytes < w.total) return LINR_ENOSPC;
-    dev.bytes = (const uint8_t*)(base + w.sbytes);
-    dev.tab = (const linr_rc_dec_entry*)(base + w.tab);
-    return 0;
-}
 
 int upload_device(const DevicePlan& keep, const DeviceStages& dev, hipStream_t s) {
     linr_poison_hook(s, PK_DECODE);
@@ -362,97 +328,116 @@ int upload_device(const DevicePlan& keep, const DeviceStages& dev, hipStream_t s
     return linr_rc_dec_upload(keep.ent.data(), (int32_t)keep.ent.size(), const_cast<linr_rc_dec_entry*>(dev.tab), s);
 }
 
-// linr_decode_scale_chunked and linr_decode_scale_device: `device` picks the decoders (then p_pinned, s_pinned and n_threads are unused)
-int decode_scale_any(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers, int32_t child_bits,
-                     const float* params, const uint8_t* codes, float min_param, float max_param, const uint8_t* const* streams_h,
-                     const int64_t* stream_len_h, void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
-                     int64_t child_cap, int64_t* child_n_h, int64_t chunk_symbols, int32_t n_threads, bool device, void* stream) {
-    if (n < 0 || !child_n_h || child_bits < 1 || child_bits > 21 || block_layers < 1) return LINR_EINVAL;
-    *child_n_h = 0;
-    if (n == 0) return 0;
-    if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !child_xyz) return LINR_EINVAL;
-    if (!device && (!p_pinned || !s_pinned)) return LINR_EINVAL;
-    // (one row looser than linr_rows_fit32, which the executor's frame check then applies to the frame built below)
-    if (child_cap < 0 || n >= ((int64_t)1 << 27)) return LINR_EINVAL;
-    if (((uintptr_t)ws) & 255u) return LINR_EALIGN;
-    ScaleWs w = layout(n, block_layers, codes ? 1 : 0, false);
-    if (ws_bytes < w.total) return LINR_ENOSPC;
-    hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)ws;
-    ScaleFrame sf;
-    sf.row_off[0] = 0; sf.row_off[1] = n;
-    StagePlan plan;                 // a malformed chunk header is refused here, in front of the first launch
-    TRY(plan_stages(sf.row_off, 1, streams_h, stream_len_h, chunk_symbols, p_pinned, s_pinned, plan));
-    DevicePlan keep;
+// What a scale entry hands the middle that both share: its n rows as n_seg segments (linr_decode_scale: its one, sf.row_off),
+// the model, the streams, the caller's buffers and its options.  `segmented` (linr_decode_scale_batch): the kernel map of segments
+// and the child region laid out for the scan; otherwise the kernel map of one list and the region of the sort.
+struct ScaleArgs {
+    const int32_t* coord; int64_t n; const int64_t* seg_off_h; int32_t n_seg; bool segmented;
+    int32_t scale_idx, model_scale_num, block_layers;
+    const float* params; const uint8_t* codes; float min_param, max_param;
+    const uint8_t* const* streams_h; const int64_t* stream_len_h;
+    void* ws; size_t ws_bytes; float* p_pinned; uint8_t* s_pinned;
+    const linr_decode_opts* opts;
+    hipStream_t s;
+};
+
+// What the middle leaves its entry for the child expansion (w, sf) and what has to live until the entry returns: `keep` owns the
+// staging copy of the device decoders' stream bytes, and `guard` - the last member, so the first to go - synchronises before that
+// copy is freed when the scale is left early.
+struct ScaleRun {
+    ScaleWs w; ScaleFrame sf; StagePlan plan; DevicePlan keep; SyncOnExit guard;
+    explicit ScaleRun(hipStream_t s) : guard{s, false} {}
+};
+
+// A scale between its entry's own argument checks and its child expansion (n > 0): the remaining checks, the workspace layout, the
+// plan of the 8 stages (a malformed chunk header is refused here, in front of the first launch), for the device decoders the plan's
+// bytes and table into the workspace (laid out for exactly them: LINR_ENOSPC when ws_bytes does not reach) under the guard, the
+// prologue and the stages.
+int scale_middle(const ScaleArgs& a, ScaleRun& r) {
+    static const linr_decode_opts plain = {0, 1, 0};
+    const linr_decode_opts& o = a.opts ? *a.opts : plain;
+    const bool device = o.device != 0;           // (then p_pinned, s_pinned and n_threads are unused)
+    if (!a.coord || (!a.params && !a.codes) || !a.streams_h || !a.stream_len_h || !a.ws) return LINR_EINVAL;
+    if (!device && (!a.p_pinned || !a.s_pinned)) return LINR_EINVAL;
+    if (((uintptr_t)a.ws) & 255u) return LINR_EALIGN;
+    const int bf16 = a.codes ? 1 : 0;
+    r.w = layout(a.n, a.block_layers, bf16, a.segmented);
+    if (a.ws_bytes < r.w.total) return LINR_ENOSPC;
+    char* base = (char*)a.ws;
+    float* p_pinned = device ? nullptr : a.p_pinned;
+    uint8_t* s_pinned = device ? nullptr : a.s_pinned;
+    TRY(plan_stages(a.seg_off_h, a.n_seg, a.streams_h, a.stream_len_h, o.chunk_symbols, p_pinned, s_pinned, r.plan));
     DeviceStages dev{nullptr, nullptr};
-    SyncOnExit guard{s, false};
     if (device) {
-        TRY(stage_device(plan, 1, sf.row_off, streams_h, stream_len_h, n, block_layers, codes ? 1 : 0, false, ws_bytes, base, keep, w, dev));
-        guard.armed = true;
-        TRY(upload_device(keep, dev, s));
+        TRY(plan_device(r.plan, a.n_seg, a.seg_off_h, a.streams_h, a.stream_len_h, a.n, r.keep));
+        r.w = layout(a.n, a.block_layers, bf16, a.segmented, (int64_t)r.keep.bytes.size(), (int64_t)r.keep.ent.size());
+        if (a.ws_bytes < r.w.total) return LINR_ENOSPC;
+        dev.bytes = (const uint8_t*)(base + r.w.sbytes);
+        dev.tab = (const linr_rc_dec_entry*)(base + r.w.tab);
+        r.guard.armed = true;
+        TRY(upload_device(r.keep, dev, a.s));
     }
-    TRY(scale_prologue(coord, n, nullptr, 0, scale_idx, model_scale_num, block_layers, base, w, sf, s));
-    TRY(decode_stages(&sf.f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, sf.row_off, 1, streams_h, stream_len_h,
-                      (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, &plan, s, device ? &dev : nullptr));
-    // upper_layer: children of the occupied octants, sorted x-major
-    const float* occ = sf.f.occ;
-    char* cbase = base + w.child;
-    int32_t* cnt = (int32_t*)(cbase + w.sort.cnt);
-    int32_t* pos = (int32_t*)(cbase + w.sort.pos);
-    uint64_t* keys0 = (uint64_t*)(cbase + w.sort.keys0);
-    uint64_t* keys1 = (uint64_t*)(cbase + w.sort.keys1);
-    linr_poison_hook(s, PK_DECODE);
-    child_count_k<<<linr_grid(n + 1, LINR_BLOCK), LINR_BLOCK, 0, s>>>(occ, n, cnt);
-    size_t cb = w.sort.cub_bytes;
-    TRY(linr_hip_rc(hipcub::DeviceScan::ExclusiveSum(cbase + w.sort.cub, cb, cnt, pos, (int)(n + 1), s)));
-    int32_t total = 0;
-    TRY(linr_hip_rc(hipMemcpyAsync(&total, pos + n, sizeof(int32_t), hipMemcpyDeviceToHost, s)));
-    child_keys_k<<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(coord, occ, pos, n, child_bits, keys0);
-    TRY(linr_hip_rc(hipStreamSynchronize(s)));                  // `total` is on the host now
-    guard.armed = false;
-    if (total > child_cap) return LINR_ENOSPC;
-    if (total > 0) {
-        cb = w.sort.cub_bytes;
-        TRY(linr_hip_rc(hipcub::DeviceRadixSort::SortKeys(cbase + w.sort.cub, cb, keys0, keys1, (int)total, 0, 3 * child_bits, s)));
-        keys_to_coord_k<<<linr_grid(total, LINR_BLOCK), LINR_BLOCK, 0, s>>>(keys1, pos + n, child_bits, child_xyz, child_cap);
-    }
-    *child_n_h = total;
-    return linr_launch_rc();
+    TRY(scale_prologue(a.coord, a.n, a.segmented ? a.seg_off_h : nullptr, a.segmented ? a.n_seg : 0, a.scale_idx, a.model_scale_num,
+                       a.block_layers, base, r.w, r.sf, a.s));
+    return decode_stages(&r.sf.f, a.params, a.codes, a.min_param, a.max_param, base + r.w.arena, r.w.arena_bytes, a.seg_off_h, a.n_seg,
+                         a.streams_h, a.stream_len_h, (float*)(base + r.w.probs), p_pinned, s_pinned, (uint8_t*)(base + r.w.sdev),
+                         device ? 1 : o.n_threads, &r.plan, a.s, device ? &dev : nullptr);
+}
+
+// stream_bytes_total -1: the host decoders' layout; >= 0: the device decoders' (0 for anything else)
+size_t scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, bool scan, int64_t stream_bytes_total, int64_t n_entries) {
+    if (stream_bytes_total < -1 || (stream_bytes_total >= 0 && n_entries < 0)) return 0;
+    return layout(n, block_layers, bf16 ? 1 : 0, scan, stream_bytes_total, n_entries).total + 256;
 }
 
 }  // namespace
 
-extern "C" int linr_decode_scale_chunked(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
-                                         int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
-                                         const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
-                                         float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
-                                         int64_t chunk_symbols, int32_t n_threads, void* stream) {
-    return decode_scale_any(coord, n, scale_idx, model_scale_num, block_layers, child_bits, params, codes, min_param, max_param, streams_h,
-                            stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap, child_n_h, chunk_symbols, n_threads, false,
-                            stream);
-}
-
-extern "C" size_t linr_decode_scale_device_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total,
-                                                    int64_t n_entries) {
-    if (n < 0 || block_layers < 1 || stream_bytes_total < 0 || n_entries < 0) return 0;
-    return layout(n, block_layers, bf16 ? 1 : 0, false, stream_bytes_total, n_entries).total + 256;
-}
-
-extern "C" int linr_decode_scale_device(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
-                                        int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
-                                        const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
-                                        int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h, int64_t chunk_symbols, void* stream) {
-    return decode_scale_any(coord, n, scale_idx, model_scale_num, block_layers, child_bits, params, codes, min_param, max_param, streams_h,
-                            stream_len_h, ws, ws_bytes, nullptr, nullptr, child_xyz, child_cap, child_n_h, chunk_symbols, 1, true, stream);
+extern "C" size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total, int64_t n_entries) {
+    if (n < 0 || block_layers < 1) return 0;
+    return scale_ws_bytes(n, block_layers, bf16, false, stream_bytes_total, n_entries);
 }
 
 extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
                                  int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
                                  const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
                                  float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
-                                 void* stream) {
-    return linr_decode_scale_chunked(coord, n, scale_idx, model_scale_num, block_layers, child_bits, params, codes, min_param, max_param,
-                                     streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap, child_n_h, 0, 1, stream);
+                                 const linr_decode_opts* opts, void* stream) {
+    if (n < 0 || !child_n_h || child_bits < 1 || child_bits > 21 || block_layers < 1) return LINR_EINVAL;
+    *child_n_h = 0;
+    if (n == 0) return 0;
+    // (one row looser than linr_rows_fit32, which the executor's frame check then applies to the frame built in the prologue)
+    if (!child_xyz || child_cap < 0 || n >= ((int64_t)1 << 27)) return LINR_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    ScaleRun r(s);
+    r.sf.row_off[0] = 0; r.sf.row_off[1] = n;          // the one segment
+    const ScaleArgs a{coord, n, r.sf.row_off, 1, false, scale_idx, model_scale_num, block_layers, params, codes, min_param, max_param,
+                      streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, opts, s};
+    TRY(scale_middle(a, r));
+    // upper_layer: children of the occupied octants, sorted x-major
+    const SortWs& w = r.w.sort;
+    const float* occ = r.sf.f.occ;
+    char* cbase = (char*)ws + r.w.child;
+    int32_t* cnt = (int32_t*)(cbase + w.cnt);
+    int32_t* pos = (int32_t*)(cbase + w.pos);
+    uint64_t* keys0 = (uint64_t*)(cbase + w.keys0);
+    uint64_t* keys1 = (uint64_t*)(cbase + w.keys1);
+    linr_poison_hook(s, PK_DECODE);
+    child_count_k<<<linr_grid(n + 1, LINR_BLOCK), LINR_BLOCK, 0, s>>>(occ, n, cnt);
+    size_t cb = w.cub_bytes;
+    TRY(linr_hip_rc(hipcub::DeviceScan::ExclusiveSum(cbase + w.cub, cb, cnt, pos, (int)(n + 1), s)));
+    int32_t total = 0;
+    TRY(linr_hip_rc(hipMemcpyAsync(&total, pos + n, sizeof(int32_t), hipMemcpyDeviceToHost, s)));
+    child_keys_k<<<linr_grid(n, LINR_BLOCK), LINR_BLOCK, 0, s>>>(coord, occ, pos, n, child_bits, keys0);
+    TRY(linr_hip_rc(hipStreamSynchronize(s)));                  // `total` is on the host now
+    r.guard.armed = false;
+    if (total > child_cap) return LINR_ENOSPC;
+    if (total > 0) {
+        cb = w.cub_bytes;
+        TRY(linr_hip_rc(hipcub::DeviceRadixSort::SortKeys(cbase + w.cub, cb, keys0, keys1, (int)total, 0, 3 * child_bits, s)));
+        keys_to_coord_k<<<linr_grid(total, LINR_BLOCK), LINR_BLOCK, 0, s>>>(keys1, pos + n, child_bits, child_xyz, child_cap);
+    }
+    *child_n_h = total;
+    return linr_launch_rc();
 }
 
 // ---- the same for the frames of a GOP in lock step: one scale of n_frames frames per call, children without a sort ------------------
@@ -608,92 +593,34 @@ extern "C" int linr_children_segments(const int32_t* coords, const float* occ, c
     return children_segments(coords, occ, tab, n, n_seg, child_xyz, child_cap, child_off_h, (char*)ws, w, (hipStream_t)stream);
 }
 
-extern "C" size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16) {
+extern "C" size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
+                                                   int64_t stream_bytes_total, int64_t n_entries) {
     if (n_total < 0 || n_total >= ((int64_t)1 << 26) || n_frames < 1 || n_frames > LINR_DECODE_MAX_FRAMES || block_layers < 1) return 0;
-    return layout(n_total, block_layers, bf16 ? 1 : 0, true).total + 256;
-}
-
-namespace {
-
-// linr_decode_scale_batch_chunked and linr_decode_scale_batch_device, as decode_scale_any
-int decode_scale_batch_any(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx, int32_t model_scale_num,
-                           int32_t block_layers, const float* params, const uint8_t* codes, float min_param, float max_param,
-                           const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes, float* p_pinned,
-                           uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h, int32_t n_threads,
-                           int64_t chunk_symbols, bool device, void* stream) {
-    LinrSegTab tab;
-    int64_t n = 0;
-    int rc = linr_seg_tab(seg_off_h, n_frames, &tab, &n);
-    if (rc) return rc;
-    if (!child_off_h || block_layers < 1 || child_cap < 0) return LINR_EINVAL;
-    const int64_t ld = (n + 63) / 64 * 64;
-    if (!linr_cmap_fits32(ld) || !linr_rows_fit32(n)) return LINR_EINVAL;
-    for (int i = 0; i <= n_frames; ++i) child_off_h[i] = 0;
-    if (n == 0) return 0;
-    if (!coord || (!params && !codes) || !streams_h || !stream_len_h || !ws || !child_xyz) return LINR_EINVAL;
-    if (!device && (!p_pinned || !s_pinned)) return LINR_EINVAL;
-    if (((uintptr_t)ws) & 255u) return LINR_EALIGN;
-    ScaleWs w = layout(n, block_layers, codes ? 1 : 0, true);
-    if (ws_bytes < w.total) return LINR_ENOSPC;
-    hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)ws;
-    ScaleFrame sf;
-    StagePlan plan;                 // a malformed chunk header is refused here, in front of the first launch
-    TRY(plan_stages(seg_off_h, n_frames, streams_h, stream_len_h, chunk_symbols, p_pinned, s_pinned, plan));
-    DevicePlan keep;
-    DeviceStages dev{nullptr, nullptr};
-    SyncOnExit guard{s, false};
-    if (device) {
-        TRY(stage_device(plan, n_frames, seg_off_h, streams_h, stream_len_h, n, block_layers, codes ? 1 : 0, true, ws_bytes, base, keep, w, dev));
-        guard.armed = true;
-        TRY(upload_device(keep, dev, s));
-    }
-    TRY(scale_prologue(coord, n, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, base, w, sf, s));
-    TRY(decode_stages(&sf.f, params, codes, min_param, max_param, base + w.arena, w.arena_bytes, seg_off_h, n_frames, streams_h,
-                      stream_len_h, (float*)(base + w.probs), p_pinned, s_pinned, (uint8_t*)(base + w.sdev), n_threads, &plan, s,
-                      device ? &dev : nullptr));
-    // (children_segments synchronises when it succeeds; the guard covers the ways out in front of that)
-    return children_segments(coord, sf.f.occ, tab, n, n_frames, child_xyz, child_cap, child_off_h, base + w.child, w.scan, s);
-}
-
-}  // namespace
-
-extern "C" int linr_decode_scale_batch_chunked(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
-                                               int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
-                                               float min_param, float max_param, const uint8_t* const* streams_h,
-                                               const int64_t* stream_len_h, void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned,
-                                               int32_t* child_xyz, int64_t child_cap, int64_t* child_off_h, int32_t n_threads,
-                                               int64_t chunk_symbols, void* stream) {
-    return decode_scale_batch_any(coord, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, params, codes, min_param, max_param,
-                                  streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap, child_off_h, n_threads,
-                                  chunk_symbols, false, stream);
-}
-
-extern "C" size_t linr_decode_scale_batch_device_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
-                                                          int64_t stream_bytes_total, int64_t n_entries) {
-    if (n_total < 0 || n_total >= ((int64_t)1 << 26) || n_frames < 1 || n_frames > LINR_DECODE_MAX_FRAMES || block_layers < 1) return 0;
-    if (stream_bytes_total < 0 || n_entries < 0) return 0;
-    return layout(n_total, block_layers, bf16 ? 1 : 0, true, stream_bytes_total, n_entries).total + 256;
-}
-
-extern "C" int linr_decode_scale_batch_device(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
-                                              int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
-                                              float min_param, float max_param, const uint8_t* const* streams_h,
-                                              const int64_t* stream_len_h, void* ws, size_t ws_bytes, int32_t* child_xyz, int64_t child_cap,
-                                              int64_t* child_off_h, int64_t chunk_symbols, void* stream) {
-    return decode_scale_batch_any(coord, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, params, codes, min_param, max_param,
-                                  streams_h, stream_len_h, ws, ws_bytes, nullptr, nullptr, child_xyz, child_cap, child_off_h, 1, chunk_symbols,
-                                  true, stream);
+    return scale_ws_bytes(n_total, block_layers, bf16, true, stream_bytes_total, n_entries);
 }
 
 extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
                                        int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
                                        float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
                                        void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
-                                       int64_t child_cap, int64_t* child_off_h, int32_t n_threads, void* stream) {
-    return linr_decode_scale_batch_chunked(coord, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, params, codes, min_param,
-                                           max_param, streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap,
-                                           child_off_h, n_threads, 0, stream);
+                                       int64_t child_cap, int64_t* child_off_h, const linr_decode_opts* opts, void* stream) {
+    LinrSegTab tab;
+    int64_t n = 0;
+    const int rc = linr_seg_tab(seg_off_h, n_frames, &tab, &n);
+    if (rc) return rc;
+    if (!child_off_h || block_layers < 1 || child_cap < 0) return LINR_EINVAL;
+    const int64_t ld = (n + 63) / 64 * 64;
+    if (!linr_cmap_fits32(ld) || !linr_rows_fit32(n)) return LINR_EINVAL;
+    for (int i = 0; i <= n_frames; ++i) child_off_h[i] = 0;
+    if (n == 0) return 0;
+    if (!child_xyz) return LINR_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    ScaleRun r(s);
+    const ScaleArgs a{coord, n, seg_off_h, n_frames, true, scale_idx, model_scale_num, block_layers, params, codes, min_param, max_param,
+                      streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, opts, s};
+    TRY(scale_middle(a, r));
+    // (children_segments synchronises when it succeeds; the guard covers the ways out in front of that)
+    return children_segments(coord, r.sf.f.occ, tab, n, n_frames, child_xyz, child_cap, child_off_h, (char*)ws + r.w.child, r.w.scan, s);
 }
 
 // ---- sorted unique coordinate list, optionally of the parents (coords >> shift); one octree level as one call ------------------------

@@ -346,27 +346,30 @@ class LINR_PCGC_Model(nn.Module):
         frame = self.make_frame([s], with_arena=self._precision(None) == 'f32')
         return self.decode_frame(frame, [streams])
 
-    def _decode_scale_args(self, size_fn, size_args, coord, streams, device_entries=None):
+    def _decode_scale_args(self, size_fn, size_args, coord, streams, chunk, n_threads, device_entries=None):
         """What decode_scale and decode_scale_batch hand their C entry alike, in the entries' order: (params, codes, lo, hi, stream
         pointers, stream lengths, aligned workspace, its bytes, pinned probabilities, pinned symbols, child buffer, its rows), the
-        workspace bytes (size_fn(*size_args, block_layers, bf16); 0: the entry refuses the size, nothing else is returned) and the
-        objects that own that memory, child buffer first: keep them until the call has returned.
-        device_entries = the table entries of the scale: the device decoders' entries, whose size_fn also takes the streams' bytes
-        together and that count, and which take no pinned buffers."""
+        options (LinrDecodeOpts), the workspace bytes (size_fn(*size_args, block_layers, bf16, stream bytes, entries); 0: the entry
+        refuses the size, nothing else is returned) and the objects that own that memory, child buffer first: keep them until the
+        call has returned.
+        device_entries = the table entries of the scale: the device decoders, whose workspace also holds the streams' bytes and that
+        many entries, and which take no pinned buffers (None in their place); None: the host decoders."""
         n = int(coord.shape[0])
         ptrs, lens, bufs = engine.stream_arrays(streams)
         bf16 = self._precision(None) == 'bf16'
-        extra = () if device_entries is None else (sum(len(b) for b in streams), int(device_entries))
+        device = device_entries is not None
+        extra = (sum(len(b) for b in streams), int(device_entries)) if device else (-1, 0)
         need = size_fn(*size_args, self.block_layers, 1 if bf16 else 0, *extra)
         if need == 0:
-            return None, 0, None
+            return None, None, 0, None
         ws = _lib.scratch(need + 256, coord.device)
         child = torch.empty((8 * n, 3), dtype=torch.int32, device=coord.device)
-        pinned = tuple(b.data_ptr() for b in self._host_buffers(n)) if device_entries is None else ()
+        pinned = (None, None) if device else tuple(b.data_ptr() for b in self._host_buffers(n))
         codes, lo, hi, params = (self._qcodes.data_ptr(), float(self._qrange[0]), float(self._qrange[1]), None) if bf16 else \
             (None, 0.0, 0.0, self._flat.data_ptr())
+        opts = _lib.LinrDecodeOpts(int(chunk), int(n_threads), 1 if device else 0)
         return (params, codes, lo, hi, ptrs, lens, (ws.data_ptr() + 255) & ~255, need, *pinned,
-                child.data_ptr(), 8 * n), need, (child, ws, bufs)
+                child.data_ptr(), 8 * n), opts, need, (child, ws, bufs)
 
     @torch.no_grad()
     def decode_scale(self, coord, scale_idx, enc_bytes, child_bits, chunk=0, n_threads=1, device_decoder=False):
@@ -374,32 +377,21 @@ class LINR_PCGC_Model(nn.Module):
         (linr_decode_scale): kernel map of `coord` (int32 [n,3] on the GPU, sorted x-major), the 8 decode stages against the
         packed stream `enc_bytes`, octree_level.upper_layer.  Returns the next finer level's coordinates (int32 [m,3]).
         chunk = S > 0: the stage streams are chunked (stream_chunks) and a stage's chunks are decoded on `n_threads` host threads
-        (linr_decode_scale_chunked).
+        (linr_decode_opts.chunk_symbols, n_threads).
         device_decoder=True (opt-in): the range decoders run on the GPU, a wave per stream or chunk, from the probabilities where the
-        stage forward left them (linr_decode_scale_device): no host round trip per stage, one synchronisation per scale; n_threads is
+        stage forward left them (linr_decode_opts.device): no host round trip per stage, one synchronisation per scale; n_threads is
         ignored.  The streams and the result are the same."""
         L = _lib.lib()
         n = int(coord.shape[0])
         if n == 0:
             return coord.new_zeros((0, 3))
         coord = coord.contiguous()
-        if device_decoder:
-            shared, _, keep = self._decode_scale_args(L.linr_decode_scale_device_ws_bytes, (n,), coord, unpack_bitstream(enc_bytes),
-                                                      8 * chunk_count(n, int(chunk)))
-            m = ctypes.c_int64(0)
-            _lib.check(L.linr_decode_scale_device(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits),
-                                                  *shared, ctypes.byref(m), int(chunk), torch.cuda.current_stream().cuda_stream),
-                       'linr_decode_scale_device')
-            return keep[0][:m.value]
-        shared, _, keep = self._decode_scale_args(L.linr_decode_scale_ws_bytes, (n,), coord, unpack_bitstream(enc_bytes))
+        entries = 8 * chunk_count(n, int(chunk)) if device_decoder else None
+        shared, opts, _, keep = self._decode_scale_args(L.linr_decode_scale_ws_bytes, (n,), coord, unpack_bitstream(enc_bytes), chunk,
+                                                        n_threads, entries)
         m = ctypes.c_int64(0)
-        if chunk:
-            _lib.check(L.linr_decode_scale_chunked(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits),
-                                                   *shared, ctypes.byref(m), int(chunk), int(n_threads),
-                                                   torch.cuda.current_stream().cuda_stream), 'linr_decode_scale_chunked')
-        else:
-            _lib.check(L.linr_decode_scale(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits), *shared,
-                                           ctypes.byref(m), torch.cuda.current_stream().cuda_stream), 'linr_decode_scale')
+        _lib.check(L.linr_decode_scale(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits), *shared,
+                                       ctypes.byref(m), ctypes.byref(opts), torch.cuda.current_stream().cuda_stream), 'linr_decode_scale')
         return keep[0][:m.value]
 
     @torch.no_grad()
@@ -408,9 +400,9 @@ class LINR_PCGC_Model(nn.Module):
         (int32 [n_i,3] on the GPU, each sorted x-major) are one row space whose kernel map never links two frames, every decode stage
         is one launch set and one copy each way for all of them, their range decoders run on `n_threads` host threads, and the
         children come from prefix sums instead of a sort.  Returns the list of the next finer levels' coordinates (int32 [m_i,3]).
-        chunk = S > 0: the stage streams are chunked (stream_chunks; linr_decode_scale_batch_chunked).
+        chunk = S > 0: the stage streams are chunked (stream_chunks; linr_decode_opts.chunk_symbols).
         device_decoder=True (opt-in): as in decode_scale - every stream or chunk of the group's frames a wave of one launch per stage
-        (linr_decode_scale_batch_device); n_threads is ignored."""
+        (linr_decode_opts.device); n_threads is ignored."""
         L = _lib.lib()
         nf = len(coords_list)
         if nf < 1 or nf > 64 or len(enc_bytes_list) != nf:
@@ -425,23 +417,14 @@ class LINR_PCGC_Model(nn.Module):
         if len(streams) != 8 * nf:
             raise ValueError('every frame needs the 8 stage streams of the scale')
         entries = 8 * sum(chunk_count(int(c.shape[0]), int(chunk)) for c in coords_list if c.shape[0]) if device_decoder else None
-        size_fn = L.linr_decode_scale_batch_device_ws_bytes if device_decoder else L.linr_decode_scale_batch_ws_bytes
-        shared, need, keep = self._decode_scale_args(size_fn, (n, nf), coord, streams, entries)
+        shared, opts, need, keep = self._decode_scale_args(L.linr_decode_scale_batch_ws_bytes, (n, nf), coord, streams, chunk, n_threads,
+                                                           entries)
         if need == 0:
             raise ValueError('%d rows in one decode group: the bound is 2^26 - 64' % n)
         off = (ctypes.c_int64 * (nf + 1))()
-        if device_decoder:
-            _lib.check(L.linr_decode_scale_batch_device(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num,
-                                                        self.block_layers, *shared, off, int(chunk),
-                                                        torch.cuda.current_stream().cuda_stream), 'linr_decode_scale_batch_device')
-        elif chunk:
-            _lib.check(L.linr_decode_scale_batch_chunked(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num,
-                                                         self.block_layers, *shared, off, int(n_threads), int(chunk),
-                                                         torch.cuda.current_stream().cuda_stream), 'linr_decode_scale_batch_chunked')
-        else:
-            _lib.check(L.linr_decode_scale_batch(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num, self.block_layers,
-                                                 *shared, off, int(n_threads), torch.cuda.current_stream().cuda_stream),
-                       'linr_decode_scale_batch')
+        _lib.check(L.linr_decode_scale_batch(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num, self.block_layers,
+                                             *shared, off, ctypes.byref(opts), torch.cuda.current_stream().cuda_stream),
+                   'linr_decode_scale_batch')
         self._lockstep_ws_peak = max(getattr(self, '_lockstep_ws_peak', 0), int(need))
         return [keep[0][off[i]:off[i + 1]] for i in range(nf)]
 

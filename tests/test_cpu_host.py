@@ -260,7 +260,7 @@ def test_c_abi_argument_checks(lib):
         assert lib.linr_inception_bwd_fused(p64, p64, p64, p64, p64, p64, ld, n, byref(q), p64, p64, 0, p64, 32, None) == -1
         assert lib.linr_occ_wgrad7(p64, g7a, p64, p64, ld, n, p64, 8, byref(rw), None) == -1
     cn = ctypes.c_int64(5)
-    assert lib.linr_decode_scale(p64, 1 << 27, 0, 7, 1, 10, p64, None, 0.0, 1.0, p64, p64, p64, 0, p64, p64, p64, 0, byref(cn), None) == -1
+    assert lib.linr_decode_scale(p64, 1 << 27, 0, 7, 1, 10, p64, None, 0.0, 1.0, p64, p64, p64, 0, p64, p64, p64, 0, byref(cn), None, None) == -1
 
 def test_param_count_matches_reference_checkpoint(lib, golden_dir):
     g = np.load(os.path.join(golden_dir, 'loot_model_kat.npz'))

@@ -188,19 +188,20 @@ def test_decode_scale_batch_argument_checks(pkg):
     streams = [np.frombuffer(b, dtype=np.uint8) for i in range(2) for b in unpack_bitstream(enc['frames'][i][-1])]
     ptrs = (ctypes.c_void_p * 16)(*[b.ctypes.data if b.size else None for b in streams])
     lens = (ctypes.c_int64 * 16)(*[int(b.size) for b in streams])
-    need = L.linr_decode_scale_batch_ws_bytes(n, 2, 1, 0)
-    assert need > 0 and L.linr_decode_scale_batch_ws_bytes(n, 0, 1, 0) == 0 and L.linr_decode_scale_batch_ws_bytes(n, 65, 1, 0) == 0
+    need = L.linr_decode_scale_batch_ws_bytes(n, 2, 1, 0, -1, 0)
+    assert need > 0 and L.linr_decode_scale_batch_ws_bytes(n, 0, 1, 0, -1, 0) == 0 and L.linr_decode_scale_batch_ws_bytes(n, 65, 1, 0, -1, 0) == 0
     ws = torch.empty(need + 512, dtype=torch.uint8, device='cuda')
     base = (ws.data_ptr() + 255) & ~255
     p_host, s_host = m._host_buffers(n)
     child = torch.full((8 * n, 3), -7, dtype=torch.int32, device='cuda')
     off = (ctypes.c_int64 * 66)()
+    opts = _lib.LinrDecodeOpts(0, 4, 0)                                              # plain streams, 4 host threads
     torch.cuda.synchronize()
 
     def call(n_frames=2, ws_ptr=base, ws_bytes=need, streams_p=ptrs, seg_h=seg):
         return L.linr_decode_scale_batch(coord.data_ptr(), seg_h.ctypes.data, n_frames, gop.scale_num - 1, gop.scale_num, 1,
                                          m.flat_parameters().data_ptr(), None, 0.0, 0.0, streams_p, lens, ws_ptr, ws_bytes,
-                                         p_host.data_ptr(), s_host.data_ptr(), child.data_ptr(), 8 * n, off, 4, _stream())
+                                         p_host.data_ptr(), s_host.data_ptr(), child.data_ptr(), 8 * n, off, ctypes.byref(opts), _stream())
     seg65 = np.concatenate([seg, np.full(63, n, dtype=np.int64)])                    # 65 segments, the last 63 empty
     assert call(n_frames=0) == -1
     assert call(n_frames=65, seg_h=seg65) == -1

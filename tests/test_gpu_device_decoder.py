@@ -1,6 +1,6 @@
 """GPU: the device range decoder (opt-in; codec.decode_gop device_decoder=True).  The kernel (linr_rc_decode_probs, csrc/ac_device_dec.hip:
 a wave per entry) against the host decoder (linr_ac_decode_binary) on entries packed back to back at odd and even byte offsets, the
-decoder's device scale entries (linr_decode_scale_device, linr_decode_scale_batch_device) against the default ones, and the paths that
+decoder's scale entries with the device decoders (linr_decode_opts.device of linr_decode_scale, linr_decode_scale_batch) against the default ones, and the paths that
 carry the option: codec.decode_gop, run.py --decode --device-decoder, python -m linr_pcgc_amd.decoder --device-decoder, decoder.decode.
 Symbols, untouched sentinels and decoded geometry, all exact; no rate and no time is asserted."""
 import json

@@ -167,7 +167,7 @@ def test_decode_scale_call_equals_stagewise_decode(pkg, precision):
     streams = [np.frombuffer(b, dtype=np.uint8) for b in unpack_bitstream(enc['frames'][0][-1])]
     ptrs = (ctypes.c_void_p * 8)(*[b.ctypes.data if b.size else None for b in streams])
     lens = (ctypes.c_int64 * 8)(*[int(b.size) for b in streams])
-    need = L.linr_decode_scale_ws_bytes(n, 1, 1 if precision == 'bf16' else 0)
+    need = L.linr_decode_scale_ws_bytes(n, 1, 1 if precision == 'bf16' else 0, -1, 0)
     ws = torch.empty(need + 512, dtype=torch.uint8, device='cuda')
     base = (ws.data_ptr() + 255) & ~255
     p_host, s_host = m._host_buffers(n)
@@ -178,7 +178,7 @@ def test_decode_scale_call_equals_stagewise_decode(pkg, precision):
     lo, hi = (float(m._qrange[0]), float(m._qrange[1])) if precision == 'bf16' else (0.0, 0.0)
     args = lambda ws_ptr, cap: (lowx.data_ptr(), n, gop.scale_num - 1, gop.scale_num, 1, 8, params, codes, lo, hi, ptrs, lens, ws_ptr, need,
                                 p_host.data_ptr(), s_host.data_ptr(), child.data_ptr(), cap, ctypes.byref(cnt),
-                                torch.cuda.current_stream().cuda_stream)
+                                None, torch.cuda.current_stream().cuda_stream)
     assert L.linr_decode_scale(*args(base + 8, 8 * n)) == -3
     assert L.linr_decode_scale(*args(base, 1)) == -2
     assert L.linr_decode_scale(*args(base, 8 * n)) == 0 and 0 < cnt.value <= 8 * n
