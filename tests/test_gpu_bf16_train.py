@@ -13,6 +13,10 @@ of it to compare a reduced-precision step with; what is checked, with the tolera
     in fp32; only the summation order differs);
   * four Adam steps track torch.optim.Adam on the emulating oracle; run-to-run bit-identical; a complete small overfit reaches
     the fp32 executor's bits/point within +1 % over three seeds and decodes losslessly through the bf16 / uint8-weight codec.
+The forward and gradient checks of this file run on the golden shell (6,821 rows, finest scale 4,983) and on frames of 1 to 257 rows:
+every backward kernel has ONE tile per wave there.  The sizes at which bbwd_k, bocc_wgrad7_k, thead_bwd_k and bocc7m_k walk several
+tiles and wgrad_reduce_k takes its unrolled branch (32,900 and 131,329 rows on 256 CUs) are held to the emulating oracle and to the
+sum of their scales' alone-frame gradients by tests/test_gpu_bf16_train_tiles.py.
 """
 import ctypes
 import os
