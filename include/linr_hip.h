@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 23
+#define LINR_ABI_VERSION 24
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -505,7 +505,7 @@ LINR_API int linr_sce_fwd_bf16(const float* pf, const linr_frame* f, uint16_t* x
  * accumulation.  ONE rounding rule: every matrix written to memory is rounded to bf16 (RNE) and every consumer sees the stored
  * value; the 3x3x3 kernels are rounded to bf16 inside the kernels; biases, 1x1 convolutions, scale-context and head MLPs, sigmoid
  * and the bits are fp32 (bits accumulate in double).  oracle/network_bf16.py emulates these roundings with autograd; tolerances
- * are in tests/test_gpu_bf16_train.py.  block_layers 1 and the compressed kernel map only.
+ * are in tests/test_gpu_bf16_train.py.  block_layers 1 (deeper: the *_deep entries below) and the compressed kernel map only.
  * arena: linr_net_train_bf16_arena_bytes(rows, 1) bytes, 64-byte aligned, shared by the calls of one step.
  * occ_bf16: NULL, or the frame's occupancy converted once by linr_occ_to_bf16 ([1 + rows][8] bf16, zero row in front; the
  * pointer passed is that of the ZERO row) - a frame's occupancy does not change over the epochs.
@@ -530,6 +530,23 @@ LINR_API int linr_net_train_step_bf16_qat(const linr_frame* f, float* params, vo
                                  float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
                                  const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay,
                                  double* bits_acc, float* qparams, int32_t bitdepth, void* stream);
+/* The same executor for block_layers 1..4 of block_in (--block_layers, main.py:521; models/resnet.py:146-162), opt-in beside the
+ * entries above, which keep refusing more than one layer.  The depth is f->block_layers.  The extra Inception layers run the
+ * same kernels one group at a time; the ResNetBlock's extra skip is ONE stored matrix S = bf16(I_last + A), and the gradient
+ * arriving at every layer's input is rounded once, after its three contributions were summed in fp32 (the rule above;
+ * tests/bf16_train_deep_ref.py emulates it with autograd, tolerances in tests/test_gpu_bf16_train_deep.py).  Same argument checks,
+ * in front of the first launch.  At block_layers 1: the launches, the arena and the results of the entries above, bit for bit.
+ * linr_net_train_bf16_deep_arena_bytes: 0 outside block_layers 1..4 or for rows < 0; at 1 linr_net_train_bf16_arena_bytes(rows, 1).
+ * linr_net_train_step_bf16_deep: qparams == NULL: the plain step (bitdepth ignored), else linr_net_train_step_bf16_qat's. */
+LINR_API size_t linr_net_train_bf16_deep_arena_bytes(int64_t rows, int32_t block_layers);
+LINR_API int linr_net_forward_train_bf16_deep(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
+                                     const uint16_t* occ_bf16, float* probs, double* bits_acc, void* stream);
+LINR_API int linr_net_backward_bf16_deep(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
+                                const uint16_t* occ_bf16, float gscale, float* grads, void* stream);
+LINR_API int linr_net_train_step_bf16_deep(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
+                                  float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
+                                  const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay,
+                                  double* bits_acc, float* qparams, int32_t bitdepth, void* stream);
 /* The backward of ONE convolution 8->8 of that executor as a stand-alone op (ME.MinkowskiConvolution's backward, models/resnet.py:15-51
  * under autograd): gin = bwd-data(gout; W) rounded to bf16 AND the kernel / bias gradient from one gather of gout.  gout / in / gin:
  * bf16 [n][8] whose row -1 exists (gout's must be zero); W fp32 [27][8][8] (rounded to bf16 in-kernel for backward-data);

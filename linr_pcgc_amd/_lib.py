@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('LINR_HIP_LIB') or os.path.join(_HERE, 'liblinr_hip.so
 LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 16
 LINR_FRAME_OCC_PADDED = 1
 LINR_PLY_TOKEN, LINR_PLY_COLUMNS, LINR_PLY_SHORT, LINR_PLY_RANGE = 1, 2, 4, 8
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -219,6 +219,12 @@ _PROTOS = {
                                                c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr, c_i32, c_ptr]),
     'linr_net_train_step_bf16_qat': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr, c_f64,
                                                     c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr, c_i32, c_ptr]),
+    # the bf16 training executor at block_layers 1..4 (ABI 24)
+    'linr_net_train_bf16_deep_arena_bytes': (c_size, [c_i64, c_i32]),
+    'linr_net_forward_train_bf16_deep': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'linr_net_backward_bf16_deep': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr]),
+    'linr_net_train_step_bf16_deep': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr, c_f64,
+                                                     c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr, c_i32, c_ptr]),
 }
 
 EXPORTS = tuple(_PROTOS)

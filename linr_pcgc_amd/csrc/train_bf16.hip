@@ -34,6 +34,22 @@
 //              ONE matrix product on v_mfma_f32_16x16x32_bf16 (columns = (group, cout) as M, rows as N, the gathered 16-byte rows ARE the B
 //              operands; 22 us against 31 for the 4x4x4 form bocc7_k, kept behind LINR_BOCC7_MFMA16=0).
 //   per step   tpack_k rounds every 3x3x3 kernel once into the operand images the kernels above load (wimg).
+//
+// block_layers 2..4 of block_in (main.py:521; models/resnet.py:146-162), through the *_deep entries only - the others refuse more than
+// one layer, and at one layer the *_deep entries run exactly their launches.  Only block_in has more than one Inception layer
+// (layout.h), and the extra layers are the same three convolutions:
+//   forward    layer l >= 1 reads X = the stored I_{l-1}: single-group launches of bconv_k<2> / bconv_k<3> from eight more images of
+//              tpack_k per layer; then S = bf16(I_last + A) (tadd_rows_k: csrc/net_bf16.hip: badd_rows_k's rounding) over I_last, which
+//              nothing else reads; the tail convolution and its weight gradient read S.
+//   backward   block_in's group of the tail (EPI 3) and dual launches is its LAST layer; gS, the tail's stored output gradient, is
+//              gI_last.  The conv0_0 launch covers the seven outter blocks (on the grid of eight groups: same slab rows as the tail
+//              launch, so an outter block's parameters stay one slab range), and block_in's chain runs one group at a time:
+//              bbwd_k<2, 4> per extra layer - gI_{l-1} = bf16(bwd(gH_l[:, 0:4]; W00_l) + gI_l + gH_l[:, 4:8] @ W10_l^T), NO ReLU mask
+//              (a layer's input is not a ReLU output), and EPI 3's G2 epilogue on the stored row for layer l-1 - then that layer's
+//              dual launch, and last bbwd_k<2, 5>: gA[0] = bf16((.. of layer 0 .. + gS) * (A[0] > 0)).  KIND 2 gathers 8-byte rows,
+//              which is the room the two epilogues need: 193 / 186 registers (180 without), no scratch, two waves per SIMD.
+//   arena      H, I, M, gI, G2, gH per extra layer (with their pad rows in BPads: 117 of 128 at four layers); block_in's slab ranges
+//              are per launch size (tbackward).
 #include "bf16_common.h"
 #include "head_bwd.h"
 #include "sce.h"
@@ -68,6 +84,9 @@ __device__ __forceinline__ s16x4 tr_read(const char* p) {
 //   KIND 1  the two 4->4 convolutions of an Inception layer: gathers G2 = [gI[:, 0:4] | gM], own rows H (also the ReLU mask)
 //   KIND 2  conv0_0 8->4: gathers gH[:, 0:4] (8 bytes per tap), own rows A (also the mask); conv1_0 (1x1) rides along
 //   EPI 3 (KIND 0, tail convolution): also gM = (gI[:, 4:8] @ W12^T) * (M > 0), G2 = [gI[:, 0:4] | gM]; conv1_2's gradients ride along
+//   EPI 4 (KIND 2, conv0_0 of an Inception layer l >= 1 of block_in): the input X = I_{l-1} is no ReLU output - NO mask - and what
+//          comes out is gI_{l-1}, so EPI 3's epilogue runs on it with the layer l-1's W12 / M / G2 / conv1_2
+//   EPI 5 (KIND 2, conv0_0 of layer 0 of a block_in with several layers): one more addend row, gS (the ResNetBlock's extra skip)
 struct BbArgs {
     const bf16_t* g;  const bf16_t* xin;  const float* P;
     bf16_t* out;  float* out_f32;
@@ -81,6 +100,7 @@ struct BbArgs {
     int64_t w1[TB_MAXG], b1[TB_MAXG];          // KIND 1: conv1_1
     int64_t wp[TB_MAXG], bp[TB_MAXG];          // EPI 3: conv1_2;  KIND 2: conv1_0
     int cin[TB_MAXG];                          // KIND 0: input channels of the kernel [27][cin][8]
+    const bf16_t* res2;  int64_t g_res2[TB_MAXG];    // EPI 5: the second addend row (behind everything the other launches read)
 };
 // One group's operands per KIND (the pattern of common.h: Conv88BwdGroup ...): matrices are the group's own pointers, *_off offsets
 // into the flat parameter vector = into a row of the weight-gradient slab.  bb_fill alone writes BbArgs' per-group slots.
@@ -102,6 +122,9 @@ struct BbC00Group {          // KIND 2: gA = (bwd(gH[:, 0:4]; W00) + gI + gH[:, 
     static constexpr int KIND = 2;
     const bf16_t *gH, *A, *gI; bf16_t* gA;
     int64_t w00_off, b00_off, w10_off, b10_off;
+    const bf16_t* M; bf16_t* G2;         // EPI 4: G2 = [gA[:, 0:4] | (gA[:, 4:8] @ W12^T) * (M > 0)] of the layer below, conv1_2's gradients
+    int64_t w12_off, b12_off;
+    const bf16_t* gS;                    // EPI 5: gA = (.. + gS) * (A > 0)
 };
 static int bb_fill(BbArgs& a, const Bb88Group* g, int ng) {
     if (ng < 1 || ng > TB_MAXG || (g[0].out_f32 && ng != 1)) return LINR_EINVAL;
@@ -126,9 +149,12 @@ static int bb_fill(BbArgs& a, const BbDualGroup* g, int ng) {
 static int bb_fill(BbArgs& a, const BbC00Group* g, int ng) {
     if (ng < 1 || ng > TB_MAXG) return LINR_EINVAL;
     a.g = g[0].gH; a.xin = g[0].A; a.out = g[0].gA; a.res = g[0].gI;
+    a.m = g[0].M; a.g2 = g[0].G2; a.res2 = g[0].gS;
     for (int i = 0; i < ng; ++i) {
         a.g_g[i] = g[i].gH - a.g; a.g_x[i] = g[i].A - a.xin; a.g_out[i] = g[i].gA - a.out; a.g_res[i] = g[i].gI - a.res;
         a.w[i] = g[i].w00_off; a.b[i] = g[i].b00_off; a.wp[i] = g[i].w10_off; a.bp[i] = g[i].b10_off;
+        a.g_m[i] = bdiff(g[i].M, a.m); a.g_g2[i] = bdiff(g[i].G2, a.g2); a.g_res2[i] = bdiff(g[i].gS, a.res2);
+        a.w1[i] = g[i].w12_off; a.b1[i] = g[i].b12_off;                      // (KIND 2 has no other use for w1 / b1)
     }
     return 0;
 }
@@ -150,6 +176,8 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
     using T = BbT<KIND>;
     constexpr int CT = T::CT, SL = T::SL, NCH = T::NCH, NG = (T::NW + 15) / 16, NACC = T::NACC;
     constexpr bool BIG = T::BIG;
+    static_assert(KIND == 2 ? (EPI == 0 || EPI == 4 || EPI == 5) : (EPI == 0 || (KIND == 0 && EPI == 3)), "no such epilogue");
+    constexpr bool G2E = EPI == 3 || EPI == 4;                               // the G2 epilogue on the row this launch stores
     __shared__ uint4 smem[BB_WAVES * T::WAVE_BYTES / 16];
     __shared__ float sbias[BB_WAVES][8];
     __shared__ float s12[BB_WAVES][20];
@@ -210,7 +238,7 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
     float bsum[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) bsum[j] = 0.0f;
-    float g12[20];                                                            // EPI 3: conv1_2's kernel [4][4] and bias gradients
+    float g12[20];                                                            // G2E: conv1_2's kernel [4][4] and bias gradients
 #pragma unroll
     for (int j = 0; j < 20; ++j) g12[j] = 0.0f;
     float wpw[32];                                                            // EPI 3: W12 [4][4];  KIND 2: W10 [8][4]
@@ -224,6 +252,13 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
 #pragma unroll
         for (int j = 0; j < 32; ++j) wpw[j] = P[a.wp[gi] + j];
     }
+    float w12[16];                                                            // G2E: W12 [4][4] (EPI 3 keeps it in wpw: see below)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w12[j] = 0.0f;
+    if constexpr (EPI == 4) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) w12[j] = P[a.w1[gi] + j];
+    }
     const int64_t n = a.n;
     const int64_t T64 = (n + 63) >> 6;
     const int64_t tb0 = (int64_t)blockIdx.x * (BB_WAVES * a.tiles_per_wave);
@@ -235,7 +270,7 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
     // phases): the index words, the own row and the epilogue's own-row operands of the wave's NEXT tile are requested at step 1 of the
     // current one; the 16 transposed reads of a chunk are issued behind its last tap and its 16 weight-gradient instructions are
     // spread over the taps of the NEXT chunk, beside that chunk's gathers and backward-data instructions (independent accumulators).
-    struct Own { uint4 xr, res, gh; uint2 m; };
+    struct Own { uint4 xr, res, gh; uint2 m; uint4 res2; };
     auto idx_load = [&](int64_t row, uint32_t (&raw)[10]) { load_words16(a.lo, a.mask, a.ld, row, raw); };
     auto idx_decode = [&](const uint32_t (&raw)[10], uint32_t (&off)[27]) {      // mirrored taps: off[k] pairs with W[k] (backward-data
         uint32_t fo[27];                                                         // gathers nbr(row, 26 - k)); absent -> 0 (the pad row)
@@ -252,7 +287,9 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
         o.xr = make_uint4(0u, 0u, 0u, 0u);
         if (live) o.xr = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(xin) + rb16);
         o.res = make_uint4(0u, 0u, 0u, 0u); o.gh = o.res; o.m = make_uint2(0u, 0u);
-        if constexpr (EPI == 3) o.m = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.m + a.g_m[gi]) + (rb16 >> 1));
+        o.res2 = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (G2E) o.m = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.m + a.g_m[gi]) + (rb16 >> 1));
+        if constexpr (EPI == 5) o.res2 = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.res2 + a.g_res2[gi]) + rb16);
         if constexpr (KIND == 2) {
             o.res = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.res + a.g_res[gi]) + rb16);
             o.gh = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(gbase) + rb16);
@@ -396,7 +433,7 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = hv[j] > 0.0f ? o[j] : 0.0f;
             }
-            if constexpr (KIND == 2) {                // gA = (bwd(gH[:, 0:4]; W00) + gI + gH[:, 4:8] @ W10^T) * (A > 0)
+            if constexpr (KIND == 2) {                // gA = (bwd(gH[:, 0:4]; W00) + gI + gH[:, 4:8] @ W10^T (+ gS: EPI 5)) * (A > 0) (EPI 4: no mask)
                 float rv[8], gh[8], av8[8];
                 unpack_row(ow.res, rv);
                 unpack_row(ow.gh, gh);
@@ -410,8 +447,16 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
                     for (int q = 0; q < 4; ++q) t = fmaf(gh[4 + q], wpw[i * 4 + q], t);
                     o[i] += t;
                 }
+                if constexpr (EPI == 5) {
+                    float sv[8];
+                    unpack_row(ow.res2, sv);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = av8[j] > 0.0f ? o[j] : 0.0f;
+                    for (int j = 0; j < 8; ++j) o[j] += sv[j];
+                }
+                if constexpr (EPI != 4) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) o[j] = av8[j] > 0.0f ? o[j] : 0.0f;
+                }
                 if (live) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) bsum[4 + q] += gh[4 + q];
@@ -421,7 +466,7 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
             {
                 if (live) {
                     const uint32_t rb16 = (uint32_t)row << 4;
-                    if (EPI == 3 || (a.flags & TB_OUT_F32)) unpack_row(po, o);   // what follows uses the STORED values
+                    if (G2E || (a.flags & TB_OUT_F32)) unpack_row(po, o);        // what follows uses the STORED values
                     if (a.flags & TB_OUT_F32) {
                         float* op = a.out_f32 + row * 8;
                         *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
@@ -429,7 +474,7 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
                     } else {
                         *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.out + a.g_out[gi]) + rb16) = po;
                     }
-                    if constexpr (EPI == 3) {             // gM = (gI[:, 4:8] @ W12^T) * (M > 0);  G2 = [gI[:, 0:4] | gM]
+                    if constexpr (G2E) {                  // gM = (gI[:, 4:8] @ W12^T) * (M > 0);  G2 = [gI[:, 0:4] | gM]
                         const float mv[4] = {bf2f((bf16_t)(ow.m.x & 0xffff)), bf2f((bf16_t)(ow.m.x >> 16)), bf2f((bf16_t)(ow.m.y & 0xffff)),
                                              bf2f((bf16_t)(ow.m.y >> 16))};
                         float g2[8];
@@ -439,7 +484,7 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
                         for (int i = 0; i < 4; ++i) {
                             float t = 0.0f;
 #pragma unroll
-                            for (int q = 0; q < 4; ++q) t = fmaf(o[4 + q], wpw[i * 4 + q], t);
+                            for (int q = 0; q < 4; ++q) t = fmaf(o[4 + q], EPI == 4 ? w12[i * 4 + q] : wpw[i * 4 + q], t);
                             g2[4 + i] = mv[i] > 0.0f ? t : 0.0f;
                         }
                         *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.g2 + a.g_g2[gi]) + rb16) = pack_row(g2);
@@ -473,7 +518,7 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
         for (int dd = 32; dd > 0; dd >>= 1) t += __shfl_xor(t, dd, 64);
         if (lane == 0) sbias[wave][j] = t;
     }
-    if constexpr (EPI == 3) {
+    if constexpr (G2E) {
 #pragma unroll
         for (int j = 0; j < 20; ++j) {
             float t = g12[j];
@@ -521,10 +566,11 @@ __global__ __launch_bounds__(BB_WAVES * 64, 2) void bbwd_k(BbArgs a) {
         else if constexpr (KIND == 1) dst[(tid < 4 ? a.b[gi] : a.b1[gi]) + (tid & 3)] = t;
         else dst[(tid < 4 ? a.b[gi] : a.bp[gi]) + (tid & 3)] = t;
     }
-    if constexpr (EPI == 3) {
+    if constexpr (G2E) {                                                     // conv1_2: wp / bp of KIND 0, w1 / b1 of KIND 2 (EPI 4)
         if (tid < 20) {
             const float t = ((s12[0][tid] + s12[1][tid]) + s12[2][tid]) + s12[3][tid];
-            dst[tid < 16 ? a.wp[gi] + tid : a.bp[gi] + (tid - 16)] = t;
+            if constexpr (EPI == 4) dst[tid < 16 ? a.w1[gi] + tid : a.b1[gi] + (tid - 16)] = t;
+            else dst[tid < 16 ? a.wp[gi] + tid : a.bp[gi] + (tid - 16)] = t;
         }
     }
 }
@@ -550,11 +596,13 @@ static void tb_grid(int64_t n, int nb, int ngroups, int& tiles_per_wave, int& bl
     if (blocks < 1) blocks = 1;
 }
 // the one launch of bbwd_k<G::KIND, EPI>: `a` holds what the groups share, g[0 .. ng) the groups; *rows = slab rows written (at most nb)
+// grid_groups: the group count the grid is sized for (0: ng) - a launch of fewer groups that must write the SAME slab rows as another
 template <int EPI, class G>
-static int bb_run(BbArgs a, const G* g, int ng, int nb, int* rows, hipStream_t s) {
+static int bb_run(BbArgs a, const G* g, int ng, int nb, int* rows, hipStream_t s, int grid_groups = 0) {
     TRY(bb_fill(a, g, ng));
-    if (EPI == 3 && (!a.m || !a.g2)) return LINR_EINVAL;
-    tb_grid(a.n, nb, ng, a.tiles_per_wave, *rows);
+    if ((EPI == 3 || EPI == 4) && (!a.m || !a.g2)) return LINR_EINVAL;
+    if (EPI == 5 && !a.res2) return LINR_EINVAL;
+    tb_grid(a.n, nb, grid_groups > 0 ? grid_groups : ng, a.tiles_per_wave, *rows);
     bbwd_k<G::KIND, EPI><<<dim3(*rows, ng), BB_WAVES * 64, 0, s>>>(a);
     return linr_launch_rc();
 }
@@ -576,7 +624,9 @@ static int bb_run(BbArgs a, const G* g, int ng, int nb, int* rows, hipStream_t s
 #define TP_OCC 183
 #define TP_OCCM 217                     // [217, 273)  the same seven convolutions as ONE matrix: 28 operand images of 16 bytes per lane (bocc7m_k)
 #define TP_IMAGES 273
-struct TPack { int64_t conv0_w[9], pr_w[8], c00_w[8], c01_w[8], c11_w[8], occ_w[7]; };
+//   [273, 273 + 8 x)  block_in's Inception layers 1 .. x (block_layers 2..4): conv0_0 x 4, then [conv0_1 | conv1_1] x 4, per layer
+#define TP_XLAYER 8
+struct TPack { int64_t conv0_w[9], pr_w[8], c00_w[8], c01_w[8], c11_w[8], occ_w[7]; int n_extra; int64_t x00_w[MAX_BL - 1], x01_w[MAX_BL - 1], x11_w[MAX_BL - 1]; };
 __host__ __device__ constexpr int oj_g(int j) { return j < 8 ? j >> 1 : 4 + ((j - 8) >> 2); }
 __host__ __device__ constexpr int oj_h(int j) { return j < 8 ? j & 1 : ((j - 8) >> 1) & 1; }
 __host__ __device__ constexpr int oj_q(int j) { return j < 8 ? 0 : (j - 8) & 1; }
@@ -587,14 +637,24 @@ __host__ __device__ constexpr int bm_tap(int s) { return s / 3 + 9 * (s % 3); }
 // (blocks behind the images clear the pad rows of the arena's matrices - zero_pads16_k's work: one launch less per step)
 __global__ __launch_bounds__(64) void tpack_k(const float* __restrict__ P, TPack t, uint2* __restrict__ wimg, bf16_t* __restrict__ pad_base, BPads pl) {
     const int m = blockIdx.x, lane = threadIdx.x;
-    if (m >= TP_IMAGES) {
-        const int b = m - TP_IMAGES;
+    const int n_img = TP_IMAGES + TP_XLAYER * t.n_extra;
+    if (m >= n_img) {
+        const int b = m - n_img;
         if (b < pl.n && lane < pl.w[b]) pad_base[pl.off[b] + lane] = 0;
         return;
     }
     const int blk = lane >> 2, i = lane & 3;
     float w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (m < TP_DUAL) {
+    if (m >= TP_IMAGES) {               // an extra layer of block_in: the blocks of the ranges TP_C00 / TP_DUAL, same registers
+        const int layer = (m - TP_IMAGES) / TP_XLAYER, r = (m - TP_IMAGES) % 4;
+        const bool dual = (m - TP_IMAGES) % TP_XLAYER >= 4;
+        const int c = 16 * r + blk, k = c >> 1;
+        if (k < 27) {
+            const float* W = P + (!dual ? t.x00_w[layer] : (c & 1) ? t.x11_w[layer] : t.x01_w[layer]);
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) w[kk] = dual ? W[(k * 4 + kk) * 4 + i] : W[(k * 8 + 4 * (c & 1) + kk) * 4 + i];
+        }
+    } else if (m < TP_DUAL) {
         // block c = 16 r + blk of the layer's register r:  cin->8 / prune: c = 4 k + 2 h + q -> W[k][4 q + kk][4 h + i];
         // conv0_0: c = 2 k + q -> W00[k][4 q + kk][i]
         const bool c00 = m >= TP_C00;
@@ -1029,6 +1089,18 @@ __global__ __launch_bounds__(LINR_BLOCK) void tsum8_k(TPtr8 src, int64_t n, bf16
 }
 
 // ---- arena --------------------------------------------------------------------------------------------------------------------------
+// dst = bf16(dst + src), row by row: the ResNetBlock's extra skip - csrc/net_bf16.hip: badd_rows_k's arithmetic and rounding
+__global__ __launch_bounds__(LINR_BLOCK) void tadd_rows_k(const bf16_t* __restrict__ src, int64_t n, bf16_t* __restrict__ dst) {
+    const int64_t r = (int64_t)blockIdx.x * LINR_BLOCK + threadIdx.x;
+    if (r >= n) return;
+    float a[8], b[8];
+    unpack_row(*reinterpret_cast<const uint4*>(src + r * 8), a);
+    unpack_row(*reinterpret_cast<const uint4*>(dst + r * 8), b);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] += a[j];
+    *reinterpret_cast<uint4*>(dst + r * 8) = pack_row(b);
+}
+
 struct TArena {
     int64_t rows;
     char* base;
@@ -1038,6 +1110,9 @@ struct TArena {
     double* part;
     bf16_t *X0, *OCC, *A[8], *H[8], *I[8], *O[8], *C[8], *M[8];
     bf16_t *gC[8], *gO[8], *gXG, *gI[8], *G2[8], *gH[8], *gA[8];
+    // block_in's Inception layers by layer (block_layers 2..4): [0] = the matrices of slot 0 above, [l >= 1] the extra layers' own
+    bf16_t *bH[MAX_BL], *bI[MAX_BL], *bM[MAX_BL], *bgI[MAX_BL], *bG2[MAX_BL], *bgH[MAX_BL];
+    bool over;                       // more matrices than BPads holds: the arena is not usable
     BPads pads;
     bf16_t* mats;
     int64_t n_params;
@@ -1050,19 +1125,21 @@ static void* tbytes(TArena& a, int64_t nbytes) {
 }
 static bf16_t* tmat(TArena& a, int w = 8) {          // [1 + rows][w] with the zero row in front
     bf16_t* p = a.base ? reinterpret_cast<bf16_t*>(a.base + a.cur) : nullptr;
-    if (a.pads.n >= BPADS_MAX) abort();                  // (99 matrices today)
+    if (a.pads.n >= BPADS_MAX) { a.over = true; return nullptr; }      // (99 matrices + 6 per extra layer of block_in: 117 at block_layers 4)
     a.pads.off[a.pads.n] = (a.cur - (int64_t)(reinterpret_cast<char*>(a.mats) - a.base)) / 2;
     a.pads.w[a.pads.n++] = w;
     a.cur += (((a.rows + 1) * w * 2) + 63) & ~(int64_t)63;
     return p ? p + w : nullptr;
 }
 
-static void make_tarena(TArena& a, int64_t rows, char* base, int64_t n_params, bool own_occ) {
-    a.rows = rows; a.base = base; a.cur = 0; a.pads.n = 0; a.n_params = n_params;
+static_assert(99 + 6 * (MAX_BL - 1) <= BPADS_MAX, "tpack_k clears one pad row per entry of BPads");
+// nl = block_layers of block_in: at 1 the arena of the parent executor, byte for byte
+static void make_tarena(TArena& a, int64_t rows, char* base, int64_t n_params, bool own_occ, int nl = 1) {
+    a.rows = rows; a.base = base; a.cur = 0; a.pads.n = 0; a.n_params = n_params; a.over = false;
     a.gX0 = (float*)tbytes(a, rows * 8 * 4);
     a.PR = (float*)tbytes(a, rows * 8 * 4);
     a.part = (double*)tbytes(a, (int64_t)8 * linr_grid(rows, LINR_BLOCK) * 8);
-    a.WIMG = (uint2*)tbytes(a, (int64_t)TP_IMAGES * 64 * 8);
+    a.WIMG = (uint2*)tbytes(a, (int64_t)(TP_IMAGES + TP_XLAYER * (nl - 1)) * 64 * 8);
     a.GSUM = (float*)tbytes(a, n_params * 4);
     a.BIG = (float*)tbytes(a, (int64_t)LINR_WG_BLOCKS * n_params * 4);
     a.mats = reinterpret_cast<bf16_t*>(base + a.cur);
@@ -1072,6 +1149,11 @@ static void make_tarena(TArena& a, int64_t rows, char* base, int64_t n_params, b
     for (int k = 0; k < 8; ++k) { a.C[k] = tmat(a); a.gC[k] = tmat(a); a.gO[k] = tmat(a); }
     a.gXG = tmat(a);
     for (int b = 0; b < 8; ++b) { a.gI[b] = tmat(a); a.G2[b] = tmat(a); a.gH[b] = tmat(a); a.gA[b] = tmat(a); }
+    a.bH[0] = a.H[0]; a.bI[0] = a.I[0]; a.bM[0] = a.M[0]; a.bgI[0] = a.gI[0]; a.bG2[0] = a.G2[0]; a.bgH[0] = a.gH[0];
+    for (int l = 1; l < MAX_BL; ++l) {
+        a.bH[l] = a.bI[l] = a.bM[l] = a.bgI[l] = a.bG2[l] = a.bgH[l] = nullptr;
+        if (l < nl) { a.bH[l] = tmat(a); a.bI[l] = tmat(a); a.bM[l] = tmat(a, 4); a.bgI[l] = tmat(a); a.bG2[l] = tmat(a); a.bgH[l] = tmat(a); }
+    }
 }
 
 extern "C" size_t linr_net_train_bf16_arena_bytes(int64_t rows, int32_t block_layers) {
@@ -1081,6 +1163,16 @@ extern "C" size_t linr_net_train_bf16_arena_bytes(int64_t rows, int32_t block_la
     TArena a;
     make_tarena(a, rows, nullptr, L.total, true);
     return (size_t)a.cur + 64;
+}
+
+// the same executor at block_layers 1..4 of block_in (the *_deep entries below); at 1 the figure above
+extern "C" size_t linr_net_train_bf16_deep_arena_bytes(int64_t rows, int32_t block_layers) {
+    if (rows < 0 || block_layers < 1 || block_layers > MAX_BL) return 0;
+    Layout L;
+    make_layout(L, MAX_SCALES, block_layers);
+    TArena a;
+    make_tarena(a, rows, nullptr, L.total, true, block_layers);
+    return a.over ? 0 : (size_t)a.cur + 64;
 }
 
 // occupancy fp32 [rows][8] -> bf16 [1 + rows][8] with the zero row in front (out points at the pad row): a frame's occupancy does
@@ -1111,18 +1203,21 @@ struct TCtx : LinrShortList {
     int64_t R;
 };
 
-static int tcheck(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16, TCtx& c) {
+// deep: the *_deep entries - block_in at the frame's block_layers (1..4); the other entries refuse more than one layer
+static int tcheck(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16, TCtx& c,
+                  bool deep = false) {
     if (!params || !arena) return LINR_EINVAL;
-    TRY(linr_frame_layout(f, 1, c.L));
-    if (f->block_layers > 1) return LINR_EINVAL;                // block_layers 1 only
+    TRY(linr_frame_layout(f, deep ? 0 : 1, c.L));
+    if (!deep && f->block_layers > 1) return LINR_EINVAL;       // block_layers 1 only
     if (f->rows > 0 && (!f->nbr_lo || !f->nbr_mask || !f->offset_feat || !f->occ || f->nbr_ld < f->rows)) return LINR_EINVAL;   // compressed map only
     if (!linr_rows_fit32(f->rows)) return LINR_EINVAL;
-    if (arena_bytes < linr_net_train_bf16_arena_bytes(f->rows, 1)) return LINR_ENOSPC;
+    if (arena_bytes < linr_net_train_bf16_deep_arena_bytes(f->rows, c.L.BL)) return LINR_ENOSPC;      // (BL 1: linr_net_train_bf16_arena_bytes)
     if (((uintptr_t)arena) & 63u) return LINR_EALIGN;
     if (occ_bf16 && (((uintptr_t)occ_bf16) & 15u)) return LINR_EALIGN;
     c.f = f; c.P = params; c.R = f->rows;
     c.nb = linr_wg_blocks_for(f->rows);
-    make_tarena(c.A, f->rows, (char*)arena, c.L.total, true);
+    make_tarena(c.A, f->rows, (char*)arena, c.L.total, true, c.L.BL);
+    if (c.A.over) return LINR_EINVAL;
     c.OCC = occ_bf16 ? reinterpret_cast<const bf16_t*>(occ_bf16) + 8 : c.A.OCC;
     return 0;
 }
@@ -1165,7 +1260,12 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
             const IncP& q = slot_block(L, k).inc[0];
             tp.pr_w[k] = L.pr_w[k]; tp.c00_w[k] = q.c00_w; tp.c01_w[k] = q.c01_w; tp.c11_w[k] = q.c11_w;
         }
-        tpack_k<<<TP_IMAGES + a.pads.n, 64, 0, c.s>>>(c.P, tp, a.WIMG, a.mats, a.pads);
+        tp.n_extra = L.BL - 1;
+        for (int l = 1; l < MAX_BL; ++l) {
+            const IncP& q = L.block_in.inc[l < L.BL ? l : 0];
+            tp.x00_w[l - 1] = q.c00_w; tp.x01_w[l - 1] = q.c01_w; tp.x11_w[l - 1] = q.c11_w;
+        }
+        tpack_k<<<TP_IMAGES + TP_XLAYER * tp.n_extra + a.pads.n, 64, 0, c.s>>>(c.P, tp, a.WIMG, a.mats, a.pads);
         const SceArgs sa = sce_args(f, L);
         PadList none;
         none.n = 0;
@@ -1202,8 +1302,21 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
         TRY(tlaunch(c, TP_C00, pw, 8));
         TRY(tlaunch(c, TP_DUAL, du, 8));
     }
+    const int last = L.BL - 1;          // block_in's last Inception layer
+    for (int l = 1; l <= last; ++l) {   // block_in's layers 1..: X = the stored I of the layer below (models/resnet.py:156-159), single launches
+        const IncP& q = L.block_in.inc[l];
+        const BPwGroup pw = bpw_group(q, a.bI[l - 1], a.bH[l]);
+        const BDualGroup du = bdual_group(q, a.bH[l], a.bI[l - 1], a.bI[l], a.bM[l]);
+        TRY(tlaunch(c, TP_IMAGES + TP_XLAYER * (l - 1), &pw, 1));
+        TRY(tlaunch(c, TP_IMAGES + TP_XLAYER * (l - 1) + 4, &du, 1));
+    }
+    if (last > 0) {                     // the ResNetBlock's extra skip (models/resnet.py:160-161): S = bf16(I_last + A), over I_last
+        ProfScope ps(c.s, TK_MISC, 1);
+        tadd_rows_k<<<linr_grid(c.R, LINR_BLOCK), LINR_BLOCK, 0, c.s>>>(a.A[0], c.R, a.bI[last]);
+        TRY(linr_launch_rc());
+    }
     {   // x_glob = O[0] = conv3(I[0]); prior_b = O[b] = conv3(I[b]) + x_glob
-        const BConvGroup glob = {a.I[0], a.O[0], nullptr, L.block_in.b_w, L.block_in.b_b, 8};
+        const BConvGroup glob = {a.bI[last], a.O[0], nullptr, L.block_in.b_w, L.block_in.b_b, 8};
         TRY(tconv(c, 1, &glob, 1, 0));
         BConvGroup last[7];
         for (int g = 0; g < 7; ++g) last[g] = {a.I[g + 1], a.O[g + 1], a.O[0], L.outter[g].b_w, L.outter[g].b_b, 8};
@@ -1220,12 +1333,12 @@ static int tforward(TCtx& c, float* probs, double* bits_acc) {
 }
 
 template <int EPI, class G>
-static int bb_launch(TCtx& c, const G* g, int ng, int kind_prof, int* rows) {
+static int bb_launch(TCtx& c, const G* g, int ng, int kind_prof, int* rows, int grid_groups = 0) {
     BbArgs a = BbArgs();
     a.P = c.P; a.lo = c.f->nbr_lo; a.mask = c.f->nbr_mask; a.ld = c.f->nbr_ld; a.n = c.R;
     a.big = c.A.BIG; a.block_stride = c.L.total;
     ProfScope ps(c.s, kind_prof, ng);
-    return bb_run<EPI>(a, g, ng, c.nb, rows, c.s);
+    return bb_run<EPI>(a, g, ng, c.nb, rows, c.s, grid_groups);
 }
 
 // backward of gscale * bits: leaves the parameter gradient in the arena's GSUM (flat, parameters() order)
@@ -1265,23 +1378,59 @@ static int tbackward(TCtx& c, float gscale) {
         //   O = conv3(I; b): gI = bwd(gO), gM, G2 = [gI[:, 0:4] | gM], the kernel / bias gradients and conv1_2's
         //   both 4->4 convs: gH = [bwd(gI[:, 0:4]; W01) | bwd(gM; W11)] * (H > 0) and their gradients, one gather of G2
         //   conv0_0 (8->4): gA = (bwd(gH[:, 0:4]; W00) + gI + gH[:, 4:8] @ W10^T) * (A > 0), its gradients and conv1_0's
+        //
+        // block_in with nl > 1 Inception layers: its group of the tail and dual launches is its LAST layer (the tail convolution reads S,
+        // kept over I_last, and its stored output gradient gS is gI_last); the conv0_0 launch covers the seven outter blocks on the
+        // SAME grid (so that an outter block's parameters stay one slab range), and block_in's chain runs as single-group launches:
+        //   for l = nl-1 .. 1   conv0_0 of layer l (EPI 4): gI_{l-1} = bwd(gH_l[:, 0:4]; W00_l) + gI_l + gH_l[:, 4:8] @ W10_l^T, no mask,
+        //                       and from the stored gI_{l-1}: gM_{l-1}, G2_{l-1}, conv1_2_{l-1}'s gradients;  then layer l-1's dual launch
+        //   conv0_0 of layer 0 (EPI 5): gA[0] = (.. + gS) * (A[0] > 0)
+        const int last = L.BL - 1;
         Bb88Group tail[8];
         BbDualGroup dual[8];
         BbC00Group c00[8];
         for (int g = 0; g < 8; ++g) {
             const BlockP& bp = slot_block(L, g);
-            const IncP& q = bp.inc[0];
+            const int l = g == 0 ? last : 0;
+            const IncP& q = bp.inc[l];
             const bf16_t* gO = g == 0 ? a.gXG : a.gO[g];       // slot 0 = block_in, whose output gradient is the fan-in sum
-            tail[g] = {gO, a.I[g], a.gI[g], bp.b_w, bp.b_b, 8, a.M[g], a.G2[g], q.c12_w, q.c12_b};
-            dual[g] = {a.G2[g], a.H[g], a.gH[g], q.c01_w, q.c01_b, q.c11_w, q.c11_b};
-            c00[g] = {a.gH[g], a.A[g], a.gI[g], a.gA[g], q.c00_w, q.c00_b, q.c10_w, q.c10_b};
+            tail[g] = {gO, g == 0 ? a.bI[l] : a.I[g], g == 0 ? a.bgI[l] : a.gI[g], bp.b_w, bp.b_b, 8, g == 0 ? a.bM[l] : a.M[g],
+                       g == 0 ? a.bG2[l] : a.G2[g], q.c12_w, q.c12_b};
+            dual[g] = {tail[g].G2, g == 0 ? a.bH[l] : a.H[g], g == 0 ? a.bgH[l] : a.gH[g], q.c01_w, q.c01_b, q.c11_w, q.c11_b};
+            c00[g] = {a.gH[g], a.A[g], a.gI[g], a.gA[g], bp.inc[0].c00_w, bp.inc[0].c00_b, bp.inc[0].c10_w, bp.inc[0].c10_b};
         }
         TRY(bb_launch<3>(c, tail, 8, TK_BWD88, &rows));
-        for (int g = 0; g < 8; ++g) c.note_short(c00[g].w00_off, tail[g].b_off + 8, rows);      // one range per block
+        for (int g = last > 0 ? 1 : 0; g < 8; ++g) c.note_short(c00[g].w00_off, tail[g].b_off + 8, rows);      // one range per block
         TRY(bb_launch<0>(c, dual, 8, TK_BWD_DUAL, &r2));
         if (r2 != rows) return LINR_EINVAL;
-        TRY(bb_launch<0>(c, c00, 8, TK_BWD_C00, &r2));
-        if (r2 != rows) return LINR_EINVAL;
+        if (last == 0) {
+            TRY(bb_launch<0>(c, c00, 8, TK_BWD_C00, &r2));
+            if (r2 != rows) return LINR_EINVAL;
+        } else {
+            TRY(bb_launch<0>(c, c00 + 1, 7, TK_BWD_C00, &r2, 8));
+            if (r2 != rows) return LINR_EINVAL;
+            int r1 = 0, r1d = 0;
+            for (int l = last; l >= 1; --l) {
+                const IncP &q = L.block_in.inc[l], &qb = L.block_in.inc[l - 1];
+                const BbC00Group up = {a.bgH[l], a.bI[l - 1], a.bgI[l], a.bgI[l - 1], q.c00_w, q.c00_b, q.c10_w, q.c10_b,
+                                       a.bM[l - 1], a.bG2[l - 1], qb.c12_w, qb.c12_b, nullptr};
+                TRY(bb_launch<4>(c, &up, 1, TK_BWD_C00, &r1));
+                const BbDualGroup dn = {a.bG2[l - 1], a.bH[l - 1], a.bgH[l - 1], qb.c01_w, qb.c01_b, qb.c11_w, qb.c11_b};
+                TRY(bb_launch<0>(c, &dn, 1, TK_BWD_DUAL, &r1d));
+                if (r1d != r1) return LINR_EINVAL;
+            }
+            BbC00Group first = c00[0];
+            first.gS = a.bgI[last];
+            TRY(bb_launch<5>(c, &first, 1, TK_BWD_C00, &r1d));
+            if (r1d != r1) return LINR_EINVAL;
+            // block_in's slab ranges: the single-group launches wrote r1 rows of everything below the last layer, of its conv0_0 and
+            // of its conv1_0; the 8-group launches `rows` of the last layer's conv0_1, conv1_1, conv1_2 and of the tail convolution
+            const IncP& ql = L.block_in.inc[last];
+            c.note_short(L.block_in.inc[0].c00_w, ql.c01_w, r1);
+            c.note_short(ql.c01_w, ql.c10_w, rows);
+            c.note_short(ql.c10_w, ql.c11_w, r1);
+            c.note_short(ql.c11_w, L.block_in.b_b + 8, rows);
+        }
     }
     {   // A[b] = relu(conv3(occ[:, :b]; a)): kernel / bias gradients of the seven first convolutions from ONE gather of the occupancy
         OwArgs o;
@@ -1313,24 +1462,40 @@ static int tbackward(TCtx& c, float gscale) {
 }
 
 // ---- C-ABI ----------------------------------------------------------------------------------------------------------------------------
-extern "C" int linr_net_forward_train_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
-                                           const uint16_t* occ_bf16, float* probs, double* bits_acc, void* stream) {
+static int tforward_entry(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
+                          float* probs, double* bits_acc, void* stream, bool deep) {
     TCtx c;
-    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
+    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c, deep));
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;
     return tforward(c, probs, bits_acc);
 }
+extern "C" int linr_net_forward_train_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
+                                           const uint16_t* occ_bf16, float* probs, double* bits_acc, void* stream) {
+    return tforward_entry(f, params, arena, arena_bytes, occ_bf16, probs, bits_acc, stream, false);
+}
+extern "C" int linr_net_forward_train_bf16_deep(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
+                                                const uint16_t* occ_bf16, float* probs, double* bits_acc, void* stream) {
+    return tforward_entry(f, params, arena, arena_bytes, occ_bf16, probs, bits_acc, stream, true);
+}
 
-extern "C" int linr_net_backward_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
-                                      const uint16_t* occ_bf16, float gscale, float* grads, void* stream) {
+static int tbackward_entry(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
+                           float gscale, float* grads, void* stream, bool deep) {
     TCtx c;
-    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
+    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c, deep));
     if (!grads) return LINR_EINVAL;
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;
     TRY(tbackward(c, gscale));
     return linr_axpy(c.A.GSUM, c.L.total, grads, 1, stream);
+}
+extern "C" int linr_net_backward_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
+                                      const uint16_t* occ_bf16, float gscale, float* grads, void* stream) {
+    return tbackward_entry(f, params, arena, arena_bytes, occ_bf16, gscale, grads, stream, false);
+}
+extern "C" int linr_net_backward_bf16_deep(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
+                                           const uint16_t* occ_bf16, float gscale, float* grads, void* stream) {
+    return tbackward_entry(f, params, arena, arena_bytes, occ_bf16, gscale, grads, stream, true);
 }
 
 // One overfit iteration (csrc/net.hip: train_step, in this executor's arithmetic): with qparams != NULL every kernel - tpack_k's
@@ -1338,10 +1503,10 @@ extern "C" int linr_net_backward_bf16(const linr_frame* f, const float* params, 
 static int ttrain_step(const linr_frame* f, float* params, float* qparams, int32_t bitdepth, void* arena, size_t arena_bytes,
                        const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
                        const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay, double* bits_acc,
-                       void* stream) {
+                       void* stream, bool deep = false) {
     if (!exp_avg || !exp_avg_sq || !bits_acc || step < 1) return LINR_EINVAL;
     TCtx c;
-    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
+    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c, deep));
     if (qparams) TRY(linr_fake_quant_check(params, c.L.total, bitdepth, qparams, nullptr));
     TRY(linr_scale_steps_check(f, c.L, scale_steps_h));          // before anything is launched
     c.s = (hipStream_t)stream;
@@ -1372,6 +1537,16 @@ extern "C" int linr_net_train_step_bf16_qat(const linr_frame* f, float* params, 
     if (!qparams || qparams == params) return LINR_EINVAL;
     return ttrain_step(f, params, qparams, bitdepth, arena, arena_bytes, occ_bf16, gscale, exp_avg, exp_avg_sq, lr, step, scale_steps_h,
                        beta1, beta2, eps, weight_decay, bits_acc, stream);
+}
+
+// block_layers 1..4 (the frame's); qparams == NULL: the plain step, else the quantisation-aware one
+extern "C" int linr_net_train_step_bf16_deep(const linr_frame* f, float* params, void* arena, size_t arena_bytes,
+                                             const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr,
+                                             int64_t step, const int64_t* scale_steps_h, double beta1, double beta2, double eps,
+                                             double weight_decay, double* bits_acc, float* qparams, int32_t bitdepth, void* stream) {
+    if (qparams && qparams == params) return LINR_EINVAL;
+    return ttrain_step(f, params, qparams, qparams ? bitdepth : 0, arena, arena_bytes, occ_bf16, gscale, exp_avg, exp_avg_sq, lr, step,
+                       scale_steps_h, beta1, beta2, eps, weight_decay, bits_acc, stream, true);
 }
 
 extern "C" int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* in, const int32_t* lo, const uint32_t* mask, int64_t ld,

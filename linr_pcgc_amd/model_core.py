@@ -870,11 +870,15 @@ def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
             raise _lib.LinrError('the bf16 training executor supports block_layers=1 only')
         engine.net_train_step_bf16(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
                                    opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale, **qat)
+    elif model.train_precision == 'bf16-deep':           # the same executor through its *_deep entries: block_layers 1..4
+        engine.net_train_step_bf16(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
+                                   opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale, deep=True,
+                                   **qat)
     elif model.train_precision == 'f32':
         engine.net_train_step(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
                               opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale, **qat)
     else:
-        raise ValueError("train_precision must be 'f32' or 'bf16'")
+        raise ValueError("train_precision must be 'f32', 'bf16' or 'bf16-deep'")
     opt.t, opt.t_scale = t, t_scale              # committed only after the call returned without an error
     opt.scheduler_step()
     return bits

@@ -54,18 +54,22 @@ class Gop:
         for f in self.frames:
             f.arena = arena
 
-    def share_train_bf16_arena(self):
-        """One arena of the bf16 training executor for all frames of the GOP (a step finishes before the next begins)."""
-        if all(getattr(f, 'arena_train_bf16', None) is not None for f in self.frames):
+    def share_train_bf16_arena(self, deep=False):
+        """One arena of the bf16 training executor for all frames of the GOP (a step finishes before the next begins).  deep: the
+        arena of its *_deep entries (block_layers 1..4)."""
+        attr = 'arena_train_bf16_deep' if deep else 'arena_train_bf16'
+        if all(getattr(f, attr, None) is not None for f in self.frames):
             return
         from . import _lib
         rows = max(f.rows for f in self.frames)
-        nbytes = _lib.lib().linr_net_train_bf16_arena_bytes(rows, self.block_layers)
+        size_fn = _lib.lib().linr_net_train_bf16_deep_arena_bytes if deep else _lib.lib().linr_net_train_bf16_arena_bytes
+        nbytes = size_fn(rows, self.block_layers)
         if nbytes == 0:
-            raise _lib.LinrError('the bf16 training executor supports block_layers=1 only')
+            raise _lib.LinrError('the bf16 training executor supports block_layers 1..4 through its deep entries only' if deep else
+                                 "the bf16 training executor supports block_layers=1 only (train_precision 'bf16-deep': 1..4)")
         arena = _lib.scratch(nbytes + 64, self.frames[0].device)
         for f in self.frames:
-            f.arena_train_bf16 = arena
+            setattr(f, attr, arena)
 
     def __len__(self):
         return len(self.frames)
@@ -163,8 +167,8 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
     qat_from = qat_first_epoch(epochs, qat_epochs)
     if qat_epochs and not 2 <= int(qat_bitdepth) <= 16:
         raise ValueError('qat_bitdepth must be in 2..16, got %r' % (qat_bitdepth,))
-    if getattr(model, 'train_precision', 'f32') == 'bf16':
-        gop.share_train_bf16_arena()
+    if getattr(model, 'train_precision', 'f32') in ('bf16', 'bf16-deep'):
+        gop.share_train_bf16_arena(deep=model.train_precision == 'bf16-deep')
     losses = []
     dev = gop.frames[0].device
     bits = torch.zeros(len(gop), dtype=torch.float64, device=dev)         # one slot per frame: no per-step torch kernels

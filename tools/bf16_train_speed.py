@@ -1,7 +1,8 @@
 """ms per training step of the bf16 training executor beside the fp32 one, on frames of a synthetic config, with the live
 per-class kernel timing of the library (linr_prof_*).  Measurement aid (profiles/r05_bf16_*.txt).
 
-  python tools/bf16_train_speed.py [--config loot10] [--frames 4] [--steps 60] [--classes]
+  python tools/bf16_train_speed.py [--config loot10] [--frames 4] [--steps 60] [--classes] [--block-layers 1]
+                                   [--train-precision bf16]          (bf16-deep: the executor's entries for block_layers 1..4)
 """
 import argparse
 import ctypes
@@ -27,18 +28,23 @@ def main():
     ap.add_argument('--frames', type=int, default=4)
     ap.add_argument('--steps', type=int, default=60)
     ap.add_argument('--classes', action='store_true', help='per-class kernel table from fully instrumented extra steps')
+    ap.add_argument('--block-layers', '--block_layers', dest='block_layers', type=int, default=1)
+    ap.add_argument('--train-precision', '--train_precision', dest='train_precision', default='bf16', choices=['bf16', 'bf16-deep'],
+                    help='what runs beside f32')
+    ap.add_argument('--ramp', type=int, default=200, help='steps taken before the timed ones')
     args = ap.parse_args()
     from linr_pcgc_amd import _lib, overfit, synthetic
     from linr_pcgc_amd.model_core import FlatAdam, train_step
     L = _lib.lib()
     clouds = [synthetic.sequence_frame_device(args.config, t, 'cuda') for t in range(args.frames)]
-    gop = overfit.Gop(None, clouds, None, 64, 'cuda')
-    out = {'config': args.config, 'rows': [f.rows for f in gop.frames], 'points': gop.point_nums}
-    for prec in ('f32', 'bf16'):
-        model = overfit.gen_model(gop.scale_num, 'cuda', seed=8807)
+    gop = overfit.Gop(None, clouds, None, 64, 'cuda', block_layers=args.block_layers)
+    out = {'config': args.config, 'rows': [f.rows for f in gop.frames], 'points': gop.point_nums, 'block_layers': args.block_layers,
+           'train_precision': args.train_precision}
+    for prec in ('f32', args.train_precision):
+        model = overfit.gen_model(gop.scale_num, 'cuda', seed=8807, block_layers=args.block_layers)
         model.train_precision = prec
-        if prec == 'bf16':
-            gop.share_train_bf16_arena()
+        if prec != 'f32':
+            gop.share_train_bf16_arena(deep=prec == 'bf16-deep')
         opt = FlatAdam(model)
         bits = torch.zeros(1, dtype=torch.float64, device='cuda')
 
@@ -46,17 +52,19 @@ def main():
             for i in range(n):
                 j = i % len(gop)
                 train_step(model, opt, gop.frames[j], gop.point_nums[j], out=bits)
-        run(200)                                        # clock ramp
+        run(args.ramp)                                  # clock ramp
         torch.cuda.synchronize()
-        best = 1e9
+        best, seen = 1e9, []
         for _ in range(5):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             run(args.steps)
             e1.record()
             torch.cuda.synchronize()
-            best = min(best, e0.elapsed_time(e1) / args.steps)
-        out[prec] = {'ms_per_step': round(best, 4)}
+            seen.append(e0.elapsed_time(e1) / args.steps)
+            best = min(best, seen[-1])
+        out[prec] = {'ms_per_step': round(best, 4), 'ms_per_step_median': round(sorted(seen)[2], 4),
+                     'ms_per_step_spread': round(max(seen) - min(seen), 4)}
         if args.classes:
             L.linr_prof_mask(0xFFFFFFFF)
             L.linr_prof_enable(1)
@@ -77,7 +85,8 @@ def main():
         b = torch.zeros(1, dtype=torch.float64, device='cuda')
         train_step(model, opt, gop.frames[0], gop.point_nums[0], out=b)
         out[prec]['bpp_frame0_now'] = round(float(b) / gop.point_nums[0], 4)
-    out['ratio'] = round(out['bf16']['ms_per_step'] / out['f32']['ms_per_step'], 3)
+    out['ratio'] = round(out[args.train_precision]['ms_per_step'] / out['f32']['ms_per_step'], 3)
+    out['ratio_of_medians'] = round(out[args.train_precision]['ms_per_step_median'] / out['f32']['ms_per_step_median'], 3)
     print(json.dumps(out, indent=1))
 
 
