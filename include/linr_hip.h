@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 24
+#define LINR_ABI_VERSION 25
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -391,23 +391,42 @@ LINR_API int linr_net_forward(const linr_frame* f, const float* params, float* a
 LINR_API int linr_net_backward(const linr_frame* f, const float* params, float* arena, size_t arena_bytes,
                       float gscale, float* grads, void* stream);
 
+/* What one overfit iteration needs beyond frame, parameters, arena and stream: the argument of linr_net_train_step and
+ * linr_net_train_step_bf16 (NULL in its place is LINR_EINVAL).  Device pointers unless marked HOST. */
+typedef struct linr_step_args {
+    float gscale;                   /* the loss is gscale * bits (main.py:314: 1 / point_num) */
+    float* exp_avg;                 /* Adam's first moment, linr_param_count floats, updated */
+    float* exp_avg_sq;              /* Adam's second moment, likewise */
+    double lr;
+    int64_t step;                   /* this update's 1-based count (>= 1) */
+    const int64_t* scale_steps_h;   /* HOST [model_scale_num] update counts of the per-scale context MLPs INCLUDING this one, or NULL */
+    double beta1, beta2, eps, weight_decay;     /* torch.optim.Adam's, L2 weight decay */
+    double* bits_acc;               /* double[1], the step's bits are added into it (caller zeroes) */
+    float* qparams;                 /* NULL: the plain step; else the quantisation-aware step evaluates the network at this fake-quantised
+                                       image of params, which the call writes (linr_param_count floats, 16-byte aligned, not params) */
+    int32_t bitdepth;               /* of the fake quantisation, 2..16; read only when qparams != NULL */
+} linr_step_args;
+
 /* One iteration of main.py:305-321 in a single call: forward (bits added into bits_acc), backward of
  * gscale * bits (gscale = 1/point_num), deterministic gradient reduction and the fused Adam update of `params`
- * (torch.optim.Adam with L2 weight decay; `step` = this update's 1-based count, bias corrections computed in double).
- * scale_steps_h: HOST [model_scale_num] update counts of the per-scale context MLPs INCLUDING this update, or NULL.  With it the
+ * (torch.optim.Adam with L2 weight decay; bias corrections computed in double).
+ * args->scale_steps_h: HOST [model_scale_num] update counts of the per-scale context MLPs INCLUDING this update, or NULL.  With it the
  * update follows torch.optim.Adam (the reference pins torch 1.13.1, enviroment.yaml:30): an MLP whose count is 0 - no frame so far
  * contained its scale (custom_dataset.py:325), its .grad is still None - is skipped entirely; every other MLP is updated with
  * its own step count, with a zero gradient when this frame lacks the scale (optimizer.zero_grad() of main.py:320 leaves zero
  * tensors, so weight decay and moment decay keep acting).  A scale of this frame with count 0 is an error.  NULL updates every
- * parameter with `step`.  Nothing synchronises with the host. */
-LINR_API int linr_net_train_step(const linr_frame* f, float* params, float* arena, size_t arena_bytes, float gscale,
-                        float* exp_avg, float* exp_avg_sq, double lr, int64_t step, const int64_t* scale_steps_h,
-                        double beta1, double beta2, double eps, double weight_decay, double* bits_acc, void* stream);
+ * parameter with `step`.  With args->qparams != NULL the forward and backward run at qparams = fake_quant(params) (see
+ * linr_params_fake_quant below) while Adam - weight decay included - updates the fp32 master `params` with that gradient
+ * (straight-through estimator): bits_acc receives the bits of the weights the codec would code with.  One launch more; the arena
+ * layout is the same.  Every argument check comes before the first launch.  Nothing synchronises with the host. */
+LINR_API int linr_net_train_step(const linr_frame* f, float* params, float* arena, size_t arena_bytes, const linr_step_args* args,
+                        void* stream);
 
 /* ---- quantisation-aware overfit (opt-in) --------------------------------------------------------------------------
  * The codec never codes geometry with the weights it trained: encode_one_gop quantises the flat parameter vector
  * (quant_uniform2, model_compression/model_size_est.py:72-91) and codes every frame with the DE-QUANTISED model
- * (encoder.py:101-103).  These entries let the overfit iteration (main.py:305-321) see that step.
+ * (encoder.py:101-103).  These entries, and linr_step_args.qparams of the training steps, let the overfit iteration
+ * (main.py:305-321) see that step.
  *
  * linr_params_fake_quant: qparams = the de-quantised image of params, bit for bit what quant_uniform2 followed by the decoder's
  *   de-quantisation computes in fp32 on the CPU:  mn = min(params), mx = max(params), r = mx - mn, s = 2^bitdepth - 1,
@@ -429,11 +448,7 @@ LINR_API int linr_net_train_step(const linr_frame* f, float* params, float* aren
  *   code back.  For (lo, hi) = (minimum, maximum) of params row k is bit for bit what linr_params_fake_quant writes.  ONE launch
  *   of K workgroups, no host synchronisation, no atomics; n == 0 launches nothing.  A bad K, stride, bound pair (lo > hi or NaN),
  *   pointer or alignment is refused before the launch.
- * linr_params_fake_quant_ranges_host: the same as a plain loop over HOST pointers (no GPU needed; no alignment asked).
- * linr_net_train_step_qat: linr_net_train_step whose forward and backward run at qparams = fake_quant(params) (written by the
- *   call: a caller-owned device buffer of linr_param_count floats, 16-byte aligned, not params itself) while Adam - weight decay
- *   included - updates the fp32 master `params` with that gradient (straight-through estimator): bits_acc receives the bits of the
- *   weights the codec would code with.  One launch more than linr_net_train_step; the arena layout is the same. */
+ * linr_params_fake_quant_ranges_host: the same as a plain loop over HOST pointers (no GPU needed; no alignment asked). */
 LINR_API int linr_params_fake_quant(const float* params, int64_t n, int32_t bitdepth, float* qparams, uint16_t* codes, float* minmax,
                                     void* stream);
 LINR_API int linr_params_fake_quant_host(const float* params, int64_t n, int32_t bitdepth, float* qparams, uint16_t* codes,
@@ -442,10 +457,6 @@ LINR_API int linr_params_fake_quant_ranges(const float* params, int64_t n, int32
                                            int64_t stride, float* qparams, uint16_t* codes, int64_t* stats, void* stream);
 LINR_API int linr_params_fake_quant_ranges_host(const float* params, int64_t n, int32_t bitdepth, const float* ranges_h, int32_t K,
                                                 int64_t stride, float* qparams, uint16_t* codes, int64_t* stats);
-LINR_API int linr_net_train_step_qat(const linr_frame* f, float* params, float* arena, size_t arena_bytes, float gscale,
-                            float* exp_avg, float* exp_avg_sq, double lr, int64_t step, const int64_t* scale_steps_h,
-                            double beta1, double beta2, double eps, double weight_decay, double* bits_acc, float* qparams,
-                            int32_t bitdepth, void* stream);
 
 /* ---- bf16 / uint8-weight inference executor (BASELINE config[4]) ------------------------------------------------
  * The codec codes the geometry with the DE-QUANTISED model (encoder.py:101-103, decoder.py:87): w = q/255*(max-min)+min
@@ -505,15 +516,21 @@ LINR_API int linr_sce_fwd_bf16(const float* pf, const linr_frame* f, uint16_t* x
  * accumulation.  ONE rounding rule: every matrix written to memory is rounded to bf16 (RNE) and every consumer sees the stored
  * value; the 3x3x3 kernels are rounded to bf16 inside the kernels; biases, 1x1 convolutions, scale-context and head MLPs, sigmoid
  * and the bits are fp32 (bits accumulate in double).  oracle/network_bf16.py emulates these roundings with autograd; tolerances
- * are in tests/test_gpu_bf16_train.py.  block_layers 1 (deeper: the *_deep entries below) and the compressed kernel map only.
- * arena: linr_net_train_bf16_arena_bytes(rows, 1) bytes, 64-byte aligned, shared by the calls of one step.
+ * are in tests/test_gpu_bf16_train.py.  The compressed kernel map only.
+ * block_layers 1..4 of block_in (--block_layers, main.py:521; models/resnet.py:146-162): the depth is f->block_layers.  The extra
+ * Inception layers run the same kernels one group at a time; the ResNetBlock's extra skip is ONE stored matrix S = bf16(I_last + A),
+ * and the gradient arriving at every layer's input is rounded once, after its three contributions were summed in fp32 (the rule
+ * above; tests/bf16_train_deep_ref.py emulates it with autograd, tolerances in tests/test_gpu_bf16_train_deep.py).
+ * arena: linr_net_train_bf16_arena_bytes(rows, block_layers) bytes (0 for rows < 0 or a depth outside 1..4), 64-byte aligned,
+ * shared by the calls of one step.
  * occ_bf16: NULL, or the frame's occupancy converted once by linr_occ_to_bf16 ([1 + rows][8] bf16, zero row in front; the
  * pointer passed is that of the ZERO row) - a frame's occupancy does not change over the epochs.
  * linr_net_forward_train_bf16: teacher-forced forward of all 8 stages, every activation the backward needs kept in the arena;
  *   probs [8][rows] stage-major or NULL; bits_acc double[1] (accumulated into) or NULL.
  * linr_net_backward_bf16: gradient of gscale * bits, ADDED into grads (fp32, linr_param_count floats); needs the forward above on
  *   the same arena.
- * linr_net_train_step_bf16: forward + backward + fixed-order reduction + Adam, arguments as linr_net_train_step. */
+ * linr_net_train_step_bf16: forward + backward + fixed-order reduction + Adam, `args` as linr_net_train_step; with args->qparams
+ *   every kernel of the step, the weight images rounded to bf16 included, reads qparams, and Adam updates `params`. */
 LINR_API size_t linr_net_train_bf16_arena_bytes(int64_t rows, int32_t block_layers);
 LINR_API int linr_occ_to_bf16(const float* occ, int64_t rows, uint16_t* out_padded, void* stream);
 LINR_API int linr_net_forward_train_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
@@ -521,32 +538,7 @@ LINR_API int linr_net_forward_train_bf16(const linr_frame* f, const float* param
 LINR_API int linr_net_backward_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
                            const uint16_t* occ_bf16, float gscale, float* grads, void* stream);
 LINR_API int linr_net_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
-                             float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
-                             const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay,
-                             double* bits_acc, void* stream);
-/* linr_net_train_step_bf16 at the fake-quantised weights (see linr_net_train_step_qat; model_size_est.py:72-91, encoder.py:101-103,
- * main.py:305-321): every kernel of the step, the weight images rounded to bf16 included, reads qparams; Adam updates `params`. */
-LINR_API int linr_net_train_step_bf16_qat(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
-                                 float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
-                                 const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay,
-                                 double* bits_acc, float* qparams, int32_t bitdepth, void* stream);
-/* The same executor for block_layers 1..4 of block_in (--block_layers, main.py:521; models/resnet.py:146-162), opt-in beside the
- * entries above, which keep refusing more than one layer.  The depth is f->block_layers.  The extra Inception layers run the
- * same kernels one group at a time; the ResNetBlock's extra skip is ONE stored matrix S = bf16(I_last + A), and the gradient
- * arriving at every layer's input is rounded once, after its three contributions were summed in fp32 (the rule above;
- * tests/bf16_train_deep_ref.py emulates it with autograd, tolerances in tests/test_gpu_bf16_train_deep.py).  Same argument checks,
- * in front of the first launch.  At block_layers 1: the launches, the arena and the results of the entries above, bit for bit.
- * linr_net_train_bf16_deep_arena_bytes: 0 outside block_layers 1..4 or for rows < 0; at 1 linr_net_train_bf16_arena_bytes(rows, 1).
- * linr_net_train_step_bf16_deep: qparams == NULL: the plain step (bitdepth ignored), else linr_net_train_step_bf16_qat's. */
-LINR_API size_t linr_net_train_bf16_deep_arena_bytes(int64_t rows, int32_t block_layers);
-LINR_API int linr_net_forward_train_bf16_deep(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
-                                     const uint16_t* occ_bf16, float* probs, double* bits_acc, void* stream);
-LINR_API int linr_net_backward_bf16_deep(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
-                                const uint16_t* occ_bf16, float gscale, float* grads, void* stream);
-LINR_API int linr_net_train_step_bf16_deep(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
-                                  float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
-                                  const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay,
-                                  double* bits_acc, float* qparams, int32_t bitdepth, void* stream);
+                             const linr_step_args* args, void* stream);
 /* The backward of ONE convolution 8->8 of that executor as a stand-alone op (ME.MinkowskiConvolution's backward, models/resnet.py:15-51
  * under autograd): gin = bwd-data(gout; W) rounded to bf16 AND the kernel / bias gradient from one gather of gout.  gout / in / gin:
  * bf16 [n][8] whose row -1 exists (gout's must be zero); W fp32 [27][8][8] (rounded to bf16 in-kernel for backward-data);

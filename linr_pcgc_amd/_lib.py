@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('LINR_HIP_LIB') or os.path.join(_HERE, 'liblinr_hip.so
 LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 16
 LINR_FRAME_OCC_PADDED = 1
 LINR_PLY_TOKEN, LINR_PLY_COLUMNS, LINR_PLY_SHORT, LINR_PLY_RANGE = 1, 2, 4, 8
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -56,6 +56,13 @@ class LinrRcStream(ctypes.Structure):
 class LinrDecodeOpts(ctypes.Structure):
     """struct linr_decode_opts (include/linr_hip.h): the options of a decoder scale; NULL in its place means (0, 1, 0)."""
     _fields_ = [('chunk_symbols', c_i64), ('n_threads', c_i32), ('device', c_i32)]
+
+
+class LinrStepArgs(ctypes.Structure):
+    """struct linr_step_args (include/linr_hip.h): what one overfit iteration takes beyond frame, parameters, arena and stream."""
+    _fields_ = [('gscale', c_f32), ('exp_avg', c_ptr), ('exp_avg_sq', c_ptr), ('lr', c_f64), ('step', c_i64), ('scale_steps_h', c_ptr),
+                ('beta1', c_f64), ('beta2', c_f64), ('eps', c_f64), ('weight_decay', c_f64), ('bits_acc', c_ptr), ('qparams', c_ptr),
+                ('bitdepth', c_i32)]
 
 
 _PROTOS = {
@@ -137,8 +144,7 @@ _PROTOS = {
     'linr_net_forward': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_i32, c_i32, c_ptr, c_ptr,
                                         c_ptr]),
     'linr_net_backward': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_f32, c_ptr, c_ptr]),
-    'linr_net_train_step': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_f32, c_ptr, c_ptr, c_f64,
-                                           c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr]),
+    'linr_net_train_step': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, ctypes.POINTER(LinrStepArgs), c_ptr]),
     'linr_net_bf16_arena_bytes': (c_size, [c_i64, c_i32]),
     'linr_net_forward_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_f32, c_f32, c_ptr, c_size, c_i32, c_i32, c_ptr,
                                              c_ptr, c_ptr]),
@@ -153,8 +159,8 @@ _PROTOS = {
     'linr_occ_to_bf16': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
     'linr_net_forward_train_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr]),
     'linr_net_backward_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr]),
-    'linr_net_train_step_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr, c_f64,
-                                                c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr]),
+    'linr_net_train_step_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, ctypes.POINTER(LinrStepArgs),
+                                                c_ptr]),
     'linr_spconv_bwd_fused_bf16': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_ptr]),
     'linr_sce_fwd': (ctypes.c_int, [c_ptr, ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_ptr, c_ptr]),
     'linr_sce_bwd': (ctypes.c_int, [c_ptr, ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_ptr, c_ptr]),
@@ -215,16 +221,6 @@ _PROTOS = {
     'linr_params_fake_quant_host': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
     'linr_params_fake_quant_ranges': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     'linr_params_fake_quant_ranges_host': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_ptr]),
-    'linr_net_train_step_qat': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_f32, c_ptr, c_ptr, c_f64,
-                                               c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr, c_i32, c_ptr]),
-    'linr_net_train_step_bf16_qat': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr, c_f64,
-                                                    c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr, c_i32, c_ptr]),
-    # the bf16 training executor at block_layers 1..4 (ABI 24)
-    'linr_net_train_bf16_deep_arena_bytes': (c_size, [c_i64, c_i32]),
-    'linr_net_forward_train_bf16_deep': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr]),
-    'linr_net_backward_bf16_deep': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr]),
-    'linr_net_train_step_bf16_deep': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_f32, c_ptr, c_ptr, c_f64,
-                                                     c_i64, c_ptr, c_f64, c_f64, c_f64, c_f64, c_ptr, c_ptr, c_i32, c_ptr]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -23,5 +23,4 @@ int linr_bwd_tail_launch(const linr_frame* f, const Layout& L, const float* P, c
 __attribute__((visibility("hidden")))
 int linr_slab_reduce_launch(const float* big, int nblocks, int64_t total, float* gsum, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_adam_step_launch(const Layout& L, float* params, const float* gsum, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
-                          const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay, hipStream_t s);
+int linr_adam_step_launch(const Layout& L, float* params, const float* gsum, const linr_step_args& a, hipStream_t s);

@@ -466,8 +466,8 @@ int linr_bwd_tail_launch(const linr_frame* f, const Layout& L, const float* P, c
 
 // torch.optim.Adam's step over the flat parameter buffer with the per-scale step counters of the scale-context MLPs (shared with
 // csrc/train_bf16.hip): bias corrections in double, like torch.optim.Adam's Python scalars
-int linr_adam_step_launch(const Layout& L, float* params, const float* gsum, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
-                          const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay, hipStream_t s) {
+int linr_adam_step_launch(const Layout& L, float* params, const float* gsum, const linr_step_args& a, hipStream_t s) {
+    const int64_t* scale_steps_h = a.scale_steps_h;
     LinrAdamRanges rg;
     rg.count = 0; rg.begin = L.m0_w[0]; rg.len = L.S > 1 ? L.m0_w[1] - L.m0_w[0] : L.block_in.a_w - L.m0_w[0];
     if (scale_steps_h) {
@@ -478,11 +478,11 @@ int linr_adam_step_launch(const Layout& L, float* params, const float* gsum, flo
         for (int sc = 0; sc < L.S; ++sc) {
             const int64_t t = scale_steps_h[sc];
             rg.active[sc] = t >= 1 ? 1 : 0;
-            rg.step_size[sc] = t >= 1 ? (float)(lr / (1.0 - pow(beta1, (double)t))) : 0.0f;
-            rg.bc2_sqrt[sc] = t >= 1 ? (float)sqrt(1.0 - pow(beta2, (double)t)) : 1.0f;
+            rg.step_size[sc] = t >= 1 ? (float)(a.lr / (1.0 - pow(a.beta1, (double)t))) : 0.0f;
+            rg.bc2_sqrt[sc] = t >= 1 ? (float)sqrt(1.0 - pow(a.beta2, (double)t)) : 1.0f;
         }
     }
-    return linr_adam_launch(params, gsum, exp_avg, exp_avg_sq, L.total, lr / (1.0 - pow(beta1, (double)step)),
-                            sqrt(1.0 - pow(beta2, (double)step)), beta1, beta2, eps, weight_decay,
+    return linr_adam_launch(params, gsum, a.exp_avg, a.exp_avg_sq, L.total, a.lr / (1.0 - pow(a.beta1, (double)a.step)),
+                            sqrt(1.0 - pow(a.beta2, (double)a.step)), a.beta1, a.beta2, a.eps, a.weight_decay,
                             scale_steps_h ? &rg : nullptr, s);
 }

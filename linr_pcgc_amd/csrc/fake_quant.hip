@@ -1,6 +1,6 @@
 // The model codec's weight quantiser on the device: qparams = dequant(quant_uniform2(params)) (model_compression/model_size_est.py:
 // 72-91, encoder.py:101-103), bit for bit what the CPU codec computes in fp32 (csrc/fake_quant.h holds the arithmetic).  The
-// quantisation-aware train steps (linr_net_train_step_qat, linr_net_train_step_bf16_qat) evaluate the network at its output.
+// quantisation-aware train steps (linr_net_train_step, linr_net_train_step_bf16 with linr_step_args.qparams) evaluate the network at its output.
 //
 // ONE launch of ONE workgroup of 1024 lanes: the global minimum and maximum stand between reading a parameter and quantising it, and
 // a grid-wide reduction would cost a second launch or float atomics.  The parameter vector is small (54,712 floats = 214 KB at

@@ -593,44 +593,26 @@ extern "C" int linr_net_backward(const linr_frame* f, const float* params, float
 }
 
 // One overfit iteration.  `weights` is what the network is evaluated at and differentiated at: the fp32 master `params` itself, or
-// with qparams != NULL its fake-quantised image (written here, csrc/fake_quant.hip) - the gradient then passes straight through to
-// the master, which Adam (weight decay included) updates either way.
-static int train_step(const linr_frame* f, float* params, float* qparams, int32_t bitdepth, float* arena, size_t arena_bytes,
-                      float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step, const int64_t* scale_steps_h,
-                      double beta1, double beta2, double eps, double weight_decay, double* bits_acc, void* stream) {
-    if (!exp_avg || !exp_avg_sq || !bits_acc || step < 1) return LINR_EINVAL;
+// with a->qparams != NULL its fake-quantised image (written here, csrc/fake_quant.hip) - the gradient then passes straight through
+// to the master, which Adam (weight decay included) updates either way.
+extern "C" int linr_net_train_step(const linr_frame* f, float* params, float* arena, size_t arena_bytes, const linr_step_args* a,
+                                   void* stream) {
+    if (!a || !a->exp_avg || !a->exp_avg_sq || !a->bits_acc || a->step < 1 || (a->qparams && a->qparams == params)) return LINR_EINVAL;
     Ctx c;
     TRY(check_frame(f, params, arena, arena_bytes, c));
-    if (qparams) TRY(linr_fake_quant_check(params, c.L.total, bitdepth, qparams, nullptr));
-    TRY(linr_scale_steps_check(f, c.L, scale_steps_h));          // before anything is launched
+    if (a->qparams) TRY(linr_fake_quant_check(params, c.L.total, a->bitdepth, a->qparams, nullptr));
+    TRY(linr_scale_steps_check(f, c.L, a->scale_steps_h));       // before anything is launched
     c.s = (hipStream_t)stream;
     const float* weights = params;
-    if (qparams) {
+    if (a->qparams) {
         ProfScope ps(c.s, PK_MISC, 0);
-        TRY(linr_fake_quant_launch(params, c.L.total, bitdepth, qparams, nullptr, nullptr, c.s));
-        weights = qparams;
+        TRY(linr_fake_quant_launch(params, c.L.total, a->bitdepth, a->qparams, nullptr, nullptr, c.s));
+        weights = a->qparams;
     }
-    TRY(linr_net_forward(f, weights, arena, arena_bytes, 0, 8, nullptr, bits_acc, stream));
+    TRY(linr_net_forward(f, weights, arena, arena_bytes, 0, 8, nullptr, a->bits_acc, stream));
     if (c.R == 0) return 0;
     c.P = weights;
-    TRY(backward_core(c, gscale));
+    TRY(backward_core(c, a->gscale));
     ProfScope ps(c.s, PK_MISC, 0);
-    return linr_adam_step_launch(c.L, params, c.A.GSUM, exp_avg, exp_avg_sq, lr, step, scale_steps_h, beta1, beta2, eps, weight_decay, c.s);
-}
-
-extern "C" int linr_net_train_step(const linr_frame* f, float* params, float* arena, size_t arena_bytes, float gscale,
-                                   float* exp_avg, float* exp_avg_sq, double lr, int64_t step, const int64_t* scale_steps_h,
-                                   double beta1, double beta2, double eps, double weight_decay, double* bits_acc,
-                                   void* stream) {
-    return train_step(f, params, nullptr, 0, arena, arena_bytes, gscale, exp_avg, exp_avg_sq, lr, step, scale_steps_h, beta1, beta2, eps,
-                      weight_decay, bits_acc, stream);
-}
-
-extern "C" int linr_net_train_step_qat(const linr_frame* f, float* params, float* arena, size_t arena_bytes, float gscale,
-                                       float* exp_avg, float* exp_avg_sq, double lr, int64_t step, const int64_t* scale_steps_h,
-                                       double beta1, double beta2, double eps, double weight_decay, double* bits_acc,
-                                       float* qparams, int32_t bitdepth, void* stream) {
-    if (!qparams || qparams == params) return LINR_EINVAL;
-    return train_step(f, params, qparams, bitdepth, arena, arena_bytes, gscale, exp_avg, exp_avg_sq, lr, step, scale_steps_h, beta1,
-                      beta2, eps, weight_decay, bits_acc, stream);
+    return linr_adam_step_launch(c.L, params, c.A.GSUM, *a, c.s);
 }

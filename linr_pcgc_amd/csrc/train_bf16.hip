@@ -35,9 +35,8 @@
 //              operands; 22 us against 31 for the 4x4x4 form bocc7_k, kept behind LINR_BOCC7_MFMA16=0).
 //   per step   tpack_k rounds every 3x3x3 kernel once into the operand images the kernels above load (wimg).
 //
-// block_layers 2..4 of block_in (main.py:521; models/resnet.py:146-162), through the *_deep entries only - the others refuse more than
-// one layer, and at one layer the *_deep entries run exactly their launches.  Only block_in has more than one Inception layer
-// (layout.h), and the extra layers are the same three convolutions:
+// block_layers 2..4 of block_in (main.py:521; models/resnet.py:146-162): the frame's depth.  Only block_in has more than one Inception
+// layer (layout.h), and the extra layers are the same three convolutions:
 //   forward    layer l >= 1 reads X = the stored I_{l-1}: single-group launches of bconv_k<2> / bconv_k<3> from eight more images of
 //              tpack_k per layer; then S = bf16(I_last + A) (tadd_rows_k: csrc/net_bf16.hip: badd_rows_k's rounding) over I_last, which
 //              nothing else reads; the tail convolution and its weight gradient read S.
@@ -1133,8 +1132,8 @@ static bf16_t* tmat(TArena& a, int w = 8) {          // [1 + rows][w] with the z
 }
 
 static_assert(99 + 6 * (MAX_BL - 1) <= BPADS_MAX, "tpack_k clears one pad row per entry of BPads");
-// nl = block_layers of block_in: at 1 the arena of the parent executor, byte for byte
-static void make_tarena(TArena& a, int64_t rows, char* base, int64_t n_params, bool own_occ, int nl = 1) {
+// nl = block_layers of block_in
+static void make_tarena(TArena& a, int64_t rows, char* base, int64_t n_params, bool own_occ, int nl) {
     a.rows = rows; a.base = base; a.cur = 0; a.pads.n = 0; a.n_params = n_params; a.over = false;
     a.gX0 = (float*)tbytes(a, rows * 8 * 4);
     a.PR = (float*)tbytes(a, rows * 8 * 4);
@@ -1157,16 +1156,6 @@ static void make_tarena(TArena& a, int64_t rows, char* base, int64_t n_params, b
 }
 
 extern "C" size_t linr_net_train_bf16_arena_bytes(int64_t rows, int32_t block_layers) {
-    if (rows < 0 || block_layers > 1) return 0;                  // block_layers 1 only (every BASELINE config)
-    Layout L;
-    make_layout(L, MAX_SCALES, 1);
-    TArena a;
-    make_tarena(a, rows, nullptr, L.total, true);
-    return (size_t)a.cur + 64;
-}
-
-// the same executor at block_layers 1..4 of block_in (the *_deep entries below); at 1 the figure above
-extern "C" size_t linr_net_train_bf16_deep_arena_bytes(int64_t rows, int32_t block_layers) {
     if (rows < 0 || block_layers < 1 || block_layers > MAX_BL) return 0;
     Layout L;
     make_layout(L, MAX_SCALES, block_layers);
@@ -1203,15 +1192,13 @@ struct TCtx : LinrShortList {
     int64_t R;
 };
 
-// deep: the *_deep entries - block_in at the frame's block_layers (1..4); the other entries refuse more than one layer
-static int tcheck(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16, TCtx& c,
-                  bool deep = false) {
+// block_in at the frame's block_layers (1..4)
+static int tcheck(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16, TCtx& c) {
     if (!params || !arena) return LINR_EINVAL;
-    TRY(linr_frame_layout(f, deep ? 0 : 1, c.L));
-    if (!deep && f->block_layers > 1) return LINR_EINVAL;       // block_layers 1 only
+    TRY(linr_frame_layout(f, 0, c.L));
     if (f->rows > 0 && (!f->nbr_lo || !f->nbr_mask || !f->offset_feat || !f->occ || f->nbr_ld < f->rows)) return LINR_EINVAL;   // compressed map only
     if (!linr_rows_fit32(f->rows)) return LINR_EINVAL;
-    if (arena_bytes < linr_net_train_bf16_deep_arena_bytes(f->rows, c.L.BL)) return LINR_ENOSPC;      // (BL 1: linr_net_train_bf16_arena_bytes)
+    if (arena_bytes < linr_net_train_bf16_arena_bytes(f->rows, c.L.BL)) return LINR_ENOSPC;
     if (((uintptr_t)arena) & 63u) return LINR_EALIGN;
     if (occ_bf16 && (((uintptr_t)occ_bf16) & 15u)) return LINR_EALIGN;
     c.f = f; c.P = params; c.R = f->rows;
@@ -1462,91 +1449,46 @@ static int tbackward(TCtx& c, float gscale) {
 }
 
 // ---- C-ABI ----------------------------------------------------------------------------------------------------------------------------
-static int tforward_entry(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
-                          float* probs, double* bits_acc, void* stream, bool deep) {
+extern "C" int linr_net_forward_train_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
+                                           const uint16_t* occ_bf16, float* probs, double* bits_acc, void* stream) {
     TCtx c;
-    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c, deep));
+    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;
     return tforward(c, probs, bits_acc);
 }
-extern "C" int linr_net_forward_train_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
-                                           const uint16_t* occ_bf16, float* probs, double* bits_acc, void* stream) {
-    return tforward_entry(f, params, arena, arena_bytes, occ_bf16, probs, bits_acc, stream, false);
-}
-extern "C" int linr_net_forward_train_bf16_deep(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
-                                                const uint16_t* occ_bf16, float* probs, double* bits_acc, void* stream) {
-    return tforward_entry(f, params, arena, arena_bytes, occ_bf16, probs, bits_acc, stream, true);
-}
 
-static int tbackward_entry(const linr_frame* f, const float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
-                           float gscale, float* grads, void* stream, bool deep) {
+extern "C" int linr_net_backward_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
+                                      const uint16_t* occ_bf16, float gscale, float* grads, void* stream) {
     TCtx c;
-    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c, deep));
+    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
     if (!grads) return LINR_EINVAL;
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;
     TRY(tbackward(c, gscale));
     return linr_axpy(c.A.GSUM, c.L.total, grads, 1, stream);
 }
-extern "C" int linr_net_backward_bf16(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
-                                      const uint16_t* occ_bf16, float gscale, float* grads, void* stream) {
-    return tbackward_entry(f, params, arena, arena_bytes, occ_bf16, gscale, grads, stream, false);
-}
-extern "C" int linr_net_backward_bf16_deep(const linr_frame* f, const float* params, void* arena, size_t arena_bytes,
-                                           const uint16_t* occ_bf16, float gscale, float* grads, void* stream) {
-    return tbackward_entry(f, params, arena, arena_bytes, occ_bf16, gscale, grads, stream, true);
-}
 
-// One overfit iteration (csrc/net.hip: train_step, in this executor's arithmetic): with qparams != NULL every kernel - tpack_k's
-// weight images included - reads the fake-quantised image of the fp32 master, and Adam updates the master.
-static int ttrain_step(const linr_frame* f, float* params, float* qparams, int32_t bitdepth, void* arena, size_t arena_bytes,
-                       const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr, int64_t step,
-                       const int64_t* scale_steps_h, double beta1, double beta2, double eps, double weight_decay, double* bits_acc,
-                       void* stream, bool deep = false) {
-    if (!exp_avg || !exp_avg_sq || !bits_acc || step < 1) return LINR_EINVAL;
+// One overfit iteration (csrc/net.hip: linr_net_train_step, in this executor's arithmetic): with a->qparams != NULL every kernel -
+// tpack_k's weight images included - reads the fake-quantised image of the fp32 master, and Adam updates the master.
+extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
+                                        const linr_step_args* a, void* stream) {
+    if (!a || !a->exp_avg || !a->exp_avg_sq || !a->bits_acc || a->step < 1 || (a->qparams && a->qparams == params)) return LINR_EINVAL;
     TCtx c;
-    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c, deep));
-    if (qparams) TRY(linr_fake_quant_check(params, c.L.total, bitdepth, qparams, nullptr));
-    TRY(linr_scale_steps_check(f, c.L, scale_steps_h));          // before anything is launched
+    TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
+    if (a->qparams) TRY(linr_fake_quant_check(params, c.L.total, a->bitdepth, a->qparams, nullptr));
+    TRY(linr_scale_steps_check(f, c.L, a->scale_steps_h));       // before anything is launched
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;
-    if (qparams) {
+    if (a->qparams) {
         ProfScope ps(c.s, TK_MISC, 0);
-        TRY(linr_fake_quant_launch(params, c.L.total, bitdepth, qparams, nullptr, nullptr, c.s));
-        c.P = qparams;
+        TRY(linr_fake_quant_launch(params, c.L.total, a->bitdepth, a->qparams, nullptr, nullptr, c.s));
+        c.P = a->qparams;
     }
-    TRY(tforward(c, nullptr, bits_acc));
-    TRY(tbackward(c, gscale));
+    TRY(tforward(c, nullptr, a->bits_acc));
+    TRY(tbackward(c, a->gscale));
     ProfScope ps(c.s, TK_MISC, 0);
-    return linr_adam_step_launch(c.L, params, c.A.GSUM, exp_avg, exp_avg_sq, lr, step, scale_steps_h, beta1, beta2, eps, weight_decay, c.s);
-}
-
-extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes,
-                                        const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr,
-                                        int64_t step, const int64_t* scale_steps_h, double beta1, double beta2, double eps,
-                                        double weight_decay, double* bits_acc, void* stream) {
-    return ttrain_step(f, params, nullptr, 0, arena, arena_bytes, occ_bf16, gscale, exp_avg, exp_avg_sq, lr, step, scale_steps_h, beta1,
-                       beta2, eps, weight_decay, bits_acc, stream);
-}
-
-extern "C" int linr_net_train_step_bf16_qat(const linr_frame* f, float* params, void* arena, size_t arena_bytes,
-                                            const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr,
-                                            int64_t step, const int64_t* scale_steps_h, double beta1, double beta2, double eps,
-                                            double weight_decay, double* bits_acc, float* qparams, int32_t bitdepth, void* stream) {
-    if (!qparams || qparams == params) return LINR_EINVAL;
-    return ttrain_step(f, params, qparams, bitdepth, arena, arena_bytes, occ_bf16, gscale, exp_avg, exp_avg_sq, lr, step, scale_steps_h,
-                       beta1, beta2, eps, weight_decay, bits_acc, stream);
-}
-
-// block_layers 1..4 (the frame's); qparams == NULL: the plain step, else the quantisation-aware one
-extern "C" int linr_net_train_step_bf16_deep(const linr_frame* f, float* params, void* arena, size_t arena_bytes,
-                                             const uint16_t* occ_bf16, float gscale, float* exp_avg, float* exp_avg_sq, double lr,
-                                             int64_t step, const int64_t* scale_steps_h, double beta1, double beta2, double eps,
-                                             double weight_decay, double* bits_acc, float* qparams, int32_t bitdepth, void* stream) {
-    if (qparams && qparams == params) return LINR_EINVAL;
-    return ttrain_step(f, params, qparams, qparams ? bitdepth : 0, arena, arena_bytes, occ_bf16, gscale, exp_avg, exp_avg_sq, lr, step,
-                       scale_steps_h, beta1, beta2, eps, weight_decay, bits_acc, stream, true);
+    return linr_adam_step_launch(c.L, params, c.A.GSUM, *a, c.s);
 }
 
 extern "C" int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* in, const int32_t* lo, const uint32_t* mask, int64_t ld,

@@ -135,17 +135,16 @@ class Frame:
 
     def train_bf16_arena(self, deep=False):
         """Arena of the bf16 training executor (linr_net_train_step_bf16): the GOP's shared one when a Gop set it, else this frame's
-        own (allocated on first use).  Returns (64-byte aligned base address, usable bytes).  deep: the arena of the *_deep entries
-        (block_layers 1..4; kept as arena_train_bf16_deep - at block_layers 1 the two have the same size)."""
-        attr = 'arena_train_bf16_deep' if deep else 'arena_train_bf16'
-        if getattr(self, attr, None) is None:
-            size_fn = _lib.lib().linr_net_train_bf16_deep_arena_bytes if deep else _lib.lib().linr_net_train_bf16_arena_bytes
-            nbytes = size_fn(self.rows, self.block_layers)
+        own (allocated on first use).  Returns (64-byte aligned base address, usable bytes).  deep: the caller accepts block_layers
+        2..4 (train_precision 'bf16-deep'); without it a deeper frame is refused here, before any library call."""
+        if self.block_layers > 1 and not deep:
+            raise _lib.LinrError("the bf16 training executor supports block_layers=1 only (train_precision 'bf16-deep': 1..4)")
+        if getattr(self, 'arena_train_bf16', None) is None:
+            nbytes = _lib.lib().linr_net_train_bf16_arena_bytes(self.rows, self.block_layers)
             if nbytes == 0:
-                raise _lib.LinrError('the bf16 training executor supports block_layers 1..4 through its deep entries only' if deep else
-                                     "the bf16 training executor supports block_layers=1 only (train_precision 'bf16-deep': 1..4)")
-            setattr(self, attr, _lib.scratch(nbytes + 64, self.device))
-        a = getattr(self, attr)
+                raise _lib.LinrError('the bf16 training executor supports block_layers 1..4 through its deep entries only')
+            self.arena_train_bf16 = _lib.scratch(nbytes + 64, self.device)
+        a = self.arena_train_bf16
         base = (a.data_ptr() + 63) & ~63
         return base, a.numel() - (base - a.data_ptr())
 
@@ -259,66 +258,49 @@ def params_fake_quant_ranges(flat, ranges, bitdepth=8, codes=True):
     return q, c, st
 
 
+def _step_args(exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits, scale_steps, qparams, bitdepth):
+    """The linr_step_args of one training step, by field name."""
+    return _lib.LinrStepArgs(gscale=float(gscale), exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), lr=float(lr),
+                             step=int(step), scale_steps_h=None if scale_steps is None else scale_steps.ctypes.data, beta1=beta1,
+                             beta2=beta2, eps=eps, weight_decay=weight_decay, bits_acc=bits.data_ptr(),
+                             qparams=None if qparams is None else qparams.data_ptr(), bitdepth=int(bitdepth))
+
+
 def net_train_step(frame, flat_params, exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits,
                    arena=None, scale_steps=None, qparams=None, bitdepth=8):
     """linr_net_train_step: forward + backward + deterministic gradient reduction + fused Adam in one call.
     scale_steps: int64 numpy array [model_scale_num] of the per-scale context MLPs' 1-based step counts (torch.optim.Adam
     semantics for scales a frame does not contain), or None = every parameter uses `step`.
-    qparams (a float32 device buffer like flat_params): the quantisation-aware step linr_net_train_step_qat - the network is
-    evaluated at the `bitdepth`-bit fake-quantised weights, written into qparams, and Adam updates flat_params."""
+    qparams (a float32 device buffer like flat_params): the quantisation-aware step - the network is evaluated at the
+    `bitdepth`-bit fake-quantised weights, written into qparams, and Adam updates flat_params."""
     arena = frame.arena if arena is None else arena
-    steps = None if scale_steps is None else scale_steps.ctypes.data
-    if qparams is not None:
-        check(_lib.lib().linr_net_train_step_qat(frame.cref(), flat_params.data_ptr(), arena.data_ptr(), arena.numel(),
-                                                 float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step), steps,
-                                                 beta1, beta2, eps, weight_decay, bits.data_ptr(), qparams.data_ptr(), int(bitdepth),
-                                                 _stream()), 'linr_net_train_step_qat')
-        return
-    check(_lib.lib().linr_net_train_step(frame.cref(), flat_params.data_ptr(), arena.data_ptr(), arena.numel(),
-                                         float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step), steps,
-                                         beta1, beta2, eps, weight_decay, bits.data_ptr(), _stream()),
-          'linr_net_train_step')
+    args = _step_args(exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits, scale_steps, qparams, bitdepth)
+    check(_lib.lib().linr_net_train_step(frame.cref(), flat_params.data_ptr(), arena.data_ptr(), arena.numel(), ctypes.byref(args),
+                                         _stream()), 'linr_net_train_step')
 
 
 def net_forward_train_bf16(frame, flat_params, probs=None, bits=None, deep=False):
     """linr_net_forward_train_bf16: the teacher-forced forward of the bf16 training executor (activations kept in its arena).
-    deep: linr_net_forward_train_bf16_deep - block_layers 1..4 (the frame's)."""
+    deep: accept block_layers 2..4 (Frame.train_bf16_arena)."""
     base, nbytes = frame.train_bf16_arena(deep)
-    name = 'linr_net_forward_train_bf16_deep' if deep else 'linr_net_forward_train_bf16'
-    check(getattr(_lib.lib(), name)(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(),
-                                    0 if probs is None else probs.data_ptr(), 0 if bits is None else bits.data_ptr(), _stream()), name)
+    check(_lib.lib().linr_net_forward_train_bf16(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(),
+                                                 0 if probs is None else probs.data_ptr(), 0 if bits is None else bits.data_ptr(),
+                                                 _stream()), 'linr_net_forward_train_bf16')
 
 
 def net_backward_bf16(frame, flat_params, flat_grads, gscale, deep=False):
-    """flat_grads += gscale * d bits / d params through the bf16 training executor (needs net_forward_train_bf16 before it, with
-    the same `deep`)."""
+    """flat_grads += gscale * d bits / d params through the bf16 training executor (needs net_forward_train_bf16 before it).
+    deep: as there."""
     base, nbytes = frame.train_bf16_arena(deep)
-    name = 'linr_net_backward_bf16_deep' if deep else 'linr_net_backward_bf16'
-    check(getattr(_lib.lib(), name)(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(), float(gscale),
-                                    flat_grads.data_ptr(), _stream()), name)
+    check(_lib.lib().linr_net_backward_bf16(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(), float(gscale),
+                                            flat_grads.data_ptr(), _stream()), 'linr_net_backward_bf16')
 
 
 def net_train_step_bf16(frame, flat_params, exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits,
                         scale_steps=None, qparams=None, bitdepth=8, deep=False):
-    """linr_net_train_step_bf16: net_train_step with bf16 feature / gradient rows, fp32 master parameters and accumulation; with
-    qparams linr_net_train_step_bf16_qat (see net_train_step).  deep: linr_net_train_step_bf16_deep - block_layers 1..4, one entry
-    for the plain and the quantisation-aware step."""
+    """linr_net_train_step_bf16: net_train_step with bf16 feature / gradient rows, fp32 master parameters and accumulation; qparams
+    as there.  deep: accept block_layers 2..4 (Frame.train_bf16_arena)."""
     base, nbytes = frame.train_bf16_arena(deep)
-    steps = None if scale_steps is None else scale_steps.ctypes.data
-    if deep:
-        check(_lib.lib().linr_net_train_step_bf16_deep(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(),
-                                                       float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step),
-                                                       steps, beta1, beta2, eps, weight_decay, bits.data_ptr(),
-                                                       None if qparams is None else qparams.data_ptr(), int(bitdepth), _stream()),
-              'linr_net_train_step_bf16_deep')
-        return
-    if qparams is not None:
-        check(_lib.lib().linr_net_train_step_bf16_qat(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(),
-                                                      float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step),
-                                                      steps, beta1, beta2, eps, weight_decay, bits.data_ptr(), qparams.data_ptr(),
-                                                      int(bitdepth), _stream()), 'linr_net_train_step_bf16_qat')
-        return
-    check(_lib.lib().linr_net_train_step_bf16(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(),
-                                              float(gscale), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), int(step), steps,
-                                              beta1, beta2, eps, weight_decay, bits.data_ptr(), _stream()),
-          'linr_net_train_step_bf16')
+    args = _step_args(exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits, scale_steps, qparams, bitdepth)
+    check(_lib.lib().linr_net_train_step_bf16(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(), ctypes.byref(args),
+                                              _stream()), 'linr_net_train_step_bf16')

@@ -843,14 +843,14 @@ def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
     StepLR, as ONE C-ABI call (linr_net_train_step).  Returns the device-resident bits accumulator (float64[1]);
     nothing synchronises with the host.  `out`: a zeroed float64[1] device tensor to add the bits into (e.g. one slot of a
     per-GOP vector that is cleared once per epoch) - saves the per-step allocation + fill.
-    qat_bitdepth > 0: the quantisation-aware step (linr_net_train_step_qat / _bf16_qat) - bits and gradient are those of the
+    qat_bitdepth > 0: the quantisation-aware step (linr_step_args.qparams) - bits and gradient are those of the
     weights the model codec would code with at that depth (quant_uniform2 and back), Adam updates the fp32 master."""
     bits = torch.zeros(1, dtype=torch.float64, device=frame.device) if out is None else out
-    qat = {}
+    extra = {}                           # keyword arguments of the step beyond the common ones
     if qat_bitdepth:
         if model._wide is not None:
             raise _lib.LinrError('quantisation-aware training exists for hidden_channel_conv=8 only')
-        qat = {'qparams': model.qat_parameters(), 'bitdepth': int(qat_bitdepth)}
+        extra = {'qparams': model.qat_parameters(), 'bitdepth': int(qat_bitdepth)}
     if model._wide is not None:          # hidden_channel_conv 16 / 32: the channel-blocked executor + the segment-wise Adam
         if model.train_precision != 'f32':
             raise _lib.LinrError('the bf16 training executor exists for hidden_channel_conv=8 only')
@@ -865,20 +865,15 @@ def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
         opt.scheduler_step()
         return bits
     t, t_scale = opt.advance(frame)
-    if model.train_precision == 'bf16':
-        if model.block_layers != 1:
-            raise _lib.LinrError('the bf16 training executor supports block_layers=1 only')
-        engine.net_train_step_bf16(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
-                                   opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale, **qat)
-    elif model.train_precision == 'bf16-deep':           # the same executor through its *_deep entries: block_layers 1..4
-        engine.net_train_step_bf16(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
-                                   opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale, deep=True,
-                                   **qat)
-    elif model.train_precision == 'f32':
-        engine.net_train_step(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
-                              opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, scale_steps=t_scale, **qat)
-    else:
+    if model.train_precision not in ('f32', 'bf16', 'bf16-deep'):
         raise ValueError("train_precision must be 'f32', 'bf16' or 'bf16-deep'")
+    if model.train_precision == 'bf16' and model.block_layers != 1:
+        raise _lib.LinrError('the bf16 training executor supports block_layers=1 only')
+    if model.train_precision != 'f32':                   # one executor; 'bf16-deep' lets it take block_layers 2..4
+        extra['deep'] = model.train_precision == 'bf16-deep'
+    step = engine.net_train_step if model.train_precision == 'f32' else engine.net_train_step_bf16
+    step(frame, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t, opt.lr, opt.betas[0], opt.betas[1],
+         opt.eps, opt.weight_decay, bits, scale_steps=t_scale, **extra)
     opt.t, opt.t_scale = t, t_scale              # committed only after the call returned without an error
     opt.scheduler_step()
     return bits

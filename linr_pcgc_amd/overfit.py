@@ -56,20 +56,18 @@ class Gop:
 
     def share_train_bf16_arena(self, deep=False):
         """One arena of the bf16 training executor for all frames of the GOP (a step finishes before the next begins).  deep: the
-        arena of its *_deep entries (block_layers 1..4)."""
-        attr = 'arena_train_bf16_deep' if deep else 'arena_train_bf16'
-        if all(getattr(f, attr, None) is not None for f in self.frames):
-            return
+        caller accepts block_layers 2..4 (Frame.train_bf16_arena); without it a deeper GOP is refused before any library call."""
         from . import _lib
-        rows = max(f.rows for f in self.frames)
-        size_fn = _lib.lib().linr_net_train_bf16_deep_arena_bytes if deep else _lib.lib().linr_net_train_bf16_arena_bytes
-        nbytes = size_fn(rows, self.block_layers)
+        if self.block_layers > 1 and not deep:
+            raise _lib.LinrError("the bf16 training executor supports block_layers=1 only (train_precision 'bf16-deep': 1..4)")
+        if all(getattr(f, 'arena_train_bf16', None) is not None for f in self.frames):
+            return
+        nbytes = _lib.lib().linr_net_train_bf16_arena_bytes(max(f.rows for f in self.frames), self.block_layers)
         if nbytes == 0:
-            raise _lib.LinrError('the bf16 training executor supports block_layers 1..4 through its deep entries only' if deep else
-                                 "the bf16 training executor supports block_layers=1 only (train_precision 'bf16-deep': 1..4)")
+            raise _lib.LinrError('the bf16 training executor supports block_layers 1..4 through its deep entries only')
         arena = _lib.scratch(nbytes + 64, self.frames[0].device)
         for f in self.frames:
-            setattr(f, attr, arena)
+            f.arena_train_bf16 = arena
 
     def __len__(self):
         return len(self.frames)

@@ -160,3 +160,12 @@ def _within_rounding(got, exact, absum, what):
     worst = float(ratio.max())
     assert bool(((got - exact).abs() <= tol).all()), '%s: worst entry at %.3g x its bound' % (what, worst)
     return worst
+
+
+# Adam's arguments as they reach a fused training step (one linr_step_args) and FlatAdam.step (positional scalars of linr_adam_step):
+# the defaults every other test uses, and a set of pairwise distinct non-default values, with a loss scale that is not
+# 1 / point_num (ADAM_DISTINCT_GSCALE_DIV times smaller) - a field of the struct that is dropped or swapped with a neighbour changes
+# the fused path alone
+ADAM_DEFAULT = dict(lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4)
+ADAM_DISTINCT = dict(lr=2e-3, betas=(0.7, 0.95), eps=1e-5, weight_decay=3e-3)
+ADAM_DISTINCT_GSCALE_DIV = 1.7

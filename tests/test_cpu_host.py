@@ -92,7 +92,11 @@ def test_c_abi_argument_checks(lib):
     assert lib.linr_spconv_wgrad_wide_slab_bytes(16, 16) == 512 * 4 * 1736 * 4 and lib.linr_spconv_wgrad_wide_slab_bytes(0, 16) == 0
     # whole network: NULL frame / parameters, stage range
     assert lib.linr_net_forward(None, p16, p16, 4096, 0, 8, None, None, None) == -1
-    assert lib.linr_net_train_step(None, p16, p16, 4096, 1.0, None, None, 0.01, 1, None, 0.9, 0.999, 1e-8, 1e-4, None, None) == -1
+    from linr_pcgc_amd._lib import LinrStepArgs
+    sargs = lambda **kw: ctypes.byref(LinrStepArgs(**{**dict(gscale=1.0, exp_avg=p16, exp_avg_sq=p16, lr=0.01, step=1, beta1=0.9, beta2=0.999,
+                                                             eps=1e-8, weight_decay=0.0, bits_acc=p16), **kw}))
+    assert lib.linr_net_train_step(None, p16, p16, 4096, sargs(exp_avg=None, exp_avg_sq=None, bits_acc=None, weight_decay=1e-4), None) == -1
+    assert lib.linr_net_train_step(None, p16, p16, 4096, sargs(), None) == -1
     assert lib.linr_param_count(0, 1) < 0
     assert lib.linr_param_count(7, 1) == 54712
     assert lib.linr_net_arena_bytes(-1, 1) == 0 and lib.linr_net_arena_bytes(100, 9) == 0
@@ -102,12 +106,15 @@ def test_c_abi_argument_checks(lib):
     assert lib.linr_ac_decode_binary(None, 4, p16, 8, p16) == -1
     tot, nl, npass = ctypes.c_double(), ctypes.c_int64(), ctypes.c_int64()
     assert lib.linr_prof_read(24, ctypes.byref(tot), ctypes.byref(nl), ctypes.byref(npass)) == -1
-    # bf16 training executor: NULL frame / arena, unsupported depth
-    assert lib.linr_net_train_step_bf16(None, p16, p16, 4096, None, 1.0, None, None, 0.01, 1, None, 0.9, 0.999, 1e-8, 1e-4, None, None) == -1
+    # bf16 training executor: NULL frame / arena, depths outside 1..4
+    assert lib.linr_net_train_step_bf16(None, p16, p16, 4096, None, sargs(exp_avg=None, exp_avg_sq=None, bits_acc=None, weight_decay=1e-4),
+                                        None) == -1
+    assert lib.linr_net_train_step_bf16(None, p16, p16, 4096, None, sargs(), None) == -1
     assert lib.linr_net_forward_train_bf16(None, p16, p16, 4096, None, None, None, None) == -1
     assert lib.linr_net_backward_bf16(None, p16, p16, 4096, None, 1.0, None, None) == -1
-    assert lib.linr_net_train_bf16_arena_bytes(-1, 1) == 0 and lib.linr_net_train_bf16_arena_bytes(100, 2) == 0
-    assert lib.linr_net_train_bf16_arena_bytes(100, 1) > 0
+    assert lib.linr_net_train_bf16_arena_bytes(-1, 1) == 0 and lib.linr_net_train_bf16_arena_bytes(100, 0) == 0
+    assert lib.linr_net_train_bf16_arena_bytes(100, 5) == 0
+    assert lib.linr_net_train_bf16_arena_bytes(100, 2) > lib.linr_net_train_bf16_arena_bytes(100, 1) > 0
     assert lib.linr_occ_to_bf16(None, 4, None, None) == -1
     rw = ctypes.c_int32(7)
     assert lib.linr_spconv_bwd_fused_bf16(None, None, None, None, 4, 4, None, None, None, 1, ctypes.byref(rw), None) == -1 and rw.value == 0
@@ -177,13 +184,14 @@ def test_c_abi_argument_checks(lib):
     below_bound = dict(rows=bound - 1, row_off=(0, 8, bound - 1))
     fwd = lambda f, a, nb: lib.linr_net_forward(f, p64, a, nb, 0, 8, None, None, None)
     bwd = lambda f, a, nb: lib.linr_net_backward(f, p64, a, nb, 1.0, p64, None)
-    step = lambda f, a, nb: lib.linr_net_train_step(f, p64, a, nb, 1.0, p64, p64, 0.01, 1, None, 0.9, 0.999, 1e-8, 0.0, p64, None)
+    s64 = dict(exp_avg=p64, exp_avg_sq=p64, bits_acc=p64)
+    step = lambda f, a, nb, **kw: lib.linr_net_train_step(f, p64, a, nb, sargs(**{**s64, **kw}), None)
     dec = lambda f, a, nb: lib.linr_net_decode_stages(f, p64, None, 0.0, 1.0, a, nb, p64, p64, p64, p64, p64, p64, None)
     bfwd = lambda f, a, nb: lib.linr_net_forward_bf16(f, p64, 0.0, 1.0, a, nb, 0, 8, p64, None, None)
     bdec = lambda f, a, nb: lib.linr_net_decode_stages(f, None, p64, 0.0, 1.0, a, nb, p64, p64, p64, p64, p64, p64, None)
     tfwd = lambda f, a, nb: lib.linr_net_forward_train_bf16(f, p64, a, nb, None, None, None, None)
     tbwd = lambda f, a, nb: lib.linr_net_backward_bf16(f, p64, a, nb, None, 1.0, p64, None)
-    tstep = lambda f, a, nb: lib.linr_net_train_step_bf16(f, p64, a, nb, None, 1.0, p64, p64, 0.01, 1, None, 0.9, 0.999, 1e-8, 0.0, p64, None)
+    tstep = lambda f, a, nb, **kw: lib.linr_net_train_step_bf16(f, p64, a, nb, None, sargs(**{**s64, **kw}), None)
     # (entries, arena bytes of the 16-row frame, arena alignment)
     for entries, need, align in (((fwd, bwd, step, dec), lib.linr_net_arena_bytes, 16),
                                  ((bfwd, bdec), lib.linr_net_bf16_arena_bytes, 64),
@@ -210,8 +218,25 @@ def test_c_abi_argument_checks(lib):
             assert call(frame(**fault), p64, 1 << 40) == -1, (call, fault)
     for call in (bfwd, bdec):
         assert call(frame(bl=2), p64, lib.linr_net_bf16_arena_bytes(16, 1)) == -2
-    for call in (tfwd, tbwd, tstep):                         # bf16 training: block_layers 1 only
-        assert call(frame(bl=2), p64, 1 << 40) == -1
+    for call in (tfwd, tbwd, tstep):                         # bf16 training: the depth is the frame's (1..4)
+        assert call(frame(bl=2), p64, lib.linr_net_train_bf16_arena_bytes(16, 1)) == -2
+    # the step of both executors: the argument struct, its moments, bits, step >= 1, the QAT image, scale_steps - on a frame and an arena
+    # that pass, so each field is what is refused
+    never, neg = (ctypes.c_int64 * 7)(0, 0, 0, 0, 0, 0, 0), (ctypes.c_int64 * 7)(1, 1, -1, 1, 1, 1, 1)
+    for call, f, nb in ((step, frame, lib.linr_net_arena_bytes(16, 1)), (tstep, frame, lib.linr_net_train_bf16_arena_bytes(16, 1)),
+                        (tstep, lambda: frame(bl=2), lib.linr_net_train_bf16_arena_bytes(16, 2))):
+        entry = lib.linr_net_train_step if call is step else lambda f, p, a, nb, sa, s: lib.linr_net_train_step_bf16(f, p, a, nb, None, sa, s)
+        assert entry(f(), p64, p64, nb, None, None) == -1                                           # no linr_step_args
+        assert call(f(), p64, nb, exp_avg=None) == -1 and call(f(), p64, nb, exp_avg_sq=None) == -1
+        assert call(f(), p64, nb, bits_acc=None) == -1 and call(f(), p64, nb, step=0) == -1
+        assert call(f(), p64, nb, qparams=p64, bitdepth=8) == -1, 'the fake-quantised image must not alias the master'
+        assert call(f(), p64, nb, qparams=p64 + 2048, bitdepth=0) == -1 and call(f(), p64, nb, qparams=p64 + 2048, bitdepth=17) == -1
+        assert call(f(), p64, nb, scale_steps_h=ctypes.addressof(never)) == -1, 'a scale with rows cannot be "never started"'
+        assert call(f(), p64, nb, scale_steps_h=ctypes.addressof(neg)) == -1
+        # their order: a NULL moment before the frame contract's ENOSPC / EALIGN, those before the QAT image and scale_steps
+        assert call(f(), p64 + 4, nb - 1, exp_avg=None) == -1
+        assert call(f(), p64, nb - 1, qparams=p64 + 2048, bitdepth=0, scale_steps_h=ctypes.addressof(never)) == -2
+        assert call(f(), p64 + 4, nb, qparams=p64 + 2048, bitdepth=17, scale_steps_h=ctypes.addressof(neg)) == -3
     assert lib.linr_net_forward_train_bf16(frame(), p64, p64, lib.linr_net_train_bf16_arena_bytes(16, 1), p64 + 4, None, None, None) == -3
     # the scale context as stand-alone ops: the frame's structure only (no row bound, no arena)
     sfwd = lambda f, a: lib.linr_sce_fwd(p64, f, None, a, p64, None)

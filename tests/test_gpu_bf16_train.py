@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 from oracle import network as onet          # noqa: E402
 from oracle import network_bf16 as obf      # noqa: E402
 from oracle import octree as ooct           # noqa: E402
-from gpu_common import _model_and_oracle    # noqa: E402
+from gpu_common import _model_and_oracle, ADAM_DEFAULT, ADAM_DISTINCT, ADAM_DISTINCT_GSCALE_DIV    # noqa: E402
 
 
 def _stream():
@@ -309,7 +309,8 @@ def test_bf16_training_rejects_what_it_does_not_support(pkg, shell):
     frame = model.make_frame(shell['scales'])
     with pytest.raises(_lib.LinrError):
         train_step(model, FlatAdam(model), frame, shell['point_num'])
-    assert _lib.lib().linr_net_train_bf16_arena_bytes(1000, 2) == 0
+    with pytest.raises(_lib.LinrError):          # the library takes the frame's depth: without deep=True Python refuses it
+        frame.train_bf16_arena()
 
 
 def test_bf16_training_does_not_depend_on_leftover_state(pkg):
@@ -492,31 +493,41 @@ def test_checkpoints_cross_the_two_training_executors(pkg, shell):
 
 
 def test_bf16_step_keeps_the_per_scale_adam_semantics(pkg, shell):
+    _bf16_step_keeps_the_per_scale_adam_semantics(pkg, shell, ADAM_DEFAULT, 1.0)
+
+
+def test_fused_bf16_step_passes_distinct_adam_arguments(pkg, shell):
+    _bf16_step_keeps_the_per_scale_adam_semantics(pkg, shell, ADAM_DISTINCT, ADAM_DISTINCT_GSCALE_DIV)
+
+
+def _bf16_step_keeps_the_per_scale_adam_semantics(pkg, shell, adam, gscale_div):
     """The context MLP of a scale no frame has contained yet is left alone (torch.optim.Adam skips .grad None; torch 1.13.1,
     enviroment.yaml:30), afterwards it is updated on every step, zero gradient or not (main.py:320): the bf16 step shares the fp32
     step's reduction and Adam.  Frames: 4 scales, 4 scales, 5 scales, 4 scales - the coarsest scale's MLP starts at step 3; the fused
-    bf16 step against its own unfused entries (forward, backward, FlatAdam.step) bit for bit."""
+    bf16 step against its own unfused entries (forward, backward, FlatAdam.step) bit for bit.  adam / gscale_div: the optimiser's
+    arguments and the loss scale 1 / (gscale_div * point_num) of both paths (gpu_common.ADAM_DISTINCT)."""
     from linr_pcgc_amd import engine
     from linr_pcgc_amd.model_core import FlatAdam, LINR_PCGC_Model, train_step
     model, sd = _model_and_oracle(pkg, 5)
     model.train_precision = 'bf16'
     full = shell['scales']
     frames = [model.make_frame(full[:-1]), model.make_frame(full[:-1]), model.make_frame(full), model.make_frame(full[:-1])]
-    opt = FlatAdam(model)
+    opt = FlatAdam(model, **adam)
+    point_num = gscale_div * shell['point_num']
     model2 = LINR_PCGC_Model({'scale_num': 5, 'in_channel': 7, 'hidden_channel_conv': 8, 'block_layers': 1, 'outstage': 8, 'instage': 1}).cuda()
     model2.load_state_dict(sd)
-    opt2 = FlatAdam(model2)
+    opt2 = FlatAdam(model2, **adam)
     frames2 = [model2.make_frame(full[:-1]), model2.make_frame(full[:-1]), model2.make_frame(full), model2.make_frame(full[:-1])]
     w4 = lambda m: dict(m.named_parameters())['scale_mlp.4.0.weight'].detach().clone()
     w4_init = w4(model)
     for it in range(6):
         j = it % 4
-        bits_fused = train_step(model, opt, frames[j], shell['point_num'])
+        bits_fused = train_step(model, opt, frames[j], point_num)
         bits = torch.zeros(1, dtype=torch.float64, device='cuda')
         engine.net_forward_train_bf16(frames2[j], model2.flat_parameters(), None, bits)
         assert float(bits_fused) == float(bits), 'bits of the fused bf16 step differ from linr_net_forward_train_bf16 at step %d' % it
         opt2.zero_grad()
-        engine.net_backward_bf16(frames2[j], model2.flat_parameters(), opt2.grad, 1.0 / shell['point_num'])
+        engine.net_backward_bf16(frames2[j], model2.flat_parameters(), opt2.grad, 1.0 / point_num)
         opt2.step(frames2[j])
         if it < 2:
             assert torch.equal(w4(model), w4_init), 'scale 4 has had no gradient yet: its MLP must be untouched'

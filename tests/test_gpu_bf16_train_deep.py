@@ -1,6 +1,6 @@
 """GPU tests of the bf16 training executor at block_layers 2..4 of block_in (--block_layers, main.py:521; models/resnet.py:146-162): the
-opt-in *_deep entries of csrc/train_bf16.hip (linr_net_forward_train_bf16_deep, linr_net_backward_bf16_deep,
-linr_net_train_step_bf16_deep) and train_precision 'bf16-deep'.
+entries of csrc/train_bf16.hip (linr_net_forward_train_bf16, linr_net_backward_bf16, linr_net_train_step_bf16) on deeper frames,
+which Python opens with deep=True and train_precision 'bf16-deep'.
 
 The reference trains in fp32 only, so - as for tests/test_gpu_bf16_train.py, whose bounds for each pair are used unchanged:
   * against the emulating reference (tests/bf16_train_deep_ref.py: oracle/network_bf16.py's pieces chained over nl layers, the extra skip
@@ -167,9 +167,9 @@ def test_deep_training_tiny_and_ragged_frames(n):
 # ---- 3: several tiles per wave --------------------------------------------------------------------------------------------------------
 def _dirty_deep_arena(frame):
     from linr_pcgc_amd import _lib
-    nbytes = _lib.lib().linr_net_train_bf16_deep_arena_bytes(frame.rows, frame.block_layers)
+    nbytes = _lib.lib().linr_net_train_bf16_arena_bytes(frame.rows, frame.block_layers)
     assert nbytes > 0
-    frame.arena_train_bf16_deep = torch.full((nbytes + 64,), 0xFF, dtype=torch.uint8, device='cuda')
+    frame.arena_train_bf16 = torch.full((nbytes + 64,), 0xFF, dtype=torch.uint8, device='cuda')
 
 
 def _run_deep(frame, flat, gscale):
@@ -277,7 +277,7 @@ def test_deep_middle_frame_matches_the_emulating_reference(middle3):
 # ---- 4: the step ----------------------------------------------------------------------------------------------------------------------
 def test_bf16_deep_at_block_layers_1_is_bf16_bit_for_bit(pkg, shell):
     """'bf16-deep' at block_layers 1 runs the launches of 'bf16': bits and parameters after three train_steps are torch.equal, and the
-    two arenas have one size."""
+    arena has the size it had when 'bf16' had an arena of its own."""
     from linr_pcgc_amd import _lib
     from linr_pcgc_amd.model_core import FlatAdam, train_step
     outs = {}
@@ -290,12 +290,11 @@ def test_bf16_deep_at_block_layers_1_is_bf16_bit_for_bit(pkg, shell):
         outs[prec] = (torch.cat(bits), model.flat_parameters().clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone())
     for a, b in zip(outs['bf16'], outs['bf16-deep']):
         assert torch.equal(a, b)
-    L = _lib.lib()
-    assert L.linr_net_train_bf16_deep_arena_bytes(6821, 1) == L.linr_net_train_bf16_arena_bytes(6821, 1)
+    assert _lib.lib().linr_net_train_bf16_arena_bytes(6821, 1) == 130606912
 
 
 def test_bf16_deep_quantisation_aware_steps(pkg, shell):
-    """Three steps at block_layers 2 with qat_bitdepth=8 (the one *_deep step entry, with qparams) run: finite, reproducible, and
+    """Three steps at block_layers 2 with qat_bitdepth=8 (the step entry with qparams) run: finite, reproducible, and
     different from the plain steps - whose first bits they stay within 5 % of (the 8-bit image of the weights is close to them)."""
     from linr_pcgc_amd.model_core import FlatAdam, train_step
     outs = {}
@@ -310,6 +309,36 @@ def test_bf16_deep_quantisation_aware_steps(pkg, shell):
     assert outs['qat'][0] == outs['qat2'][0] and torch.equal(outs['qat'][1], outs['qat2'][1])
     assert outs['qat'][0] != outs['plain'][0] and not torch.equal(outs['qat'][1], outs['plain'][1])
     assert abs(outs['qat'][0][0] - outs['plain'][0][0]) <= 0.05 * outs['plain'][0][0], 'the 8-bit image of the weights is close to them'
+
+
+@pytest.mark.parametrize('qat_bitdepth', [0, 8], ids=['plain', 'qat'])
+def test_bf16_deep_fused_step_is_its_unfused_entries_bit_for_bit(pkg, shell, qat_bitdepth):
+    """block_layers 2 through 'bf16-deep', Adam's arguments pairwise distinct and none at its default, a loss scale that is not
+    1 / point_num (gpu_common.ADAM_DISTINCT): three fused steps (one linr_step_args) against the forward entry, the backward entry and
+    FlatAdam.step (linr_adam_step, positional scalars) - with qat_bitdepth both at the fake-quantised image of the master.  Bits of
+    every step, parameters and both moments torch.equal."""
+    from gpu_common import ADAM_DISTINCT, ADAM_DISTINCT_GSCALE_DIV
+    from linr_pcgc_amd import engine
+    from linr_pcgc_amd.model_core import FlatAdam, train_step
+    point_num = ADAM_DISTINCT_GSCALE_DIV * shell['point_num']
+    (model, _), (model2, _) = _model(pkg, 5, 2), _model(pkg, 5, 2)
+    model.train_precision = 'bf16-deep'
+    frame, frame2 = model.make_frame(shell['scales']), model2.make_frame(shell['scales'])
+    opt, opt2 = FlatAdam(model, **ADAM_DISTINCT), FlatAdam(model2, **ADAM_DISTINCT)
+    for it in range(3):
+        bits_fused = train_step(model, opt, frame, point_num, qat_bitdepth=qat_bitdepth)
+        at = model2.flat_parameters()
+        if qat_bitdepth:
+            at, _ = engine.params_fake_quant(at, qat_bitdepth)
+        bits = torch.zeros(1, dtype=torch.float64, device='cuda')
+        engine.net_forward_train_bf16(frame2, at, None, bits, deep=True)
+        assert torch.equal(bits_fused, bits), 'bits of the fused step differ from the forward entry at step %d' % it
+        opt2.zero_grad()
+        engine.net_backward_bf16(frame2, at, opt2.grad, 1.0 / point_num, deep=True)
+        opt2.step(frame2)
+    assert opt.t == opt2.t == 3
+    assert torch.equal(model.flat_parameters(), model2.flat_parameters()), 'fused step and forward + backward + FlatAdam.step differ'
+    assert torch.equal(opt.exp_avg, opt2.exp_avg) and torch.equal(opt.exp_avg_sq, opt2.exp_avg_sq)
 
 
 def test_bf16_deep_rejects_what_it_does_not_support(pkg, shell):

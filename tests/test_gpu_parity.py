@@ -13,6 +13,7 @@ from oracle import network as onet          # noqa: E402,F401
 from oracle import octree as ooct           # noqa: E402,F401
 from oracle import ac as oac                # noqa: E402,F401
 from gpu_common import _dev, _close, _model_and_oracle, _grads_close_per_tensor          # noqa: E402,F401
+from gpu_common import ADAM_DEFAULT, ADAM_DISTINCT, ADAM_DISTINCT_GSCALE_DIV          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -400,40 +401,51 @@ def test_overfit_is_run_to_run_deterministic(pkg):
 
 
 def test_adam_skips_a_scale_until_its_first_gradient(pkg, shell):
+    _adam_skips_a_scale_until_its_first_gradient(pkg, shell, ADAM_DEFAULT, 1.0)
+
+
+def test_fused_step_passes_distinct_adam_arguments(pkg, shell):
+    _adam_skips_a_scale_until_its_first_gradient(pkg, shell, ADAM_DISTINCT, ADAM_DISTINCT_GSCALE_DIV)
+
+
+def _adam_skips_a_scale_until_its_first_gradient(pkg, shell, adam, gscale_div):
     """torch.optim.Adam skips parameters whose .grad is None and keeps a step counter per parameter.  The reference pins torch
     1.13.1 (enviroment.yaml:30), whose optimizer.zero_grad() (main.py:320) leaves ZERO tensors: the context MLP of a scale is left
     alone only until a frame containing the scale gives it its first gradient (custom_dataset.py:325 drops the coarsest scales of
     small frames); afterwards it is updated on every step, zero gradient or not.  Frames: 4 scales, 4 scales, 5 scales, 4 scales,
     ... - the coarsest scale's MLP starts at step 3.  Fused steps against torch.optim.Adam on the oracle with
-    zero_grad(set_to_none=False), and against the package's own unfused path (net_backward + FlatAdam.step)."""
+    zero_grad(set_to_none=False), and against the package's own unfused path (net_backward + FlatAdam.step).
+    adam / gscale_div: the optimiser's arguments and the loss scale 1 / (gscale_div * point_num) of all three paths; the tolerances
+    against torch.optim.Adam are those of the default arguments, so the distinct set stops after the package's two paths."""
     from linr_pcgc_amd import engine
     from linr_pcgc_amd.model_core import FlatAdam, LINR_PCGC_Model, train_step
     model, sd = _model_and_oracle(pkg, 5)
     full = shell['scales']
     frames = [model.make_frame(full[:-1]), model.make_frame(full[:-1]), model.make_frame(full), model.make_frame(full[:-1])]
     tscs = [onet.to_torch_scales(full[:-1]), onet.to_torch_scales(full[:-1]), onet.to_torch_scales(full), onet.to_torch_scales(full[:-1])]
-    opt = FlatAdam(model)
+    opt = FlatAdam(model, **adam)
+    point_num = gscale_div * shell['point_num']
     # second model on the unfused path: same parameters
     model2 = LINR_PCGC_Model({'scale_num': 5, 'in_channel': 7, 'hidden_channel_conv': 8, 'block_layers': 1, 'outstage': 8,
                               'instage': 1}).cuda()
     model2.load_state_dict(sd)
-    opt2 = FlatAdam(model2)
+    opt2 = FlatAdam(model2, **adam)
     frames2 = [model2.make_frame(full[:-1]), model2.make_frame(full[:-1]), model2.make_frame(full), model2.make_frame(full[:-1])]
     sdo = {k: v.clone().requires_grad_() for k, v in sd.items()}
     names = list(sdo)
-    opt_o = torch.optim.Adam(list(sdo.values()), lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4)
+    opt_o = torch.optim.Adam(list(sdo.values()), **adam)
     for it in range(7):
         j = it % 4
-        bits_fused = train_step(model, opt, frames[j], shell['point_num'])
+        bits_fused = train_step(model, opt, frames[j], point_num)
         bits = torch.zeros(1, dtype=torch.float64, device='cuda')
         engine.net_forward(frames2[j], model2.flat_parameters(), 0, 8, None, bits)
         # the fused step (linr_net_train_step: forward, backward, reduction, Adam in one call) against the unfused entries: the bits of
         # every step bitwise
         assert float(bits_fused) == float(bits), 'bits of the fused step differ from linr_net_forward at step %d' % it
         opt2.zero_grad()
-        engine.net_backward(frames2[j], model2.flat_parameters(), opt2.grad, 1.0 / shell['point_num'])
+        engine.net_backward(frames2[j], model2.flat_parameters(), opt2.grad, 1.0 / point_num)
         opt2.step(frames2[j])
-        (onet.frame_bits(sdo, tscs[j]) / shell['point_num']).backward()
+        (onet.frame_bits(sdo, tscs[j]) / point_num).backward()
         if it < 2:
             assert sdo['scale_mlp.4.0.weight'].grad is None           # not started yet: torch skips it
         opt_o.step()
@@ -444,6 +456,8 @@ def test_adam_skips_a_scale_until_its_first_gradient(pkg, shell):
     # the package's two training paths apply the same update
     assert torch.equal(model.flat_parameters(), model2.flat_parameters()), 'fused train_step and net_backward + FlatAdam.step differ'
     assert torch.equal(opt.exp_avg, opt2.exp_avg) and torch.equal(opt.exp_avg_sq, opt2.exp_avg_sq), 'Adam moments of the two paths differ'
+    if adam is not ADAM_DEFAULT:
+        return
     flat_o = torch.cat([v.detach().reshape(-1) for v in sdo.values()])
     _close(model.flat_parameters(), flat_o, 0, 3e-3, 'parameters after 7 Adam steps over frames with 4 / 5 scales')
     off = 0

@@ -1,5 +1,5 @@
 """GPU tests of the opt-in quantisation-aware overfit: the device quantiser (linr_params_fake_quant) against its host twin, the two
-train steps (linr_net_train_step_qat, linr_net_train_step_bf16_qat) against the plain steps they are built from, one oracle
+train steps with linr_step_args.qparams (linr_net_train_step, linr_net_train_step_bf16) against the plain steps they are built from, one oracle
 anchor, and the drivers (overfit_gop qat_epochs=, run.py --qat-epochs, the stand-alone decoder).
 
 What is exact here and why: the quantiser is six individually rounded fp32 operations behind an exact min / max, so host and device
@@ -17,6 +17,7 @@ import torch
 
 from oracle import network as onet                                      # noqa: E402
 from gpu_common import _dev, _close, _model_and_oracle                  # noqa: E402
+from gpu_common import ADAM_DEFAULT, ADAM_DISTINCT, ADAM_DISTINCT_GSCALE_DIV       # noqa: E402
 from test_fake_quant_host import SCALES, fake_quant_host, planted      # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -70,8 +71,9 @@ def test_device_quantiser_without_optional_outputs(pkg):
     assert torch.equal(q0, q1) and int(c0.cpu().numpy().max()) == 255
 
 
-def _adam64(M, g, m, v, t, wd):
+def _adam64(M, g, m, v, t, wd, adam):
     """torch.optim.Adam's update in float64."""
+    LR, (B1, B2), EPS = adam['lr'], adam['betas'], adam['eps']
     M, g, m, v = M.double(), g.double(), m.double(), v.double()
     g = g + wd * M
     m = B1 * m + (1 - B1) * g
@@ -80,12 +82,14 @@ def _adam64(M, g, m, v, t, wd):
     return M - LR / (1 - B1 ** t) * m / denom
 
 
-def _step_identity(model, frame, point_num, step_fn, fwd_bwd):
-    """step_fn(params, exp_avg, exp_avg_sq, t, t_scale, weight_decay, bits, **qat): one train step of the executor under test;
-    fwd_bwd(params, grads): its forward and backward at `params`, the gradient of bits / point_num added into grads."""
+def _step_identity(model, frame, point_num, step_fn, fwd_bwd, adam=ADAM_DEFAULT):
+    """step_fn(params, exp_avg, exp_avg_sq, t, t_scale, weight_decay, bits, **qat): one train step of the executor under test with
+    Adam's other arguments from `adam`; fwd_bwd(params, grads): its forward and backward at `params`, the gradient of
+    bits / point_num added into grads."""
     from linr_pcgc_amd import engine
     from linr_pcgc_amd.model_core import FlatAdam, train_step
-    opt = FlatAdam(model)
+    opt = FlatAdam(model, **adam)
+    WD = adam['weight_decay']
     for _ in range(2):
         train_step(model, opt, frame, point_num)          # plain steps: moments and counters to start from
     M, m0, v0 = model.flat_parameters().clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone()
@@ -108,31 +112,46 @@ def _step_identity(model, frame, point_num, step_fn, fwd_bwd):
     assert torch.equal(bits_a, bits_b) and float(bits_a) > 0
     assert torch.equal(ma, mb) and torch.equal(va, vb)
     assert not torch.equal(pa, pb)                          # ... while the update lands on the master, not on Q
-    # weight_decay 1e-4 acts on the master: Adam's formula in float64 on (M, g at Q)
+    # the optimiser's weight decay acts on the master: Adam's formula in float64 on (M, g at Q)
     g = torch.zeros_like(M)
     fwd_bwd(Q, g)
-    pw, _, _, bits_w = run(M, 1e-4, qparams=qbuf, bitdepth=8)
+    pw, mw, vw, bits_w = run(M, WD, qparams=qbuf, bitdepth=8)
     assert torch.equal(bits_w, bits_a)
-    _close(pw, _adam64(M, g, m0, v0, t, 1e-4), 2e-6, 2e-7, 'master after a quantisation-aware step')
-    _close(pa, _adam64(M, g, m0, v0, t, 0.0), 2e-6, 2e-7, 'master after a quantisation-aware step, no weight decay')
+    _close(pw, _adam64(M, g, m0, v0, t, WD, adam), 2e-6, 2e-7, 'master after a quantisation-aware step')
+    _close(pa, _adam64(M, g, m0, v0, t, 0.0, adam), 2e-6, 2e-7, 'master after a quantisation-aware step, no weight decay')
+    # and bit for bit the unfused path: the forward and backward entries at Q, then FlatAdam.step (linr_adam_step, positional
+    # scalars) on the master with that gradient - the model and opt still hold M, m0, v0
+    opt.grad.copy_(g)
+    opt.step(frame)
+    assert torch.equal(model.flat_parameters(), pw), 'fused quantisation-aware step and forward + backward at Q + FlatAdam.step differ'
+    assert torch.equal(opt.exp_avg, mw) and torch.equal(opt.exp_avg_sq, vw)
     return Q, float(bits_a)
 
 
 @pytest.mark.parametrize('block_layers', [1, 3])
 def test_fp32_qat_step_is_the_plain_step_at_the_quantised_weights(pkg, shell, block_layers):
+    _fp32_qat_step(pkg, shell, block_layers, ADAM_DEFAULT, 1.0)
+
+
+def test_fp32_qat_step_passes_distinct_adam_arguments(pkg, shell):
+    _fp32_qat_step(pkg, shell, 1, ADAM_DISTINCT, ADAM_DISTINCT_GSCALE_DIV)
+
+
+def _fp32_qat_step(pkg, shell, block_layers, adam, gscale_div):
     from linr_pcgc_amd import engine
     model, sd = _model_and_oracle(pkg, 5, block_layers=block_layers)
     frame = model.make_frame(shell['scales'])
-    gscale = 1.0 / shell['point_num']
+    point_num = gscale_div * shell['point_num']
+    gscale = 1.0 / point_num
 
     def step_fn(p, m, v, t, ts, wd, bits, **qat):
-        engine.net_train_step(frame, p, m, v, gscale, t, LR, B1, B2, EPS, wd, bits, scale_steps=ts, **qat)
+        engine.net_train_step(frame, p, m, v, gscale, t, adam['lr'], *adam['betas'], adam['eps'], wd, bits, scale_steps=ts, **qat)
 
     def fwd_bwd(p, g):
         engine.net_forward(frame, p, 0, 8, None, None)
         engine.net_backward(frame, p, g, gscale)
 
-    Q, bits = _step_identity(model, frame, shell['point_num'], step_fn, fwd_bwd)
+    Q, bits = _step_identity(model, frame, point_num, step_fn, fwd_bwd, adam)
     if block_layers == 1:
         # the oracle anchor: the bits of the step are those of the network with the state dict filled with Q
         sdq, off, qc = {}, 0, Q.cpu()
@@ -146,20 +165,29 @@ def test_fp32_qat_step_is_the_plain_step_at_the_quantised_weights(pkg, shell, bl
 
 
 def test_bf16_qat_step_is_the_plain_step_at_the_quantised_weights(pkg, shell):
+    _bf16_qat_step(pkg, shell, ADAM_DEFAULT, 1.0)
+
+
+def test_bf16_qat_step_passes_distinct_adam_arguments(pkg, shell):
+    _bf16_qat_step(pkg, shell, ADAM_DISTINCT, ADAM_DISTINCT_GSCALE_DIV)
+
+
+def _bf16_qat_step(pkg, shell, adam, gscale_div):
     from linr_pcgc_amd import engine
     model, _ = _model_and_oracle(pkg, 5)
     model.train_precision = 'bf16'
     frame = model.make_frame(shell['scales'])
-    gscale = 1.0 / shell['point_num']
+    point_num = gscale_div * shell['point_num']
+    gscale = 1.0 / point_num
 
     def step_fn(p, m, v, t, ts, wd, bits, **qat):
-        engine.net_train_step_bf16(frame, p, m, v, gscale, t, LR, B1, B2, EPS, wd, bits, scale_steps=ts, **qat)
+        engine.net_train_step_bf16(frame, p, m, v, gscale, t, adam['lr'], *adam['betas'], adam['eps'], wd, bits, scale_steps=ts, **qat)
 
     def fwd_bwd(p, g):
         engine.net_forward_train_bf16(frame, p, None, None)
         engine.net_backward_bf16(frame, p, g, gscale)
 
-    _step_identity(model, frame, shell['point_num'], step_fn, fwd_bwd)
+    _step_identity(model, frame, point_num, step_fn, fwd_bwd, adam)
 
 
 def test_qat_step_refuses_bad_arguments(pkg, shell):
