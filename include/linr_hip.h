@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 25
+#define LINR_ABI_VERSION 26
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -41,6 +41,9 @@ extern "C" {
 #define LINR_NO_BIAS   8u
 #define LINR_PAD_ROW  16u    /* the gathered operand has a readable all-zero row at index -1 (in - in_ld):
                                 absent neighbours are read from it instead of being branched around      */
+#define LINR_MUL_BF16 16u    /* the wide 3x3x3 convolutions only (linr_spconv_wide, _wide_pw, linr_spconv_wgrad_wide_f, _wide2_f;
+                                they take no LINR_PAD_ROW): the PRODUCTS on bf16 matrix instructions - operands rounded to
+                                bf16 (nearest even) at the multiply, fp32 sums; memory and everything else stay fp32    */
 
 LINR_API int linr_abi_version(void);
 /* number of float parameters of LINR_PCGC_Model(scale_num, hidden=8, block_layers, outstage=8, instage=1)
@@ -164,7 +167,10 @@ LINR_API int linr_spconv_cmap(int32_t bwd, const float* in, int32_t in_ld, const
  * input blocks per tap feeds every output channel (csrc/wide.hip).  in_h / out_h / res_h / act_h: HOST arrays of device pointers to
  * the blocks.  fwd: gathers ceil(cin / 8) blocks (cin < 8: channels >= cin of the one block are ignored), produces cout / 8 blocks;
  * bwd: gathers the output gradient's cout / 8 blocks at the mirrored taps, produces cin / 8 blocks.  cin, cout <= 32 (8, 16, 32;
- * cin < 8 forward only).  W [27][cin][cout], bias [cout] or NULL; flags: LINR_RELU, LINR_ACCUM, LINR_RELU_MASK. */
+ * cin < 8 forward only).  W [27][cin][cout], bias [cout] or NULL; flags: LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_MUL_BF16.
+ * LINR_MUL_BF16 (csrc/wide_mul.hip; training option 'bf16-mul'): out = bias + sum rb(x) rb(W), backward-data gx = sum rb(g) rb(W), rb =
+ * round to nearest even to bf16 of the fp32 value in memory, products exact, sums fp32; bias, residual, LINR_ACCUM, masks, ReLU and the
+ * pointwise side paths of linr_spconv_wide_pw are computed in fp32 on the unrounded values, as without the flag. */
 LINR_API int linr_spconv_wide(int32_t bwd, const float* const* in_h, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
                               const float* W, const float* bias, int32_t cin, int32_t cout, const float* const* res_h,
                               const float* const* act_h, float* const* out_h, uint32_t flags, void* stream);
@@ -193,6 +199,12 @@ LINR_API int linr_spconv_wide_pw(int32_t bwd, const float* const* in_h, const in
 LINR_API size_t linr_spconv_wgrad_wide_slab_bytes(int32_t cin, int32_t cout);
 LINR_API int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
                                     const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, void* stream);
+/* The same with a flags word (linr_spconv_wgrad_wide = flags 0).  LINR_MUL_BF16, the only flag: gW = sum over rows of rb(x) rb(g) on
+ * bf16 matrix instructions with fp32 sums, gb = sum g on the unrounded gradient; the same slab layout and reduction.  It needs the
+ * one-launch form (the tiled table, 16-byte aligned, cout in {8, 16, 32}): LINR_EINVAL otherwise, and for any other bit. */
+LINR_API int linr_spconv_wgrad_wide_f(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
+                                      const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, uint32_t flags,
+                                      void* stream);
 
 /* Pointwise layers of the wide network on blocked activations (MinkowskiConvolution kernel_size 1: models/resnet.py:25-46 conv1_0,
  * conv1_2; the head's nn.Linear(C, 24): models/upsample.py:73-76) as ONE launch: out = [ReLU]([mask]((bias + in @ W) + res + old)).
@@ -228,6 +240,10 @@ LINR_API int32_t linr_spconv_wgrad_wide_blocks(int32_t cout, int32_t tiled);
  * linr_wide_reduce_many: kind 0, slab = the start of its part, nblocks 256, ws_ci = the row stride in floats. */
 LINR_API int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h, const float* const* gB_h,
                                      int32_t h, const int32_t* tile8t, int64_t n, float* slab, void* stream);
+/* ... with a flags word (linr_spconv_wgrad_wide2 = flags 0): LINR_MUL_BF16 as in linr_spconv_wgrad_wide_f, any other bit LINR_EINVAL. */
+LINR_API int linr_spconv_wgrad_wide2_f(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h,
+                                       const float* const* gB_h, int32_t h, const int32_t* tile8t, int64_t n, float* slab, uint32_t flags,
+                                       void* stream);
 LINR_API int32_t linr_linear_wgrad_wide_blocks(int64_t n);
 LINR_API int linr_wide_reduce_many(const linr_wide_reduce* items_h, int32_t count, void* stream);
 

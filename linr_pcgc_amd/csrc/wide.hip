@@ -10,39 +10,14 @@
 // instructions where the blocked form issued 8 gathers for them, and 32 -> 32 is 8 for 256 instead of 32 for 256.
 // Per-output arithmetic: bias, then taps in LINR_TAP order, gathered channel ascending over ALL input blocks - one chain per output,
 // the same in training, encoding and stage-by-stage decoding (wide_net.py runs the same launches in all three).
+// What wconv_k / wwgrad_k share with their bf16-product forms (flags & LINR_MUL_BF16: csrc/wide_mul.hip) is in csrc/wide_common.h.
 #include "common.h"
 #include "conv_common.h"
+#include "wide_common.h"
 #include "bwd_tail.h"
 #include "prof.h"
 #include <stdlib.h>
 
-#ifndef LINR_CONV_BLOCK
-#define LINR_CONV_BLOCK 256
-#endif
-#define WC_MAXB 4
-struct WcArgs {
-    const float* in[WC_MAXB];      // gathered blocks (fwd: the input, bwd: the output gradient), each with its zero row at [-8, 0)
-    const float* res[2];           // per produced block or nullptr
-    const float* act[2];           // LINR_RELU_MASK: mask by act > 0
-    float* out[2];                 // produced blocks
-    const float* W;                // [27][cin][cout] (ME layout)
-    const float* bias;             // fwd: [cout] or nullptr
-    int cin, cout;                 // of the convolution (fwd: gathered = cin, produced = cout; bwd: the other way round)
-    int gvalid;                    // gathered channels that exist (first convolutions of the outter blocks: cin = k < 8)
-    int pb0;                       // first produced block of this launch
-    unsigned flags;
-    // pointwise side path of a wide Inception layer fused into the epilogue (models/resnet.py:55-60; template parameter EPI):
-    //   EPI 1 (fwd conv0_0 C -> h): out2 = relu(own input row @ W10 + b10)                         (conv1_0 reads the centre tap's row)
-    //   EPI 2 (fwd conv1_1 h -> h): out2 = (this kernel's output row) @ W12 + b12 + aux            (conv1_2 + the residual's upper half)
-    //   EPI 3 (bwd tail conv):      out2 = ((produced upper half) @ W12^T) * (aux > 0)             (backward of conv1_2 and of M's ReLU)
-    //   EPI 4 (bwd conv0_0):        produced += (aux own row) @ W10^T, in front of the mask        (backward-data of conv1_0; aux = gH1)
-    // pw_W: [cin_pw][cout_pw] (ME layout), pw_b [cout_pw] or nullptr; pw_on: this launch runs the side path (EPI 3: the launch that
-    // produces the upper half, whose first local block is pw_hi0)
-    const float* pw_W; const float* pw_b;
-    const float* pw_aux[2];
-    float* pw_out[2];
-    int pw_on, pw_hi0;
-};
 
 template <int GB, int PB, bool BWD, int EPI = 0>
 __global__ __launch_bounds__(LINR_CONV_BLOCK) void wconv_k(WcArgs a, const int32_t* __restrict__ lo, const uint32_t* __restrict__ mask,
@@ -71,15 +46,10 @@ __global__ __launch_bounds__(LINR_CONV_BLOCK) void wconv_k(WcArgs a, const int32
         }
     }
     // the side path's weights behind the image (read back with uniform addresses: LDS broadcasts)
-    constexpr int PWI = EPI == 1 ? 8 * GB : EPI == 2 ? 8 * PB : EPI == 3 ? 4 * GB : EPI == 4 ? 16 * GB : 0;      // rows of pw_W (cin_pw)
-    constexpr int PWO = EPI == 1 ? 8 * PB : EPI == 2 ? 8 * PB : EPI == 3 ? 4 * GB : EPI == 4 ? 8 * GB : 0;       // columns (cout_pw)
     float* wp = wl + 27 * NV * 64;
     // read through a pointer that is per-lane in form: with a uniform one the compiler keeps the weights in SGPRs and spills hundreds
     const float* wq = wp + __builtin_amdgcn_mbcnt_lo(0u, 0u);
-    if constexpr (EPI != 0) {
-        for (int e = threadIdx.x; e < PWI * PWO; e += LINR_CONV_BLOCK) wp[e] = a.pw_W[e];
-        if (EPI <= 2) for (int e = threadIdx.x; e < PWO; e += LINR_CONV_BLOCK) wp[PWI * PWO + e] = a.pw_b ? a.pw_b[e] : 0.0f;
-    }
+    wc_pw_stage<GB, PB, EPI>(a, wp);
     __syncthreads();
     // the produced channels' bias: once per workgroup (uniform loads), not once per tile
     float bz[NQ][4];
@@ -141,143 +111,15 @@ __global__ __launch_bounds__(LINR_CONV_BLOCK) void wconv_k(WcArgs a, const int32
             __builtin_amdgcn_sched_barrier(0);
         });
         if (!live) continue;
-        // epilogue order of the 8-wide kernels: + res, + old (LINR_ACCUM), [EPI 4: + the pointwise backward], * (act > 0)
-        // (LINR_RELU_MASK), ReLU
-        float o[PB][8];
-#pragma unroll
-        for (int pb = 0; pb < PB; ++pb) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[pb][4 * h + j] = acc[2 * pb + h][j];
-            if (a.res[pb]) {
-                const float* r = a.res[pb] + row * 8;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[pb][j] += r[j];
-            }
-            if (a.flags & LINR_ACCUM) {
-                const float* op = a.out[pb] + row * 8;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[pb][j] += op[j];
-            }
-        }
-        if constexpr (EPI == 4) {
-            // + gH1[row] @ W10^T: per produced channel ci the chain of linr_linear_wide's backward-data pass (gradient channels
-            // ascending from 0), added to what the convolution, the residual's share and the old content gave
-            float gh[8 * GB];
-#pragma unroll
-            for (int b = 0; b < GB; ++b) {
-                const float4 t0 = *reinterpret_cast<const float4*>(a.pw_aux[b] + row * 8), t1 = *reinterpret_cast<const float4*>(a.pw_aux[b] + row * 8 + 4);
-                gh[8 * b] = t0.x; gh[8 * b + 1] = t0.y; gh[8 * b + 2] = t0.z; gh[8 * b + 3] = t0.w;
-                gh[8 * b + 4] = t1.x; gh[8 * b + 5] = t1.y; gh[8 * b + 6] = t1.z; gh[8 * b + 7] = t1.w;
-            }
-#pragma unroll
-            for (int pb = 0; pb < PB; ++pb)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float* wrow = wq + (8 * (a.pb0 + pb) + j) * PWO;
-                    float t = 0.0f;
-#pragma unroll
-                    for (int co = 0; co < PWO; ++co) t = fmaf(gh[co], wrow[co], t);
-                    o[pb][j] = t + o[pb][j];
-                }
-        }
-#pragma unroll
-        for (int pb = 0; pb < PB; ++pb) {
-            if (a.flags & LINR_RELU_MASK) {
-                const float* m = a.act[pb] + row * 8;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[pb][j] = m[j] > 0.0f ? o[pb][j] : 0.0f;
-            }
-            if (a.flags & LINR_RELU) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[pb][j] = fmaxf(o[pb][j], 0.0f);
-            }
-            float* op = a.out[pb] + row * 8;
-            *reinterpret_cast<float4*>(op) = make_float4(o[pb][0], o[pb][1], o[pb][2], o[pb][3]);
-            *reinterpret_cast<float4*>(op + 4) = make_float4(o[pb][4], o[pb][5], o[pb][6], o[pb][7]);
-        }
-        if constexpr (EPI == 1) {
-            // conv1_0 on the row itself: bias, then the input channels ascending (linr_linear_wide's chain), ReLU
-            float xin[8 * GB];
-#pragma unroll
-            for (int b = 0; b < GB; ++b) {
-                const float4 t0 = *reinterpret_cast<const float4*>(a.in[b] + row * 8), t1 = *reinterpret_cast<const float4*>(a.in[b] + row * 8 + 4);
-                xin[8 * b] = t0.x; xin[8 * b + 1] = t0.y; xin[8 * b + 2] = t0.z; xin[8 * b + 3] = t0.w;
-                xin[8 * b + 4] = t1.x; xin[8 * b + 5] = t1.y; xin[8 * b + 6] = t1.z; xin[8 * b + 7] = t1.w;
-            }
-            float y[PWO];
-#pragma unroll
-            for (int j = 0; j < PWO; ++j) y[j] = wq[PWI * PWO + j];
-#pragma unroll
-            for (int i = 0; i < PWI; ++i)
-#pragma unroll
-                for (int j = 0; j < PWO; ++j) y[j] = fmaf(xin[i], wq[i * PWO + j], y[j]);
-#pragma unroll
-            for (int b = 0; b < PB; ++b) {
-                float* q = a.pw_out[b] + row * 8;
-                *reinterpret_cast<float4*>(q) = make_float4(fmaxf(y[8 * b], 0.f), fmaxf(y[8 * b + 1], 0.f), fmaxf(y[8 * b + 2], 0.f), fmaxf(y[8 * b + 3], 0.f));
-                *reinterpret_cast<float4*>(q + 4) = make_float4(fmaxf(y[8 * b + 4], 0.f), fmaxf(y[8 * b + 5], 0.f), fmaxf(y[8 * b + 6], 0.f), fmaxf(y[8 * b + 7], 0.f));
-            }
-        }
-        if constexpr (EPI == 2) {
-            // conv1_2 on this kernel's own output row M, + the residual's upper half
-            float y[PWO];
-#pragma unroll
-            for (int j = 0; j < PWO; ++j) y[j] = wq[PWI * PWO + j];
-#pragma unroll
-            for (int i = 0; i < PWI; ++i)
-#pragma unroll
-                for (int j = 0; j < PWO; ++j) y[j] = fmaf(o[i / 8][i % 8], wq[i * PWO + j], y[j]);
-#pragma unroll
-            for (int b = 0; b < PB; ++b) {
-                const float* r = a.pw_aux[b] + row * 8;
-                float* q = a.pw_out[b] + row * 8;
-                *reinterpret_cast<float4*>(q) = make_float4(y[8 * b] + r[0], y[8 * b + 1] + r[1], y[8 * b + 2] + r[2], y[8 * b + 3] + r[3]);
-                *reinterpret_cast<float4*>(q + 4) = make_float4(y[8 * b + 4] + r[4], y[8 * b + 5] + r[5], y[8 * b + 6] + r[6], y[8 * b + 7] + r[7]);
-            }
-        }
-        if constexpr (EPI == 3) {
-            // gM = (gI[upper half] @ W12^T) * (M > 0): per channel ci of M the gradient channels ascending (the backward-data chain)
-            if (a.pw_on) {          // uniform
-                constexpr int NHB = PWI / 8;                         // blocks of the upper half = of M
-                constexpr int HI0 = GB == 2 ? 1 : 0;                 // its first local block: C = 16: the launch makes blocks 0, 1; C = 32: 2, 3
-#pragma unroll
-                for (int b = 0; b < NHB; ++b) {
-                    const float* mrow = a.pw_aux[b] + row * 8;
-                    float g[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float* wrow = wq + (8 * b + j) * PWO;
-                        float t = 0.0f;
-#pragma unroll
-                        for (int co = 0; co < PWO; ++co) t = fmaf(o[HI0 + co / 8][co % 8], wrow[co], t);
-                        g[j] = mrow[j] > 0.0f ? t : 0.0f;
-                    }
-                    float* q = a.pw_out[b] + row * 8;
-                    *reinterpret_cast<float4*>(q) = make_float4(g[0], g[1], g[2], g[3]);
-                    *reinterpret_cast<float4*>(q + 4) = make_float4(g[4], g[5], g[6], g[7]);
-                }
-            }
-        }
+        wc_epilogue<GB, PB, EPI>(a, acc, row, wq);
     }
 }
 
 template <int GB, int PB, bool BWD, int EPI = 0>
 static int wc_launch(const WcArgs& a, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n, hipStream_t s) {
-    constexpr int PWI = EPI == 1 ? 8 * GB : EPI == 2 ? 8 * PB : EPI == 3 ? 4 * GB : EPI == 4 ? 16 * GB : 0;
-    constexpr int PWO = EPI == 1 ? 8 * PB : EPI == 2 ? 8 * PB : EPI == 3 ? 4 * GB : EPI == 4 ? 8 * GB : 0;
+    constexpr int PWI = WcPw<GB, PB, EPI>::PWI, PWO = WcPw<GB, PB, EPI>::PWO;
     constexpr size_t lds = ((size_t)27 * GB * PB * 64 + (size_t)PWI * PWO + PWO) * 4;
-    static const int cus = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) v = 256;
-        return v;
-    }();
-    // the weight image is built once per workgroup, which then loops over row tiles (two workgroups per CU as in occ_conv7_k)
-    const int64_t tiles = linr_grid(n, LINR_CONV_BLOCK);
-    const int64_t want = (int64_t)cus * 2;
-    const int64_t per = (tiles + want - 1) / want;
-    const int64_t grid = (tiles + per - 1) / per;
+    const int64_t grid = wc_grid(n);
     wconv_k<GB, PB, BWD, EPI><<<(unsigned)grid, LINR_CONV_BLOCK, lds, s>>>(a, lo, mask, ld, n);
     return linr_launch_rc();
 }
@@ -318,7 +160,7 @@ static int spconv_wide_impl(int32_t bwd, const float* const* in_h, const int32_t
     if (n < 0 || ld < n || cin < 1 || cin > 32 || cout < 8 || cout > 32 || cout % 8) return LINR_EINVAL;
     if (n == 0) return 0;
     if (!in_h || !out_h || !lo || !mask || !W) return LINR_EINVAL;
-    if (flags & ~(LINR_RELU | LINR_ACCUM | LINR_RELU_MASK)) return LINR_EINVAL;
+    if (flags & ~(LINR_RELU | LINR_ACCUM | LINR_RELU_MASK | LINR_MUL_BF16)) return LINR_EINVAL;
     if ((flags & LINR_RELU_MASK) && !act_h) return LINR_EINVAL;
     if (bwd && cin % 8) return LINR_EINVAL;
     if (!bwd && cin > 8 && cin % 8) return LINR_EINVAL;
@@ -330,7 +172,7 @@ static int spconv_wide_impl(int32_t bwd, const float* const* in_h, const int32_t
     for (int g = 0; g < WC_MAXB; ++g) a.in[g] = g < gb ? in_h[g] : nullptr;
     for (int g = 0; g < gb; ++g)
         if (!a.in[g] || !linr_aligned16(a.in[g])) return a.in[g] ? LINR_EALIGN : LINR_EINVAL;
-    a.W = W; a.bias = bwd ? nullptr : bias; a.cin = cin; a.cout = cout; a.gvalid = gch; a.flags = flags;
+    a.W = W; a.bias = bwd ? nullptr : bias; a.cin = cin; a.cout = cout; a.gvalid = gch; a.flags = flags & ~LINR_MUL_BF16;
     a.pw_W = nullptr; a.pw_b = nullptr; a.pw_aux[0] = a.pw_aux[1] = nullptr; a.pw_out[0] = a.pw_out[1] = nullptr; a.pw_on = 0; a.pw_hi0 = 0;
     int epi = 0;
     if (pw && pw->mode != 0) {
@@ -372,7 +214,8 @@ static int spconv_wide_impl(int32_t bwd, const float* const* in_h, const int32_t
             if (!a.pw_on) e = 0;
             else if (a.pw_hi0 != (gb == 2 ? 1 : 0)) return LINR_EINVAL;          // the kernel's compile-time layout
         }
-        const int rc = bwd ? wc_dispatch<true>(gb, pb, e, a, lo, mask, ld, n, s) : wc_dispatch<false>(gb, pb, e, a, lo, mask, ld, n, s);
+        const int rc = (flags & LINR_MUL_BF16) ? linr_wide_mul_conv(bwd, gb, pb, e, a, lo, mask, ld, n, s)          // csrc/wide_mul.hip
+                       : bwd ? wc_dispatch<true>(gb, pb, e, a, lo, mask, ld, n, s) : wc_dispatch<false>(gb, pb, e, a, lo, mask, ld, n, s);
         if (rc) return rc;
     }
     return 0;
@@ -402,7 +245,6 @@ extern "C" int linr_spconv_wide_pw(int32_t bwd, const float* const* in_h, const 
 // transposing kernel (csrc/wgrad.hip: spconv_wgrad_t_k), all pairs of the convolution as the groups of grouped launches (8 pairs per
 // launch) into ONE slab, then one fixed-order reduction straight into the dense [27][cin][cout] kernel gradient and the bias gradient
 // (round 3: a launch, a reduction and two copies per pair).
-#define WW_PAIR 1736          // slab elements of a pair: [27][8][8] kernel block + 8 bias sums
 __global__ __launch_bounds__(LINR_BLOCK) void wide_slab_reduce_k(const float* __restrict__ slab, int nblocks, int npairs, int cin, int cout,
                                                                  float* __restrict__ gW, float* __restrict__ gb) {
     // 16 elements per workgroup, 16 slices of the slab rows per element (each 4 interleaved partial sums), slices folded in order
@@ -447,16 +289,7 @@ __global__ __launch_bounds__(LINR_BLOCK) void wide_slab_reduce_k(const float* __
 // gathered rows multiplied with the 8-row tiles of NGB gradient blocks (group = input block, blockIdx.y) - the gathers, index loads
 // and LDS transposes of a pair launch are paid once per input block instead of once per (input, gradient) pair; per accumulator the
 // same v_mfma_f32_4x4x1 sequence in the same row order and the same wave fold as the pair kernel, so the slab holds the same bits.
-#define WW_WAVES 4
 #define WW_PITCH 288                  // bytes per tap in the LDS image: 8 rows x 32 B + 32 B
-#define WW_TAPS 28                    // 27 taps + the dump slot of the 7th gather's unused lane group
-struct WwArgs {
-    const float* in[WC_MAXB];         // the groups' input blocks (zero row at [-8, 0))
-    const float* g[WC_MAXB][WC_MAXB]; // per group: the gradient blocks [n][8] (one convolution: the same for every group)
-    int cw[WC_MAXB];                  // live channels of a group's input block
-    int64_t slab_off[WC_MAXB];        // per group: where its NGB pairs start in a slab row (one convolution: bi * nbo * WW_PAIR)
-    float* slab; int64_t block_stride;
-};
 
 template <int NGB>
 __global__ __launch_bounds__(WW_WAVES * 64) void wwgrad_k(WwArgs a, const int32_t* __restrict__ tile8t, int64_t n) {
@@ -602,48 +435,18 @@ __global__ __launch_bounds__(WW_WAVES * 64) void wwgrad_k(WwArgs a, const int32_
             });
         });
     });
-    // bias sums: lane l holds the partial column sum of channel gc over rows gu, gu + 8, ...: the 8 row phases by a fixed xor tree
-#pragma unroll
-    for (int b = 0; b < NGB; ++b) {
-        float t = bsum[b];
-#pragma unroll
-        for (int m = 8; m < 64; m <<= 1) t += __shfl_xor(t, m, 64);
-        if (lane < 8) sbias[b][wave][lane] = t;
-    }
-    const int cinv = a.cw[bi];
-    const int per_k = cinv * 8, total = 27 * per_k;
-    float* dst0 = a.slab + (int64_t)blockIdx.x * a.block_stride + a.slab_off[bi];
-    static_for<NGB>([&](auto bc) {
-        constexpr int b = decltype(bc)::value;
-        __syncthreads();                       // the images (b = 0) or the previous block's fold are done with
-        {
-            float* mine = sacc + (wave * 64 + lane) * (NA + 1);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) mine[(c * 2 + h) * 4 + i] = acc[b][c][h][i];
-        }
-        __syncthreads();
-        float* dst = dst0 + (int64_t)b * WW_PAIR;
-        const int tid = threadIdx.x;
-        if (tid < 8) {
-            float t = sbias[b][0][tid];
-            for (int w = 1; w < WW_WAVES; ++w) t += sbias[b][w][tid];
-            dst[1728 + tid] = t;
-        }
-        for (int e = tid; e < total; e += WW_WAVES * 64) {
-            const int kq = e / per_k, r = e - kq * per_k;
-            const int ci = r >> 3, co = r & 7;
-            const int idx = (2 * kq + (ci >> 2)) * (NA + 1) + ((ci & 3) * 2 + (co >> 2)) * 4 + (co & 3);
-            constexpr int W = 64 * (NA + 1);
-            float t = sacc[idx];
-#pragma unroll
-            for (int w = 1; w < WW_WAVES; ++w) t += sacc[w * W + idx];
-            dst[e] = t;
-        }
-    });
+    ww_fold<NGB>(acc, bsum, sacc, sbias, a, bi, wave, lane);
+}
+
+// nblk persistent workgroups per group, `groups` groups of ngb gradient blocks: the fp32 kernel above or its bf16-product form
+static int ww_launch(int ngb, int nblk, int groups, const WwArgs& a, const int32_t* tile8t, int64_t n, uint32_t flags, hipStream_t s) {
+    if (flags & LINR_MUL_BF16) return linr_wide_mul_wgrad(ngb, nblk, groups, a, tile8t, n, s);
+    const dim3 grid(nblk, groups);
+    if (ngb == 1) wwgrad_k<1><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
+    else if (ngb == 2) wwgrad_k<2><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
+    else if (ngb == 4) wwgrad_k<4><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
+    else return LINR_EINVAL;
+    return linr_launch_rc();
 }
 
 extern "C" size_t linr_spconv_wgrad_wide_slab_bytes(int32_t cin, int32_t cout) {
@@ -653,15 +456,20 @@ extern "C" size_t linr_spconv_wgrad_wide_slab_bytes(int32_t cin, int32_t cout) {
 
 // in_h: HOST array of the ceil(cin / 8) input blocks (zero row in front), g_h: of the cout / 8 output-gradient blocks [n][8];
 // nbr / tile8t: the frame's kernel map and its tiled copy (linr_kmap_tile8t); slab: linr_spconv_wgrad_wide_slab_bytes(cin, cout) bytes.
-// Writes gW [27][cin][cout] and gb [cout] (gb may be NULL).
-extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
-                                      const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, void* stream) {
+// Writes gW [27][cin][cout] and gb [cout] (gb may be NULL).  flags: LINR_MUL_BF16 (the products on bf16 matrix instructions,
+// csrc/wide_mul.hip: needs the tiled table and cout in {8, 16, 32} - there is no pair-by-pair form of it) or 0.
+extern "C" int linr_spconv_wgrad_wide_f(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
+                                        const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, uint32_t flags,
+                                        void* stream) {
+    if (flags & ~LINR_MUL_BF16) return LINR_EINVAL;
     if (n < 0 || ld < n || cin < 1 || cin > 32 || cout < 8 || cout > 32 || cout % 8 || (cin > 8 && cin % 8)) return LINR_EINVAL;
     if (!in_h || !g_h || !nbr || !slab) return LINR_EINVAL;
     if (!linr_rows_fit32(n)) return LINR_EINVAL;
+    const int nbi = (cin + 7) / 8, nbo = cout / 8, npairs = nbi * nbo;
+    const bool one_launch = tile8t && linr_aligned16(tile8t) && (nbo == 1 || nbo == 2 || nbo == 4);
+    if ((flags & LINR_MUL_BF16) && !one_launch) return LINR_EINVAL;          // no quiet fp32 pair-by-pair form
     hipStream_t s = (hipStream_t)stream;
     linr_poison_hook(s, PK_WIDE);
-    const int nbi = (cin + 7) / 8, nbo = cout / 8, npairs = nbi * nbo;
     if (n == 0) {
         if (!gW) return LINR_EINVAL;                     // deferred reductions (gW == NULL) need rows
         if (hipMemsetAsync(gW, 0, (size_t)27 * cin * cout * sizeof(float), s) != hipSuccess) return LINR_EINVAL;
@@ -670,7 +478,7 @@ extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, con
     for (int i = 0; i < nbi; ++i) if (!in_h[i] || !linr_aligned16(in_h[i])) return in_h[i] ? LINR_EALIGN : LINR_EINVAL;
     for (int i = 0; i < nbo; ++i) if (!g_h[i]) return LINR_EINVAL;
     int nblk = LINR_WG_BLOCKS;
-    if (tile8t && linr_aligned16(tile8t) && (nbo == 1 || nbo == 2 || nbo == 4)) {
+    if (one_launch) {
         // one launch: group = input block, all gradient blocks from its one gather
         WwArgs a;
         for (int i = 0; i < WC_MAXB; ++i) {
@@ -681,11 +489,7 @@ extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, con
         a.slab = slab; a.block_stride = (int64_t)npairs * WW_PAIR;
         // 256 persistent blocks per input block (sweep 128 .. 512 on loot10, profiles/r04_wide.txt: 16 -> 16 86 us at 256, 96 at 384, 108 at 512)
         nblk = 256;
-        const dim3 grid(nblk, nbi);
-        if (nbo == 1) wwgrad_k<1><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
-        else if (nbo == 2) wwgrad_k<2><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
-        else wwgrad_k<4><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
-        const int rc = linr_launch_rc();
+        const int rc = ww_launch(nbo, nblk, nbi, a, tile8t, n, flags, s);
         if (rc) return rc;
     } else
     for (int p0 = 0; p0 < npairs; p0 += LINR_MAXG) {
@@ -704,12 +508,20 @@ extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, con
     return linr_launch_rc();
 }
 
+extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
+                                      const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, void* stream) {
+    return linr_spconv_wgrad_wide_f(in_h, cin, g_h, cout, nbr, tile8t, ld, n, slab, gW, gb, 0u, stream);
+}
+
 // Two convolutions of the SAME shape (cin = cout = h in {8, 16}: conv0_1 and conv1_1 of a wide Inception layer, which do not depend on
 // each other) as ONE launch of 2 h / 8 groups: alone, an 8 -> 8 weight gradient is 256 workgroups - one wave per SIMD.  Partials only:
 // a slab row holds convolution A's pairs, then B's (row stride 2 (h / 8)^2 WW_PAIR floats); reduce with linr_wide_reduce_many (kind 0,
 // slab = the row's A or B part, ws_ci = the row stride).
-extern "C" int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h, const float* const* gB_h,
-                                       int32_t h, const int32_t* tile8t, int64_t n, float* slab, void* stream) {
+// flags: LINR_MUL_BF16 or 0, as in linr_spconv_wgrad_wide_f.
+extern "C" int linr_spconv_wgrad_wide2_f(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h,
+                                         const float* const* gB_h, int32_t h, const int32_t* tile8t, int64_t n, float* slab, uint32_t flags,
+                                         void* stream) {
+    if (flags & ~LINR_MUL_BF16) return LINR_EINVAL;
     if (n < 1 || (h != 8 && h != 16) || !inA_h || !gA_h || !inB_h || !gB_h || !tile8t || !slab) return LINR_EINVAL;
     if (!linr_aligned16(tile8t) || !linr_rows_fit32(n)) return LINR_EINVAL;
     const int nb = h / 8, npairs = nb * nb;
@@ -727,10 +539,12 @@ extern "C" int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* c
     a.slab = slab; a.block_stride = (int64_t)2 * npairs * WW_PAIR;
     hipStream_t s = (hipStream_t)stream;
     linr_poison_hook(s, PK_WIDE);
-    const dim3 grid(256, 2 * nb);
-    if (nb == 1) wwgrad_k<1><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
-    else wwgrad_k<2><<<grid, WW_WAVES * 64, 0, s>>>(a, tile8t, n);
-    return linr_launch_rc();
+    return ww_launch(nb, 256, 2 * nb, a, tile8t, n, flags, s);
+}
+
+extern "C" int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h, const float* const* gB_h,
+                                       int32_t h, const int32_t* tile8t, int64_t n, float* slab, void* stream) {
+    return linr_spconv_wgrad_wide2_f(inA_h, gA_h, inB_h, gB_h, h, tile8t, n, slab, 0u, stream);
 }
 
 // slab rows linr_spconv_wgrad_wide writes (the `nblocks` of its deferred reduction): 256 with the tiled table and cout in {8, 16, 32}

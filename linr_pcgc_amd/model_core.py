@@ -838,6 +838,9 @@ class FlatAdam:
         self.t = steps.pop() if steps else 0
 
 
+TRAIN_PRECISIONS = ('f32', 'bf16', 'bf16-deep', 'bf16-mul')
+
+
 def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
     """One iteration of main.py:305-321 on a batched frame: bits -> loss = bits/point_num -> backward -> Adam ->
     StepLR, as ONE C-ABI call (linr_net_train_step).  Returns the device-resident bits accumulator (float64[1]);
@@ -845,6 +848,13 @@ def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
     per-GOP vector that is cleared once per epoch) - saves the per-step allocation + fill.
     qat_bitdepth > 0: the quantisation-aware step (linr_step_args.qparams) - bits and gradient are those of the
     weights the model codec would code with at that depth (quant_uniform2 and back), Adam updates the fp32 master."""
+    # what cannot run is refused before anything is allocated or called
+    if model.train_precision not in TRAIN_PRECISIONS:
+        raise ValueError('train_precision must be one of ' + ', '.join(repr(p) for p in TRAIN_PRECISIONS))
+    if model._wide is not None and model.train_precision in ('bf16', 'bf16-deep'):
+        raise _lib.LinrError('the bf16 training executor exists for hidden_channel_conv=8 only')
+    if model._wide is None and model.train_precision == 'bf16-mul':          # the wide step with bf16 products (wide_net._mul)
+        raise _lib.LinrError("train_precision 'bf16-mul' exists for hidden_channel_conv 16 / 32 only: width 8 has the bf16 training executor")
     bits = torch.zeros(1, dtype=torch.float64, device=frame.device) if out is None else out
     extra = {}                           # keyword arguments of the step beyond the common ones
     if qat_bitdepth:
@@ -852,8 +862,6 @@ def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
             raise _lib.LinrError('quantisation-aware training exists for hidden_channel_conv=8 only')
         extra = {'qparams': model.qat_parameters(), 'bitdepth': int(qat_bitdepth)}
     if model._wide is not None:          # hidden_channel_conv 16 / 32: the channel-blocked executor + the segment-wise Adam
-        if model.train_precision != 'f32':
-            raise _lib.LinrError('the bf16 training executor exists for hidden_channel_conv=8 only')
         with torch.no_grad(), model._wide.lock:          # (the pooled buffers of the forward must survive until the backward has run)
             tape = model._wide.forward(frame, 0, 8, None, bits, keep=True, pool=True)
             model._ensure_grad_views()
@@ -865,8 +873,6 @@ def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
         opt.scheduler_step()
         return bits
     t, t_scale = opt.advance(frame)
-    if model.train_precision not in ('f32', 'bf16', 'bf16-deep'):
-        raise ValueError("train_precision must be 'f32', 'bf16' or 'bf16-deep'")
     if model.train_precision == 'bf16' and model.block_layers != 1:
         raise _lib.LinrError('the bf16 training executor supports block_layers=1 only')
     if model.train_precision != 'f32':                   # one executor; 'bf16-deep' lets it take block_layers 2..4

@@ -190,17 +190,26 @@ def _ptr_array(blocks):
     return (ctypes.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks])
 
 
-def spconv_wide(xs, lo, mask, n, kernel, bias=None, bwd=False, res=None, act=None, relu=False, outs=None, accumulate=False, pw=None):
+def _mul_flag(mul):
+    """mul='f32' | 'bf16' of the wide convolutions -> LINR_MUL_BF16 or 0."""
+    if mul not in ('f32', 'bf16'):
+        raise ValueError("mul must be 'f32' or 'bf16', got %r" % (mul,))
+    return _lib.LINR_MUL_BF16 if mul == 'bf16' else 0
+
+
+def spconv_wide(xs, lo, mask, n, kernel, bias=None, bwd=False, res=None, act=None, relu=False, outs=None, accumulate=False, pw=None,
+                mul='f32'):
     """linr_spconv_wide: a 3x3x3 convolution on channel-blocked activations, one gather of all input blocks per tap.
     xs: the gathered blocks (views buf[1:] of [n+1, 8] buffers whose row 0 is zero); kernel [27, cin, cout]; outs / res / act: lists
     of [n, 8] blocks of the produced side (cout / 8 forward, cin / 8 backward).  pw = (mode, W, b, aux blocks, out2 blocks): a pointwise
-    layer of the wide Inception layer fused into the epilogue (linr_spconv_wide_pw, include/linr_hip.h)."""
+    layer of the wide Inception layer fused into the epilogue (linr_spconv_wide_pw, include/linr_hip.h).  mul='bf16': the convolution's
+    products on bf16 matrix instructions (LINR_MUL_BF16: operands rounded at the multiply, fp32 sums; everything else as with 'f32')."""
     import ctypes
     cin, cout = kernel.shape[1], kernel.shape[2]
     npb = (cin if bwd else cout) // 8
     if outs is None:
         outs = [torch.empty((n, 8), dtype=torch.float32, device=xs[0].device) for _ in range(npb)]
-    flags = (LINR_RELU if relu else 0) | (LINR_ACCUM if accumulate else 0) | (LINR_RELU_MASK if act is not None else 0)
+    flags = (LINR_RELU if relu else 0) | (LINR_ACCUM if accumulate else 0) | (LINR_RELU_MASK if act is not None else 0) | _mul_flag(mul)
     args = (1 if bwd else 0, _ptr_array(xs), lo.data_ptr(), mask.data_ptr(), lo.stride(0), n, kernel.data_ptr(), _ptr(bias), cin, cout,
             None if res is None else _ptr_array(res), None if act is None else _ptr_array(act), _ptr_array(outs), flags)
     if pw is None:
@@ -215,10 +224,11 @@ def spconv_wide(xs, lo, mask, n, kernel, bias=None, bwd=False, res=None, act=Non
     return outs
 
 
-def spconv_wgrad_wide(xs, gouts, nbr, tile8t, n, cin, cout, gw=None, gb=None, defer=None):
+def spconv_wgrad_wide(xs, gouts, nbr, tile8t, n, cin, cout, gw=None, gb=None, defer=None, mul='f32'):
     """linr_spconv_wgrad_wide: kernel / bias gradient of a convolution on channel-blocked activations (one launch whose groups are the
     input blocks, one reduction).  gw [27, cin, cout] / gb [cout]: contiguous destinations (e.g. views of the flat gradient) or None.
-    defer: a list - the partials stay in their slab and the reduction is appended to it for wide_reduce_many()."""
+    defer: a list - the partials stay in their slab and the reduction is appended to it for wide_reduce_many().  mul='bf16': the products
+    x g on bf16 matrix instructions (LINR_MUL_BF16; needs tile8t), the bias gradient stays the fp32 sum of g."""
     L = _lib.lib()
     dev = xs[0].device
     if gw is None:
@@ -228,24 +238,25 @@ def spconv_wgrad_wide(xs, gouts, nbr, tile8t, n, cin, cout, gw=None, gb=None, de
     assert gw.is_contiguous() and gb.is_contiguous()
     slab = _lib.scratch(L.linr_spconv_wgrad_wide_slab_bytes(cin, cout), dev)
     deferred = defer is not None and n > 0
-    check(L.linr_spconv_wgrad_wide(_ptr_array(xs), cin, _ptr_array(gouts), cout, nbr.data_ptr(), _ptr(tile8t), nbr.stride(0), n,
-                                   slab.data_ptr(), None if deferred else gw.data_ptr(), gb.data_ptr(), _stream()), 'linr_spconv_wgrad_wide')
+    check(L.linr_spconv_wgrad_wide_f(_ptr_array(xs), cin, _ptr_array(gouts), cout, nbr.data_ptr(), _ptr(tile8t), nbr.stride(0), n,
+                                     slab.data_ptr(), None if deferred else gw.data_ptr(), gb.data_ptr(), _mul_flag(mul), _stream()),
+          'linr_spconv_wgrad_wide_f')
     if deferred:
         nblk = int(L.linr_spconv_wgrad_wide_blocks(cout, 1 if tile8t is not None else 0))
         defer.append((_lib.LinrWideReduce(0, nblk, cin, cout, 0, 0, slab.data_ptr(), gw.data_ptr(), gb.data_ptr()), slab, gw, gb))
     return gw, gb
 
 
-def spconv_wgrad_wide2(xsA, gsA, gwA, gbA, xsB, gsB, gwB, gbB, tile8t, n, defer):
+def spconv_wgrad_wide2(xsA, gsA, gwA, gbA, xsB, gsB, gwB, gbB, tile8t, n, defer, mul='f32'):
     """linr_spconv_wgrad_wide2: the weight gradients of two h -> h convolutions (h = 8 len(xsA)) as one launch; their reductions are
-    appended to `defer` (wide_reduce_many)."""
+    appended to `defer` (wide_reduce_many).  mul: as in spconv_wgrad_wide."""
     L = _lib.lib()
     nb = len(xsA)
     h = 8 * nb
     stride = 2 * nb * nb * 1736
     slab = _lib.scratch(256 * stride * 4, xsA[0].device)
-    check(L.linr_spconv_wgrad_wide2(_ptr_array(xsA), _ptr_array(gsA), _ptr_array(xsB), _ptr_array(gsB), h, tile8t.data_ptr(), n,
-                                    slab.data_ptr(), _stream()), 'linr_spconv_wgrad_wide2')
+    check(L.linr_spconv_wgrad_wide2_f(_ptr_array(xsA), _ptr_array(gsA), _ptr_array(xsB), _ptr_array(gsB), h, tile8t.data_ptr(), n,
+                                      slab.data_ptr(), _mul_flag(mul), _stream()), 'linr_spconv_wgrad_wide2_f')
     for cv, (gw, gb) in enumerate(((gwA, gbA), (gwB, gbB))):
         assert gw.is_contiguous() and gb.is_contiguous()
         defer.append((_lib.LinrWideReduce(0, 256, h, h, stride, 0, slab.data_ptr() + 4 * cv * nb * nb * 1736, gw.data_ptr(), gb.data_ptr()),

@@ -50,10 +50,12 @@ def parse(argv=None):
                     help='arithmetic of the coding forward: f32, or bf16 features with the uint8 weight codes de-quantised in-kernel (BASELINE config[4]); '
                          'every --hidden-channel-conv (8, 16, 32) and --block_layers (1..4); wide models train in fp32, deeper ones in fp32 unless '
                          '--train-precision bf16-deep asks otherwise; travels in side_info.json')
-    ap.add_argument('--train-precision', '--train_precision', dest='train_precision', default=None, choices=['f32', 'bf16', 'bf16-deep'],
+    ap.add_argument('--train-precision', '--train_precision', dest='train_precision', default=None, choices=['f32', 'bf16', 'bf16-deep', 'bf16-mul'],
                     help='arithmetic of the overfit step: f32 (the headline), or bf16 feature / gradient rows with fp32 master weights and '
                          'accumulation (BASELINE config[4] "bf16 SparseConv"; hidden_channel_conv 8, block_layers 1); bf16-deep: the same '
-                         'executor for --block_layers 1..4 (opt-in; at 1 it is bf16).  Default: follows --precision')
+                         'executor for --block_layers 1..4 (opt-in; at 1 it is bf16); bf16-mul (opt-in, --hidden-channel-conv 16 / 32 only): the fp32 '
+                         'step with the products of its 3x3x3 convolutions on bf16 matrix instructions (operands rounded at the multiply, fp32 '
+                         'sums and storage).  Default: follows --precision')
     ap.add_argument('--device-codes', '--device_codes', dest='device_codes', action='store_true',
                     help="the range coder's 16-bit code values and symbol bits are computed on the GPU (linr_ac_codes): 17 bits per symbol "
                          'cross to the host instead of 40; the streams are byte for byte those of the default path')
@@ -131,7 +133,7 @@ def parse(argv=None):
 def train_precision(args):
     """--train-precision, or what --precision says when it is not given (--precision bf16 = BASELINE config[4]: bf16 SparseConv for
     the overfit AND the codec); the wide models (hidden_channel_conv 16 / 32) train in fp32 only, deeper block_in variants in fp32 unless --train-precision
-    bf16-deep is given (this default rule never picks it)."""
+    bf16-deep is given; bf16-mul (wide models only) is opt-in as well (this default rule never picks either)."""
     tp = getattr(args, 'train_precision', None)
     if tp is None:
         tp = getattr(args, 'precision', 'f32')

@@ -17,6 +17,10 @@ The schedule is Python (~190 launches per step; GPU-bound on the BASELINE-sized 
 training step at widths 16 / 32 on the loot-like frame (profiles/r04_wide.txt; ~3.7x / ~14x the convolution work of width 8).  The
 8-wide model (every BASELINE config, the reference's default and its shipped checkpoint) never comes here.
 
+train_precision 'bf16-mul' (opt-in): a training forward (keep=True) and its backward run the same launches with LINR_MUL_BF16 - the
+products of the 3x3x3 convolutions on bf16 matrix instructions, operands rounded at the multiply, everything else fp32 (csrc/wide_mul.hip;
+_mul() below; 5.31 / 13.8 ms per step, profiles/wide_bf16_mul.txt).  Every other forward multiplies in fp32.
+
 forward_bf16 is the inference forward of --precision bf16 (BASELINE config[4]'s numerics) on csrc/wide_bf16.hip: the uint8 weight codes
 as the model, bf16 channel-blocked activations, fp32 accumulation, one launch per layer in the same schedule (profiles/r07_wide_bf16.txt).
 """
@@ -79,6 +83,12 @@ def _defer():
     return getattr(_TLS, 'defer', None)
 
 
+def _mul():
+    """What the running pass multiplies its 3x3x3 convolutions in: 'bf16' inside a training forward (keep=True) / backward of a model
+    with train_precision 'bf16-mul', else 'f32' (every codec, decoder and probability forward)."""
+    return getattr(_TLS, 'mul', 'f32')
+
+
 def _blocks(n, nb, dev):
     """nb zero-padded [n, 8] matrices (views buf[1:] of [n + 1, 8] buffers whose row 0 is zero)."""
     if _pool() is not None:
@@ -113,7 +123,8 @@ class _Conv:
         pw: a pointwise layer fused into the epilogue (ops.spconv_wide)."""
         n = xs[0].shape[0]
         outs = _blocks(n, self.nbo, xs[0].device)
-        ops.spconv_wide(xs[:self.nbi], net.lo, net.mask, n, self.mod.kernel, self.mod.bias.reshape(-1), res=res, relu=relu, outs=outs, pw=pw)
+        ops.spconv_wide(xs[:self.nbi], net.lo, net.mask, n, self.mod.kernel, self.mod.bias.reshape(-1), res=res, relu=relu, outs=outs, pw=pw,
+                        mul=_mul())
         return outs
 
     def bwd(self, net, xs, gouts, gins=None, act=None, need_input_grad=True, res=None, pw=None, wgrad=True):
@@ -124,7 +135,7 @@ class _Conv:
         # fixed-order reduction straight into the parameter gradients (views of the flat gradient)
         if wgrad:
             ops.spconv_wgrad_wide(xs[:self.nbi], gouts[:self.nbo], net.nbr_full, net.tile8t, n, self.ci, self.co,
-                                  gw=self.mod.kernel.grad, gb=self.mod.bias.grad.reshape(-1), defer=_defer())
+                                  gw=self.mod.kernel.grad, gb=self.mod.bias.grad.reshape(-1), defer=_defer(), mul=_mul())
         if not need_input_grad:
             return None
         fresh = gins is None
@@ -135,7 +146,7 @@ class _Conv:
         acc = gins[0][1]
         assert all(g[1] == acc for g in gins)
         ops.spconv_wide(gouts[:self.nbo], net.lo, net.mask, n, self.mod.kernel, None, bwd=True, act=act, res=res,
-                        outs=[g[0] for g in gins], accumulate=acc, pw=pw)
+                        outs=[g[0] for g in gins], accumulate=acc, pw=pw, mul=_mul())
         for g in gins:
             g[1] = True
         return [g for g, _ in gins] if fresh else None
@@ -263,7 +274,7 @@ class _Block:
             if pair:
                 c01, c11 = q['c01'].mod, q['c11'].mod
                 ops.spconv_wgrad_wide2(t['h0'], g_i[:nh], c01.kernel.grad, c01.bias.grad.reshape(-1), t['h1'], g_m, c11.kernel.grad,
-                                       c11.bias.grad.reshape(-1), net.tile8t, n, _defer())
+                                       c11.bias.grad.reshape(-1), net.tile8t, n, _defer(), mul=_mul())
             # the layer's input gradient: the residual's share g_i rides in conv0_0's backward-data epilogue (+ res), conv1_0's share
             # is added last - and with it, for the block's first layer of a one-layer block, the ReLU mask of a = relu(first conv)
             last_mask = tape['a'] if (nl == 1 and li == nl - 1) else None
@@ -323,6 +334,10 @@ class WideNet:
         self._built = True
 
     # ---- shared pieces ------------------------------------------------------------------------------------------------
+    def _train_mul(self):
+        """The products of a training pass: bf16 for train_precision 'bf16-mul' (csrc/wide_mul.hip), else fp32."""
+        return 'bf16' if getattr(self.model, 'train_precision', 'f32') == 'bf16-mul' else 'f32'
+
     def _bind(self, frame):
         if not self._built:
             self._build()
@@ -366,10 +381,11 @@ class WideNet:
                     self._pool = _Pool()
                 self._pool.reset()
             _TLS.pool = self._pool if pool else None
+            _TLS.mul = self._train_mul() if keep else 'f32'
             try:
                 return self._forward(frame, k0, k1, probs, bits, keep)
             finally:
-                _TLS.pool = None
+                _TLS.pool, _TLS.mul = None, 'f32'
 
     def _forward(self, frame, k0, k1, probs, bits, keep):
         x0, sce_tape = self._scale_context(frame, keep)
@@ -399,11 +415,12 @@ class WideNet:
         with self.lock:
             _TLS.pool = self._pool if pool else None
             _TLS.defer = []
+            _TLS.mul = self._train_mul()
             try:
                 self._backward(frame, tape, gscale)
                 ops.wide_reduce_many(_TLS.defer)          # the ~64 slab reductions of the pass, 32 per launch
             finally:
-                _TLS.pool, _TLS.defer = None, None
+                _TLS.pool, _TLS.defer, _TLS.mul = None, None, 'f32'
 
     def _backward(self, frame, tape, gscale):
         self._bind(frame)
