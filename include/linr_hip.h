@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LINR_ABI_VERSION 26
+#define LINR_ABI_VERSION 27
 #define LINR_API __attribute__((visibility("default")))
 
 #define LINR_EINVAL   (-1)   /* bad argument (null pointer, negative size, unsupported channel count) */
@@ -41,7 +41,7 @@ extern "C" {
 #define LINR_NO_BIAS   8u
 #define LINR_PAD_ROW  16u    /* the gathered operand has a readable all-zero row at index -1 (in - in_ld):
                                 absent neighbours are read from it instead of being branched around      */
-#define LINR_MUL_BF16 16u    /* the wide 3x3x3 convolutions only (linr_spconv_wide, _wide_pw, linr_spconv_wgrad_wide_f, _wide2_f;
+#define LINR_MUL_BF16 16u    /* the wide 3x3x3 convolutions only (linr_spconv_wide, linr_spconv_wgrad_wide, _wide2;
                                 they take no LINR_PAD_ROW): the PRODUCTS on bf16 matrix instructions - operands rounded to
                                 bf16 (nearest even) at the multiply, fp32 sums; memory and everything else stay fp32    */
 
@@ -170,11 +170,8 @@ LINR_API int linr_spconv_cmap(int32_t bwd, const float* in, int32_t in_ld, const
  * cin < 8 forward only).  W [27][cin][cout], bias [cout] or NULL; flags: LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_MUL_BF16.
  * LINR_MUL_BF16 (csrc/wide_mul.hip; training option 'bf16-mul'): out = bias + sum rb(x) rb(W), backward-data gx = sum rb(g) rb(W), rb =
  * round to nearest even to bf16 of the fp32 value in memory, products exact, sums fp32; bias, residual, LINR_ACCUM, masks, ReLU and the
- * pointwise side paths of linr_spconv_wide_pw are computed in fp32 on the unrounded values, as without the flag. */
-LINR_API int linr_spconv_wide(int32_t bwd, const float* const* in_h, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                              const float* W, const float* bias, int32_t cin, int32_t cout, const float* const* res_h,
-                              const float* const* act_h, float* const* out_h, uint32_t flags, void* stream);
-/* ... with a pointwise layer of the wide Inception layer (models/resnet.py:55-60) fused into the epilogue - pw->mode:
+ * pointwise side path `pw` are computed in fp32 on the unrounded values, as without the flag.
+ * pw (NULL or mode 0: none): a pointwise layer of the wide Inception layer (models/resnet.py:55-60) fused into the epilogue - pw->mode:
  *   1 forward conv0_0 (C -> h = C / 2): out2 = relu(in @ W10 + b10) of the row itself (conv1_0)
  *   2 forward conv1_1 (h -> h): out2 = (the produced row) @ W12 + b12 + aux (conv1_2 and the residual's upper half)
  *   3 backward of the block's tail convolution (C <- C): out2 = ((produced upper half) @ W12^T) * (aux > 0), aux = M
@@ -188,23 +185,21 @@ typedef struct {
     const float* const* aux_h;
     float* const* out2_h;
 } linr_wide_pw;
-LINR_API int linr_spconv_wide_pw(int32_t bwd, const float* const* in_h, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                                 const float* W, const float* bias, int32_t cin, int32_t cout, const float* const* res_h,
-                                 const float* const* act_h, float* const* out_h, uint32_t flags, const linr_wide_pw* pw, void* stream);
+LINR_API int linr_spconv_wide(int32_t bwd, const float* const* in_h, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
+                              const float* W, const float* bias, int32_t cin, int32_t cout, const float* const* res_h,
+                              const float* const* act_h, float* const* out_h, uint32_t flags, const linr_wide_pw* pw, void* stream);
 /* Weight gradient of that convolution: gW [27][cin][cout], gb [cout] (may be NULL) from the ceil(cin / 8) input blocks in_h (zero row in
  * front) and the cout / 8 output-gradient blocks g_h: one launch whose groups are the input blocks - the gathered, LDS-transposed rows
  * of a block multiply the tiles of ALL gradient blocks (cout 8 / 16 / 32 with the tiled table; else block pair by block pair) - into
  * `slab` (linr_spconv_wgrad_wide_slab_bytes(cin, cout) bytes), then ONE fixed-order reduction into the dense tensors.
- * nbr / tile8t: the frame's kernel map [27][ld] and its tiled copy (linr_kmap_tile8t). */
+ * nbr / tile8t: the frame's kernel map [27][ld] and its tiled copy (linr_kmap_tile8t).
+ * flags: 0, or LINR_MUL_BF16, the only flag: gW = sum over rows of rb(x) rb(g) on bf16 matrix instructions with fp32 sums, gb = sum g
+ * on the unrounded gradient; the same slab layout and reduction.  It needs the one-launch form (the tiled table, 16-byte aligned, cout
+ * in {8, 16, 32}): LINR_EINVAL otherwise, and for any other bit. */
 LINR_API size_t linr_spconv_wgrad_wide_slab_bytes(int32_t cin, int32_t cout);
 LINR_API int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
-                                    const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, void* stream);
-/* The same with a flags word (linr_spconv_wgrad_wide = flags 0).  LINR_MUL_BF16, the only flag: gW = sum over rows of rb(x) rb(g) on
- * bf16 matrix instructions with fp32 sums, gb = sum g on the unrounded gradient; the same slab layout and reduction.  It needs the
- * one-launch form (the tiled table, 16-byte aligned, cout in {8, 16, 32}): LINR_EINVAL otherwise, and for any other bit. */
-LINR_API int linr_spconv_wgrad_wide_f(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
-                                      const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, uint32_t flags,
-                                      void* stream);
+                                    const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, uint32_t flags,
+                                    void* stream);
 
 /* Pointwise layers of the wide network on blocked activations (MinkowskiConvolution kernel_size 1: models/resnet.py:25-46 conv1_0,
  * conv1_2; the head's nn.Linear(C, 24): models/upsample.py:73-76) as ONE launch: out = [ReLU]([mask]((bias + in @ W) + res + old)).
@@ -237,13 +232,11 @@ typedef struct {
 LINR_API int32_t linr_spconv_wgrad_wide_blocks(int32_t cout, int32_t tiled);
 /* The weight gradients of TWO convolutions of the same shape h -> h (h in {8, 16}: conv0_1 and conv1_1 of a wide Inception layer) as one
  * launch - partials only: a slab row (2 (h / 8)^2 x 1736 floats; 256 rows) holds A's block pairs, then B's; reduce each with
- * linr_wide_reduce_many: kind 0, slab = the start of its part, nblocks 256, ws_ci = the row stride in floats. */
-LINR_API int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h, const float* const* gB_h,
-                                     int32_t h, const int32_t* tile8t, int64_t n, float* slab, void* stream);
-/* ... with a flags word (linr_spconv_wgrad_wide2 = flags 0): LINR_MUL_BF16 as in linr_spconv_wgrad_wide_f, any other bit LINR_EINVAL. */
-LINR_API int linr_spconv_wgrad_wide2_f(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h,
-                                       const float* const* gB_h, int32_t h, const int32_t* tile8t, int64_t n, float* slab, uint32_t flags,
-                                       void* stream);
+ * linr_wide_reduce_many: kind 0, slab = the start of its part, nblocks 256, ws_ci = the row stride in floats.
+ * flags: 0 or LINR_MUL_BF16 as in linr_spconv_wgrad_wide, any other bit LINR_EINVAL. */
+LINR_API int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h,
+                                     const float* const* gB_h, int32_t h, const int32_t* tile8t, int64_t n, float* slab, uint32_t flags,
+                                     void* stream);
 LINR_API int32_t linr_linear_wgrad_wide_blocks(int64_t n);
 LINR_API int linr_wide_reduce_many(const linr_wide_reduce* items_h, int32_t count, void* stream);
 

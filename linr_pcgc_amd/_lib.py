@@ -13,7 +13,7 @@ LINR_RELU, LINR_ACCUM, LINR_RELU_MASK, LINR_NO_BIAS, LINR_PAD_ROW = 1, 2, 4, 8, 
 LINR_MUL_BF16 = 16          # the wide convolutions' entries only (they take no LINR_PAD_ROW): bf16 products, fp32 sums
 LINR_FRAME_OCC_PADDED = 1
 LINR_PLY_TOKEN, LINR_PLY_COLUMNS, LINR_PLY_SHORT, LINR_PLY_RANGE = 1, 2, 4, 8
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 c_i32, c_i64, c_u32, c_f32, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 c_ptr, c_size = ctypes.c_void_p, ctypes.c_size_t
@@ -103,16 +103,13 @@ _PROTOS = {
                                        c_ptr, c_i32, c_u32, c_ptr]),
     'linr_spconv_bwd_data': (ctypes.c_int, [c_ptr, c_i32, c_ptr, c_i64, c_i64, c_ptr, c_i32, c_i32, c_ptr, c_i32,
                                             c_ptr, c_i32, c_u32, c_ptr]),
-    'linr_spconv_wide': (ctypes.c_int, [c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_ptr, ctypes.c_uint32, c_ptr]),
+    'linr_spconv_wide': (ctypes.c_int, [c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_u32,
+                                        ctypes.POINTER(LinrWidePw), c_ptr]),
     'linr_spconv_wgrad_wide_slab_bytes': (ctypes.c_size_t, [c_i32, c_i32]),
-    'linr_spconv_wgrad_wide': (ctypes.c_int, [c_ptr, c_i32, c_ptr, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'linr_spconv_wgrad_wide': (ctypes.c_int, [c_ptr, c_i32, c_ptr, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_u32, c_ptr]),
     'linr_linear_wide': (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_int32, c_ptr, ctypes.c_int32, ctypes.c_int32, c_ptr, ctypes.c_int32,
                                         ctypes.c_int32, c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_uint32, c_ptr]),
-    'linr_spconv_wide_pw': (ctypes.c_int, [c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_u32,
-                                           ctypes.POINTER(LinrWidePw), c_ptr]),
-    'linr_spconv_wgrad_wide2': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_ptr]),
-    'linr_spconv_wgrad_wide_f': (ctypes.c_int, [c_ptr, c_i32, c_ptr, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_u32, c_ptr]),
-    'linr_spconv_wgrad_wide2_f': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_u32, c_ptr]),
+    'linr_spconv_wgrad_wide2': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i64, c_ptr, c_u32, c_ptr]),
     'linr_spconv_wgrad_wide_blocks': (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),
     'linr_linear_wgrad_wide_blocks': (ctypes.c_int32, [c_i64]),
     'linr_wide_reduce_many': (ctypes.c_int, [ctypes.POINTER(LinrWideReduce), ctypes.c_int32, c_ptr]),

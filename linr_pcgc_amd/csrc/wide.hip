@@ -154,9 +154,16 @@ static int wc_dispatch(int gb, int pb, int epi, const WcArgs& a, const int32_t* 
 // fwd (bwd = 0): gathers cin channels in ceil(cin / 8) blocks (cin < 8: one block whose channels >= cin are ignored), produces cout / 8
 // blocks.  bwd (bwd = 1): gathers the output gradient in cout / 8 blocks at the mirrored taps, produces the input gradient in cin / 8
 // blocks (cin a multiple of 8).  flags: LINR_RELU, LINR_ACCUM, LINR_RELU_MASK as in linr_spconv_cmap.  Up to 32 channels either side.
-static int spconv_wide_impl(int32_t bwd, const float* const* in_h, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                            const float* W, const float* bias, int32_t cin, int32_t cout, const float* const* res_h,
-                            const float* const* act_h, float* const* out_h, uint32_t flags, const linr_wide_pw* pw, void* stream) {
+// pw (NULL or mode 0: none): a pointwise layer of the wide Inception layer fused into the epilogue (pw->mode, models/resnet.py:55-60):
+//   1  forward conv0_0 (C -> h):   out2 = relu(in @ W10 + b10) of the row itself (conv1_0);            W = W10 [C][h], b = b10
+//   2  forward conv1_1 (h -> h):   out2 = (the produced row) @ W12 + b12 + aux (conv1_2 + residual);     W = W12 [h][h], b = b12
+//   3  backward of the tail conv (C <- C): out2 = ((produced upper half) @ W12^T) * (aux > 0)  (gM);      W = W12, aux = M
+//   4  backward of conv0_0 (C <- h): produced += aux @ W10^T in front of the ReLU mask (aux = gH1);       W = W10
+// aux_h / out2_h: HOST arrays of h / 8 block pointers.  Per output the fmaf chains of linr_linear_wide, so the fused and the two-launch
+// forms give the same bits.
+extern "C" int linr_spconv_wide(int32_t bwd, const float* const* in_h, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
+                                const float* W, const float* bias, int32_t cin, int32_t cout, const float* const* res_h,
+                                const float* const* act_h, float* const* out_h, uint32_t flags, const linr_wide_pw* pw, void* stream) {
     if (n < 0 || ld < n || cin < 1 || cin > 32 || cout < 8 || cout > 32 || cout % 8) return LINR_EINVAL;
     if (n == 0) return 0;
     if (!in_h || !out_h || !lo || !mask || !W) return LINR_EINVAL;
@@ -219,25 +226,6 @@ static int spconv_wide_impl(int32_t bwd, const float* const* in_h, const int32_t
         if (rc) return rc;
     }
     return 0;
-}
-
-extern "C" int linr_spconv_wide(int32_t bwd, const float* const* in_h, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                                const float* W, const float* bias, int32_t cin, int32_t cout, const float* const* res_h,
-                                const float* const* act_h, float* const* out_h, uint32_t flags, void* stream) {
-    return spconv_wide_impl(bwd, in_h, lo, mask, ld, n, W, bias, cin, cout, res_h, act_h, out_h, flags, nullptr, stream);
-}
-
-// The same convolution with a pointwise layer of the wide Inception layer fused into its epilogue (pw->mode, models/resnet.py:55-60):
-//   1  forward conv0_0 (C -> h):   out2 = relu(in @ W10 + b10) of the row itself (conv1_0);            W = W10 [C][h], b = b10
-//   2  forward conv1_1 (h -> h):   out2 = (the produced row) @ W12 + b12 + aux (conv1_2 + residual);     W = W12 [h][h], b = b12
-//   3  backward of the tail conv (C <- C): out2 = ((produced upper half) @ W12^T) * (aux > 0)  (gM);      W = W12, aux = M
-//   4  backward of conv0_0 (C <- h): produced += aux @ W10^T in front of the ReLU mask (aux = gH1);       W = W10
-// aux_h / out2_h: HOST arrays of h / 8 block pointers.  Per output the fmaf chains of linr_linear_wide, so the fused and the two-launch
-// forms give the same bits.
-extern "C" int linr_spconv_wide_pw(int32_t bwd, const float* const* in_h, const int32_t* lo, const uint32_t* mask, int64_t ld, int64_t n,
-                                   const float* W, const float* bias, int32_t cin, int32_t cout, const float* const* res_h,
-                                   const float* const* act_h, float* const* out_h, uint32_t flags, const linr_wide_pw* pw, void* stream) {
-    return spconv_wide_impl(bwd, in_h, lo, mask, ld, n, W, bias, cin, cout, res_h, act_h, out_h, flags, pw, stream);
 }
 
 // ---- weight gradient of a wide convolution -------------------------------------------------------------------------------------------
@@ -458,9 +446,9 @@ extern "C" size_t linr_spconv_wgrad_wide_slab_bytes(int32_t cin, int32_t cout) {
 // nbr / tile8t: the frame's kernel map and its tiled copy (linr_kmap_tile8t); slab: linr_spconv_wgrad_wide_slab_bytes(cin, cout) bytes.
 // Writes gW [27][cin][cout] and gb [cout] (gb may be NULL).  flags: LINR_MUL_BF16 (the products on bf16 matrix instructions,
 // csrc/wide_mul.hip: needs the tiled table and cout in {8, 16, 32} - there is no pair-by-pair form of it) or 0.
-extern "C" int linr_spconv_wgrad_wide_f(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
-                                        const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, uint32_t flags,
-                                        void* stream) {
+extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
+                                      const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, uint32_t flags,
+                                      void* stream) {
     if (flags & ~LINR_MUL_BF16) return LINR_EINVAL;
     if (n < 0 || ld < n || cin < 1 || cin > 32 || cout < 8 || cout > 32 || cout % 8 || (cin > 8 && cin % 8)) return LINR_EINVAL;
     if (!in_h || !g_h || !nbr || !slab) return LINR_EINVAL;
@@ -508,19 +496,14 @@ extern "C" int linr_spconv_wgrad_wide_f(const float* const* in_h, int32_t cin, c
     return linr_launch_rc();
 }
 
-extern "C" int linr_spconv_wgrad_wide(const float* const* in_h, int32_t cin, const float* const* g_h, int32_t cout, const int32_t* nbr,
-                                      const int32_t* tile8t, int64_t ld, int64_t n, float* slab, float* gW, float* gb, void* stream) {
-    return linr_spconv_wgrad_wide_f(in_h, cin, g_h, cout, nbr, tile8t, ld, n, slab, gW, gb, 0u, stream);
-}
-
 // Two convolutions of the SAME shape (cin = cout = h in {8, 16}: conv0_1 and conv1_1 of a wide Inception layer, which do not depend on
 // each other) as ONE launch of 2 h / 8 groups: alone, an 8 -> 8 weight gradient is 256 workgroups - one wave per SIMD.  Partials only:
 // a slab row holds convolution A's pairs, then B's (row stride 2 (h / 8)^2 WW_PAIR floats); reduce with linr_wide_reduce_many (kind 0,
 // slab = the row's A or B part, ws_ci = the row stride).
-// flags: LINR_MUL_BF16 or 0, as in linr_spconv_wgrad_wide_f.
-extern "C" int linr_spconv_wgrad_wide2_f(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h,
-                                         const float* const* gB_h, int32_t h, const int32_t* tile8t, int64_t n, float* slab, uint32_t flags,
-                                         void* stream) {
+// flags: LINR_MUL_BF16 or 0, as in linr_spconv_wgrad_wide.
+extern "C" int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h,
+                                       const float* const* gB_h, int32_t h, const int32_t* tile8t, int64_t n, float* slab, uint32_t flags,
+                                       void* stream) {
     if (flags & ~LINR_MUL_BF16) return LINR_EINVAL;
     if (n < 1 || (h != 8 && h != 16) || !inA_h || !gA_h || !inB_h || !gB_h || !tile8t || !slab) return LINR_EINVAL;
     if (!linr_aligned16(tile8t) || !linr_rows_fit32(n)) return LINR_EINVAL;
@@ -540,11 +523,6 @@ extern "C" int linr_spconv_wgrad_wide2_f(const float* const* inA_h, const float*
     hipStream_t s = (hipStream_t)stream;
     linr_poison_hook(s, PK_WIDE);
     return ww_launch(nb, 256, 2 * nb, a, tile8t, n, flags, s);
-}
-
-extern "C" int linr_spconv_wgrad_wide2(const float* const* inA_h, const float* const* gA_h, const float* const* inB_h, const float* const* gB_h,
-                                       int32_t h, const int32_t* tile8t, int64_t n, float* slab, void* stream) {
-    return linr_spconv_wgrad_wide2_f(inA_h, gA_h, inB_h, gB_h, h, tile8t, n, slab, 0u, stream);
 }
 
 // slab rows linr_spconv_wgrad_wide writes (the `nblocks` of its deferred reduction): 256 with the tiled table and cout in {8, 16, 32}

@@ -853,7 +853,7 @@ def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
         raise ValueError('train_precision must be one of ' + ', '.join(repr(p) for p in TRAIN_PRECISIONS))
     if model._wide is not None and model.train_precision in ('bf16', 'bf16-deep'):
         raise _lib.LinrError('the bf16 training executor exists for hidden_channel_conv=8 only')
-    if model._wide is None and model.train_precision == 'bf16-mul':          # the wide step with bf16 products (wide_net._mul)
+    if model._wide is None and model.train_precision == 'bf16-mul':          # the wide step with bf16 products (wide_net._Pass.mul)
         raise _lib.LinrError("train_precision 'bf16-mul' exists for hidden_channel_conv 16 / 32 only: width 8 has the bf16 training executor")
     bits = torch.zeros(1, dtype=torch.float64, device=frame.device) if out is None else out
     extra = {}                           # keyword arguments of the step beyond the common ones

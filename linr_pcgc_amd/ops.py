@@ -202,7 +202,7 @@ def spconv_wide(xs, lo, mask, n, kernel, bias=None, bwd=False, res=None, act=Non
     """linr_spconv_wide: a 3x3x3 convolution on channel-blocked activations, one gather of all input blocks per tap.
     xs: the gathered blocks (views buf[1:] of [n+1, 8] buffers whose row 0 is zero); kernel [27, cin, cout]; outs / res / act: lists
     of [n, 8] blocks of the produced side (cout / 8 forward, cin / 8 backward).  pw = (mode, W, b, aux blocks, out2 blocks): a pointwise
-    layer of the wide Inception layer fused into the epilogue (linr_spconv_wide_pw, include/linr_hip.h).  mul='bf16': the convolution's
+    layer of the wide Inception layer fused into the epilogue (linr_wide_pw, include/linr_hip.h).  mul='bf16': the convolution's
     products on bf16 matrix instructions (LINR_MUL_BF16: operands rounded at the multiply, fp32 sums; everything else as with 'f32')."""
     import ctypes
     cin, cout = kernel.shape[1], kernel.shape[2]
@@ -210,17 +210,16 @@ def spconv_wide(xs, lo, mask, n, kernel, bias=None, bwd=False, res=None, act=Non
     if outs is None:
         outs = [torch.empty((n, 8), dtype=torch.float32, device=xs[0].device) for _ in range(npb)]
     flags = (LINR_RELU if relu else 0) | (LINR_ACCUM if accumulate else 0) | (LINR_RELU_MASK if act is not None else 0) | _mul_flag(mul)
-    args = (1 if bwd else 0, _ptr_array(xs), lo.data_ptr(), mask.data_ptr(), lo.stride(0), n, kernel.data_ptr(), _ptr(bias), cin, cout,
-            None if res is None else _ptr_array(res), None if act is None else _ptr_array(act), _ptr_array(outs), flags)
-    if pw is None:
-        check(_lib.lib().linr_spconv_wide(*args, _stream()), 'linr_spconv_wide')
-    else:
+    st = None
+    if pw is not None:
         mode, w, b, aux, out2 = pw
         aux_a = None if aux is None else _ptr_array(aux)
         out_a = None if out2 is None else _ptr_array(out2)
-        st = _lib.LinrWidePw(mode, w.data_ptr(), _ptr(b), None if aux_a is None else ctypes.cast(aux_a, ctypes.c_void_p),
-                             None if out_a is None else ctypes.cast(out_a, ctypes.c_void_p))
-        check(_lib.lib().linr_spconv_wide_pw(*args, ctypes.byref(st), _stream()), 'linr_spconv_wide_pw')
+        st = ctypes.byref(_lib.LinrWidePw(mode, w.data_ptr(), _ptr(b), None if aux_a is None else ctypes.cast(aux_a, ctypes.c_void_p),
+                                          None if out_a is None else ctypes.cast(out_a, ctypes.c_void_p)))
+    check(_lib.lib().linr_spconv_wide(1 if bwd else 0, _ptr_array(xs), lo.data_ptr(), mask.data_ptr(), lo.stride(0), n, kernel.data_ptr(),
+                                      _ptr(bias), cin, cout, None if res is None else _ptr_array(res),
+                                      None if act is None else _ptr_array(act), _ptr_array(outs), flags, st, _stream()), 'linr_spconv_wide')
     return outs
 
 
@@ -238,9 +237,9 @@ def spconv_wgrad_wide(xs, gouts, nbr, tile8t, n, cin, cout, gw=None, gb=None, de
     assert gw.is_contiguous() and gb.is_contiguous()
     slab = _lib.scratch(L.linr_spconv_wgrad_wide_slab_bytes(cin, cout), dev)
     deferred = defer is not None and n > 0
-    check(L.linr_spconv_wgrad_wide_f(_ptr_array(xs), cin, _ptr_array(gouts), cout, nbr.data_ptr(), _ptr(tile8t), nbr.stride(0), n,
-                                     slab.data_ptr(), None if deferred else gw.data_ptr(), gb.data_ptr(), _mul_flag(mul), _stream()),
-          'linr_spconv_wgrad_wide_f')
+    check(L.linr_spconv_wgrad_wide(_ptr_array(xs), cin, _ptr_array(gouts), cout, nbr.data_ptr(), _ptr(tile8t), nbr.stride(0), n,
+                                   slab.data_ptr(), None if deferred else gw.data_ptr(), gb.data_ptr(), _mul_flag(mul), _stream()),
+          'linr_spconv_wgrad_wide')
     if deferred:
         nblk = int(L.linr_spconv_wgrad_wide_blocks(cout, 1 if tile8t is not None else 0))
         defer.append((_lib.LinrWideReduce(0, nblk, cin, cout, 0, 0, slab.data_ptr(), gw.data_ptr(), gb.data_ptr()), slab, gw, gb))
@@ -255,8 +254,8 @@ def spconv_wgrad_wide2(xsA, gsA, gwA, gbA, xsB, gsB, gwB, gbB, tile8t, n, defer,
     h = 8 * nb
     stride = 2 * nb * nb * 1736
     slab = _lib.scratch(256 * stride * 4, xsA[0].device)
-    check(L.linr_spconv_wgrad_wide2_f(_ptr_array(xsA), _ptr_array(gsA), _ptr_array(xsB), _ptr_array(gsB), h, tile8t.data_ptr(), n,
-                                      slab.data_ptr(), _mul_flag(mul), _stream()), 'linr_spconv_wgrad_wide2_f')
+    check(L.linr_spconv_wgrad_wide2(_ptr_array(xsA), _ptr_array(gsA), _ptr_array(xsB), _ptr_array(gsB), h, tile8t.data_ptr(), n,
+                                    slab.data_ptr(), _mul_flag(mul), _stream()), 'linr_spconv_wgrad_wide2')
     for cv, (gw, gb) in enumerate(((gwA, gbA), (gwB, gbB))):
         assert gw.is_contiguous() and gb.is_contiguous()
         defer.append((_lib.LinrWideReduce(0, 256, h, h, stride, 0, slab.data_ptr() + 4 * cv * nb * nb * 1736, gw.data_ptr(), gb.data_ptr()),

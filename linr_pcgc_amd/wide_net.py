@@ -5,7 +5,7 @@ Every C-wide activation is kept as C / 8 separate [rows + 1][8] matrices (zero r
 layer is ONE launch of a kernel of csrc/wide.hip: a convolution Ci -> Co ``linr_spconv_wide`` (every input block of a row gathered
 once per tap, the weights of a tap as an A-operand image in LDS, all output channels from that one gather; the same for
 backward-data at the mirrored taps; the Inception layer's pointwise convolutions conv1_0 / conv1_2 and their backward-data passes ride
-in its epilogue: ``linr_spconv_wide_pw``), its weight gradient ``linr_spconv_wgrad_wide`` (one gather per input block for all gradient
+in its epilogue: its ``pw`` argument), its weight gradient ``linr_spconv_wgrad_wide`` (one gather per input block for all gradient
 blocks; conv0_1 and conv1_1 together: ``linr_spconv_wgrad_wide2``), the pointwise weight gradients ``linr_linear_wgrad_wide``, a stage's
 head ``linr_head_wide_fwd`` and the backward of all 8 heads ``linr_head_wide_bwd``; the scale context (width-independent) runs on the
 8-wide network's kernels (``linr_sce_fwd``, ``linr_sce_bwd_params``).  The ~64 slab reductions of a backward pass are deferred into
@@ -19,7 +19,11 @@ training step at widths 16 / 32 on the loot-like frame (profiles/r04_wide.txt; ~
 
 train_precision 'bf16-mul' (opt-in): a training forward (keep=True) and its backward run the same launches with LINR_MUL_BF16 - the
 products of the 3x3x3 convolutions on bf16 matrix instructions, operands rounded at the multiply, everything else fp32 (csrc/wide_mul.hip;
-_mul() below; 5.31 / 13.8 ms per step, profiles/wide_bf16_mul.txt).  Every other forward multiplies in fp32.
+_Pass.mul below; 5.31 / 13.8 ms per step, profiles/wide_bf16_mul.txt).  Every other forward multiplies in fp32.
+
+What a running pass needs beyond its inputs - the frame's tables, the buffer pool, the list of deferred reductions, the precision of the
+products - travels in a _Pass that forward / backward build per call and hand to every layer method: nothing is kept per thread or on
+the executor, so passes of several models and frames interleave freely (the model's lock guards its pool, _build and the bf16 state).
 
 forward_bf16 is the inference forward of --precision bf16 (BASELINE config[4]'s numerics) on csrc/wide_bf16.hip: the uint8 weight codes
 as the model, bf16 channel-blocked activations, fp32 accumulation, one launch per layer in the same schedule (profiles/r07_wide_bf16.txt).
@@ -67,35 +71,26 @@ class _Pool:
         return [b[j, 1:] for j in range(nb)]
 
 
-_FUSE_PW = os.environ.get('LINR_WIDE_FUSE_PW', '1') != '0'          # the pointwise layers of an Inception layer in the convolutions' epilogues
-# Per-THREAD state of the running pass (two threads may train two wide models at once, each call sees only its own): `pool` = the
-# buffer pool of the running forward / backward (WideNet.forward(pool=True)), else fresh buffers; `defer` = the running backward's
-# list of deferred weight-gradient reductions (one launch per 32 at its end), else None.  One MODEL is used by one thread at a
-# time: WideNet.forward / backward hold the model's lock (its pool and the frame bound by _bind() are per-model state).
-_TLS = threading.local()
+class _Pass:
+    """What ONE WideNet.forward / backward call runs on, handed to every layer method that launches: the frame's tables and row count,
+    `pool` = the model's _Pool (train_step) or None for fresh buffers, `defer` = the backward's list of deferred weight-gradient
+    reductions (one launch per 32 at its end) or None in a forward, `mul` = what the 3x3x3 convolutions multiply in ('bf16' in the
+    training passes of a train_precision 'bf16-mul' model, else 'f32': every codec, decoder and probability forward), `fuse_pw` = the
+    pointwise layers of an Inception layer in the convolutions' epilogues.  Nothing of a pass is kept on the executor or the thread."""
+    __slots__ = ('lo', 'mask', 'nbr', 'tile8t', 'n', 'dev', 'pool', 'defer', 'mul', 'fuse_pw')
 
+    def __init__(self, frame, pool, defer, mul, fuse_pw):
+        self.lo, self.mask, self.nbr, self.tile8t = frame.nbr_lo, frame.nbr_mask, frame.nbr, frame.nbr8t
+        self.n, self.dev = frame.rows, frame.occ.device          # (the device WITH its index: what the blocks and _ZW are keyed by)
+        self.pool, self.defer, self.mul, self.fuse_pw = pool, defer, mul, fuse_pw
 
-def _pool():
-    return getattr(_TLS, 'pool', None)
-
-
-def _defer():
-    return getattr(_TLS, 'defer', None)
-
-
-def _mul():
-    """What the running pass multiplies its 3x3x3 convolutions in: 'bf16' inside a training forward (keep=True) / backward of a model
-    with train_precision 'bf16-mul', else 'f32' (every codec, decoder and probability forward)."""
-    return getattr(_TLS, 'mul', 'f32')
-
-
-def _blocks(n, nb, dev):
-    """nb zero-padded [n, 8] matrices (views buf[1:] of [n + 1, 8] buffers whose row 0 is zero)."""
-    if _pool() is not None:
-        return _pool().take(n, nb, dev if isinstance(dev, torch.device) else torch.device(dev))
-    buf = torch.empty((nb, n + 1, B), dtype=torch.float32, device=dev)
-    buf[:, 0].zero_()
-    return [buf[i, 1:] for i in range(nb)]
+    def blocks(self, nb):
+        """nb zero-padded [n, 8] matrices (views buf[1:] of [n + 1, 8] buffers whose row 0 is zero)."""
+        if self.pool is not None:
+            return self.pool.take(self.n, nb, self.dev)
+        buf = torch.empty((nb, self.n + 1, B), dtype=torch.float32, device=self.dev)
+        buf[:, 0].zero_()
+        return [buf[i, 1:] for i in range(nb)]
 
 
 def _lin_bwd_data(gout, w, w_off, ws_ci, ws_co, cin, cout, out, act=None, accumulate=False):
@@ -118,38 +113,29 @@ class _Conv:
         self.ci, self.co = mod.kernel.shape[1], mod.kernel.shape[2]
         self.nbi, self.nbo = (self.ci + B - 1) // B, self.co // B
 
-    def fwd(self, net, xs, relu=False, res=None, pw=None):
+    def fwd(self, ps, xs, relu=False, res=None, pw=None):
         """ONE launch (linr_spconv_wide): every input block of a row is gathered once per tap and feeds all output channels.
         pw: a pointwise layer fused into the epilogue (ops.spconv_wide)."""
-        n = xs[0].shape[0]
-        outs = _blocks(n, self.nbo, xs[0].device)
-        ops.spconv_wide(xs[:self.nbi], net.lo, net.mask, n, self.mod.kernel, self.mod.bias.reshape(-1), res=res, relu=relu, outs=outs, pw=pw,
-                        mul=_mul())
+        outs = ps.blocks(self.nbo)
+        ops.spconv_wide(xs[:self.nbi], ps.lo, ps.mask, ps.n, self.mod.kernel, self.mod.bias.reshape(-1), res=res, relu=relu, outs=outs,
+                        pw=pw, mul=ps.mul)
         return outs
 
-    def bwd(self, net, xs, gouts, gins=None, act=None, need_input_grad=True, res=None, pw=None, wgrad=True):
-        """Parameter gradients into .grad; input gradient (+ res, masked by act > 0: the ReLU that produced xs) accumulated into
-        gins (list of (buffer, has_content)) or returned as fresh blocks."""
-        n = gouts[0].shape[0]
+    def bwd(self, ps, xs, gouts, act=None, need_input_grad=True, res=None, pw=None, wgrad=True, into=None, accumulate=False):
+        """Parameter gradients into .grad; the input gradient (+ res, masked by act > 0: the ReLU that produced xs) written to (or,
+        accumulate, added to) the blocks `into`, or to fresh blocks.  Returns the input gradient's blocks."""
         # weight gradients: all (input block, gradient block) pairs as groups of grouped launches of the transposing 8-wide kernel, ONE
         # fixed-order reduction straight into the parameter gradients (views of the flat gradient)
         if wgrad:
-            ops.spconv_wgrad_wide(xs[:self.nbi], gouts[:self.nbo], net.nbr_full, net.tile8t, n, self.ci, self.co,
-                                  gw=self.mod.kernel.grad, gb=self.mod.bias.grad.reshape(-1), defer=_defer(), mul=_mul())
+            ops.spconv_wgrad_wide(xs[:self.nbi], gouts[:self.nbo], ps.nbr, ps.tile8t, ps.n, self.ci, self.co,
+                                  gw=self.mod.kernel.grad, gb=self.mod.bias.grad.reshape(-1), defer=ps.defer, mul=ps.mul)
         if not need_input_grad:
             return None
-        fresh = gins is None
-        if fresh:
-            gins = [[g, False] for g in _blocks(n, self.nbi, gouts[0].device)]
-        # backward-data in one launch: the output gradient's blocks gathered once per (mirrored) tap for all input channels; blocks that
-        # already hold a gradient are accumulated into (all of them or none: the callers fill a list uniformly)
-        acc = gins[0][1]
-        assert all(g[1] == acc for g in gins)
-        ops.spconv_wide(gouts[:self.nbo], net.lo, net.mask, n, self.mod.kernel, None, bwd=True, act=act, res=res,
-                        outs=[g[0] for g in gins], accumulate=acc, pw=pw, mul=_mul())
-        for g in gins:
-            g[1] = True
-        return [g for g, _ in gins] if fresh else None
+        gins = ps.blocks(self.nbi) if into is None else into
+        # backward-data in one launch: the output gradient's blocks gathered once per (mirrored) tap for all input channels
+        ops.spconv_wide(gouts[:self.nbo], ps.lo, ps.mask, ps.n, self.mod.kernel, None, bwd=True, act=act, res=res, outs=gins,
+                        accumulate=accumulate, pw=pw, mul=ps.mul)
+        return gins
 
 
 class _Pointwise:
@@ -164,37 +150,27 @@ class _Pointwise:
         self.cw = B if self.blocked_out else cout
         self.ws = (cout, 1) if layout == 'me' else (1, cin)          # element (ci, co) at ci ws[0] + co ws[1]
 
-    def fwd(self, xs, relu=False, res=None, padded=True):
-        n, dev = xs[0].shape[0], xs[0].device
-        outs = _blocks(n, self.nbo, dev) if (self.blocked_out and padded) else \
-            [torch.empty((n, self.cw), dtype=torch.float32, device=dev) for _ in range(self.nbo)]
+    def fwd(self, ps, xs, relu=False, res=None, padded=True):
+        outs = ps.blocks(self.nbo) if (self.blocked_out and padded) else \
+            [torch.empty((ps.n, self.cw), dtype=torch.float32, device=ps.dev) for _ in range(self.nbo)]
         return ops.linear_wide(xs[:self.nbi], self.cin, self.w, self.ws[0], self.ws[1], self.b.reshape(-1), self.cout, outs,
                                out_blocked=self.blocked_out, res=res, relu=relu)
 
-    def wgrad(self, xs, gouts):
-        """Parameter gradients only (the backward-data pass rides in a convolution's epilogue)."""
+    def wgrad(self, ps, xs, gouts):
+        """Parameter gradients into .grad (one grouped launch + one reduction); alone where the backward-data pass rides in a
+        convolution's epilogue."""
         ops.linear_wgrad_wide(xs[:self.nbi], self.cin, gouts[:self.nbo], self.cout, self.w.grad, self.ws[0], self.ws[1],
-                              self.b.grad.reshape(-1), g_blocked=self.blocked_out, defer=_defer())
+                              self.b.grad.reshape(-1), g_blocked=self.blocked_out, defer=ps.defer)
 
-    def bwd(self, xs, gouts, gins=None, act=None, need_input_grad=True):
-        """Parameter gradients into .grad (one grouped launch + one reduction); the input gradient (masked by act > 0) accumulated
-        into gins (list of [buffer, has_content]) or returned as fresh blocks."""
-        n = gouts[0].shape[0]
-        ops.linear_wgrad_wide(xs[:self.nbi], self.cin, gouts[:self.nbo], self.cout, self.w.grad, self.ws[0], self.ws[1],
-                              self.b.grad.reshape(-1), g_blocked=self.blocked_out, defer=_defer())
-        if not need_input_grad:
-            return None
-        fresh = gins is None
-        if fresh:
-            gins = [[g, False] for g in _blocks(n, self.nbi, gouts[0].device)]
-        acc = gins[0][1]
-        assert all(g[1] == acc for g in gins)
+    def bwd(self, ps, xs, gouts, act=None, into=None, accumulate=False):
+        """wgrad(), then the input gradient (masked by act > 0) written to (or, accumulate, added to) the blocks `into`, or to fresh
+        blocks.  Returns the input gradient's blocks."""
+        self.wgrad(ps, xs, gouts)
+        gins = ps.blocks(self.nbi) if into is None else into
         # backward-data: the same kernel with the roles of cin / cout and the weight strides swapped
-        ops.linear_wide(gouts[:self.nbo], self.cout, self.w, self.ws[1], self.ws[0], None, self.cin, [g[0] for g in gins],
-                        in_blocked=self.blocked_out, act=act, accumulate=acc)
-        for g in gins:
-            g[1] = True
-        return [g for g, _ in gins] if fresh else None
+        ops.linear_wide(gouts[:self.nbo], self.cout, self.w, self.ws[1], self.ws[0], None, self.cin, gins, in_blocked=self.blocked_out,
+                        act=act, accumulate=accumulate)
+        return gins
 
 
 class _Block:
@@ -210,53 +186,51 @@ class _Block:
                                 'c10': _Pointwise(lay.conv1_0.kernel, lay.conv1_0.bias, C, h, 'me'), 'c11': _Conv(lay.conv1_1),
                                 'c12': _Pointwise(lay.conv1_2.kernel, lay.conv1_2.bias, h, h, 'me')})
 
-    def fwd(self, net, xs, res=None):
+    def fwd(self, ps, xs, res=None):
         nh = self.h // B
-        a = self.first.fwd(net, xs, relu=True)
+        a = self.first.fwd(ps, xs, relu=True)
         tape = {'in': xs, 'a': a, 'layers': []}
         x = a
-        n, dev = xs[0].shape[0], xs[0].device
         for q in self.layers:
             # conv1_0 rides in conv0_0's launch (it reads the row itself: the centre tap), conv1_2 + the residual in conv1_1's: the
-            # fmaf chains of the stand-alone pointwise kernel, so the bits are those of the five-launch form (LINR_WIDE_FUSE_PW=0)
-            if _FUSE_PW:
-                h1 = _blocks(n, nh, dev)
-                h0 = q['c00'].fwd(net, x, relu=True, pw=(1, q['c10'].w, q['c10'].b.reshape(-1), None, h1))
+            # fmaf chains of the stand-alone pointwise kernel, so the bits are those of the five-launch form (fuse_pw False)
+            if ps.fuse_pw:
+                h1 = ps.blocks(nh)
+                h0 = q['c00'].fwd(ps, x, relu=True, pw=(1, q['c10'].w, q['c10'].b.reshape(-1), None, h1))
             else:
-                h0 = q['c00'].fwd(net, x, relu=True)
-                h1 = q['c10'].fwd(x, relu=True)
-            i_lo = q['c01'].fwd(net, h0, res=x[:nh])
-            if _FUSE_PW:
-                i_hi = _blocks(n, nh, dev)
-                m = q['c11'].fwd(net, h1, relu=True, pw=(2, q['c12'].w, q['c12'].b.reshape(-1), x[nh:], i_hi))
+                h0 = q['c00'].fwd(ps, x, relu=True)
+                h1 = q['c10'].fwd(ps, x, relu=True)
+            i_lo = q['c01'].fwd(ps, h0, res=x[:nh])
+            if ps.fuse_pw:
+                i_hi = ps.blocks(nh)
+                m = q['c11'].fwd(ps, h1, relu=True, pw=(2, q['c12'].w, q['c12'].b.reshape(-1), x[nh:], i_hi))
             else:
-                m = q['c11'].fwd(net, h1, relu=True)
-                i_hi = q['c12'].fwd(m, res=x[nh:])
+                m = q['c11'].fwd(ps, h1, relu=True)
+                i_hi = q['c12'].fwd(ps, m, res=x[nh:])
             tape['layers'].append({'x': x, 'h0': h0, 'h1': h1, 'm': m})
             x = i_lo + i_hi
         if len(self.layers) > 1:           # ResNetBlock.forward: out += x (models/resnet.py:160-161)
             for blk, ab in zip(x, a):
                 _axpy(ab, blk)
         tape['il'] = x
-        return self.tail.fwd(net, x, res=res), tape
+        return self.tail.fwd(ps, x, res=res), tape
 
-    def bwd(self, net, tape, g_out, need_input_grad):
+    def bwd(self, ps, tape, g_out, need_input_grad):
         """g_out: gradient blocks of the block output.  Returns the input gradient blocks (or None)."""
         nh = self.h // B
-        n, dev = g_out[0].shape[0], g_out[0].device
         nl = len(self.layers)
-        fuse = _FUSE_PW
+        fuse = ps.fuse_pw
         g_m_last = None
         if fuse:
             # gM of the LAST Inception layer (backward of conv1_2 and of M's ReLU) rides in the tail convolution's backward-data launch
             lastq, lastt = self.layers[-1], tape['layers'][-1]
-            g_m_last = _blocks(n, nh, dev)
-            g_il = self.tail.bwd(net, tape['il'], g_out, pw=(3, lastq['c12'].w, None, lastt['m'], g_m_last))
+            g_m_last = ps.blocks(nh)
+            g_il = self.tail.bwd(ps, tape['il'], g_out, pw=(3, lastq['c12'].w, None, lastt['m'], g_m_last))
         else:
-            g_il = self.tail.bwd(net, tape['il'], g_out)
+            g_il = self.tail.bwd(ps, tape['il'], g_out)
         g_a = None
         if len(self.layers) > 1:           # the extra skip: a receives g_il as well
-            g_a = _blocks(n, self.C // B, dev)
+            g_a = ps.blocks(self.C // B)
             for s, d in zip(g_il, g_a):
                 _axpy(s, d, accumulate=False)
         g_i = g_il
@@ -264,26 +238,26 @@ class _Block:
             x = t['x']
             if fuse and li == 0:
                 g_m = g_m_last
-                q['c12'].wgrad(t['m'], g_i[nh:])
+                q['c12'].wgrad(ps, t['m'], g_i[nh:])
             else:
-                g_m = q['c12'].bwd(t['m'], g_i[nh:], act=t['m'])
+                g_m = q['c12'].bwd(ps, t['m'], g_i[nh:], act=t['m'])
             # the weight gradients of conv0_1 and conv1_1 (same shape, independent) as ONE launch: alone each is one wave per SIMD
-            pair = fuse and _defer() is not None and net.tile8t is not None and n > 0
-            g_h1 = q['c11'].bwd(net, t['h1'], g_m, act=t['h1'], wgrad=not pair)
-            g_h0 = q['c01'].bwd(net, t['h0'], g_i[:nh], act=t['h0'], wgrad=not pair)
+            pair = fuse and ps.defer is not None and ps.tile8t is not None and ps.n > 0
+            g_h1 = q['c11'].bwd(ps, t['h1'], g_m, act=t['h1'], wgrad=not pair)
+            g_h0 = q['c01'].bwd(ps, t['h0'], g_i[:nh], act=t['h0'], wgrad=not pair)
             if pair:
                 c01, c11 = q['c01'].mod, q['c11'].mod
                 ops.spconv_wgrad_wide2(t['h0'], g_i[:nh], c01.kernel.grad, c01.bias.grad.reshape(-1), t['h1'], g_m, c11.kernel.grad,
-                                       c11.bias.grad.reshape(-1), net.tile8t, n, _defer(), mul=_mul())
+                                       c11.bias.grad.reshape(-1), ps.tile8t, ps.n, ps.defer, mul=ps.mul)
             # the layer's input gradient: the residual's share g_i rides in conv0_0's backward-data epilogue (+ res), conv1_0's share
             # is added last - and with it, for the block's first layer of a one-layer block, the ReLU mask of a = relu(first conv)
             last_mask = tape['a'] if (nl == 1 and li == nl - 1) else None
             if fuse:
-                q['c10'].wgrad(x, g_h1)
-                g_x = q['c00'].bwd(net, x, g_h0, res=g_i, act=last_mask, pw=(4, q['c10'].w, None, g_h1, None))
+                q['c10'].wgrad(ps, x, g_h1)
+                g_x = q['c00'].bwd(ps, x, g_h0, res=g_i, act=last_mask, pw=(4, q['c10'].w, None, g_h1, None))
             else:
-                g_x = q['c00'].bwd(net, x, g_h0, res=g_i)
-                q['c10'].bwd(x, g_h1, gins=[[g, True] for g in g_x], act=last_mask)
+                g_x = q['c00'].bwd(ps, x, g_h0, res=g_i)
+                q['c10'].bwd(ps, x, g_h1, act=last_mask, into=g_x, accumulate=True)
             g_i = g_x
         if g_a is not None:
             for s, d in zip(g_a, g_i):
@@ -291,14 +265,14 @@ class _Block:
         if nl != 1:
             # g_i is the gradient of a = relu(first conv): mask it
             for g, ab in zip(g_i, tape['a']):
-                _mask_inplace(g, ab)
-        return self.first.bwd(net, tape['in'], g_i, need_input_grad=need_input_grad)
+                _mask_inplace(ps, g, ab)
+        return self.first.bwd(ps, tape['in'], g_i, need_input_grad=need_input_grad)
 
 
-def _mask_inplace(g, act):
+def _mask_inplace(ps, g, act):
     """g *= (act > 0) through the pointwise kernel's ReLU-mask epilogue on an identity-free path: g = 0 * W + g masked."""
     # linr_linear_bwd_data with cin = cout = 8, a zero weight block, accumulate and mask: out = (0 + old) * (act > 0)
-    z = _zeros_w(g.device)
+    z = _zeros_w(ps.dev)
     _lin_bwd_data(g, z, 0, 8, 1, B, B, g, act=act, accumulate=True)
 
 
@@ -313,13 +287,17 @@ def _zeros_w(dev):
 
 
 class WideNet:
+    # the pointwise layers of an Inception layer in the convolutions' epilogues; False (LINR_WIDE_FUSE_PW=0, or set on an executor): one
+    # launch per pointwise layer, the same bits
+    fuse_pw = os.environ.get('LINR_WIDE_FUSE_PW', '1') != '0'
+
     def __init__(self, model, hidden):
         if hidden % 16 != 0 or hidden > 32:
             raise ValueError('hidden_channel_conv must be 8 (the tuned kernels) or 16 / 32 (channel-blocked executor), got %d' % hidden)
         self.model, self.C = model, hidden
         self._built = False
         self._pool = None
-        # one thread at a time per model: the pool and the frame bound by _bind() are per-model state (train_step holds it across forward,
+        # one thread at a time per model: the pool, _build() and the bf16 state are per-model state (train_step holds it across forward,
         # backward and the optimiser step)
         self.lock = threading.RLock()
 
@@ -338,19 +316,16 @@ class WideNet:
         """The products of a training pass: bf16 for train_precision 'bf16-mul' (csrc/wide_mul.hip), else fp32."""
         return 'bf16' if getattr(self.model, 'train_precision', 'f32') == 'bf16-mul' else 'f32'
 
-    def _bind(self, frame):
-        if not self._built:
-            self._build()
-        # the op-level wrappers take the row count from the table's width: a view of its first `rows` columns (same stride)
-        self.nbr, self.lo, self.mask = frame.nbr[:, :frame.rows], frame.nbr_lo, frame.nbr_mask
-        self.nbr_full, self.tile8t = frame.nbr, frame.nbr8t
-        self.n = frame.rows
+    def _pass(self, frame, training, pool, defer=None):
+        """The pass object of one call: a training pass (forward(keep=True), backward) multiplies as the model's train_precision says,
+        every other forward in fp32."""
+        return _Pass(frame, self._pool if pool else None, defer, self._train_mul() if training else 'f32', self.fuse_pw)
 
-    def _scale_context(self, frame, keep):
+    def _scale_context(self, ps, frame, keep):
         """x0 [rows, 8] (one block): PointwiseMLP([15, 16, 8]) of the rows' scale on [emb | offset features] (model_core.py:48-53) - all
         scales in ONE launch of the library's scale-context kernel (linr_sce_fwd: the parameters of the scale context lead the flat
         parameter order whatever the width of the rest of the network); the hidden layer is kept for the backward pass."""
-        x0 = _blocks(frame.rows, 1, frame.device)
+        x0 = ps.blocks(1)
         hid = torch.empty((frame.rows, 16), dtype=torch.float32, device=frame.device)
         check(_lib.lib().linr_sce_fwd(self.model.flat_parameters().data_ptr(), frame.cref(), None, hid.data_ptr(), x0[0].data_ptr(),
                                       _stream()), 'linr_sce_fwd')
@@ -359,9 +334,9 @@ class WideNet:
     def _occ_block(self, frame):
         return [frame.occ]                     # [rows, 8] view of a buffer with the zero row in front (engine.Frame)
 
-    def _head(self, k, prior, frame, p, partial):
+    def _head(self, ps, k, prior, frame, p, partial):
         """Stage k behind `prior`: the prune convolution, then the head MLP + sigmoid (+ the stage's bits partials) as one launch."""
-        c = self.prune[k].fwd(self, prior)
+        c = self.prune[k].fwd(ps, prior)
         lin0, lin2 = self.heads[k]
         ops.head_wide_fwd(c, lin0.weight, lin0.bias, lin2.weight, lin2.bias, frame.occ[:, k] if partial is not None else None, p,
                           partial=partial)
@@ -373,23 +348,19 @@ class WideNet:
         (float64[1]) += their cost.  keep: record the activations for backward (k0 = 0, k1 = 8).  pool: the padded block buffers
         come from this executor's pool, i.e. they are valid until the NEXT pooled forward (train_step: forward, backward, done)."""
         with self.lock:
-            self._bind(frame)
+            if not self._built:
+                self._build()
             if frame.rows == 0:
                 return None
             if pool:
                 if self._pool is None:
                     self._pool = _Pool()
                 self._pool.reset()
-            _TLS.pool = self._pool if pool else None
-            _TLS.mul = self._train_mul() if keep else 'f32'
-            try:
-                return self._forward(frame, k0, k1, probs, bits, keep)
-            finally:
-                _TLS.pool, _TLS.mul = None, 'f32'
+            return self._forward(self._pass(frame, keep, pool), frame, k0, k1, probs, bits, keep)
 
-    def _forward(self, frame, k0, k1, probs, bits, keep):
-        x0, sce_tape = self._scale_context(frame, keep)
-        xg, bin_tape = self.block_in.fwd(self, x0)
+    def _forward(self, ps, frame, k0, k1, probs, bits, keep):
+        x0, sce_tape = self._scale_context(ps, frame, keep)
+        xg, bin_tape = self.block_in.fwd(ps, x0)
         tape = {'sce': sce_tape, 'bin': bin_tape, 'xg': xg, 'stages': []} if keep else None
         nb = (frame.rows + 255) // 256                      # per-block bits partials of a stage (linr_head_wide_workspace_bytes / 8)
         parts = torch.empty(((k1 - k0) * nb,), dtype=torch.float64, device=frame.device) if bits is not None else None
@@ -399,9 +370,9 @@ class WideNet:
                 prior = xg
             else:
                 occ = self._occ_block(frame)
-                prior, blk_tape = self.outter[k - 1].fwd(self, occ, res=xg)
+                prior, blk_tape = self.outter[k - 1].fwd(ps, occ, res=xg)
             p = probs[k] if probs is not None else torch.empty((frame.rows,), dtype=torch.float32, device=frame.device)
-            c = self._head(k, prior, frame, p, None if parts is None else parts[(k - k0) * nb:(k - k0 + 1) * nb])
+            c = self._head(ps, k, prior, frame, p, None if parts is None else parts[(k - k0) * nb:(k - k0 + 1) * nb])
             if keep:
                 tape['stages'].append({'prior': prior, 'c': c, 'p': p, 'blk': blk_tape})
         if parts is not None:
@@ -413,26 +384,21 @@ class WideNet:
         """d (gscale * bits) / d params into the parameters' .grad (model._ensure_grad_views(): views of the flat gradient).
         pool: continue in the pool of the forward that made `tape`."""
         with self.lock:
-            _TLS.pool = self._pool if pool else None
-            _TLS.defer = []
-            _TLS.mul = self._train_mul()
-            try:
-                self._backward(frame, tape, gscale)
-                ops.wide_reduce_many(_TLS.defer)          # the ~64 slab reductions of the pass, 32 per launch
-            finally:
-                _TLS.pool, _TLS.defer, _TLS.mul = None, None, 'f32'
+            if not self._built:
+                self._build()
+            ps = self._pass(frame, True, pool, defer=[])
+            self._backward(ps, frame, tape, gscale)
+            ops.wide_reduce_many(ps.defer)          # the ~64 slab reductions of the pass, 32 per launch
 
-    def _backward(self, frame, tape, gscale):
-        self._bind(frame)
+    def _backward(self, ps, frame, tape, gscale):
         self.model._ensure_grad_views()
-        n, dev = frame.rows, frame.device
         C = self.C
         gz_scale = float(gscale) * 1.4426950408889634          # d(bits)/d(nats) = 1 / ln 2
-        g_xg = [[g, False] for g in _blocks(n, C // B, dev)]
+        g_xg = ps.blocks(C // B)
         # all 8 heads first, as one grouped launch (their inputs - c, p, the occupancy columns - exist once the forward has run): the
         # gradients of the prune convolutions' outputs and the heads' parameter gradients, straight into the flat gradient
         stages = tape['stages']
-        g_cs = [_blocks(n, C // B, dev) for _ in range(8)]
+        g_cs = [ps.blocks(C // B) for _ in range(8)]
         first = self.heads[0][0].weight.grad
         per = 24 * C + 49
         for k, (lin0, lin2) in enumerate(self.heads):           # the reference's parameter order: the 8 inner_mlps back to back
@@ -447,21 +413,21 @@ class WideNet:
             st = stages[k]
             g_c = g_cs[k]
             if k == 0:
-                self.prune[k].bwd(self, st['prior'], g_c, gins=g_xg)
+                self.prune[k].bwd(ps, st['prior'], g_c, into=g_xg, accumulate=False)
             else:
-                g_prior = self.prune[k].bwd(self, st['prior'], g_c)
+                g_prior = self.prune[k].bwd(ps, st['prior'], g_c)
                 g_priors.append(g_prior)                            # prior_k = x_glob + block output: both receive g_prior
-                self.outter[k - 1].bwd(self, st['blk'], g_prior, need_input_grad=False)
+                self.outter[k - 1].bwd(ps, st['blk'], g_prior, need_input_grad=False)
         # x_glob's gradient: stage 0's (in g_xg) + the seven priors' - one pass per block instead of a read-modify-write pass per stage
-        for b, (dst, _) in enumerate(g_xg):
+        for b, dst in enumerate(g_xg):
             check(_lib.lib().linr_sum_many(ops._ptr_array([gp[b] for gp in g_priors]), len(g_priors), dst.numel(), dst.data_ptr(), 1,
                                            _stream()), 'linr_sum_many')
-        g_x0 = self.block_in.bwd(self, tape['bin'], [g for g, _ in g_xg], need_input_grad=True)[0]
+        g_x0 = self.block_in.bwd(ps, tape['bin'], g_xg, need_input_grad=True)[0]
         # scale context: ghid, the four parameter gradients of every scale's MLP and the embedding rows in one call, straight into the
         # flat gradient (its leading linr_sce_param_count floats)
         L = _lib.lib()
         m = self.model
-        slab = _lib.scratch(L.linr_sce_bwd_params_slab_bytes(m.scale_num), dev)
+        slab = _lib.scratch(L.linr_sce_bwd_params_slab_bytes(m.scale_num), frame.device)
         check(L.linr_sce_bwd_params(m.flat_parameters().data_ptr(), frame.cref(), g_x0.data_ptr(), tape['sce'].data_ptr(), slab.data_ptr(),
                                     slab.numel(), m._flat_grad.data_ptr(), _stream()), 'linr_sce_bwd_params')
 
@@ -471,7 +437,6 @@ class WideNet:
         launch per call; bf16 channel-blocked activations from a pool of per-role buffers; no tape.  Stages [k0, k1) as in forward():
         the decoder's one-stage calls run the same launches as the encoder's [0, 8), so their probabilities are bit-identical."""
         with self.lock:
-            self._bind(frame)
             if frame.rows == 0:
                 return
             m = self.model
@@ -482,39 +447,40 @@ class WideNet:
             ops.sce_fwd_bf16(st['pf'], frame, x0[0] - 16)
             occ = st['pool'].take('occ', n, 1, dev)         # converted on every call: the decoder fills frame.occ column by column
             check(L.linr_occ_to_bf16(frame.occ.data_ptr(), n, occ[0] - 16, _stream()), 'linr_occ_to_bf16')
-            xg = self._block_bf16(st, st['blocks'][0], x0, 'bin', None)
+            xg = self._block_bf16(frame, st, st['blocks'][0], x0, 'bin', None)
             nb = (n + 255) // 256
             parts = torch.empty(((k1 - k0) * nb,), dtype=torch.float64, device=dev) if bits is not None else None
             for k in range(k0, k1):
-                prior = xg if k == 0 else self._block_bf16(st, st['blocks'][k], occ, 'out', xg)
+                prior = xg if k == 0 else self._block_bf16(frame, st, st['blocks'][k], occ, 'out', xg)
                 p = probs[k] if probs is not None else torch.empty((n,), dtype=torch.float32, device=dev)
                 h = st['heads'][k]
-                ops.head_wide_bf16(prior, self.C, self.lo, self.mask, n, h['img'], h['bias'], h['w1'], h['b1'], h['w2'], h['b2'],
+                ops.head_wide_bf16(prior, self.C, frame.nbr_lo, frame.nbr_mask, n, h['img'], h['bias'], h['w1'], h['b1'], h['w2'], h['b2'],
                                    frame.occ.data_ptr(), k, p, None if parts is None else parts[(k - k0) * nb:(k - k0 + 1) * nb])
             if parts is not None:
                 ops.bits_finish(parts, (k1 - k0) * nb, bits)
 
-    def _block_bf16(self, st, bd, xin, tag, res):
+    def _block_bf16(self, frame, st, bd, xin, tag, res):
         """make_block on bf16 blocks: conv3 -> ReLU -> Inception layers (conv1_0 in conv0_0's epilogue, conv1_2 + the residual in conv1_1's,
         the extra skip of models/resnet.py:160-161 in the last layer's two launches) -> conv3 (+ res: x_glob)."""
-        n, dev, C = self.n, self.model._flat.device, self.C
+        n, dev, C = frame.rows, self.model._flat.device, self.C
+        lo, mask = frame.nbr_lo, frame.nbr_mask
         nbC, nh, h = C // B, C // (2 * B), C // 2
         pool = st['pool']
         conv = ops.spconv_wide_bf16
         a = pool.take(tag + 'a', n, nbC, dev)
-        conv(0, xin, bd['cin'], self.lo, self.mask, n, bd['first'][0], bd['first'][1], C, a, relu=True)
+        conv(0, xin, bd['cin'], lo, mask, n, bd['first'][0], bd['first'][1], C, a, relu=True)
         x, nl = a, len(bd['layers'])
         for li, q in enumerate(bd['layers']):
             skip = a if (nl > 1 and li == nl - 1) else None
             H = pool.take(tag + 'h%d' % li, n, nbC, dev)
             I = pool.take(tag + 'i%d' % li, n, nbC, dev)
-            conv(1, x, C, self.lo, self.mask, n, q['c00'][0], q['c00'][1], h, H, pw=q['c10'])
-            conv(0, H, h, self.lo, self.mask, n, q['c01'][0], q['c01'][1], h, I, res=x, res2=skip)
-            conv(2, _sub(H, nh), h, self.lo, self.mask, n, q['c11'][0], q['c11'][1], h, _sub(I, nh), res=_sub(x, nh),
+            conv(1, x, C, lo, mask, n, q['c00'][0], q['c00'][1], h, H, pw=q['c10'])
+            conv(0, H, h, lo, mask, n, q['c01'][0], q['c01'][1], h, I, res=x, res2=skip)
+            conv(2, _sub(H, nh), h, lo, mask, n, q['c11'][0], q['c11'][1], h, _sub(I, nh), res=_sub(x, nh),
                  res2=None if skip is None else _sub(skip, nh), pw=q['c12'])
             x = I
         o = pool.take(tag + 'o', n, nbC, dev)
-        conv(0, x, C, self.lo, self.mask, n, bd['tail'][0], bd['tail'][1], C, o, res=res)
+        conv(0, x, C, lo, mask, n, bd['tail'][0], bd['tail'][1], C, o, res=res)
         return o
 
     def _bf16_state(self, dev):

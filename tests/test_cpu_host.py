@@ -78,17 +78,21 @@ def test_c_abi_argument_checks(lib):
     assert lib.linr_octree_level(p16, 8, 10, p16, p16, None, p16, 1024, None) == -1                         # no count
     assert lib.linr_coords_minmax(p16, 0, p16, None) == -1 and lib.linr_coords_minmax(p16, 8, None, None) == -1
     b2 = (ctypes.c_void_p * 2)(p16, p16)
-    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 16, 12, None, None, b2, 0, None) == -1   # cout not a multiple of 8
-    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 40, 16, None, None, b2, 0, None) == -1   # cin > 32
-    assert lib.linr_spconv_wide(0, None, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, 0, None) == -1
-    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, 64, None) == -1  # unknown flag
-    assert lib.linr_spconv_wide(1, b2, p16, p16, 16, 16, p16, p16, 4, 16, None, None, b2, 0, None) == -1    # backward needs cin % 8 == 0
-    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, 4, None) == -1   # LINR_RELU_MASK without act blocks
+    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 16, 12, None, None, b2, 0, None, None) == -1   # cout not a multiple of 8
+    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 40, 16, None, None, b2, 0, None, None) == -1   # cin > 32
+    assert lib.linr_spconv_wide(0, None, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, 0, None, None) == -1
+    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, 64, None, None) == -1  # unknown flag
+    assert lib.linr_spconv_wide(1, b2, p16, p16, 16, 16, p16, p16, 4, 16, None, None, b2, 0, None, None) == -1    # backward needs cin % 8 == 0
+    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, 4, None, None) == -1   # LINR_RELU_MASK without act blocks
     b2m = (ctypes.c_void_p * 2)(p16, p16 + 4)
-    assert lib.linr_spconv_wide(0, b2m, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, 0, None) == -3  # a gathered block misaligned
-    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 0, p16, p16, 16, 16, None, None, b2, 0, None) == 0     # empty input is fine
-    assert lib.linr_spconv_wgrad_wide(b2, 16, b2, 5, p16, None, 16, 16, p16, p16, p16, None) == -1          # cout 5
-    assert lib.linr_spconv_wgrad_wide(b2, 16, b2, 16, p16, None, 16, 16, None, p16, p16, None) == -1        # no slab
+    assert lib.linr_spconv_wide(0, b2m, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, 0, None, None) == -3  # a gathered block misaligned
+    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 0, p16, p16, 16, 16, None, None, b2, 0, None, None) == 0     # empty input is fine
+    from linr_pcgc_amd._lib import LinrWidePw
+    pw0 = ctypes.byref(LinrWidePw(0, None, None, None, None))                   # mode 0 = no epilogue = NULL: accepted and refused alike
+    for blocks, n, cout, rc in ((b2, 0, 16, 0), (b2m, 16, 16, -3), (b2, 16, 12, -1)):
+        assert [lib.linr_spconv_wide(0, blocks, p16, p16, 16, n, p16, p16, 16, cout, None, None, b2, 0, e, None) for e in (None, pw0)] == [rc, rc]
+    assert lib.linr_spconv_wgrad_wide(b2, 16, b2, 5, p16, None, 16, 16, p16, p16, p16, 0, None) == -1          # cout 5
+    assert lib.linr_spconv_wgrad_wide(b2, 16, b2, 16, p16, None, 16, 16, None, p16, p16, 0, None) == -1        # no slab
     assert lib.linr_spconv_wgrad_wide_slab_bytes(16, 16) == 512 * 4 * 1736 * 4 and lib.linr_spconv_wgrad_wide_slab_bytes(0, 16) == 0
     # whole network: NULL frame / parameters, stage range
     assert lib.linr_net_forward(None, p16, p16, 4096, 0, 8, None, None, None) == -1
@@ -120,13 +124,12 @@ def test_c_abi_argument_checks(lib):
     assert lib.linr_spconv_bwd_fused_bf16(None, None, None, None, 4, 4, None, None, None, 1, ctypes.byref(rw), None) == -1 and rw.value == 0
     # round-4 entries on blocked activations: pointwise layers, their weight gradients, the occupancy head, the scale context's backward
     b4 = (ctypes.c_void_p * 4)(p16, p16, p16, p16)
-    from linr_pcgc_amd._lib import LinrWidePw
     pw = LinrWidePw(1, p16, p16, None, None)
-    assert lib.linr_spconv_wide_pw(0, b4, p16, p16, 16, 16, p16, p16, 16, 8, None, None, b4, 1, ctypes.byref(pw), None) == -1      # mode 1 without out2
+    assert lib.linr_spconv_wide(0, b4, p16, p16, 16, 16, p16, p16, 16, 8, None, None, b4, 1, ctypes.byref(pw), None) == -1      # mode 1 without out2
     pw = LinrWidePw(3, p16, None, ctypes.cast(b4, ctypes.c_void_p), ctypes.cast(b4, ctypes.c_void_p))
-    assert lib.linr_spconv_wide_pw(0, b4, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b4, 0, ctypes.byref(pw), None) == -1     # mode 3 is a backward epilogue
+    assert lib.linr_spconv_wide(0, b4, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b4, 0, ctypes.byref(pw), None) == -1     # mode 3 is a backward epilogue
     pw = LinrWidePw(2, p16, p16, ctypes.cast(b4, ctypes.c_void_p), ctypes.cast(b4, ctypes.c_void_p))
-    assert lib.linr_spconv_wide_pw(0, b4, p16, p16, 16, 16, p16, p16, 16, 8, None, None, b4, 1, ctypes.byref(pw), None) == -1      # mode 2 needs h -> h
+    assert lib.linr_spconv_wide(0, b4, p16, p16, 16, 16, p16, p16, 16, 8, None, None, b4, 1, ctypes.byref(pw), None) == -1      # mode 2 needs h -> h
     assert lib.linr_linear_wide(b4, 12, 1, p16, 8, 1, p16, 8, 1, None, None, b4, 8, 0, None) == -1            # blocked cin not a multiple of 8
     assert lib.linr_linear_wide(b4, 16, 1, p16, 7, 1, p16, 8, 1, None, None, b4, 8, 0, None) == -1            # strides of no dense layout
     assert lib.linr_linear_wide(b4, 16, 1, p16, 8, 1, p16, 8, 1, None, None, b4, -1, 0, None) == -1           # n < 0
@@ -267,17 +270,17 @@ def test_c_abi_argument_checks(lib):
     for n, rc, rc_ws in ((bound, -1, -1), (bound - 1, -3, -2)):
         assert lib.linr_spconv_wgrad_cmap(p64, 8, p64, 8, p64, p64 + 4, n, n, 8, 8, p64, None) == rc
         assert lib.linr_head_fwd(p64, p64, p64, n, n, p64, p64, p64, p64, p64, p64, p64, 8, p64, p64, p64, p64, 0, None) == rc_ws
-        assert lib.linr_spconv_wgrad_wide2(b2m, b2a, b2a, b2a, 8, p64, n, p64, None) == rc
+        assert lib.linr_spconv_wgrad_wide2(b2m, b2a, b2a, b2a, 8, p64, n, p64, 0, None) == rc
         assert lib.linr_spconv_wide_bf16(0, p64 + 4, 0, 8, p64, p64, n, n, p64, p64, 8, None, 0, None, 0, None, None, 0, p64, 0, None) == rc
         assert lib.linr_head_wide_bf16_fwd(p64 + 4, 8 * (n + 1), 16, p64, p64, n, n, p64, p64, p64, p64, p64, p64, None, 0, p64, None,
                                            None) == rc
     for ld, rc in ((ld_bound, -1), (ld_bound - 1, -3)):
-        assert lib.linr_spconv_wide(0, b2m, p64, p64, ld, 16, p64, p64, 16, 16, None, None, b2a, 0, None) == rc
+        assert lib.linr_spconv_wide(0, b2m, p64, p64, ld, 16, p64, p64, 16, 16, None, None, b2a, 0, None, None) == rc
     assert lib.linr_inception_fwd(p64, p64, p64, bound, bound, byref(q), p64, p64, p64, None) == -1
     assert lib.linr_inception_bwd_data(p64, p64, p64, p64, p64, p64, bound, bound, byref(q), p64, p64, p64, 0, None) == -1
     assert lib.linr_occ_conv7(p64, p64, p64, bound, bound, p64, offs7, offs7, p64, offs7, None) == -1
     assert lib.linr_spconv_wgrad_dual44(p64, p64, 4, p64, 4, p64, None, bound, bound, p64, None) == -1
-    assert lib.linr_spconv_wgrad_wide(b2a, 16, b2a, 16, p64, None, bound, bound, p64, p64, p64, None) == -1
+    assert lib.linr_spconv_wgrad_wide(b2a, 16, b2a, 16, p64, None, bound, bound, p64, p64, p64, 0, None) == -1
     assert lib.linr_spconv_bwd_fused_bf16(p64, p64, p64, p64, bound, bound, p64, p64, p64, 1, byref(rw), None) == -1
     g7a = (ctypes.c_void_p * 7)(*([p64] * 7))
     for n, ld in ((bound, bound), (16, ld_bound)):

@@ -417,30 +417,56 @@ def test_wide_results_do_not_depend_on_leftover_onchip_state(pkg):
 
 @pytest.mark.parametrize('hidden,block_layers', [(16, 1), (32, 1), (16, 2), (32, 3)])
 def test_wide_fused_pointwise_epilogues_equal_the_separate_launches(pkg, hidden, block_layers):
-    """conv1_0 / conv1_2 of a wide Inception layer and their backward-data passes in the convolutions' epilogues (linr_spconv_wide_pw)
+    """conv1_0 / conv1_2 of a wide Inception layer and their backward-data passes in the convolutions' epilogues (linr_spconv_wide's pw)
     keep the fmaf chains of the stand-alone pointwise kernel: two training steps give the same parameters, moments and bits, bit for
-    bit, as with LINR_WIDE_FUSE_PW=0 (one launch per pointwise layer)."""
-    from linr_pcgc_amd import overfit, synthetic, wide_net
+    bit, as with LINR_WIDE_FUSE_PW=0 (fuse_pw False on the executor: one launch per pointwise layer)."""
+    from linr_pcgc_amd import overfit, synthetic
     from linr_pcgc_amd.model_core import FlatAdam, train_step
     gop = overfit.Gop(None, [synthetic.sequence_frame_device('sphere8', 0, 'cuda')], None, 64, 'cuda', block_layers=block_layers)
 
     def run(fuse):
-        old = wide_net._FUSE_PW
-        wide_net._FUSE_PW = fuse
-        try:
-            m = overfit.gen_model(gop.scale_num, 'cuda', seed=8807, hidden=hidden, block_layers=block_layers)
-            o = FlatAdam(m)
-            bits = torch.zeros(2, dtype=torch.float64, device='cuda')
-            for s in range(2):
-                train_step(m, o, gop.frames[0], gop.point_nums[0], out=bits[s:s + 1])
-            torch.cuda.synchronize()
-        finally:
-            wide_net._FUSE_PW = old
+        m = overfit.gen_model(gop.scale_num, 'cuda', seed=8807, hidden=hidden, block_layers=block_layers)
+        m._wide.fuse_pw = fuse
+        o = FlatAdam(m)
+        bits = torch.zeros(2, dtype=torch.float64, device='cuda')
+        for s in range(2):
+            train_step(m, o, gop.frames[0], gop.point_nums[0], out=bits[s:s + 1])
+        torch.cuda.synchronize()
         return m.flat_parameters().clone(), o.exp_avg.clone(), o.exp_avg_sq.clone(), bits.cpu()
     a, b = run(True), run(False)
     assert bool(torch.isfinite(a[0]).all())
     for x, y in zip(a, b):
         assert torch.equal(x, y)
+
+
+def test_wide_passes_of_two_models_and_frames_do_not_leak_into_each_other(pkg):
+    """What a pass runs on travels in the pass object and nowhere else: between the training forward and the backward of a 'bf16-mul'
+    model A on one frame, a plain fp32 model B runs a forward on ANOTHER frame on the same thread.  A's gradient and bits are bitwise
+    those of the undisturbed pass (its backward still sees its own frame's tables, bf16 products and a fresh deferred list) and B's
+    probabilities are bitwise those of B alone (fp32 products, its own frame)."""
+    from linr_pcgc_amd import overfit, synthetic
+    gop = overfit.Gop(None, [synthetic.sequence_frame_device('sphere8', t, 'cuda') for t in (0, 1)], None, 64, 'cuda', block_layers=1)
+    fa, fb = gop.frames
+    assert fa.rows != fb.rows
+    A = overfit.gen_model(gop.scale_num, 'cuda', seed=8807, hidden=16)
+    A.train_precision = 'bf16-mul'
+    B = overfit.gen_model(gop.scale_num, 'cuda', seed=4242, hidden=16)
+
+    def train_pass(between):
+        A._ensure_grad_views()
+        bits = torch.zeros(1, dtype=torch.float64, device='cuda')
+        with torch.no_grad():
+            A._flat_grad.zero_()
+            tape = A._wide.forward(fa, 0, 8, None, bits, keep=True)
+            other = between()
+            A._wide.backward(fa, tape, 1.0 / gop.point_nums[0])
+        return A._flat_grad.clone(), bits, other
+    g_alone, bits_alone, _ = train_pass(lambda: None)
+    p_alone, pbits_alone = B.frame_probs(fb)
+    g, bits, (p, pbits) = train_pass(lambda: B.frame_probs(fb))
+    assert bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0
+    assert torch.equal(g, g_alone) and torch.equal(bits, bits_alone)
+    assert torch.equal(p, p_alone) and torch.equal(pbits, pbits_alone)
 
 
 # ---- tiny, ragged and multi-tile frames ------------------------------------------------------------------------------------------------

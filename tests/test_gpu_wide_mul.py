@@ -193,7 +193,7 @@ def _paired(pkg, m, h):
 
 @pytest.mark.parametrize('h', [8, 16])
 def test_paired_entry_small(pkg, h):
-    """linr_spconv_wgrad_wide2_f with the flag through the deferred reductions, 257 rows (most of the 256 slab rows empty)."""
+    """linr_spconv_wgrad_wide2 with the flag through the deferred reductions, 257 rows (most of the 256 slab rows empty)."""
     _paired(pkg, _small(pkg, 257), h)
 
 
@@ -267,23 +267,17 @@ def test_fused_epilogues_are_bitwise_the_two_launch_form(pkg, shell, hidden, blo
     """EPI 1 .. 4 with the flag: the side outputs computed in the convolutions' epilogues (h1 = conv1_0, the layer output's upper half =
     conv1_2 + residual; gM and conv1_0's backward-data, which every upstream gradient depends on) are bitwise those of linr_linear_wide
     on the fp32 rows (LINR_WIDE_FUSE_PW=0's schedule): the side paths read unrounded values and keep their fmaf chains."""
-    from linr_pcgc_amd import wide_net
-
     def run(fuse):
-        old = wide_net._FUSE_PW
-        wide_net._FUSE_PW = fuse
-        try:
-            model, _ = _model(hidden, block_layers=block_layers)
-            frame = model.make_frame(shell['scales'])
-            tape, bits, grads = _train_pass(model, frame, 1.0 / shell['point_num'])
-            side = []
-            for bt in [tape['bin']] + [st['blk'] for st in tape['stages'] if st['blk'] is not None]:
-                for lt in bt['layers']:
-                    side += [b.clone() for b in lt['h1']]
-                side += [b.clone() for b in bt['il']]
-            return side, bits, grads
-        finally:
-            wide_net._FUSE_PW = old
+        model, _ = _model(hidden, block_layers=block_layers)
+        model._wide.fuse_pw = fuse
+        frame = model.make_frame(shell['scales'])
+        tape, bits, grads = _train_pass(model, frame, 1.0 / shell['point_num'])
+        side = []
+        for bt in [tape['bin']] + [st['blk'] for st in tape['stages'] if st['blk'] is not None]:
+            for lt in bt['layers']:
+                side += [b.clone() for b in lt['h1']]
+            side += [b.clone() for b in bt['il']]
+        return side, bits, grads
     (sa, ba, ga), (sb, bb, gb) = run(True), run(False)
     assert len(sa) == len(sb) and len(sa) > 0 and bool(torch.isfinite(ga).all())
     for x, y in zip(sa, sb):

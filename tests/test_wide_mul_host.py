@@ -27,21 +27,23 @@ def p16():
     del buf
 
 
-def test_abi_26_declares_the_flag_and_the_flags_taking_entries(lib):
-    assert _lib.ABI_VERSION == 26 and lib.linr_abi_version() == 26
+def test_abi_declares_the_flag_and_one_entry_per_wide_op(lib):
+    assert _lib.ABI_VERSION == 27 and lib.linr_abi_version() == 27
     assert _lib.LINR_MUL_BF16 == MUL
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'linr_hip.h')).read()
-    assert '#define LINR_MUL_BF16 16u' in header and '#define LINR_ABI_VERSION 26' in header
-    for name in ('linr_spconv_wgrad_wide_f', 'linr_spconv_wgrad_wide2_f'):
-        assert name in _lib.EXPORTS and hasattr(lib, name)
+    assert '#define LINR_MUL_BF16 16u' in header and '#define LINR_ABI_VERSION 27' in header
+    for name in ('linr_spconv_wide', 'linr_spconv_wgrad_wide', 'linr_spconv_wgrad_wide2'):          # each takes the flags word itself
+        assert name in _lib.EXPORTS and hasattr(lib, name) and name + '(' in header
+    for name in ('linr_spconv_wide_pw', 'linr_spconv_wgrad_wide_f', 'linr_spconv_wgrad_wide2_f'):   # ABI 26's twins are gone
+        assert name not in _lib.EXPORTS and name not in header and not hasattr(lib, name)
 
 
 def test_conv_entries_take_flag_16_and_still_refuse_every_other_bit(lib, p16):
     b2 = (ctypes.c_void_p * 2)(p16, p16)
     pw = _lib.LinrWidePw(1, p16, p16, None, ctypes.cast(b2, ctypes.c_void_p))
-    conv = lambda cout, flags, n=16: lib.linr_spconv_wide(0, b2, p16, p16, 16, n, p16, p16, 16, cout, None, None, b2, flags, None)
-    conv_pw = lambda cout, flags, n=16: lib.linr_spconv_wide_pw(0, b2, p16, p16, 16, n, p16, p16, 16, cout, None, None, b2, flags,
-                                                                 ctypes.byref(pw), None)
+    conv = lambda cout, flags, n=16: lib.linr_spconv_wide(0, b2, p16, p16, 16, n, p16, p16, 16, cout, None, None, b2, flags, None, None)
+    conv_pw = lambda cout, flags, n=16: lib.linr_spconv_wide(0, b2, p16, p16, 16, n, p16, p16, 16, cout, None, None, b2, flags,
+                                                              ctypes.byref(pw), None)
     for entry, cout in ((conv, 16), (conv_pw, 8)):
         for flags in (64, MUL | 64, 32):
             assert entry(cout, flags) == -1, flags
@@ -49,16 +51,16 @@ def test_conv_entries_take_flag_16_and_still_refuse_every_other_bit(lib, p16):
     b2m = (ctypes.c_void_p * 2)(p16, p16 + 4)
     # flag 16 passes the flags check: a later check answers (a misaligned gathered block: LINR_EALIGN, not the flag's LINR_EINVAL)
     for flags in (MUL, MUL | 1 | 2):
-        assert lib.linr_spconv_wide(0, b2m, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, flags, None) == -3
-    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, MUL | 4, None) == -1    # mask without act
+        assert lib.linr_spconv_wide(0, b2m, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, flags, None, None) == -3
+    assert lib.linr_spconv_wide(0, b2, p16, p16, 16, 16, p16, p16, 16, 16, None, None, b2, MUL | 4, None, None) == -1    # mask without act
 
 
 def test_wgrad_entries_with_flags_refuse_every_bit_but_16_and_what_the_old_entries_refuse(lib, p16):
     b2 = (ctypes.c_void_p * 2)(p16, p16)
     b2m = (ctypes.c_void_p * 2)(p16 + 4, p16 + 4)
-    wg = lambda flags, cout=16, slab=p16, tile=p16, n=16: lib.linr_spconv_wgrad_wide_f(b2, 16, b2, cout, p16, tile, 16, n, slab, p16, p16,
-                                                                                       flags, None)
-    wg2 = lambda flags, h=8, n=16, a=b2: lib.linr_spconv_wgrad_wide2_f(a, b2, b2, b2, h, p16, n, p16, flags, None)
+    wg = lambda flags, cout=16, slab=p16, tile=p16, n=16: lib.linr_spconv_wgrad_wide(b2, 16, b2, cout, p16, tile, 16, n, slab, p16, p16,
+                                                                                     flags, None)
+    wg2 = lambda flags, h=8, n=16, a=b2: lib.linr_spconv_wgrad_wide2(a, b2, b2, b2, h, p16, n, p16, flags, None)
     for bit in range(32):
         if (1 << bit) != MUL:
             assert wg(1 << bit) == -1 and wg(MUL | (1 << bit)) == -1, bit
@@ -72,7 +74,7 @@ def test_wgrad_entries_with_flags_refuse_every_bit_but_16_and_what_the_old_entri
     # the bf16 products exist in the one-launch form only: without the tiled table there is nothing to fall back to
     assert wg(MUL, tile=None) == -1 and wg(MUL, cout=24) == -1
     # n == 0 launches nothing: zeroed gradients, as without the flag (checked on the host: the memsets would need a device)
-    assert lib.linr_spconv_wgrad_wide_f(b2, 16, b2, 16, p16, p16, 16, 0, p16, None, p16, MUL, None) == -1      # deferred + no rows
+    assert lib.linr_spconv_wgrad_wide(b2, 16, b2, 16, p16, p16, 16, 0, p16, None, p16, MUL, None) == -1      # deferred + no rows
 
 
 def _fake_model(wide, tp):
@@ -121,10 +123,21 @@ def test_run_parser_takes_bf16_mul_and_the_default_rule_never_picks_it():
 
 
 def test_a_pass_multiplies_in_bf16_only_while_training_a_bf16_mul_model():
-    """wide_net._mul() is per-pass state: 'f32' outside a pass and for every model that did not ask."""
+    """What a pass multiplies in is a field of the pass object that forward / backward build per call (WideNet._pass): 'bf16' in the
+    training passes of a 'bf16-mul' model, 'f32' in its other forwards and in every pass of a model that did not ask."""
+    import torch
     from linr_pcgc_amd import wide_net
-    assert wide_net._mul() == 'f32'
+    frame = types.SimpleNamespace(nbr_lo=None, nbr_mask=None, nbr=None, nbr8t=None, rows=3, occ=torch.zeros(3, 8))
     net = wide_net.WideNet(types.SimpleNamespace(train_precision='bf16-mul'), 16)
-    assert net._train_mul() == 'bf16'
+    assert net._pass(frame, True, False).mul == 'bf16'                      # forward(keep=True)
+    assert net._pass(frame, False, False).mul == 'f32'                      # forward(keep=False): codec, decoder, probabilities
+    back = net._pass(frame, True, False, defer=[])                          # backward
+    assert back.mul == 'bf16' and back.defer == [] and net._pass(frame, True, False).defer is None
     net.model.train_precision = 'f32'
-    assert net._train_mul() == 'f32'
+    for training in (True, False):
+        assert net._pass(frame, training, False).mul == 'f32'
+        assert net._pass(frame, training, False, defer=[]).mul == 'f32'
+    # a pass is its own object: nothing of it stays on the executor, and a fresh-buffer pass hands out zero-padded blocks of the frame
+    assert back.pool is None and back.n == 3 and not {'lo', 'mask', 'nbr', 'tile8t', 'n', 'mul', 'defer'} & set(vars(net))
+    blk = back.blocks(2)
+    assert len(blk) == 2 and all(b.shape == (3, 8) and not b._base[:, 0].any() for b in blk)
