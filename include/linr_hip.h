@@ -51,8 +51,9 @@ LINR_API int linr_abi_version(void);
  * Inception layers of block_in's ResNetBlock, 1..4 - the outter blocks always have one, upsample.py:72-76).
  * 54,712 for scale_num = 7, block_layers = 1.  This count and the whole-network entry points (linr_net_*) are the
  * hidden_channel_conv = 8 model (main.py:520 default): their kernels are specialised for 8-wide rows.  Widths 16 / 32 run on
- * the channel-blocked executor of the host mirror (linr_pcgc_amd/wide_net.py), which drives the op-level entries below on
- * 8-wide channel blocks and keeps its own parameter count. */
+ * the channel-blocked executor: the op-level entries below on 8-wide channel blocks.  Its inference forward and its decoder scales
+ * are C entries, too (linr_param_count_wide, linr_net_forward_wide[_bf16], linr_decode_scale[_batch]_wide); its training step is
+ * scheduled by the host mirror (linr_pcgc_amd/wide_net.py). */
 LINR_API int64_t linr_param_count(int32_t scale_num, int32_t block_layers);
 
 /* ---- kernel map -------------------------------------------------------------------------------------------
@@ -518,6 +519,34 @@ LINR_API int linr_head_wide_bf16_fwd(const uint16_t* in, int64_t in_bs, int32_t 
                                      const float* b2, const float* target, int32_t t_col, float* p, double* partial, void* stream);
 LINR_API int linr_sce_fwd_bf16(const float* pf, const linr_frame* f, uint16_t* x0_padded, void* stream);
 
+/* ---- the inference forward of hidden_channel_conv 16 / 32 as one call (csrc/wide_fwd.hip) ---------------------------------------
+ * LINR_PCGC_Model.logic_core / forward (models/model_core.py:38-81) + CNP.forward (models/upsample.py:163-217) at channels = 16 / 32:
+ * the schedule of the host mirror (WideNet._forward with the pointwise layers fused; WideNet.forward_bf16) launch for launch through
+ * the op-level entries above, with the arguments the mirror hands them - the probabilities and bits are the mirror's bit for bit.
+ * linr_param_count_wide: the float parameters of LINR_PCGC_Model(scale_num, hidden, block_layers) in parameters() order (the scale
+ *   context first, as at width 8; then block_in, the 8 inner_mlps Linear(hidden, 24) / Linear(24, 1), the 8 prune convolutions, the 7
+ *   outter blocks); 0 for a hidden other than 16 / 32, a scale_num outside 1..16 or block_layers outside 1..4.
+ * linr_net_wide_arena_bytes: the arena of one frame (any scale_num): per-role channel blocks that all blocks and stages reuse, the
+ *   stages' bits partials and, for bf16 != 0, the de-quantised parameters, the prologue's convolution table and the weight images;
+ *   0 for rows < 0 or over the row bound of linr_frame, and for a hidden / block_layers as above.
+ * linr_net_forward_wide / _bf16: stages [stage_begin, stage_end) as linr_net_forward / linr_net_forward_bf16 run them.  stage_begin
+ *   == 0 computes the scale context and block_in (bf16: the de-quantisation prologue first) and leaves x_glob (and the images) in the
+ *   arena; stage_begin > 0 needs the preceding call on the same frame and arena to have done so, and reads the occupancy columns
+ *   decoded so far from f->occ (LINR_FRAME_OCC_PADDED honoured; without it the fp32 forward gathers a padded copy it makes per call).
+ *   probs [8][rows] stage-major or NULL; bits_acc double[1], accumulated into, or NULL.  arena: 64-byte aligned.  codes: the uint8
+ *   codes of linr_param_count_wide parameters.  Checked in front of the first launch, in this order: a NULL f / params / codes /
+ *   arena (LINR_EINVAL), the arena's alignment (LINR_EALIGN), hidden, the stage range (LINR_EINVAL), the arena's size (LINR_EINVAL
+ *   where linr_net_wide_arena_bytes is 0, else LINR_ENOSPC), then the frame (linr_frame's structure, its matrices, nbr_ld).  rows
+ *   == 0 returns 0 behind the checks.  The one kernel of its own (zero rows of the arena's blocks, the bf16 table) is in poison
+ *   class 16. */
+LINR_API int64_t linr_param_count_wide(int32_t scale_num, int32_t block_layers, int32_t hidden);
+LINR_API size_t linr_net_wide_arena_bytes(int64_t rows, int32_t hidden, int32_t block_layers, int32_t bf16);
+LINR_API int linr_net_forward_wide(const linr_frame* f, const float* params, int32_t hidden, void* arena, size_t arena_bytes,
+                                   int32_t stage_begin, int32_t stage_end, float* probs, double* bits_acc, void* stream);
+LINR_API int linr_net_forward_wide_bf16(const linr_frame* f, const uint8_t* codes, float min_param, float max_param, int32_t hidden,
+                                        void* arena, size_t arena_bytes, int32_t stage_begin, int32_t stage_end, float* probs,
+                                        double* bits_acc, void* stream);
+
 /* ---- bf16 training executor (BASELINE config[4]: "bf16 SparseConv"; beside the fp32 step above, never instead of it) --
  * The overfit iteration of main.py:305-321 - forward of models/model_core.py:38-81 / models/upsample.py:88-97,137-217 /
  * models/resnet.py:12-60, the autograd backward of main.py:315-316, Adam of main.py:231-237,319 - with bf16 feature AND gradient
@@ -644,6 +673,24 @@ LINR_API int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_of
                             float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
                             void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap,
                             int64_t* child_off_h, const linr_decode_opts* opts, void* stream);
+/* The same four for a model of hidden_channel_conv = `hidden`: 16 / 32 run the stages on linr_net_forward_wide[_bf16] (params /
+ * codes: linr_param_count_wide elements), 8 is the entries above; anything else is LINR_EINVAL (a size of 0).  Everything else -
+ * the workspace layout but for the arena, the options, the checks and their order - is shared (csrc/decode.hip: scale_middle).
+ * `hidden` belongs in linr_decode_opts: it moves there at the next ABI bump, and these four go. */
+LINR_API size_t linr_decode_scale_wide_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total,
+                                                int64_t n_entries, int32_t hidden);
+LINR_API int linr_decode_scale_wide(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                           int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                           const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                           float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
+                           const linr_decode_opts* opts, int32_t hidden, void* stream);
+LINR_API size_t linr_decode_scale_batch_wide_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
+                                                      int64_t stream_bytes_total, int64_t n_entries, int32_t hidden);
+LINR_API int linr_decode_scale_batch_wide(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                 int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                 float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                                 void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap,
+                                 int64_t* child_off_h, const linr_decode_opts* opts, int32_t hidden, void* stream);
 LINR_API size_t linr_children_segments_ws_bytes(int64_t n);
 LINR_API int linr_children_segments(const int32_t* coords, const float* occ, const int64_t* seg_off_h, int32_t n_seg, int32_t* child_xyz,
                            int64_t child_cap, int64_t* child_off_h, void* ws, size_t ws_bytes, void* stream);

@@ -155,6 +155,11 @@ _PROTOS = {
     'linr_head_wide_bf16_fwd': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                                c_ptr, c_i32, c_ptr, c_ptr, c_ptr]),
     'linr_sce_fwd_bf16': (ctypes.c_int, [c_ptr, ctypes.POINTER(LinrFrame), c_ptr, c_ptr]),
+    'linr_param_count_wide': (c_i64, [c_i32, c_i32, c_i32]),
+    'linr_net_wide_arena_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    'linr_net_forward_wide': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_i32, c_ptr, c_size, c_i32, c_i32, c_ptr, c_ptr, c_ptr]),
+    'linr_net_forward_wide_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_f32, c_f32, c_i32, c_ptr, c_size, c_i32, c_i32, c_ptr,
+                                                  c_ptr, c_ptr]),
     'linr_net_train_bf16_arena_bytes': (c_size, [c_i64, c_i32]),
     'linr_occ_to_bf16': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
     'linr_net_forward_train_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr]),
@@ -191,7 +196,13 @@ _PROTOS = {
     'linr_decode_scale_batch_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32, c_i64, c_i64]),
     'linr_decode_scale_batch': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
                                                c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, ctypes.POINTER(LinrDecodeOpts), c_ptr]),
-    'linr_ac_decode_binary_twin': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    'linr_decode_scale_wide_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i64, c_i64, c_i32]),
+    'linr_decode_scale_wide': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_size,
+                                              c_ptr, c_ptr, c_ptr, c_i64, c_ptr, ctypes.POINTER(LinrDecodeOpts), c_i32, c_ptr]),
+    'linr_decode_scale_batch_wide_ws_bytes': (c_size, [c_i64, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32]),
+    'linr_decode_scale_batch_wide': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
+                                                    c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, ctypes.POINTER(LinrDecodeOpts), c_i32, c_ptr]),
+    'linr_ac_decode_binary_twin':(ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     'linr_rc_decode_ws_bytes': (c_size, [c_i32]),
     'linr_rc_decode_probs': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i32, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
     'linr_ac_decode_binary_batch': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_i32]),

@@ -324,13 +324,7 @@ def decode_one_frame(model, frame_enc_bytes, xyz_low, chunk=0, n_threads=1, devi
     frame is seven buffer allocations.  chunk = S > 0: the stage streams are chunked (side_info's stream_chunk) and a stage's chunks are
     decoded on n_threads host threads.  device_decoder=True: the range decoders run on the GPU (model.decode_scale(device_decoder=True)
     -> linr_decode_opts.device), no host round trip per stage; n_threads is ignored."""
-    if getattr(model, '_wide', None) is not None:          # hidden_channel_conv 16 / 32: no single-call decoder scale
-        if chunk:
-            raise ValueError('chunked stage streams decode with hidden_channel_conv 8 only')
-        if device_decoder:
-            raise ValueError('the device decoder needs hidden_channel_conv 8: the widths 16 and 32 decode stage-wise in Python')
-        return decode_one_frame_stagewise(model, frame_enc_bytes, xyz_low)
-    lowx = unique_sorted(xyz_low)
+    lowx = unique_sorted(xyz_low)          # (hidden_channel_conv 16 / 32: the same loop, model.decode_scale -> linr_decode_scale_wide)
     bits = max(1, int(xyz_low.max()).bit_length()) if xyz_low.numel() else 1       # coordinates of the coarsest level
     for s_idx in range(len(frame_enc_bytes) - 1, -1, -1):
         bits = min(bits + 1, 21)
@@ -390,7 +384,8 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
     lockstep=B > 0 (opt-in; 0 = the per-frame path below, untouched): the requested frames are decoded in groups of up to B
     consecutive entries, the scales of a group from coarsest to finest in lock step (decode_frames_lockstep), the group's range
     decoders on `n_threads` host threads (default: the cores this process may use, at most 16).  `workers` then means groups in
-    flight, each on its own stream.  Models of hidden_channel_conv 16 / 32 ignore it.  The streams are the same either way.
+    flight, each on its own stream.  Models of hidden_channel_conv 16 / 32 take workers and lockstep as width 8 does: their scales are
+    C calls, too (linr_decode_scale_wide / _batch_wide), which keep nothing on the model.  The streams are the same either way.
     `timing` (a dict) receives 'setup_s': the once-per-GOP part (model.bin -> parameters, the coarsest coordinates), and with
     lockstep 'lockstep_ws_bytes': the largest device workspace of a lock-step call.
     side_info's 'stream_chunk' = S (absent or 0: nothing changes): the stage streams are chunked (stream_chunks.py) and a stage's
@@ -442,9 +437,6 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
         dec = decode_one_frame(model, list(enc['frames'][i]), xyz_low, chunk, per_frame, device_decoder)['dec_coord']
         return dec + torch.tensor(mins[i], device=device, dtype=torch.int32)
 
-    if getattr(model, '_wide', None) is not None:
-        workers = 1          # the channel-blocked executor keeps per-call state on the model: frames one after the other
-        lockstep = 0
     if lockstep and lockstep > 0 and todo:
         out = _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, min(int(lockstep), LOCKSTEP_MAX_FRAMES), n_threads, chunk,
                                    device_decoder)

@@ -8,6 +8,8 @@
 // in lock step; they share everything between their argument checks and the child expansion (scale_middle: the workspace layout, the
 // stage plan, the device decoders' upload, scale_prologue, decode_stages) and differ in the kernel map (one list / segments) and in the
 // child expansion (radix sort / prefix sums).  linr_decode_opts picks chunked streams, the host threads and the device decoders.
+// The _wide twins of the four scale entries take the model's hidden_channel_conv: 16 / 32 size the arena for, and run the stages on,
+// the wide forwards of csrc/wide_fwd.hip; the plain entries are the twins at 8.
 #include "common.h"
 #include "layout.h"
 #include "prof.h"
@@ -69,7 +71,8 @@ struct ScaleWs {
 // stream_bytes >= 0: with the device decoders' two regions - the stream bytes padded to 256 bytes (at least one such block, so this
 // layout is the host decoders' plus 512 bytes or more) plus one 256-byte window, so that every aligned window a wave could ask for
 // lies inside, and n_entries table entries
-ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan, int64_t stream_bytes = -1, int64_t n_entries = 0) {
+// hidden: 8, or 16 / 32 for the arena of the wide forwards (csrc/wide_fwd.hip)
+ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan, int hidden, int64_t stream_bytes = -1, int64_t n_entries = 0) {
     ScaleWs w;
     w.ld = (n + 63) / 64 * 64;
     size_t cur = 0;
@@ -85,7 +88,8 @@ ScaleWs layout(int64_t n, int block_layers, int bf16, bool scan, int64_t stream_
     w.is_scan = scan;
     if (scan) w.scan = child_layout(n); else w.sort = sort_layout(n);
     w.child = take(scan ? w.scan.total : w.sort.total);
-    w.arena_bytes = bf16 ? linr_net_bf16_arena_bytes(n, block_layers) : linr_net_arena_bytes(n, block_layers);
+    w.arena_bytes = hidden != 8 ? linr_net_wide_arena_bytes(n, hidden, block_layers, bf16)
+                                : bf16 ? linr_net_bf16_arena_bytes(n, block_layers) : linr_net_arena_bytes(n, block_layers);
     w.arena = take(w.arena_bytes);
     w.sbytes = w.tab = cur;
     if (stream_bytes >= 0) {
@@ -233,13 +237,16 @@ struct DeviceStages { const uint8_t* bytes; const linr_rc_dec_entry* tab; };
 int decode_stages(const linr_frame* f, const float* params, const uint8_t* codes, float min_param, float max_param, void* arena,
                   size_t arena_bytes, const int64_t* seg_off_h, int n_seg, const uint8_t* const* streams_h,
                   const int64_t* stream_len_h, float* probs, float* p_pinned, uint8_t* s_pinned, uint8_t* s_dev, int n_threads,
-                  const StagePlan* ready, hipStream_t s, const DeviceStages* dev = nullptr) {
+                  const StagePlan* ready, hipStream_t s, const DeviceStages* dev = nullptr, int hidden = 8) {
     const int64_t R = f->rows;
     if (R == 0) return 0;
     float* occ = const_cast<float*>(f->occ);
     StagePlan own;
     for (int k = 0; k < 8; ++k) {
-        if (codes) TRY(linr_net_forward_bf16(f, codes, min_param, max_param, arena, arena_bytes, k, k + 1, probs, nullptr, s));
+        // the stage's forward, one of four: width 8 or the channel-blocked widths, fp32 parameters or the uint8 codes
+        if (hidden != 8 && codes) TRY(linr_net_forward_wide_bf16(f, codes, min_param, max_param, hidden, arena, arena_bytes, k, k + 1, probs, nullptr, s));
+        else if (hidden != 8) TRY(linr_net_forward_wide(f, params, hidden, arena, arena_bytes, k, k + 1, probs, nullptr, s));
+        else if (codes) TRY(linr_net_forward_bf16(f, codes, min_param, max_param, arena, arena_bytes, k, k + 1, probs, nullptr, s));
         else TRY(linr_net_forward(f, params, (float*)arena, arena_bytes, k, k + 1, probs, nullptr, s));
         if (dev) {
             linr_poison_hook(s, PK_DECODE);
@@ -333,7 +340,7 @@ int upload_device(const DevicePlan& keep, const DeviceStages& dev, hipStream_t s
 // and the child region laid out for the scan; otherwise the kernel map of one list and the region of the sort.
 struct ScaleArgs {
     const int32_t* coord; int64_t n; const int64_t* seg_off_h; int32_t n_seg; bool segmented;
-    int32_t scale_idx, model_scale_num, block_layers;
+    int32_t scale_idx, model_scale_num, block_layers, hidden;
     const float* params; const uint8_t* codes; float min_param, max_param;
     const uint8_t* const* streams_h; const int64_t* stream_len_h;
     void* ws; size_t ws_bytes; float* p_pinned; uint8_t* s_pinned;
@@ -361,7 +368,7 @@ int scale_middle(const ScaleArgs& a, ScaleRun& r) {
     if (!device && (!a.p_pinned || !a.s_pinned)) return LINR_EINVAL;
     if (((uintptr_t)a.ws) & 255u) return LINR_EALIGN;
     const int bf16 = a.codes ? 1 : 0;
-    r.w = layout(a.n, a.block_layers, bf16, a.segmented);
+    r.w = layout(a.n, a.block_layers, bf16, a.segmented, a.hidden);
     if (a.ws_bytes < r.w.total) return LINR_ENOSPC;
     char* base = (char*)a.ws;
     float* p_pinned = device ? nullptr : a.p_pinned;
@@ -370,7 +377,7 @@ int scale_middle(const ScaleArgs& a, ScaleRun& r) {
     DeviceStages dev{nullptr, nullptr};
     if (device) {
         TRY(plan_device(r.plan, a.n_seg, a.seg_off_h, a.streams_h, a.stream_len_h, a.n, r.keep));
-        r.w = layout(a.n, a.block_layers, bf16, a.segmented, (int64_t)r.keep.bytes.size(), (int64_t)r.keep.ent.size());
+        r.w = layout(a.n, a.block_layers, bf16, a.segmented, a.hidden, (int64_t)r.keep.bytes.size(), (int64_t)r.keep.ent.size());
         if (a.ws_bytes < r.w.total) return LINR_ENOSPC;
         dev.bytes = (const uint8_t*)(base + r.w.sbytes);
         dev.tab = (const linr_rc_dec_entry*)(base + r.w.tab);
@@ -381,28 +388,37 @@ int scale_middle(const ScaleArgs& a, ScaleRun& r) {
                        a.block_layers, base, r.w, r.sf, a.s));
     return decode_stages(&r.sf.f, a.params, a.codes, a.min_param, a.max_param, base + r.w.arena, r.w.arena_bytes, a.seg_off_h, a.n_seg,
                          a.streams_h, a.stream_len_h, (float*)(base + r.w.probs), p_pinned, s_pinned, (uint8_t*)(base + r.w.sdev),
-                         device ? 1 : o.n_threads, &r.plan, a.s, device ? &dev : nullptr);
+                         device ? 1 : o.n_threads, &r.plan, a.s, device ? &dev : nullptr, a.hidden);
 }
 
 // stream_bytes_total -1: the host decoders' layout; >= 0: the device decoders' (0 for anything else)
-size_t scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, bool scan, int64_t stream_bytes_total, int64_t n_entries) {
-    if (stream_bytes_total < -1 || (stream_bytes_total >= 0 && n_entries < 0)) return 0;
-    return layout(n, block_layers, bf16 ? 1 : 0, scan, stream_bytes_total, n_entries).total + 256;
+inline bool width_ok(int hidden) { return hidden == 8 || hidden == 16 || hidden == 32; }
+
+size_t scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, bool scan, int hidden, int64_t stream_bytes_total, int64_t n_entries) {
+    if (stream_bytes_total < -1 || (stream_bytes_total >= 0 && n_entries < 0) || !width_ok(hidden)) return 0;
+    const ScaleWs w = layout(n, block_layers, bf16 ? 1 : 0, scan, hidden, stream_bytes_total, n_entries);
+    if (hidden != 8 && w.arena_bytes == 0) return 0;          // (a depth the wide forwards do not have)
+    return w.total + 256;
 }
 
 }  // namespace
 
-extern "C" size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total, int64_t n_entries) {
+extern "C" size_t linr_decode_scale_wide_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total, int64_t n_entries,
+                                                  int32_t hidden) {
     if (n < 0 || block_layers < 1) return 0;
-    return scale_ws_bytes(n, block_layers, bf16, false, stream_bytes_total, n_entries);
+    return scale_ws_bytes(n, block_layers, bf16, false, hidden, stream_bytes_total, n_entries);
 }
 
-extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
-                                 int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
-                                 const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
-                                 float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
-                                 const linr_decode_opts* opts, void* stream) {
-    if (n < 0 || !child_n_h || child_bits < 1 || child_bits > 21 || block_layers < 1) return LINR_EINVAL;
+extern "C" size_t linr_decode_scale_ws_bytes(int64_t n, int32_t block_layers, int32_t bf16, int64_t stream_bytes_total, int64_t n_entries) {
+    return linr_decode_scale_wide_ws_bytes(n, block_layers, bf16, stream_bytes_total, n_entries, 8);
+}
+
+extern "C" int linr_decode_scale_wide(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                                      int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                                      const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                                      float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
+                                      const linr_decode_opts* opts, int32_t hidden, void* stream) {
+    if (n < 0 || !child_n_h || child_bits < 1 || child_bits > 21 || block_layers < 1 || !width_ok(hidden)) return LINR_EINVAL;
     *child_n_h = 0;
     if (n == 0) return 0;
     // (one row looser than linr_rows_fit32, which the executor's frame check then applies to the frame built in the prologue)
@@ -410,7 +426,7 @@ extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_
     hipStream_t s = (hipStream_t)stream;
     ScaleRun r(s);
     r.sf.row_off[0] = 0; r.sf.row_off[1] = n;          // the one segment
-    const ScaleArgs a{coord, n, r.sf.row_off, 1, false, scale_idx, model_scale_num, block_layers, params, codes, min_param, max_param,
+    const ScaleArgs a{coord, n, r.sf.row_off, 1, false, scale_idx, model_scale_num, block_layers, hidden, params, codes, min_param, max_param,
                       streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, opts, s};
     TRY(scale_middle(a, r));
     // upper_layer: children of the occupied octants, sorted x-major
@@ -438,6 +454,15 @@ extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_
     }
     *child_n_h = total;
     return linr_launch_rc();
+}
+
+extern "C" int linr_decode_scale(const int32_t* coord, int64_t n, int32_t scale_idx, int32_t model_scale_num, int32_t block_layers,
+                                 int32_t child_bits, const float* params, const uint8_t* codes, float min_param, float max_param,
+                                 const uint8_t* const* streams_h, const int64_t* stream_len_h, void* ws, size_t ws_bytes,
+                                 float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz, int64_t child_cap, int64_t* child_n_h,
+                                 const linr_decode_opts* opts, void* stream) {
+    return linr_decode_scale_wide(coord, n, scale_idx, model_scale_num, block_layers, child_bits, params, codes, min_param, max_param,
+                                  streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap, child_n_h, opts, 8, stream);
 }
 
 // ---- the same for the frames of a GOP in lock step: one scale of n_frames frames per call, children without a sort ------------------
@@ -593,22 +618,28 @@ extern "C" int linr_children_segments(const int32_t* coords, const float* occ, c
     return children_segments(coords, occ, tab, n, n_seg, child_xyz, child_cap, child_off_h, (char*)ws, w, (hipStream_t)stream);
 }
 
-extern "C" size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
-                                                   int64_t stream_bytes_total, int64_t n_entries) {
+extern "C" size_t linr_decode_scale_batch_wide_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
+                                                        int64_t stream_bytes_total, int64_t n_entries, int32_t hidden) {
     if (n_total < 0 || n_total >= ((int64_t)1 << 26) || n_frames < 1 || n_frames > LINR_DECODE_MAX_FRAMES || block_layers < 1) return 0;
-    return scale_ws_bytes(n_total, block_layers, bf16, true, stream_bytes_total, n_entries);
+    return scale_ws_bytes(n_total, block_layers, bf16, true, hidden, stream_bytes_total, n_entries);
 }
 
-extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
-                                       int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
-                                       float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
-                                       void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
-                                       int64_t child_cap, int64_t* child_off_h, const linr_decode_opts* opts, void* stream) {
+extern "C" size_t linr_decode_scale_batch_ws_bytes(int64_t n_total, int32_t n_frames, int32_t block_layers, int32_t bf16,
+                                                   int64_t stream_bytes_total, int64_t n_entries) {
+    return linr_decode_scale_batch_wide_ws_bytes(n_total, n_frames, block_layers, bf16, stream_bytes_total, n_entries, 8);
+}
+
+extern "C" int linr_decode_scale_batch_wide(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                            int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                            float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                                            void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
+                                            int64_t child_cap, int64_t* child_off_h, const linr_decode_opts* opts, int32_t hidden,
+                                            void* stream) {
     LinrSegTab tab;
     int64_t n = 0;
     const int rc = linr_seg_tab(seg_off_h, n_frames, &tab, &n);
     if (rc) return rc;
-    if (!child_off_h || block_layers < 1 || child_cap < 0) return LINR_EINVAL;
+    if (!child_off_h || block_layers < 1 || child_cap < 0 || !width_ok(hidden)) return LINR_EINVAL;
     const int64_t ld = (n + 63) / 64 * 64;
     if (!linr_cmap_fits32(ld) || !linr_rows_fit32(n)) return LINR_EINVAL;
     for (int i = 0; i <= n_frames; ++i) child_off_h[i] = 0;
@@ -616,11 +647,21 @@ extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_
     if (!child_xyz) return LINR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     ScaleRun r(s);
-    const ScaleArgs a{coord, n, seg_off_h, n_frames, true, scale_idx, model_scale_num, block_layers, params, codes, min_param, max_param,
+    const ScaleArgs a{coord, n, seg_off_h, n_frames, true, scale_idx, model_scale_num, block_layers, hidden, params, codes, min_param, max_param,
                       streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, opts, s};
     TRY(scale_middle(a, r));
     // (children_segments synchronises when it succeeds; the guard covers the ways out in front of that)
     return children_segments(coord, r.sf.f.occ, tab, n, n_frames, child_xyz, child_cap, child_off_h, (char*)ws + r.w.child, r.w.scan, s);
+}
+
+extern "C" int linr_decode_scale_batch(const int32_t* coord, const int64_t* seg_off_h, int32_t n_frames, int32_t scale_idx,
+                                       int32_t model_scale_num, int32_t block_layers, const float* params, const uint8_t* codes,
+                                       float min_param, float max_param, const uint8_t* const* streams_h, const int64_t* stream_len_h,
+                                       void* ws, size_t ws_bytes, float* p_pinned, uint8_t* s_pinned, int32_t* child_xyz,
+                                       int64_t child_cap, int64_t* child_off_h, const linr_decode_opts* opts, void* stream) {
+    return linr_decode_scale_batch_wide(coord, seg_off_h, n_frames, scale_idx, model_scale_num, block_layers, params, codes, min_param,
+                                        max_param, streams_h, stream_len_h, ws, ws_bytes, p_pinned, s_pinned, child_xyz, child_cap,
+                                        child_off_h, opts, 8, stream);
 }
 
 // ---- sorted unique coordinate list, optionally of the parents (coords >> shift); one octree level as one call ------------------------

@@ -120,11 +120,18 @@ class LINR_PCGC_Model(nn.Module):
         self._flatten()
 
     # ---- flat parameter buffer ------------------------------------------------------------------------------------
+    def _lib_param_count(self):
+        """The library's count of this model's parameters: the layout its whole-network entries index the flat buffer by."""
+        L = _lib.lib()
+        if self.hidden == 8:
+            return L.linr_param_count(self.scale_num, self.block_layers)
+        return L.linr_param_count_wide(self.scale_num, self.block_layers, self.hidden)
+
     def _flatten(self):
         """Re-home all parameters as views of one contiguous buffer in parameters() order (the kernels' layout)."""
         plist = list(self.parameters())
         total = sum(p.numel() for p in plist)
-        if plist and plist[0].is_cuda and self.hidden == 8 and total != _lib.lib().linr_param_count(self.scale_num, self.block_layers):
+        if plist and plist[0].is_cuda and total != self._lib_param_count():
             raise _lib.LinrError('parameter layout mismatch with liblinr_hip.so')
         flat = torch.empty(total, dtype=torch.float32, device=plist[0].device)
         off = 0
@@ -154,7 +161,7 @@ class LINR_PCGC_Model(nn.Module):
             out = super()._apply(fn, *args, **kwargs)
             self._flatten()
             return out
-        if flat.is_cuda and self.hidden == 8 and flat.numel() != _lib.lib().linr_param_count(self.scale_num, self.block_layers):
+        if flat.is_cuda and flat.numel() != self._lib_param_count():
             raise _lib.LinrError('parameter layout mismatch with liblinr_hip.so')
         off = 0
         with torch.no_grad():
@@ -257,7 +264,11 @@ class LINR_PCGC_Model(nn.Module):
     def _stage_forward(self, frame, k0, k1, probs, bits, precision):
         if self._wide is not None:
             with torch.no_grad():
-                if precision == 'bf16':          # csrc/wide_bf16.hip: the uint8 codes as the model, bf16 activations
+                if self._wide.c_forward and (k0, k1) == (0, 8):
+                    # the full-range inference forward as one C call (csrc/wide_fwd.hip); stage ranges - decode_frame's loop - stay on
+                    # the Python schedule, the same launches
+                    self._wide.forward_c(frame, probs, bits, precision == 'bf16')
+                elif precision == 'bf16':          # csrc/wide_bf16.hip: the uint8 codes as the model, bf16 activations
                     self._wide.forward_bf16(frame, k0, k1, probs, bits)
                 else:
                     self._wide.forward(frame, k0, k1, probs, bits)
@@ -349,9 +360,9 @@ class LINR_PCGC_Model(nn.Module):
     def _decode_scale_args(self, size_fn, size_args, coord, streams, chunk, n_threads, device_entries=None):
         """What decode_scale and decode_scale_batch hand their C entry alike, in the entries' order: (params, codes, lo, hi, stream
         pointers, stream lengths, aligned workspace, its bytes, pinned probabilities, pinned symbols, child buffer, its rows), the
-        options (LinrDecodeOpts), the workspace bytes (size_fn(*size_args, block_layers, bf16, stream bytes, entries); 0: the entry
-        refuses the size, nothing else is returned) and the objects that own that memory, child buffer first: keep them until the
-        call has returned.
+        options (LinrDecodeOpts), the workspace bytes (size_fn(*size_args, block_layers, bf16, stream bytes, entries, and for the
+        widths 16 / 32 - the _wide entries - hidden); 0: the entry refuses the size, nothing else is returned) and the objects that own
+        that memory, child buffer first: keep them until the call has returned.
         device_entries = the table entries of the scale: the device decoders, whose workspace also holds the streams' bytes and that
         many entries, and which take no pinned buffers (None in their place); None: the host decoders."""
         n = int(coord.shape[0])
@@ -359,7 +370,7 @@ class LINR_PCGC_Model(nn.Module):
         bf16 = self._precision(None) == 'bf16'
         device = device_entries is not None
         extra = (sum(len(b) for b in streams), int(device_entries)) if device else (-1, 0)
-        need = size_fn(*size_args, self.block_layers, 1 if bf16 else 0, *extra)
+        need = size_fn(*size_args, self.block_layers, 1 if bf16 else 0, *extra, *self._width_arg())
         if need == 0:
             return None, None, 0, None
         ws = _lib.scratch(need + 256, coord.device)
@@ -371,11 +382,16 @@ class LINR_PCGC_Model(nn.Module):
         return (params, codes, lo, hi, ptrs, lens, (ws.data_ptr() + 255) & ~255, need, *pinned,
                 child.data_ptr(), 8 * n), opts, need, (child, ws, bufs)
 
+    def _width_arg(self):
+        """What the _wide twin of a decoder entry takes behind the plain entry's arguments: (hidden,) for the widths 16 / 32."""
+        return () if self._wide is None else (self.hidden,)
+
     @torch.no_grad()
     def decode_scale(self, coord, scale_idx, enc_bytes, child_bits, chunk=0, n_threads=1, device_decoder=False):
         """One scale of decoder.decode_one_frame (decoder.py:153-176) as ONE C call that does not hold the GIL
-        (linr_decode_scale): kernel map of `coord` (int32 [n,3] on the GPU, sorted x-major), the 8 decode stages against the
-        packed stream `enc_bytes`, octree_level.upper_layer.  Returns the next finer level's coordinates (int32 [m,3]).
+        (linr_decode_scale; hidden_channel_conv 16 / 32: linr_decode_scale_wide, the same scale on the wide C forward): kernel map
+        of `coord` (int32 [n,3] on the GPU, sorted x-major), the 8 decode stages against the packed stream `enc_bytes`,
+        octree_level.upper_layer.  Returns the next finer level's coordinates (int32 [m,3]).
         chunk = S > 0: the stage streams are chunked (stream_chunks) and a stage's chunks are decoded on `n_threads` host threads
         (linr_decode_opts.chunk_symbols, n_threads).
         device_decoder=True (opt-in): the range decoders run on the GPU, a wave per stream or chunk, from the probabilities where the
@@ -387,11 +403,15 @@ class LINR_PCGC_Model(nn.Module):
             return coord.new_zeros((0, 3))
         coord = coord.contiguous()
         entries = 8 * chunk_count(n, int(chunk)) if device_decoder else None
-        shared, opts, _, keep = self._decode_scale_args(L.linr_decode_scale_ws_bytes, (n,), coord, unpack_bitstream(enc_bytes), chunk,
-                                                        n_threads, entries)
+        size_fn, entry = (L.linr_decode_scale_ws_bytes, L.linr_decode_scale) if self._wide is None else \
+            (L.linr_decode_scale_wide_ws_bytes, L.linr_decode_scale_wide)
+        shared, opts, need, keep = self._decode_scale_args(size_fn, (n,), coord, unpack_bitstream(enc_bytes), chunk, n_threads, entries)
+        if need == 0:
+            raise ValueError('linr_decode_scale has no workspace for %d rows at block_layers %d' % (n, self.block_layers))
         m = ctypes.c_int64(0)
-        _lib.check(L.linr_decode_scale(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits), *shared,
-                                       ctypes.byref(m), ctypes.byref(opts), torch.cuda.current_stream().cuda_stream), 'linr_decode_scale')
+        _lib.check(entry(coord.data_ptr(), n, int(scale_idx), self.scale_num, self.block_layers, int(child_bits), *shared,
+                         ctypes.byref(m), ctypes.byref(opts), *self._width_arg(), torch.cuda.current_stream().cuda_stream),
+                   'linr_decode_scale')
         return keep[0][:m.value]
 
     @torch.no_grad()
@@ -417,13 +437,14 @@ class LINR_PCGC_Model(nn.Module):
         if len(streams) != 8 * nf:
             raise ValueError('every frame needs the 8 stage streams of the scale')
         entries = 8 * sum(chunk_count(int(c.shape[0]), int(chunk)) for c in coords_list if c.shape[0]) if device_decoder else None
-        shared, opts, need, keep = self._decode_scale_args(L.linr_decode_scale_batch_ws_bytes, (n, nf), coord, streams, chunk, n_threads,
-                                                           entries)
+        size_fn, entry = (L.linr_decode_scale_batch_ws_bytes, L.linr_decode_scale_batch) if self._wide is None else \
+            (L.linr_decode_scale_batch_wide_ws_bytes, L.linr_decode_scale_batch_wide)
+        shared, opts, need, keep = self._decode_scale_args(size_fn, (n, nf), coord, streams, chunk, n_threads, entries)
         if need == 0:
             raise ValueError('%d rows in one decode group: the bound is 2^26 - 64' % n)
         off = (ctypes.c_int64 * (nf + 1))()
-        _lib.check(L.linr_decode_scale_batch(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num, self.block_layers,
-                                             *shared, off, ctypes.byref(opts), torch.cuda.current_stream().cuda_stream),
+        _lib.check(entry(coord.data_ptr(), seg.ctypes.data, nf, int(scale_idx), self.scale_num, self.block_layers,
+                         *shared, off, ctypes.byref(opts), *self._width_arg(), torch.cuda.current_stream().cuda_stream),
                    'linr_decode_scale_batch')
         self._lockstep_ws_peak = max(getattr(self, '_lockstep_ws_peak', 0), int(need))
         return [keep[0][off[i]:off[i + 1]] for i in range(nf)]

@@ -17,6 +17,11 @@ The schedule is Python (~190 launches per step; GPU-bound on the BASELINE-sized 
 training step at widths 16 / 32 on the loot-like frame (profiles/r04_wide.txt; ~3.7x / ~14x the convolution work of width 8).  The
 8-wide model (every BASELINE config, the reference's default and its shipped checkpoint) never comes here.
 
+The full-range inference forward (frame_probs, the encoder) does not run this schedule by default: WideNet.c_forward sends it to the
+same launches scheduled in C (csrc/wide_fwd.hip: forward_c), and the decoder's scales are C calls on that forward
+(model.decode_scale -> linr_decode_scale_wide).  Training passes and stage ranges (model.decode's stage loop, the cross-check of
+those entries) stay here; the bits are the same on either schedule.
+
 train_precision 'bf16-mul' (opt-in): a training forward (keep=True) and its backward run the same launches with LINR_MUL_BF16 - the
 products of the 3x3x3 convolutions on bf16 matrix instructions, operands rounded at the multiply, everything else fp32 (csrc/wide_mul.hip;
 _Pass.mul below; 5.31 / 13.8 ms per step, profiles/wide_bf16_mul.txt).  Every other forward multiplies in fp32.
@@ -290,6 +295,9 @@ class WideNet:
     # the pointwise layers of an Inception layer in the convolutions' epilogues; False (LINR_WIDE_FUSE_PW=0, or set on an executor): one
     # launch per pointwise layer, the same bits
     fuse_pw = os.environ.get('LINR_WIDE_FUSE_PW', '1') != '0'
+    # the full-range inference forward (stages 0..8, no tape) as one C call (csrc/wide_fwd.hip: forward_c below); False
+    # (LINR_WIDE_C_FORWARD=0, or set on an executor): the Python schedule, the same launches and the same bits
+    c_forward = os.environ.get('LINR_WIDE_C_FORWARD', '1') != '0'
 
     def __init__(self, model, hidden):
         if hidden % 16 != 0 or hidden > 32:
@@ -378,6 +386,24 @@ class WideNet:
         if parts is not None:
             ops.bits_finish(parts, (k1 - k0) * nb, bits)          # all stages' partials in one fixed-order pass
         return tape
+
+    def forward_c(self, frame, probs, bits, bf16=False):
+        """All 8 stages of forward() (keep=False) or forward_bf16() as ONE call into the library (linr_net_forward_wide[_bf16]): the
+        same launches with the same arguments from a C schedule, on an arena of per-role blocks from _lib.scratch.  Nothing is kept on
+        the executor and no lock is taken: calls of several threads, frames and models interleave freely."""
+        if frame.rows == 0:
+            return
+        L, m = _lib.lib(), self.model
+        need = int(L.linr_net_wide_arena_bytes(frame.rows, self.C, m.block_layers, 1 if bf16 else 0))
+        ws = _lib.scratch(need + 64, frame.device)
+        base = (ws.data_ptr() + 63) & ~63
+        p, b = (0 if probs is None else probs.data_ptr()), (0 if bits is None else bits.data_ptr())
+        if bf16:
+            check(L.linr_net_forward_wide_bf16(frame.cref(), m._qcodes.data_ptr(), float(m._qrange[0]), float(m._qrange[1]), self.C, base,
+                                               need, 0, 8, p, b, _stream()), 'linr_net_forward_wide_bf16')
+        else:
+            check(L.linr_net_forward_wide(frame.cref(), m.flat_parameters().data_ptr(), self.C, base, need, 0, 8, p, b, _stream()),
+                  'linr_net_forward_wide')
 
     # ---- backward --------------------------------------------------------------------------------------------------------
     def backward(self, frame, tape, gscale, pool=False):
