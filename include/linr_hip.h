@@ -52,8 +52,8 @@ LINR_API int linr_abi_version(void);
  * 54,712 for scale_num = 7, block_layers = 1.  This count and the whole-network entry points (linr_net_*) are the
  * hidden_channel_conv = 8 model (main.py:520 default): their kernels are specialised for 8-wide rows.  Widths 16 / 32 run on
  * the channel-blocked executor: the op-level entries below on 8-wide channel blocks.  Its inference forward and its decoder scales
- * are C entries, too (linr_param_count_wide, linr_net_forward_wide[_bf16], linr_decode_scale[_batch]_wide); its training step is
- * scheduled by the host mirror (linr_pcgc_amd/wide_net.py). */
+ * are C entries, too (linr_param_count_wide, linr_net_forward_wide[_bf16], linr_decode_scale[_batch]_wide), and so is its training
+ * step (linr_net_train_step_wide and its split entries): the host mirror (linr_pcgc_amd/wide_net.py) is their cross-check. */
 LINR_API int64_t linr_param_count(int32_t scale_num, int32_t block_layers);
 
 /* ---- kernel map -------------------------------------------------------------------------------------------
@@ -546,6 +546,41 @@ LINR_API int linr_net_forward_wide(const linr_frame* f, const float* params, int
 LINR_API int linr_net_forward_wide_bf16(const linr_frame* f, const uint8_t* codes, float min_param, float max_param, int32_t hidden,
                                         void* arena, size_t arena_bytes, int32_t stage_begin, int32_t stage_end, float* probs,
                                         double* bits_acc, void* stream);
+
+/* ---- the training step of hidden_channel_conv 16 / 32 as C calls (csrc/wide_train.hip) ---------------------------------------------
+ * The overfit iteration of main.py:305-321 at channels = 16 / 32: the teacher-forced forward (main.py:305-313, models/model_core.py:
+ * 38-81), the autograd backward of main.py:315-316 and Adam of main.py:319 - the schedule of the host mirror (WideNet._forward(keep) /
+ * _backward with the pointwise layers fused and the weight gradients of conv0_1 / conv1_1 paired) launch for launch through the
+ * op-level entries above with the arguments the mirror hands them: bits, gradient and updated parameters are the mirror's bit for bit.
+ * flags: 0, or LINR_MUL_BF16 = the products of every 3x3x3 convolution of the pass (forward, backward-data, weight gradient) on bf16
+ *   matrix instructions (training option 'bf16-mul'); the forward and the backward of one step take the same flags.
+ * linr_net_wide_train_arena_bytes: the arena of one frame (any scale_num): the tape - every activation in blocks of its own, since all
+ *   of them stay live until the backward -, gradient blocks reused by role, the head and scale-context slabs, a 64 MiB region for the
+ *   slabs of the deferred weight-gradient reductions (reduced in batches whenever it is full: every reduction is independent and keeps
+ *   its fixed order), the bits partials and a gradient vector; 0 for rows < 0 or over the row bound of linr_frame, a hidden other than
+ *   16 / 32, block_layers outside 1..4.  64-byte aligned; the library initialises whatever it reads of it.
+ * linr_net_forward_train_wide (main.py:305-313): stages 0..8, the tape kept in the arena; bits_acc double[1], accumulated into, or NULL.
+ * linr_net_backward_wide (main.py:315-316): WRITES d (gscale * bits) / d params into grads (linr_param_count_wide floats) - it does not
+ *   add like linr_net_backward: the wide reductions write their destination, an adding form would need a second buffer and a pass
+ *   over it.  Needs linr_net_forward_train_wide on the same frame, params, arena and flags before it.  The heads' gradient scale is
+ *   (float)((double)gscale * log2 e).
+ * linr_net_train_step_wide (main.py:305-321): forward, backward, Adam in one launch over the flat buffer; `args` as linr_net_train_step
+ *   (scale_steps_h: an MLP whose count is 0 is skipped, every other one uses its own count, a scale of this frame with count 0 is an
+ *   error; qparams: the fake quantisation runs in front, forward and backward read qparams, Adam - weight decay included - updates
+ *   params).
+ * Checked in front of the first launch, in this order: a NULL f / params / arena / args [/ grads] (LINR_EINVAL); the arena's alignment
+ * (LINR_EALIGN); hidden; flags (LINR_EINVAL); the arena's size (LINR_EINVAL where linr_net_wide_train_arena_bytes is 0, else
+ * LINR_ENOSPC); the step's arguments as linr_net_train_step checks them (step >= 1, the moments and bits_acc, qparams != params, its
+ * alignment, bitdepth 2..16); the frame (linr_frame's structure, its matrices, nbr_ld, and nbr / nbr8t, which the weight-gradient
+ * kernels read), then scale_steps_h against it.  rows == 0 returns 0 behind the checks and changes nothing.  No entry synchronises
+ * with the host or keeps state in the library; the kernels of its own are in poison class 16. */
+LINR_API size_t linr_net_wide_train_arena_bytes(int64_t rows, int32_t hidden, int32_t block_layers);
+LINR_API int linr_net_forward_train_wide(const linr_frame* f, const float* params, int32_t hidden, void* arena, size_t arena_bytes,
+                                         uint32_t flags, double* bits_acc, void* stream);
+LINR_API int linr_net_backward_wide(const linr_frame* f, const float* params, int32_t hidden, void* arena, size_t arena_bytes,
+                                    uint32_t flags, float gscale, float* grads, void* stream);
+LINR_API int linr_net_train_step_wide(const linr_frame* f, float* params, int32_t hidden, void* arena, size_t arena_bytes,
+                                      uint32_t flags, const linr_step_args* args, void* stream);
 
 /* ---- bf16 training executor (BASELINE config[4]: "bf16 SparseConv"; beside the fp32 step above, never instead of it) --
  * The overfit iteration of main.py:305-321 - forward of models/model_core.py:38-81 / models/upsample.py:88-97,137-217 /

@@ -160,6 +160,11 @@ _PROTOS = {
     'linr_net_forward_wide': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_i32, c_ptr, c_size, c_i32, c_i32, c_ptr, c_ptr, c_ptr]),
     'linr_net_forward_wide_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_f32, c_f32, c_i32, c_ptr, c_size, c_i32, c_i32, c_ptr,
                                                   c_ptr, c_ptr]),
+    'linr_net_wide_train_arena_bytes': (c_size, [c_i64, c_i32, c_i32]),
+    'linr_net_forward_train_wide': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_i32, c_ptr, c_size, c_u32, c_ptr, c_ptr]),
+    'linr_net_backward_wide': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_i32, c_ptr, c_size, c_u32, c_f32, c_ptr, c_ptr]),
+    'linr_net_train_step_wide': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_i32, c_ptr, c_size, c_u32, ctypes.POINTER(LinrStepArgs),
+                                                c_ptr]),
     'linr_net_train_bf16_arena_bytes': (c_size, [c_i64, c_i32]),
     'linr_occ_to_bf16': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
     'linr_net_forward_train_bf16': (ctypes.c_int, [ctypes.POINTER(LinrFrame), c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr]),

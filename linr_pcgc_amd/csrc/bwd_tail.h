@@ -23,4 +23,6 @@ int linr_bwd_tail_launch(const linr_frame* f, const Layout& L, const float* P, c
 __attribute__((visibility("hidden")))
 int linr_slab_reduce_launch(const float* big, int nblocks, int64_t total, float* gsum, hipStream_t s);
 __attribute__((visibility("hidden")))
-int linr_adam_step_launch(const Layout& L, float* params, const float* gsum, const linr_step_args& a, hipStream_t s);
+// L: the layout whose scale context leads the flat order (at every width: layout.h, wide_layout.h) - its MLPs take their own step counts
+// from a.scale_steps_h; total: all parameters of the model (L.total at width 8, linr_param_count_wide at 16 / 32), the rest use a.step
+int linr_adam_step_launch(const Layout& L, int64_t total, float* params, const float* gsum, const linr_step_args& a, hipStream_t s);

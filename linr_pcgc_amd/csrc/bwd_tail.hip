@@ -464,9 +464,10 @@ int linr_bwd_tail_launch(const linr_frame* f, const Layout& L, const float* P, c
     return linr_launch_rc();
 }
 
-// torch.optim.Adam's step over the flat parameter buffer with the per-scale step counters of the scale-context MLPs (shared with
-// csrc/train_bf16.hip): bias corrections in double, like torch.optim.Adam's Python scalars
-int linr_adam_step_launch(const Layout& L, float* params, const float* gsum, const linr_step_args& a, hipStream_t s) {
+// torch.optim.Adam's step over the flat parameter buffer of `total` floats with the per-scale step counters of the scale-context MLPs,
+// which lead the flat order at every width (shared with csrc/train_bf16.hip and csrc/wide_train.hip): bias corrections in double, like
+// torch.optim.Adam's Python scalars
+int linr_adam_step_launch(const Layout& L, int64_t total, float* params, const float* gsum, const linr_step_args& a, hipStream_t s) {
     const int64_t* scale_steps_h = a.scale_steps_h;
     LinrAdamRanges rg;
     rg.count = 0; rg.begin = L.m0_w[0]; rg.len = L.S > 1 ? L.m0_w[1] - L.m0_w[0] : L.block_in.a_w - L.m0_w[0];
@@ -482,7 +483,7 @@ int linr_adam_step_launch(const Layout& L, float* params, const float* gsum, con
             rg.bc2_sqrt[sc] = t >= 1 ? (float)sqrt(1.0 - pow(a.beta2, (double)t)) : 1.0f;
         }
     }
-    return linr_adam_launch(params, gsum, a.exp_avg, a.exp_avg_sq, L.total, a.lr / (1.0 - pow(a.beta1, (double)a.step)),
+    return linr_adam_launch(params, gsum, a.exp_avg, a.exp_avg_sq, total, a.lr / (1.0 - pow(a.beta1, (double)a.step)),
                             sqrt(1.0 - pow(a.beta2, (double)a.step)), a.beta1, a.beta2, a.eps, a.weight_decay,
                             scale_steps_h ? &rg : nullptr, s);
 }

@@ -614,5 +614,5 @@ extern "C" int linr_net_train_step(const linr_frame* f, float* params, float* ar
     c.P = weights;
     TRY(backward_core(c, a->gscale));
     ProfScope ps(c.s, PK_MISC, 0);
-    return linr_adam_step_launch(c.L, params, c.A.GSUM, *a, c.s);
+    return linr_adam_step_launch(c.L, c.L.total, params, c.A.GSUM, *a, c.s);
 }

@@ -1488,7 +1488,7 @@ extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void
     TRY(tforward(c, nullptr, a->bits_acc));
     TRY(tbackward(c, a->gscale));
     ProfScope ps(c.s, TK_MISC, 0);
-    return linr_adam_step_launch(c.L, params, c.A.GSUM, *a, c.s);
+    return linr_adam_step_launch(c.L, c.L.total, params, c.A.GSUM, *a, c.s);
 }
 
 extern "C" int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* in, const int32_t* lo, const uint32_t* mask, int64_t ld,

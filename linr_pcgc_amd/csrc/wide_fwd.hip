@@ -4,65 +4,15 @@
 // bits are those of the Python executor bit for bit, whichever of the two a frame was coded with.  Forward of
 // models/model_core.py:38-81, models/upsample.py:88-97,137-217 and models/resnet.py:12-60 at channels = 16 / 32.
 //
-// Here: the wide parameter layout (parameters() order), the arena (per-role blocks reused by all blocks and stages, as the Python
+// Here (the wide parameter layout, parameters() order, is csrc/wide_layout.h): the arena (per-role blocks reused by all blocks and stages, as the Python
 // executor's bf16 pool does), the two schedules and their entries.  The only device code is glue: one launch per (0, ...) call that
 // clears the zero rows of all arena blocks and, for bf16, writes the convolution table of the prologue.
 #include "common.h"
 #include "layout.h"
 #include "prof.h"
-
-#define TRY(e) do { int rc_ = (e); if (rc_) return rc_; } while (0)
+#include "wide_layout.h"
 
 namespace {
-
-// ---- parameter layout ------------------------------------------------------------------------------------------------------------
-struct WInc { int64_t c00_w, c00_b, c01_w, c01_b, c10_w, c10_b, c11_w, c11_b, c12_w, c12_b; };
-struct WBlock {
-    int cin, nl;
-    int64_t a_w, a_b;         // .0  conv3 cin -> C
-    WInc inc[MAX_BL];         // .2.layers.l: conv0_0 C -> h, conv0_1 h -> h, conv1_0 1x1 C -> h, conv1_1 h -> h, conv1_2 1x1 h -> h
-    int64_t b_w, b_b;         // .3  conv3 C -> C
-};
-struct WLayout {
-    int C, BL;
-    WBlock block_in;
-    int64_t h0_w[8], h0_b[8], h2_w[8], h2_b[8];      // inner_mlps.k.0: Linear(C, 24), Linear(24, 1)
-    int64_t pr_w[8], pr_b[8];                        // prune_blocks.k.0.conv: conv3 C -> C
-    WBlock outter[7];
-    int64_t total;
-};
-
-void wlayout_block(WBlock& b, int cin, int C, int nl, int64_t& cur) {
-    const int h = C / 2;
-    b.cin = cin; b.nl = nl;
-    b.a_w = take(cur, 27 * cin * C); b.a_b = take(cur, C);
-    for (int l = 0; l < nl; ++l) {
-        WInc& q = b.inc[l];
-        q.c00_w = take(cur, 27 * C * h); q.c00_b = take(cur, h);
-        q.c01_w = take(cur, 27 * h * h); q.c01_b = take(cur, h);
-        q.c10_w = take(cur, C * h);      q.c10_b = take(cur, h);
-        q.c11_w = take(cur, 27 * h * h); q.c11_b = take(cur, h);
-        q.c12_w = take(cur, h * h);      q.c12_b = take(cur, h);
-    }
-    b.b_w = take(cur, 27 * C * C); b.b_b = take(cur, C);
-}
-
-// the scale context leads the flat order at every width (layout.h: the 8-wide layout up to its block_in)
-bool make_wlayout(WLayout& W, int S, int BL, int C) {
-    Layout L8;
-    if ((C != 16 && C != 32) || !make_layout(L8, S, 1) || BL < 1 || BL > MAX_BL) return false;
-    W.C = C; W.BL = BL;
-    int64_t cur = L8.block_in.a_w;
-    wlayout_block(W.block_in, 8, C, BL, cur);
-    for (int k = 0; k < 8; ++k) {
-        W.h0_w[k] = take(cur, 24 * C); W.h0_b[k] = take(cur, 24);
-        W.h2_w[k] = take(cur, 24);     W.h2_b[k] = take(cur, 1);
-    }
-    for (int k = 0; k < 8; ++k) { W.pr_w[k] = take(cur, 27 * C * C); W.pr_b[k] = take(cur, C); }
-    for (int k = 0; k < 7; ++k) wlayout_block(W.outter[k], k + 1, C, 1, cur);
-    W.total = cur;
-    return true;
-}
 
 // ---- the convolutions of the bf16 prologue's table, in the Python executor's order --------------------------------------------------
 #define WF_MAX_CONV 64
@@ -110,7 +60,6 @@ struct WArena {
     size_t blocks; int nblk; size_t block_bytes;
     size_t total;
 };
-inline size_t wup256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // n_params / n_img: of the model (bf16), else 0
 bool make_warena(WArena& a, int64_t rows, int C, int bf16, int64_t n_params, int n_conv, int64_t n_img) {
@@ -171,12 +120,7 @@ int check_call(const linr_frame* f, const void* model, const void* arena, size_t
     tab.n = 0; tab.n_img = 0;
     if (bf16) make_wtab(W, tab, im);
     if (!make_warena(A, f->rows, hidden, bf16, W.total, tab.n, tab.n_img)) return LINR_EINVAL;
-    if (f->rows > 0) {
-        if (!f->nbr_lo || !f->nbr_mask || !f->offset_feat || !f->occ) return LINR_EINVAL;
-        if (f->nbr_ld < f->rows || !linr_cmap_fits32(f->nbr_ld)) return LINR_EINVAL;
-        if (!linr_aligned16(f->occ)) return LINR_EALIGN;
-    }
-    return 0;
+    return wide_frame_matrices_check(f);
 }
 
 // ---- fp32 schedule (WideNet._forward) ---------------------------------------------------------------------------------------------------

@@ -279,6 +279,20 @@ def net_train_step(frame, flat_params, exp_avg, exp_avg_sq, gscale, step, lr, be
                                          _stream()), 'linr_net_train_step')
 
 
+def net_train_step_wide(frame, flat_params, hidden, arena, exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits,
+                        mul='f32', scale_steps=None, qparams=None, bitdepth=8):
+    """linr_net_train_step_wide: net_train_step for hidden_channel_conv 16 / 32 - the training forward, the backward and Adam of the
+    channel-blocked executor as one call.  arena: a uint8 device buffer of at least linr_net_wide_train_arena_bytes + 64 bytes (aligned
+    here); mul='bf16': the products of the 3x3x3 convolutions on bf16 matrix instructions (LINR_MUL_BF16); qparams as in net_train_step."""
+    if mul not in ('f32', 'bf16'):
+        raise ValueError("mul must be 'f32' or 'bf16', got %r" % (mul,))
+    base = (arena.data_ptr() + 63) & ~63
+    args = _step_args(exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits, scale_steps, qparams, bitdepth)
+    check(_lib.lib().linr_net_train_step_wide(frame.cref(), flat_params.data_ptr(), int(hidden), base, arena.numel() - (base - arena.data_ptr()),
+                                              _lib.LINR_MUL_BF16 if mul == 'bf16' else 0, ctypes.byref(args), _stream()),
+          'linr_net_train_step_wide')
+
+
 def net_forward_train_bf16(frame, flat_params, probs=None, bits=None, deep=False):
     """linr_net_forward_train_bf16: the teacher-forced forward of the bf16 training executor (activations kept in its arena).
     deep: accept block_layers 2..4 (Frame.train_bf16_arena)."""

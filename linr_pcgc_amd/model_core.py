@@ -879,10 +879,20 @@ def train_step(model, opt, frame, point_num, out=None, qat_bitdepth=0):
     bits = torch.zeros(1, dtype=torch.float64, device=frame.device) if out is None else out
     extra = {}                           # keyword arguments of the step beyond the common ones
     if qat_bitdepth:
-        if model._wide is not None:
-            raise _lib.LinrError('quantisation-aware training exists for hidden_channel_conv=8 only')
+        if model._wide is not None and not model._wide.c_step:
+            raise _lib.LinrError('quantisation-aware training exists for hidden_channel_conv=8 only, and for 16 / 32 with the one-call '
+                                 'step (WideNet.c_step, LINR_WIDE_C_STEP=1)')
         extra = {'qparams': model.qat_parameters(), 'bitdepth': int(qat_bitdepth)}
-    if model._wide is not None:          # hidden_channel_conv 16 / 32: the channel-blocked executor + the segment-wise Adam
+    if model._wide is not None and model._wide.c_step:          # hidden_channel_conv 16 / 32, opt-in: one C call (csrc/wide_train.hip)
+        t, t_scale = opt.advance(frame)
+        w = model._wide
+        engine.net_train_step_wide(frame, model.flat_parameters(), w.C, w.step_arena(frame), opt.exp_avg, opt.exp_avg_sq, 1.0 / float(point_num), t,
+                                   opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, bits, mul=w._train_mul(),
+                                   scale_steps=t_scale, **extra)
+        opt.t, opt.t_scale = t, t_scale              # committed only after the call returned without an error
+        opt.scheduler_step()
+        return bits
+    if model._wide is not None:          # the default: the channel-blocked executor's Python schedule + the segment-wise Adam
         with torch.no_grad(), model._wide.lock:          # (the pooled buffers of the forward must survive until the backward has run)
             tape = model._wide.forward(frame, 0, 8, None, bits, keep=True, pool=True)
             model._ensure_grad_views()

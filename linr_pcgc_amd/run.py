@@ -77,7 +77,8 @@ def parse(argv=None):
                     help='the last N epochs of every overfit (--first-epoch and --others-epoch alike) are quantisation-aware: the network is '
                          'evaluated at the --model_bitdepth-bit weights the model codec will code with, the gradient goes straight through to '
                          'the fp32 weights, and with --keep best only those epochs compete.  0 (default): the plain overfit.  '
-                         '--hidden-channel-conv 8 only; streams decode as ever')
+                         'At --hidden-channel-conv 16 / 32 it needs the one-call training step (LINR_WIDE_C_STEP=1); '
+                         'streams decode as ever')
     ap.add_argument('--qrange-search', '--qrange_search', dest='qrange_search', action='store_true',
                     help="the encoder chooses the weight quantiser's range by measured rate (codec.search_qrange): candidate ranges that let "
                          'the --qrange-trims smallest and largest weights saturate are each quantised and asked for their bits on '
@@ -109,7 +110,10 @@ def parse(argv=None):
     if args.qat_epochs < 0:
         ap.error('--qat-epochs must be >= 0')
     if args.qat_epochs and args.hidden_channel_conv != 8:
-        ap.error('--qat-epochs: quantisation-aware training exists for --hidden-channel-conv 8 only')
+        from .wide_net import WideNet
+        if not WideNet.c_step:
+            ap.error('--qat-epochs: quantisation-aware training exists for --hidden-channel-conv 8 only, and for 16 / 32 with the one-call '
+                     'step (LINR_WIDE_C_STEP=1)')
     if args.qat_epochs and not 2 <= args.model_bitdepth <= 16:
         ap.error('--qat-epochs needs --model_bitdepth in 2..16')
     if args.qrange_trims is not None:

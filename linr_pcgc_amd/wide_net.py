@@ -13,14 +13,20 @@ two launches (``linr_wide_reduce_many``).  Concatenations are free; the padded b
 Deterministic (fixed launch order, no atomics); the forward is the same launches in training, encoding and stage-by-stage decoding,
 so streams decode losslessly.
 
-The schedule is Python (~190 launches per step; GPU-bound on the BASELINE-sized frames, launch-bound on small ones): 5.9 / 18.1 ms per
-training step at widths 16 / 32 on the loot-like frame (profiles/r04_wide.txt; ~3.7x / ~14x the convolution work of width 8).  The
+The schedule below is Python (~190 launches per step; GPU-bound on the BASELINE-sized frames, launch-bound on small ones): 5.9 / 18.1 ms
+per training step at widths 16 / 32 on the loot-like frame (profiles/r04_wide.txt; ~3.7x / ~14x the convolution work of width 8).  The
 8-wide model (every BASELINE config, the reference's default and its shipped checkpoint) never comes here.
+
+Opt-in (WideNet.c_step, LINR_WIDE_C_STEP=1): model_core.train_step sends the whole step - the forward with its tape, the backward, Adam,
+and with qat_bitdepth the fake quantisation in front - to ONE C call (csrc/wide_train.hip: linr_net_train_step_wide), which makes the
+same launches with the same arguments on an arena of its own (step_arena below: per model, no pool, no lock), so the bits, the moments
+and the parameters are those of this schedule bit for bit (tests/test_gpu_wide_step.py; profiles/wide_step.txt).  Without it
+forward(keep=True) / backward / FlatAdam.step run as ever; they, the _Pool and the autograd surface are the C call's cross-check.
 
 The full-range inference forward (frame_probs, the encoder) does not run this schedule by default: WideNet.c_forward sends it to the
 same launches scheduled in C (csrc/wide_fwd.hip: forward_c), and the decoder's scales are C calls on that forward
-(model.decode_scale -> linr_decode_scale_wide).  Training passes and stage ranges (model.decode's stage loop, the cross-check of
-those entries) stay here; the bits are the same on either schedule.
+(model.decode_scale -> linr_decode_scale_wide).  Stage ranges (model.decode's stage loop, the cross-check of those entries) and the
+training passes of the autograd surface stay here; the bits are the same on either schedule.
 
 train_precision 'bf16-mul' (opt-in): a training forward (keep=True) and its backward run the same launches with LINR_MUL_BF16 - the
 products of the 3x3x3 convolutions on bf16 matrix instructions, operands rounded at the multiply, everything else fp32 (csrc/wide_mul.hip;
@@ -33,6 +39,7 @@ the executor, so passes of several models and frames interleave freely (the mode
 forward_bf16 is the inference forward of --precision bf16 (BASELINE config[4]'s numerics) on csrc/wide_bf16.hip: the uint8 weight codes
 as the model, bf16 channel-blocked activations, fp32 accumulation, one launch per layer in the same schedule (profiles/r07_wide_bf16.txt).
 """
+import ctypes
 import os
 import threading
 
@@ -298,6 +305,10 @@ class WideNet:
     # the full-range inference forward (stages 0..8, no tape) as one C call (csrc/wide_fwd.hip: forward_c below); False
     # (LINR_WIDE_C_FORWARD=0, or set on an executor): the Python schedule, the same launches and the same bits
     c_forward = os.environ.get('LINR_WIDE_C_FORWARD', '1') != '0'
+    # opt-in (LINR_WIDE_C_STEP=1, or set on an executor): the training step (forward with the tape, backward, Adam) as one C call
+    # (csrc/wide_train.hip: model_core.train_step) - the same launches and bits as forward(keep=True) / backward / FlatAdam.step below,
+    # which stay the default; quantisation-aware steps exist on the C call only
+    c_step = os.environ.get('LINR_WIDE_C_STEP', '0') == '1'
 
     def __init__(self, model, hidden):
         if hidden % 16 != 0 or hidden > 32:
@@ -305,6 +316,7 @@ class WideNet:
         self.model, self.C = model, hidden
         self._built = False
         self._pool = None
+        self._step_arena = None            # the arena of the C training step: grows to the largest frame seen, follows the device
         # one thread at a time per model: the pool, _build() and the bf16 state are per-model state (train_step holds it across forward,
         # backward and the optimiser step)
         self.lock = threading.RLock()
@@ -405,6 +417,15 @@ class WideNet:
             check(L.linr_net_forward_wide(frame.cref(), m.flat_parameters().data_ptr(), self.C, base, need, 0, 8, p, b, _stream()),
                   'linr_net_forward_wide')
 
+    def step_arena(self, frame):
+        """The arena of linr_net_train_step_wide for `frame`: one buffer per model (the steps of one model follow each other on its
+        stream), re-made when a frame needs more than the largest so far or lives on another device."""
+        need = int(_lib.lib().linr_net_wide_train_arena_bytes(frame.rows, self.C, self.model.block_layers)) + 64
+        a = self._step_arena
+        if a is None or a.numel() < need or a.device != frame.device:
+            a = self._step_arena = _lib.scratch(need, frame.device)
+        return a
+
     # ---- backward --------------------------------------------------------------------------------------------------------
     def backward(self, frame, tape, gscale, pool=False):
         """d (gscale * bits) / d params into the parameters' .grad (model._ensure_grad_views(): views of the flat gradient).
@@ -419,7 +440,9 @@ class WideNet:
     def _backward(self, ps, frame, tape, gscale):
         self.model._ensure_grad_views()
         C = self.C
-        gz_scale = float(gscale) * 1.4426950408889634          # d(bits)/d(nats) = 1 / ln 2
+        # the loss scale is a float, as it crosses the C-ABI as one (linr_step_args.gscale, linr_net_backward_wide): this schedule and
+        # the C one differentiate the same loss.  d(bits)/d(nats) = 1 / ln 2, multiplied in double and rounded once by the call
+        gz_scale = ctypes.c_float(float(gscale)).value * 1.4426950408889634
         g_xg = ps.blocks(C // B)
         # all 8 heads first, as one grouped launch (their inputs - c, p, the occupancy columns - exist once the forward has run): the
         # gradients of the prune convolutions' outputs and the heads' parameter gradients, straight into the flat gradient
