@@ -166,12 +166,18 @@ def test_wide_bf16_ignores_leftover_state(shell, models):
         assert torch.equal(p0, p1) and torch.equal(b0, b1)
 
 
-@pytest.mark.parametrize('n', [1, 2, 63, 65, 257])
-def test_wide_bf16_tiny_and_ragged_frames(models, n):
-    coded, sd = models[(16, 2)]
+# the model (16, 2) keeps the ids it had when it was the only one ('1', '2', ...); (32, 1) and (32, 3) are named in theirs
+RAGGED_NS = [1, 2, 63, 64, 65, 255, 256, 257, 1025]
+RAGGED = [pytest.param(m, n, id=str(n) if m == (16, 2) else '%dx%d-%d' % (m[0], m[1], n)) for m in [(16, 2), (32, 1), (32, 3)] for n in RAGGED_NS]
+
+
+@pytest.mark.parametrize('model,n', RAGGED)
+def test_wide_bf16_tiny_and_ragged_frames(models, model, n):
+    coded, sd = models[model]
     rng = np.random.default_rng(n)
-    c = ooct.unique_sorted(rng.integers(0, 8, size=(4 * n, 3)))[:n]
-    n = len(c)
+    side = 8 if n <= 257 else 16                 # 512 cells hold the sizes up to 257; 1025 rows need the 16-cube
+    c = ooct.unique_sorted(rng.integers(0, side, size=(4 * n, 3)))[:n]
+    assert len(c) == n
     sc = {'coord': c, 'occ': (rng.random((n, 8)) < 0.5).astype(np.float32), 'offset_tensor': ooct.offset_tensor(c), 'scale_idx': 1}
     frame = coded.make_frame([sc, {'coord': np.zeros((0, 3), np.int32), 'occ': np.zeros((0, 8), np.float32),
                                    'offset_tensor': np.zeros((0, 7), np.float32), 'scale_idx': 0}])
