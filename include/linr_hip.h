@@ -316,7 +316,7 @@ LINR_API int linr_prof_mask(uint32_t mask);
  * linr_net_forward / _backward / _train_step whose kernel class (the list above) has its bit set in kind_mask is preceded by a kernel that fills the LDS of every CU with 0xFFFFFFFF (a NaN
  * pattern) - results must not change: a kernel may not read on-chip state it did not write (on a GPU shared with another
  * process the leftovers are not one's own finite numbers). */
-LINR_API int linr_debug_poison(uint32_t kind_mask);          /* bits 0..13: the classes above; 14: bf16 executor; 15: the decoder scales of csrc/decode.hip (linr_decode_scale, linr_decode_scale_batch, linr_children_segments) and linr_kmap_build_segments; 16: the entries of csrc/wide.hip */
+LINR_API int linr_debug_poison(uint32_t kind_mask);          /* bits 0..13: the classes above; 14: bf16 executor; 15: the decoder scales of csrc/decode.hip (linr_decode_scale, linr_decode_scale_batch, linr_children_segments) and linr_kmap_build_segments; 16: the entries of csrc/wide.hip.  The epoch kernels of linr_overfit_gop (csrc/overfit.hip) are in class 12 for every executor: no new class, the per-class launch counts of a single training step stay what they are */
 LINR_API int linr_debug_poison_now(void* stream);           /* the same poisoning, once, on `stream` (in front of an op-level call) */
 LINR_API int linr_prof_enable(int32_t mode);
 LINR_API int linr_prof_read(int32_t kind, double* total_ms, int64_t* launches, int64_t* passes);
@@ -619,6 +619,87 @@ LINR_API int linr_net_train_step_bf16(const linr_frame* f, float* params, void* 
 LINR_API int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* in, const int32_t* lo, const uint32_t* mask, int64_t ld,
                                int64_t n, const float* W, uint16_t* gin, float* slab, int32_t nblocks, int32_t* rows_written,
                                void* stream);
+
+/* ---- the overfit of a whole GOP as one call (opt-in; csrc/overfit.hip) ---------------------------------------------------------
+ * main.py:297-437: `epochs` passes over the frames of a GOP in fixed order, one optimiser step and one StepLR step per frame
+ * (main.py:305-321), the learning-rate clamp after each epoch (main.py:433-437), and the reference's checkpoint policy - keep the epoch
+ * with the lowest mean loss (main.py:413-426,440-451).  Nothing of that depends on a value the host has to read: the learning rate and
+ * the step counts follow from which frames hold which scales, the choice of the best epoch is a comparison of device values followed by a
+ * conditional device copy.  So the whole GOP is queued at once and the stream is synchronised once, at its end.
+ *
+ * linr_overfit_plan (HOST only, no GPU call): the schedule.  frames_h: HOST [n_frames] pointers to linr_frame, of which n_scales,
+ *   row_off_h, scale_idx_h are read (n_scales 1..16, every scale_idx_h in [0, model_scale_num)); the starting state (step = optimiser
+ *   steps taken, sched_steps = StepLR steps taken, lr, scale_steps_h [model_scale_num] = updates of every per-scale context MLP so far,
+ *   NULL = all zero); step_size >= 1, gamma, min_lr.  Step k = epoch * n_frames + frame receives lr_out[k] (the rate its update uses),
+ *   step_out[k] (its 1-based count) and scale_steps_out[k * model_scale_num + s] (the counts of linr_step_args.scale_steps_h: a scale
+ *   that has rows in the frame starts its counter, a started counter advances on every step - torch 1.13's optimizer.zero_grad() leaves
+ *   zero tensors, see linr_net_train_step; a scale of a frame with zero rows is not present).  Behind every step: sched_steps += 1 and,
+ *   when sched_steps % step_size == 0, lr *= gamma (one double multiply, the chainable StepLR form - a clamp persists).  Behind every epoch
+ *   the state BEFORE the clamp goes to end_step / end_sched / end_lr [epochs] and end_scale_steps [epochs][model_scale_num], then
+ *   lr = min_lr where lr < min_lr.  Any output may be NULL.  LINR_EINVAL: frames_h NULL, n_frames < 1, epochs < 0, model_scale_num
+ *   outside 1..16, step_size < 1, a malformed frame.
+ * linr_overfit_ws_bytes: the workspace of linr_overfit_gop - bits and point numbers [n_frames], losses [epochs], the flags and the
+ *   snapshot of parameters and both moments (3 n_params floats); 0 for a negative argument.  16-byte aligned, uninitialised.
+ * linr_overfit_gop: the overfit.  frames: HOST [args->n_frames]; args, result: HOST.  Checked in front of the first launch, in this
+ *   order: NULL frames / args / result, params / exp_avg / exp_avg_sq / arena / ws (LINR_EINVAL); n_frames < 1; a NULL frame; epochs < 0,
+ *   result->losses_h NULL with epochs > 0; qat_from outside [0, epochs]; qparams NULL with qat_from < epochs, bitdepth outside 2..16
+ *   with qparams; step_size < 1, step < 0 or sched_steps < 0, a point_num that is not a positive finite number; an unknown executor; hidden (8 for
+ *   LINR_OVERFIT_F32 / _BF16, 16 or 32 for _WIDE) and flags (0, or LINR_MUL_BF16 for _WIDE) (all LINR_EINVAL); frames that differ in
+ *   model_scale_num or block_layers (LINR_EINVAL); params / ws alignment (LINR_EALIGN); ws_bytes (LINR_ENOSPC); then every frame with
+ *   the arguments of its first step - and of its first quantisation-aware step - exactly as the executor's step entry checks them
+ *   (the arena's size is LINR_ENOSPC there; a scale of a frame whose count would be 0 at its own step is LINR_EINVAL).
+ *   Then, per epoch and frame, the executor's step (linr_net_train_step, _bf16, _wide: the same launches with the same arguments,
+ *   gscale = (float)(1.0 / point_num), bits into the frame's slot), from epoch qat_from on with qparams; per epoch params_finite_k,
+ *   epoch_close_k - losses[epoch] = (sum_j bits[j] / point_num[j]) / n_frames, summed in frame order in double, +inf when a parameter
+ *   is not finite; the epoch is taken when it competes and its loss is below the best so far, so NaN and inf never win - and, with
+ *   keep_best, snapshot_k (the conditional copy).  With keep_best and qat_from < epochs only epochs >= qat_from compete.  At the end
+ *   the restore (on the device's own flag: only when an epoch was taken), ONE stream synchronisation, and `result`.
+ *   No other host synchronisation, no state in the library.  A diverged overfit is no error code: its losses are inf, best_epoch -1.
+ *   The three kernels are in profiler / poison class 12 (sums, reduction, Adam) for every executor. */
+#define LINR_OVERFIT_F32  0          /* linr_net_train_step; hidden 8 */
+#define LINR_OVERFIT_BF16 1          /* linr_net_train_step_bf16; hidden 8, the frames' block_layers 1..4 */
+#define LINR_OVERFIT_WIDE 2          /* linr_net_train_step_wide; hidden 16 / 32, flags 0 or LINR_MUL_BF16 */
+typedef struct linr_overfit_frame {
+    const linr_frame* f;
+    double point_num;               /* the frame's loss is bits / point_num (main.py:314) */
+    const uint16_t* occ_bf16;       /* LINR_OVERFIT_BF16 only: as in linr_net_train_step_bf16, or NULL */
+} linr_overfit_frame;
+typedef struct linr_overfit_args {
+    int32_t executor, hidden;
+    uint32_t flags;
+    int32_t n_frames;
+    float* params;                  /* linr_param_count[_wide] floats, 16-byte aligned, updated */
+    float* exp_avg;
+    float* exp_avg_sq;
+    double beta1, beta2, eps, weight_decay;          /* as in linr_step_args */
+    double lr, min_lr, gamma;
+    int64_t step_size;
+    int64_t step, sched_steps;      /* the starting counters */
+    const int64_t* scale_steps_h;   /* HOST [model_scale_num] or NULL (all zero) */
+    int32_t epochs, keep_best;
+    int32_t qat_from, bitdepth;     /* first quantisation-aware epoch (epochs: none); bitdepth is read with qparams */
+    float* qparams;                 /* as in linr_step_args, or NULL */
+    void* arena;                    /* the executor's arena for the largest frame, shared by all steps */
+    size_t arena_bytes;
+    void* ws;                       /* linr_overfit_ws_bytes(n_params, n_frames, epochs) bytes */
+    size_t ws_bytes;
+} linr_overfit_args;
+typedef struct linr_overfit_result {          /* HOST; filled after the synchronisation */
+    double* losses_h;               /* [epochs] */
+    int32_t best_epoch;             /* -1: no finite competing epoch (or keep_best = 0) */
+    double best_loss;               /* +inf then */
+    /* the optimiser state that belongs to what is left in params: with keep_best and a best epoch that epoch's, before its clamp; else
+     * the state after the last epoch's clamp */
+    int64_t step, sched_steps;
+    double lr;
+    int64_t* scale_steps_h;         /* [model_scale_num] or NULL */
+} linr_overfit_result;
+LINR_API int linr_overfit_plan(const linr_frame* const* frames_h, int32_t n_frames, int32_t epochs, int32_t model_scale_num, int64_t step,
+                               int64_t sched_steps, double lr, const int64_t* scale_steps_h, int64_t step_size, double gamma, double min_lr,
+                               double* lr_out, int64_t* step_out, int64_t* scale_steps_out, int64_t* end_step, int64_t* end_sched,
+                               double* end_lr, int64_t* end_scale_steps);
+LINR_API size_t linr_overfit_ws_bytes(int64_t n_params, int32_t n_frames, int32_t epochs);
+LINR_API int linr_overfit_gop(const linr_overfit_frame* frames, const linr_overfit_args* args, linr_overfit_result* result, void* stream);
 
 /* Staged DECODE of one frame object (decoder.decode_one_frame, decoder.py:153-176 + CNP.decode, models/upsample.py:249-295) as
  * ONE call: for stage k = 0..7 { linr_net_forward[_bf16](k, k+1); probabilities of the stage -> pinned host buffer; the range

@@ -66,6 +66,28 @@ class LinrStepArgs(ctypes.Structure):
                 ('bitdepth', c_i32)]
 
 
+class LinrOverfitFrame(ctypes.Structure):
+    """struct linr_overfit_frame (include/linr_hip.h): one frame of linr_overfit_gop."""
+    _fields_ = [('f', ctypes.POINTER(LinrFrame)), ('point_num', c_f64), ('occ_bf16', c_ptr)]
+
+
+class LinrOverfitArgs(ctypes.Structure):
+    """struct linr_overfit_args (include/linr_hip.h)."""
+    _fields_ = [('executor', c_i32), ('hidden', c_i32), ('flags', c_u32), ('n_frames', c_i32), ('params', c_ptr), ('exp_avg', c_ptr),
+                ('exp_avg_sq', c_ptr), ('beta1', c_f64), ('beta2', c_f64), ('eps', c_f64), ('weight_decay', c_f64), ('lr', c_f64),
+                ('min_lr', c_f64), ('gamma', c_f64), ('step_size', c_i64), ('step', c_i64), ('sched_steps', c_i64), ('scale_steps_h', c_ptr),
+                ('epochs', c_i32), ('keep_best', c_i32), ('qat_from', c_i32), ('bitdepth', c_i32), ('qparams', c_ptr), ('arena', c_ptr),
+                ('arena_bytes', c_size), ('ws', c_ptr), ('ws_bytes', c_size)]
+
+
+class LinrOverfitResult(ctypes.Structure):
+    """struct linr_overfit_result (include/linr_hip.h)."""
+    _fields_ = [('losses_h', c_ptr), ('best_epoch', c_i32), ('best_loss', c_f64), ('step', c_i64), ('sched_steps', c_i64), ('lr', c_f64),
+                ('scale_steps_h', c_ptr)]
+
+
+LINR_OVERFIT_F32, LINR_OVERFIT_BF16, LINR_OVERFIT_WIDE = 0, 1, 2
+
 _PROTOS = {
     'linr_abi_version': (ctypes.c_int, []),
     'linr_param_count': (c_i64, [c_i32, c_i32]),
@@ -237,6 +259,11 @@ _PROTOS = {
     'linr_params_fake_quant_host': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
     'linr_params_fake_quant_ranges': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     'linr_params_fake_quant_ranges_host': (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_ptr]),
+    'linr_overfit_plan': (ctypes.c_int, [c_ptr, c_i32, c_i32, c_i32, c_i64, c_i64, c_f64, c_ptr, c_i64, c_f64, c_f64, c_ptr, c_ptr, c_ptr,
+                                         c_ptr, c_ptr, c_ptr, c_ptr]),
+    'linr_overfit_ws_bytes': (c_size, [c_i64, c_i32, c_i32]),
+    'linr_overfit_gop': (ctypes.c_int, [ctypes.POINTER(LinrOverfitFrame), ctypes.POINTER(LinrOverfitArgs), ctypes.POINTER(LinrOverfitResult),
+                                        c_ptr]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -271,7 +298,7 @@ class _Poisoned:
     CUs freshly filled with a NaN pattern (linr_debug_poison_now in front of it, linr_debug_poison(all classes) for the launches
     inside the executors).  The test suite must pass unchanged under it: no kernel may read on-chip state it did not write."""
     _HOST = ('linr_ac_', 'linr_stream_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host',
-             'linr_params_fake_quant_ranges_host')
+             'linr_params_fake_quant_ranges_host', 'linr_overfit_plan')
 
     def __init__(self, handle):
         self._h = handle

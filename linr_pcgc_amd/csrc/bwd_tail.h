@@ -26,3 +26,14 @@ __attribute__((visibility("hidden")))
 // L: the layout whose scale context leads the flat order (at every width: layout.h, wide_layout.h) - its MLPs take their own step counts
 // from a.scale_steps_h; total: all parameters of the model (L.total at width 8, linr_param_count_wide at 16 / 32), the rest use a.step
 int linr_adam_step_launch(const Layout& L, int64_t total, float* params, const float* gsum, const linr_step_args& a, hipStream_t s);
+// The three training steps behind their C entries (csrc/net.hip, csrc/train_bf16.hip, csrc/wide_train.hip).  dry: every check of the
+// entry in its order and no launch - linr_overfit_gop (csrc/overfit.hip) checks a whole GOP in front of its first launch.
+__attribute__((visibility("hidden")))
+int linr_train_step_f32(const linr_frame* f, float* params, float* arena, size_t arena_bytes, const linr_step_args* a, void* stream,
+                        bool dry);
+__attribute__((visibility("hidden")))
+int linr_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
+                         const linr_step_args* a, void* stream, bool dry);
+__attribute__((visibility("hidden")))
+int linr_train_step_wide(const linr_frame* f, float* params, int32_t hidden, void* arena, size_t arena_bytes, uint32_t flags,
+                         const linr_step_args* a, void* stream, bool dry);

@@ -595,13 +595,15 @@ extern "C" int linr_net_backward(const linr_frame* f, const float* params, float
 // One overfit iteration.  `weights` is what the network is evaluated at and differentiated at: the fp32 master `params` itself, or
 // with a->qparams != NULL its fake-quantised image (written here, csrc/fake_quant.hip) - the gradient then passes straight through
 // to the master, which Adam (weight decay included) updates either way.
-extern "C" int linr_net_train_step(const linr_frame* f, float* params, float* arena, size_t arena_bytes, const linr_step_args* a,
-                                   void* stream) {
+// dry: every check of the entry, no launch (csrc/overfit.hip checks a whole GOP in front of its first launch).
+int linr_train_step_f32(const linr_frame* f, float* params, float* arena, size_t arena_bytes, const linr_step_args* a, void* stream,
+                        bool dry) {
     if (!a || !a->exp_avg || !a->exp_avg_sq || !a->bits_acc || a->step < 1 || (a->qparams && a->qparams == params)) return LINR_EINVAL;
     Ctx c;
     TRY(check_frame(f, params, arena, arena_bytes, c));
     if (a->qparams) TRY(linr_fake_quant_check(params, c.L.total, a->bitdepth, a->qparams, nullptr));
     TRY(linr_scale_steps_check(f, c.L, a->scale_steps_h));       // before anything is launched
+    if (dry) return 0;
     c.s = (hipStream_t)stream;
     const float* weights = params;
     if (a->qparams) {
@@ -615,4 +617,9 @@ extern "C" int linr_net_train_step(const linr_frame* f, float* params, float* ar
     TRY(backward_core(c, a->gscale));
     ProfScope ps(c.s, PK_MISC, 0);
     return linr_adam_step_launch(c.L, c.L.total, params, c.A.GSUM, *a, c.s);
+}
+
+extern "C" int linr_net_train_step(const linr_frame* f, float* params, float* arena, size_t arena_bytes, const linr_step_args* a,
+                                   void* stream) {
+    return linr_train_step_f32(f, params, arena, arena_bytes, a, stream, false);
 }

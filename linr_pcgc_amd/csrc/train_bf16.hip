@@ -1471,13 +1471,15 @@ extern "C" int linr_net_backward_bf16(const linr_frame* f, const float* params, 
 
 // One overfit iteration (csrc/net.hip: linr_net_train_step, in this executor's arithmetic): with a->qparams != NULL every kernel -
 // tpack_k's weight images included - reads the fake-quantised image of the fp32 master, and Adam updates the master.
-extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
-                                        const linr_step_args* a, void* stream) {
+// dry: every check of the entry, no launch (csrc/overfit.hip checks a whole GOP in front of its first launch).
+int linr_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
+                         const linr_step_args* a, void* stream, bool dry) {
     if (!a || !a->exp_avg || !a->exp_avg_sq || !a->bits_acc || a->step < 1 || (a->qparams && a->qparams == params)) return LINR_EINVAL;
     TCtx c;
     TRY(tcheck(f, params, arena, arena_bytes, occ_bf16, c));
     if (a->qparams) TRY(linr_fake_quant_check(params, c.L.total, a->bitdepth, a->qparams, nullptr));
     TRY(linr_scale_steps_check(f, c.L, a->scale_steps_h));       // before anything is launched
+    if (dry) return 0;
     c.s = (hipStream_t)stream;
     if (c.R == 0) return 0;
     if (a->qparams) {
@@ -1489,6 +1491,11 @@ extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void
     TRY(tbackward(c, a->gscale));
     ProfScope ps(c.s, TK_MISC, 0);
     return linr_adam_step_launch(c.L, c.L.total, params, c.A.GSUM, *a, c.s);
+}
+
+extern "C" int linr_net_train_step_bf16(const linr_frame* f, float* params, void* arena, size_t arena_bytes, const uint16_t* occ_bf16,
+                                        const linr_step_args* a, void* stream) {
+    return linr_train_step_bf16(f, params, arena, arena_bytes, occ_bf16, a, stream, false);
 }
 
 extern "C" int linr_spconv_bwd_fused_bf16(const uint16_t* gout, const uint16_t* in, const int32_t* lo, const uint32_t* mask, int64_t ld,

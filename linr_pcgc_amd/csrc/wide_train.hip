@@ -385,8 +385,9 @@ extern "C" int linr_net_backward_wide(const linr_frame* f, const float* params, 
 // One overfit iteration.  `weights` is what the network is evaluated and differentiated at: the fp32 master `params` itself, or with
 // a->qparams != NULL its fake-quantised image (written here) - the gradient then passes straight through to the master, which Adam
 // (weight decay included) updates either way.
-extern "C" int linr_net_train_step_wide(const linr_frame* f, float* params, int32_t hidden, void* arena, size_t arena_bytes,
-                                        uint32_t flags, const linr_step_args* a, void* stream) {
+// dry: every check of the entry, no launch (csrc/overfit.hip checks a whole GOP in front of its first launch).
+int linr_train_step_wide(const linr_frame* f, float* params, int32_t hidden, void* arena, size_t arena_bytes, uint32_t flags,
+                         const linr_step_args* a, void* stream, bool dry) {
     if (!a) return LINR_EINVAL;
     TRY(check_head(f, params, arena, arena_bytes, hidden, flags));
     if (!a->exp_avg || !a->exp_avg_sq || !a->bits_acc || a->step < 1 || (a->qparams && a->qparams == params)) return LINR_EINVAL;
@@ -394,7 +395,7 @@ extern "C" int linr_net_train_step_wide(const linr_frame* f, float* params, int3
     Layout L8; WLayout W; TArena A;
     TRY(check_frame(f, hidden, L8, W, A));
     TRY(linr_scale_steps_check(f, L8, a->scale_steps_h));       // before anything is launched
-    if (f->rows == 0) return 0;
+    if (dry || f->rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const float* weights = params;
     if (a->qparams) {
@@ -411,4 +412,9 @@ extern "C" int linr_net_train_step_wide(const linr_frame* f, float* params, int3
     TRY(backward(c, a->gscale));
     linr_poison_hook(s, PK_WIDE);
     return linr_adam_step_launch(L8, W.total, params, gvec, *a, s);
+}
+
+extern "C" int linr_net_train_step_wide(const linr_frame* f, float* params, int32_t hidden, void* arena, size_t arena_bytes,
+                                        uint32_t flags, const linr_step_args* a, void* stream) {
+    return linr_train_step_wide(f, params, hidden, arena, arena_bytes, flags, a, stream, false);
 }

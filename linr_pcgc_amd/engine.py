@@ -318,3 +318,60 @@ def net_train_step_bf16(frame, flat_params, exp_avg, exp_avg_sq, gscale, step, l
     args = _step_args(exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits, scale_steps, qparams, bitdepth)
     check(_lib.lib().linr_net_train_step_bf16(frame.cref(), flat_params.data_ptr(), base, nbytes, frame.occ_bf16(), ctypes.byref(args),
                                               _stream()), 'linr_net_train_step_bf16')
+
+
+def overfit_plan(frames, epochs, model_scale_num, step=0, sched_steps=0, lr=0.01, scale_steps=None, step_size=32, gamma=0.992, min_lr=4e-4):
+    """linr_overfit_plan (host only, no GPU call): the schedule of an overfit of `epochs` epochs over `frames` - anything with
+    n_scales / row_off / scale_idx (engine.Frame) - from the starting state of a FlatAdam (t, sched_steps, lr, t_scale).  Returns a
+    dict: 'lr' float64 [steps], 'step' int64 [steps], 'scale_steps' int64 [steps, model_scale_num] of every step (epoch-major), and the
+    state BEFORE the clamp at every epoch's end: 'end_step', 'end_sched', 'end_lr' [epochs], 'end_scale_steps' [epochs, model_scale_num]."""
+    n, S, E = len(frames), int(model_scale_num), int(epochs)
+    keep, cf = [], (_lib.LinrFrame * max(n, 1))()
+    for j, f in enumerate(frames):
+        ro = np.ascontiguousarray(f.row_off, dtype=np.int64)
+        si = np.ascontiguousarray(f.scale_idx, dtype=np.int32)
+        keep += [ro, si]
+        cf[j] = _lib.LinrFrame(rows=int(ro[-1]) if len(ro) else 0, n_scales=int(f.n_scales), model_scale_num=S, block_layers=1,
+                               row_off_h=ro.ctypes.data, scale_idx_h=si.ctypes.data)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.addressof(cf[j]) for j in range(max(n, 1))])
+    k = max(E, 0) * n
+    out = {'lr': np.empty(k, np.float64), 'step': np.empty(k, np.int64), 'scale_steps': np.empty((k, max(S, 0)), np.int64),
+           'end_step': np.empty(max(E, 0), np.int64), 'end_sched': np.empty(max(E, 0), np.int64), 'end_lr': np.empty(max(E, 0), np.float64),
+           'end_scale_steps': np.empty((max(E, 0), max(S, 0)), np.int64)}
+    ss = None if scale_steps is None else np.ascontiguousarray(scale_steps, dtype=np.int64)
+    check(_lib.lib().linr_overfit_plan(ptrs, n, E, S, int(step), int(sched_steps), float(lr), None if ss is None else ss.ctypes.data,
+                                       int(step_size), float(gamma), float(min_lr), *[out[key].ctypes.data for key in
+                                       ('lr', 'step', 'scale_steps', 'end_step', 'end_sched', 'end_lr', 'end_scale_steps')]),
+          'linr_overfit_plan')
+    return out
+
+
+def overfit_gop(frames, point_nums, executor, flat_params, exp_avg, exp_avg_sq, arena, arena_bytes, epochs, lr, min_lr, gamma, step_size,
+                step, sched_steps, scale_steps, beta1, beta2, eps, weight_decay, keep_best=True, qat_from=None, bitdepth=8, qparams=None,
+                hidden=8, flags=0, occ_bf16=None):
+    """linr_overfit_gop: the whole overfit of a GOP - every epoch, every frame's training step, the epoch's mean loss and the choice of
+    the best epoch - queued by ONE call that synchronises the current stream once, at its end; ctypes releases the GIL for its duration.
+    frames: engine.Frame list; arena: the executor's arena address for the largest frame; occ_bf16: per-frame addresses (bf16 executor).
+    Returns (losses float64 [epochs], best_epoch, best_loss, step, sched_steps, lr, scale_steps) - the optimiser state that belongs to
+    what the call left in flat_params (include/linr_hip.h: linr_overfit_result)."""
+    L = _lib.lib()
+    n, E = len(frames), int(epochs)
+    fr = (_lib.LinrOverfitFrame * n)()
+    for j, f in enumerate(frames):
+        fr[j].f = ctypes.pointer(f._c)
+        fr[j].point_num = float(point_nums[j])
+        fr[j].occ_bf16 = None if occ_bf16 is None else occ_bf16[j]
+    ws = _lib.scratch(L.linr_overfit_ws_bytes(flat_params.numel(), n, E) + 16, flat_params.device)
+    base = (ws.data_ptr() + 15) & ~15
+    ss = np.ascontiguousarray(scale_steps, dtype=np.int64)
+    losses, out_ss = np.empty(max(E, 1), np.float64), np.zeros_like(ss)
+    args = _lib.LinrOverfitArgs(executor=int(executor), hidden=int(hidden), flags=int(flags), n_frames=n, params=flat_params.data_ptr(),
+                                exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), beta1=beta1, beta2=beta2, eps=eps,
+                                weight_decay=weight_decay, lr=float(lr), min_lr=float(min_lr), gamma=float(gamma), step_size=int(step_size),
+                                step=int(step), sched_steps=int(sched_steps), scale_steps_h=ss.ctypes.data, epochs=E,
+                                keep_best=1 if keep_best else 0, qat_from=E if qat_from is None else int(qat_from), bitdepth=int(bitdepth),
+                                qparams=None if qparams is None else qparams.data_ptr(), arena=arena, arena_bytes=int(arena_bytes),
+                                ws=base, ws_bytes=ws.numel() - (base - ws.data_ptr()))
+    res = _lib.LinrOverfitResult(losses_h=losses.ctypes.data, scale_steps_h=out_ss.ctypes.data)
+    check(L.linr_overfit_gop(fr, ctypes.byref(args), ctypes.byref(res), _stream()), 'linr_overfit_gop')
+    return losses[:E].copy(), int(res.best_epoch), float(res.best_loss), int(res.step), int(res.sched_steps), float(res.lr), out_ss

@@ -5,6 +5,8 @@ The reference re-reads a pickle from disk, rebuilds ~60 coordinate maps per scal
 occupancy), a step is one stream-ordered launch sequence (forward, backward, fused Adam) and the host reads the loss
 once per epoch.
 """
+import os
+
 import torch
 
 from .model_core import LINR_PCGC_Model, train_step
@@ -151,7 +153,63 @@ def qat_first_epoch(epochs, qat_epochs):
     return max(0, int(epochs) - int(qat_epochs))
 
 
-def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best', info=None, qat_epochs=0, qat_bitdepth=8):
+# opt-in (LINR_C_OVERFIT=1, or overfit_gop(c_loop=True)): the whole overfit of a GOP as ONE C call (csrc/overfit.hip: linr_overfit_gop)
+C_OVERFIT = os.environ.get('LINR_C_OVERFIT', '0') == '1'
+
+
+def _overfit_gop_c(model, opt, gop, epochs, min_lr, keep, info, qat_epochs, qat_from, qat_bitdepth):
+    """overfit_gop's loop as one call of linr_overfit_gop: the same launches and the same host doubles, one synchronisation."""
+    import math
+    from . import _lib, engine
+    from .model_core import TRAIN_PRECISIONS
+    tp = model.train_precision
+    if tp not in TRAIN_PRECISIONS:
+        raise ValueError('train_precision must be one of ' + ', '.join(repr(p) for p in TRAIN_PRECISIONS))
+    if model._wide is not None and tp in ('bf16', 'bf16-deep'):
+        raise _lib.LinrError('the bf16 training executor exists for hidden_channel_conv=8 only')
+    if model._wide is None and tp == 'bf16-mul':
+        raise _lib.LinrError("train_precision 'bf16-mul' exists for hidden_channel_conv 16 / 32 only: width 8 has the bf16 training executor")
+    big = max(gop.frames, key=lambda f: f.rows)
+    extra = {}
+    if model._wide is not None:          # whatever WideNet.c_step says: the C step is what the call runs
+        w = model._wide
+        a = w.step_arena(big)
+        base = (a.data_ptr() + 63) & ~63
+        nbytes = a.numel() - (base - a.data_ptr())
+        executor = _lib.LINR_OVERFIT_WIDE
+        extra = {'hidden': w.C, 'flags': _lib.LINR_MUL_BF16 if w._train_mul() == 'bf16' else 0}
+    elif tp == 'f32':
+        arenas = {f.arena.data_ptr() for f in gop.frames if f.arena is not None}
+        if len(arenas) != 1 or any(f.arena is None for f in gop.frames):
+            raise _lib.LinrError('overfit_gop(c_loop=True) needs the frames of the GOP to share one arena (overfit.Gop)')
+        base, nbytes, executor = big.arena.data_ptr(), min(f.arena.numel() for f in gop.frames), _lib.LINR_OVERFIT_F32
+    else:
+        base, nbytes = big.train_bf16_arena(tp == 'bf16-deep')          # the GOP's shared one (share_train_bf16_arena)
+        executor = _lib.LINR_OVERFIT_BF16
+        extra = {'occ_bf16': [f.occ_bf16() for f in gop.frames]}
+    if qat_epochs:
+        extra.update(qparams=model.qat_parameters(), qat_from=qat_from, bitdepth=int(qat_bitdepth))
+    losses, best_epoch, best_loss, t, sched, lr, t_scale = engine.overfit_gop(
+        gop.frames, gop.point_nums, executor, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, base, nbytes, epochs, opt.lr, min_lr,
+        opt.gamma, opt.step_size, opt.t, opt.sched_steps, opt.t_scale, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay,
+        keep_best=keep == 'best', **extra)
+    opt.t, opt.sched_steps, opt.lr = t, sched, lr
+    opt.t_scale = t_scale.astype(opt.t_scale.dtype)
+    losses = [float(x) for x in losses]
+    if (keep == 'best' and best_epoch < 0 and losses) or (keep != 'best' and losses and not math.isfinite(losses[-1])):
+        err = FloatingPointError('the overfit diverged: epoch losses %s (no finite epoch to keep; learning rate %g)'
+                                 % (['%.4g' % x for x in losses], opt.lr))
+        err.losses = losses          # (run.py writes the epochs' records from them: no on_epoch has seen them)
+        raise err
+    if info is not None:
+        info['coded_epoch'] = best_epoch if keep == 'best' else epochs - 1
+        info['coded_loss'] = best_loss if keep == 'best' else (losses[-1] if losses else None)
+        if qat_epochs:
+            info['qat_from'] = qat_from
+    return losses
+
+
+def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best', info=None, qat_epochs=0, qat_bitdepth=8, c_loop=None):
     """main.py:297-437: frames in fixed order, one optimiser + StepLR step per frame, lr clamp after each epoch.
     keep='best' (the reference's policy, main.py:413-426,440-451): model and optimiser are left in the state at the end of the epoch
     with the lowest mean loss; keep='last': in the state after the last epoch.  Returns the per-epoch mean loss (bits per point),
@@ -159,7 +217,15 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
     qat_epochs > 0 (opt-in; 0 is the plain overfit, untouched): the last min(qat_epochs, epochs) epochs are quantisation-aware
     (train_step qat_bitdepth=): their loss is the rate of the weights encode_gop will code with at `qat_bitdepth` bits.  With
     keep='best' only those epochs compete - the loss of a plain epoch belongs to weights that are never coded.  The state left
-    behind is the fp32 master either way; `info` also receives 'qat_from', the first quantisation-aware epoch."""
+    behind is the fp32 master either way; `info` also receives 'qat_from', the first quantisation-aware epoch.
+    c_loop (opt-in; None: LINR_C_OVERFIT=1, read once): the loop below as ONE C call (linr_overfit_gop) that queues every step of
+    every epoch and synchronises once - the same launches and the same host doubles, so parameters, moments and counters are those of
+    the loop; the returned losses are summed in frame order instead of torch's reduction order (a few ulp).  Wide models then run
+    their one-call step whatever WideNet.c_step says.  Epochs cannot be observed from outside the call: on_epoch is refused."""
+    if c_loop is None:
+        c_loop = C_OVERFIT
+    if c_loop and on_epoch is not None:
+        raise ValueError('overfit_gop(c_loop=True) runs all epochs in one call: on_epoch cannot be served')
     if keep not in ('best', 'last'):
         raise ValueError("keep must be 'best' or 'last'")
     qat_from = qat_first_epoch(epochs, qat_epochs)
@@ -167,6 +233,8 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
         raise ValueError('qat_bitdepth must be in 2..16, got %r' % (qat_bitdepth,))
     if getattr(model, 'train_precision', 'f32') in ('bf16', 'bf16-deep'):
         gop.share_train_bf16_arena(deep=model.train_precision == 'bf16-deep')
+    if c_loop:
+        return _overfit_gop_c(model, opt, gop, epochs, min_lr, keep, info, qat_epochs, qat_from, qat_bitdepth)
     losses = []
     dev = gop.frames[0].device
     bits = torch.zeros(len(gop), dtype=torch.float64, device=dev)         # one slot per frame: no per-step torch kernels

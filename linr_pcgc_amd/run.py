@@ -101,6 +101,12 @@ def parse(argv=None):
                     help='code, write and check GOP g on a background thread with a HIP stream of its own while GOP g+1 overfits (at most one '
                          'such finish in flight); the encoded files and the losses are those of the plain flow.  Up to three GOPs are resident '
                          'in HBM at once: one finishing, one training, one staged ahead')
+    ap.add_argument('--c-overfit', '--c_overfit', dest='c_overfit', action='store_true',
+                    help='the overfit of every GOP as ONE library call (linr_overfit_gop: every step of every epoch queued at once, the best '
+                         'epoch chosen on the GPU, one synchronisation per GOP) instead of the Python loop; the encoded files and the '
+                         'checkpoint are those of the loop.  The per-epoch records of info.log and result.json are written after the call '
+                         '(their train_time is the whole call\'s).  At --hidden-channel-conv 16 / 32 it runs the one-call training step.  Not '
+                         'with --mid-test, which measures between epochs')
     ap.add_argument('--mid-test', action='store_true',
                     help='main.py --mid_test: measure the model through Test_one_gop (model.codec) at epochs 0..9 and every --check-freq-th '
                          'epoch of every GOP; results under <out>/output/<gop>/<epoch>/ and <out>/output/<gop>/result.json')
@@ -109,7 +115,11 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.qat_epochs < 0:
         ap.error('--qat-epochs must be >= 0')
-    if args.qat_epochs and args.hidden_channel_conv != 8:
+    if overfit.C_OVERFIT:          # LINR_C_OVERFIT=1 is the same switch: the same refusals and exemptions hold
+        args.c_overfit = True
+    if args.c_overfit and args.mid_test:
+        ap.error('--c-overfit runs all epochs of a GOP in one call: --mid-test cannot measure between them')
+    if args.qat_epochs and args.hidden_channel_conv != 8 and not args.c_overfit:
         from .wide_net import WideNet
         if not WideNet.c_step:
             ap.error('--qat-epochs: quantisation-aware training exists for --hidden-channel-conv 8 only, and for 16 / 32 with the one-call '
@@ -290,14 +300,29 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                 json.dump(mid, f, indent=4)
             clock['mark'] = time.time()
 
+        # --c-overfit (read with getattr: callers that build their own namespace are untouched): one call for all epochs, their
+        # records are written behind it
+        loop = {'c_loop': True, 'on_epoch': None} if (getattr(args, 'c_overfit', False) or overfit.C_OVERFIT) else {'on_epoch': on_epoch}
+        if loop['on_epoch'] is None and getattr(args, 'mid_test', False):          # (parse() refuses it; a caller's own namespace ends here)
+            log.close()
+            raise ValueError('the one-call overfit (--c-overfit, LINR_C_OVERFIT=1) runs all epochs of a GOP in one call: the mid-test '
+                             'cannot measure between them')
         try:
             qat_epochs = int(getattr(args, 'qat_epochs', 0) or 0)
             if qat_epochs:
                 model.qat_epochs = min(qat_epochs, epochs)           # informational, for side_info.json (codec.encode_gop)
-                losses = overfit.overfit_gop(model, opt, gop, epochs, args.min_lr, keep=getattr(args, 'keep', 'best'), info=info, on_epoch=on_epoch,
-                                             qat_epochs=qat_epochs, qat_bitdepth=getattr(args, 'model_bitdepth', 8))
+                losses = overfit.overfit_gop(model, opt, gop, epochs, args.min_lr, keep=getattr(args, 'keep', 'best'), info=info,
+                                             qat_epochs=qat_epochs, qat_bitdepth=getattr(args, 'model_bitdepth', 8), **loop)
             else:
-                losses = overfit.overfit_gop(model, opt, gop, epochs, args.min_lr, keep=getattr(args, 'keep', 'best'), info=info, on_epoch=on_epoch)
+                losses = overfit.overfit_gop(model, opt, gop, epochs, args.min_lr, keep=getattr(args, 'keep', 'best'), info=info, **loop)
+            if loop['on_epoch'] is None:
+                for epoch, loss_mean in enumerate(losses):
+                    on_epoch(epoch, loss_mean)
+        except FloatingPointError as e:
+            if loop['on_epoch'] is None:          # a diverged overfit: the Python loop has written its epochs' records before it raises
+                for epoch, loss_mean in enumerate(getattr(e, 'losses', ())):
+                    on_epoch(epoch, loss_mean)
+            raise
         finally:
             log.close()
         torch.cuda.synchronize()                 # overfit_s ends here, and the model is complete before another stream reads it
