@@ -1029,6 +1029,33 @@ LINR_API int linr_rc_decode_probs(const float* probs_dev, int64_t n_probs, const
                          const linr_rc_dec_entry* entries_host, int32_t n_entries, float* occ_col_dev, int64_t occ_ld, int64_t n_rows,
                          uint8_t* sym_dev, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- geometry digests (opt-in; csrc/digest.hip, body: csrc/digest_body.h) -------------------------------------------------------
+ * What an encoder records of every octree level of a frame and a decoder checks as soon as it has decoded the level
+ * (linr_pcgc_amd/stream_digests.py: bins/digests.bin holds D >> 32).  The digest of a multiset of int32 rows (x, y, z), with an
+ * optional origin added first; all arithmetic unsigned 64-bit and wrapping, u32(a) the 32-bit pattern of a:
+ *   G        = 0x9E3779B97F4A7C15
+ *   m(v):      v ^= v >> 30;  v *= 0xBF58476D1CE4E5B9;  v ^= v >> 27;  v *= 0x94D049BB133111EB;  v ^= v >> 31
+ *   r(x,y,z) = m( m( u32(x) | u32(y) << 32 ) + u32(z) + G )       with (x, y, z) = row + origin, added in int32 (wrapping)
+ *   S        = sum of r over the n rows (mod 2^64);   D = m( S ^ m(n + G) )
+ * Integer adds and multiplies only, so any reduction order gives the same value: it is a digest of the SET of rows, not of their order
+ * (the decoders' row order is fixed by construction).  It detects errors; it is not cryptographic.
+ * linr_coords_digest_segments: coords_dev [N][3] int32, 4-byte aligned; segment j is rows [seg_off_h[j], seg_off_h[j + 1]) of it
+ * (seg_off_h: n_seg + 1 HOST offsets, non-negative and non-decreasing; empty segments allowed), 1 <= n_seg <= LINR_DECODE_MAX_FRAMES;
+ * origins_h: HOST int32 [n_seg][3] or NULL (all zero).  digest_dev[j] (8-byte aligned) holds D of segment j once `stream` reaches that
+ * point; the entry does not synchronise and writes nothing but digest_dev[0 .. n_seg) and its workspace (ws:
+ * linr_coords_digest_ws_bytes(n_seg) bytes - 0 for n_seg out of range -, 8-byte aligned, uninitialised).  The table travels as kernel
+ * arguments: the host arrays are free on return.  Two launches - a grid of (at most 256 workgroups, segment) that leaves one partial sum
+ * per workgroup in ws, one wave per segment that sums them and finalises -, no atomics.  Checked before the first launch, and a refused
+ * call writes nothing: LINR_EINVAL for a NULL pointer (origins_h may be NULL; coords_dev too when every segment is empty), n_seg out of
+ * range, a negative or decreasing seg_off_h; LINR_EALIGN for a misaligned coords_dev, digest_dev or ws; LINR_ENOSPC for a short
+ * workspace.  The kernels sit behind linr_debug_poison class 15 (the decoder scales') and belong to no linr_prof_* class.
+ * linr_coords_digest_host: the same D for n rows in HOST memory with one origin (HOST int32 [3] or NULL) as a plain loop; no GPU
+ * involved, thread-safe.  n <= 0 (or coords_h NULL): the digest of no rows. */
+LINR_API size_t   linr_coords_digest_ws_bytes(int32_t n_seg);
+LINR_API int      linr_coords_digest_segments(const int32_t* coords_dev, const int64_t* seg_off_h, int32_t n_seg, const int32_t* origins_h,
+                                     uint64_t* digest_dev, void* ws, size_t ws_bytes, void* stream);
+LINR_API uint64_t linr_coords_digest_host(const int32_t* coords_h, int64_t n, const int32_t* origin_h);
+
 /* ---- frame input (host) ----------------------------------------------------------------------------------------------
  * Body of an ASCII PLY (datautils/custom_dataset.py:9-14 read_ply_o3d - open3d's C++ reader - followed by :263-269, which keeps
  * the rounded x, y, z).  text_h / len: the bytes BEHIND "end_header\n"; n_rows vertices of n_cols whitespace-separated numbers,

@@ -264,6 +264,9 @@ _PROTOS = {
     'linr_overfit_ws_bytes': (c_size, [c_i64, c_i32, c_i32]),
     'linr_overfit_gop': (ctypes.c_int, [ctypes.POINTER(LinrOverfitFrame), ctypes.POINTER(LinrOverfitArgs), ctypes.POINTER(LinrOverfitResult),
                                         c_ptr]),
+    'linr_coords_digest_ws_bytes': (c_size, [c_i32]),
+    'linr_coords_digest_segments': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    'linr_coords_digest_host': (ctypes.c_uint64, [c_ptr, c_i64, c_ptr]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -272,6 +275,19 @@ _lib = None
 
 class LinrError(RuntimeError):
     pass
+
+
+class LinrDigestError(LinrError):
+    """A decoded octree level does not have the digest its GOP carries (bins/digests.bin; codec.decode_gop verify=True).
+    frame: the frame's index in the GOP; scale: the scale whose children differ; want: the stream's value; got: the value of what was
+    decoded (both D >> 32 of stream_digests.py)."""
+
+    def __init__(self, frame, scale, want, got):
+        self.frame, self.scale, self.want, self.got = int(frame), int(scale), int(want), int(got)
+        super().__init__('frame %d, scale %d: the decoded level has digest %08x, the stream records %08x.  This usually means that '
+                         'the stream was encoded by another build of the library or on another GPU than this decoder runs on (the '
+                         'probabilities must be reproduced bit for bit), or that one of the GOP\'s files is damaged'
+                         % (self.frame, self.scale, self.got, self.want))
 
 
 def lib():
@@ -298,7 +314,7 @@ class _Poisoned:
     CUs freshly filled with a NaN pattern (linr_debug_poison_now in front of it, linr_debug_poison(all classes) for the launches
     inside the executors).  The test suite must pass unchanged under it: no kernel may read on-chip state it did not write."""
     _HOST = ('linr_ac_', 'linr_stream_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host',
-             'linr_params_fake_quant_ranges_host', 'linr_overfit_plan')
+             'linr_params_fake_quant_ranges_host', 'linr_overfit_plan', 'linr_coords_digest_host')
 
     def __init__(self, handle):
         self._h = handle

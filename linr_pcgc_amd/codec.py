@@ -17,6 +17,7 @@ from .function_utils import pack_bitstream, unpack_bitstream
 from .model_codec import Model_Estimate, candidate_ranges, laplace_bits_est
 from .model_core import DeviceCoderSet, codes_word_off, encode_streams, encode_streams_codes
 from .module_utils import octree_level_obj, qscTensor, unique_sorted  # noqa: F401
+from . import stream_digests
 from .stream_chunks import SIDE_BITS as STREAM_CHUNK_SIDE_BITS, check_chunk
 
 # The probabilities the range coder sees must be reproduced BIT FOR BIT by the decoder, so the fp32 evaluation order of the
@@ -112,7 +113,76 @@ def _code_frames_device(coded_model, gop, coder_group, chunk=0):
     return frames_bytes, bits_dev
 
 
-def _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found=None):
+def _levels_back_to_back(levels):
+    """Whether the coordinate lists are consecutive slices of one buffer (the levels of a frame staged by ops.octree_levels are)."""
+    for a, b in zip(levels, levels[1:]):
+        # (by storage offsets: an empty slice has no data pointer to compare)
+        if not (a.is_contiguous() and b.is_contiguous() and b.storage_offset() == a.storage_offset() + a.numel() and
+                a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()):
+            return False
+    return levels[0].is_contiguous()
+
+
+def _as_segments(levels):
+    """(coords, seg_off) of coordinate lists as the segments of ONE list: a view where they lie back to back in one buffer (the
+    levels ops.octree_levels stages, the children of a lock-step call), a copy otherwise."""
+    seg = np.zeros(len(levels) + 1, dtype=np.int64)
+    seg[1:] = np.cumsum([int(c.shape[0]) for c in levels])
+    if len(levels) == 1:
+        return levels[0].contiguous(), seg
+    if _levels_back_to_back(levels):
+        return levels[0].new_empty(0).set_(levels[0].untyped_storage(), levels[0].storage_offset(), (int(seg[-1]), 3)), seg
+    return torch.cat(levels, dim=0), seg
+
+
+def verify_levels(levels, wants, frame_ids, scale, origins=None):
+    """The decoder's check of one scale (decode_gop verify=True): the digests of the decoded children `levels` (one list per frame;
+    origins: per frame the origin to add, scale 0) against the stream's values `wants` (D >> 32) - one ops.coords_digest call and one
+    small read.  The first frame that differs raises _lib.LinrDigestError."""
+    from . import ops
+    from ._lib import LinrDigestError
+    coords, seg = _as_segments(levels)
+    got = ops.coords_digest(coords, seg, origins).cpu().numpy().view(np.uint64) >> np.uint64(32)
+    for f, w, g in zip(frame_ids, wants, got.tolist()):
+        if int(w) != int(g):
+            raise LinrDigestError(f, scale, w, g)
+
+
+def gop_digests_launch(gop):
+    """The digests of every octree level of every frame of a staged GOP - an overfit.Gop, or any sequence of prepare_frame's frame
+    dicts (encoder.encode_one_gop's reading data) - (stream_digests.py: D(i, s) of
+    gop.infos[i]['all_input_info'][s]['ground_truth'], scale 0 with gop.coord_mins[i] as origin), launched on the caller's stream:
+    per frame one call for scale 0 and one segmented call for the levels s >= 1 where they lie back to back in one buffer (a call per
+    level otherwise).  No synchronisation, no draw from torch's generator.  Returns (device int64 [sum n_scales] - frame by frame,
+    scale 0 first -, the frames' scale counts); gop_digests_bin reads it."""
+    from . import ops
+    infos = gop.infos if hasattr(gop, 'infos') else list(gop)
+    coord_mins = gop.coord_mins if hasattr(gop, 'coord_mins') else [fr['coord_data_min'] for fr in infos]
+    levels = [[sc['ground_truth'] for sc in info['all_input_info']] for info in infos]
+    n_scales = [len(lv) for lv in levels]
+    out = torch.empty(sum(n_scales), dtype=torch.int64, device=levels[0][0].device)
+    at = 0
+    for lv, cmin in zip(levels, coord_mins):
+        ops.coords_digest(lv[0].contiguous(), origins=[cmin], out=out[at:at + 1])
+        rest = lv[1:]
+        if 1 < len(rest) <= LOCKSTEP_MAX_FRAMES and _levels_back_to_back(rest):
+            ops.coords_digest(*_as_segments(rest), out=out[at + 1:at + len(lv)])
+        else:
+            for s, c in enumerate(rest, 1):
+                ops.coords_digest(c.contiguous(), out=out[at + s:at + s + 1])
+        at += len(lv)
+    return out, n_scales
+
+
+def gop_digests_bin(launched):
+    """digests.bin of what gop_digests_launch returned: the GOP's one host read."""
+    dev, n_scales = launched
+    vals = dev.cpu().numpy().view(np.uint64).tolist()
+    it = iter(vals)
+    return stream_digests.pack([[next(it) for _ in range(n)] for n in n_scales])
+
+
+def _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found=None, digests=None):
     bits_est = float(torch.stack(bits_dev).sum())
     low = enc_all_frame_low_xyz(gop)
     points = sum(gop.point_nums)
@@ -121,6 +191,13 @@ def _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found=None):
     side_bits = EXTRA_SIDE_BITS + (STREAM_CHUNK_SIDE_BITS if side_info.get('stream_chunk') else 0)
     extra = {} if found is None else {'qrange': {'trims': found['trims'], 'objective_bits': found['objective_bits'],
                                                  'chosen': found['trims'][found['chosen']], 'search_s': found['search_s']}}
+    if digests is not None:
+        # ... and the digests, when the GOP has them: their file and the one-byte field (stream_digests.bits)
+        digests_bin = gop_digests_bin(digests)
+        if [len(fb) for fb in frames_bytes] != digests[1]:
+            raise AssertionError('a frame has another number of scale streams than of staged levels')
+        side_bits += stream_digests.bits(digests_bin)
+        extra.update({'digests_bin': digests_bin, 'digest_bits': stream_digests.bits(digests_bin)})
     return {**extra, 'frames': frames_bytes, 'model_bin': comp['final_bytes'], 'side_info': side_info, 'low_enc_bytes': low,
             'point_num': points, 'bits_est': bits_est,
             # the five one-byte side-info fields this codec adds (arith_version, precision, scale_num, block_layers,
@@ -189,7 +266,7 @@ def search_qrange(model, model_ori, gop, bitdepth=8, precision='f32', trims=None
 
 
 def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32', device_codes=False, device_coder=False,
-               coder_group=8, qrange_search=False, qrange_trims=None, qrange_frames=4, stream_chunk=0):
+               coder_group=8, qrange_search=False, qrange_trims=None, qrange_frames=4, stream_chunk=0, digests=False):
     """encoder.encode_one_gop: quantise the model, then per frame ONE forward over all scales and 8 x scales
     independent arithmetic-coded streams (thread pool).  precision='bf16': the forward runs on the bf16 / uint8-weight
     executor (BASELINE config[4]); the choice is recorded in side_info so that the decoder reproduces it.
@@ -208,7 +285,12 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     symbols is cut into chunks of S symbols that are coded - and later decoded - independently, on the coder threads or a wave each,
     at a few bytes per chunk.  The decoder needs S: side_info gets 'stream_chunk', counted as 32 bits in model_bpp / bpp_all, and a
     build that does not know the field cannot decode such a GOP.  The three coder paths write the same bytes at the same S; a GOP
-    whose streams all have at most S symbols differs from the plain one in that field only.  hidden_channel_conv 8 only."""
+    whose streams all have at most S symbols differs from the plain one in that field only.  hidden_channel_conv 8 only.
+    digests=True (opt-in; stream_digests.py has the format): the GOP becomes self-checking.  The digest of every octree level of every
+    frame is computed on the GPU where the staged levels are (gop_digests_launch: two library calls per frame on the caller's stream,
+    ONE host read per GOP, no draw from torch's generator) and returned as 'digests_bin' (write_gop: bins/digests.bin); side_info gets
+    'digests' = 1, and 8 * len(digests_bin) + 8 bits are counted in model_bpp / bpp_all and reported as 'digest_bits'.  Every stream
+    and every other file is what digests=False writes; decode_gop checks each level as it decodes it."""
     if device_coder and not 1 <= int(coder_group) <= 64:
         raise ValueError('coder_group must be in 1..64, got %r' % (coder_group,))
     stream_chunk = check_chunk(stream_chunk)
@@ -229,6 +311,10 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     side_info.update(model_shape(model))
     if stream_chunk:
         side_info['stream_chunk'] = stream_chunk
+    launched = None
+    if digests:
+        side_info['digests'] = stream_digests.VERSION
+        launched = gop_digests_launch(gop)               # read in _gop_result, behind the coding
     # informational (the decoder does not need it): which training executor produced the coded model
     side_info['train_precision'] = getattr(model, 'train_precision', 'f32')
     # ... and, when the driver says so, how many of its last epochs were quantisation-aware (overfit_gop qat_epochs=): not counted
@@ -242,7 +328,7 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
         side_info['qrange_candidates'] = len(found['trims'])
     if device_coder:
         frames_bytes, bits_dev = _code_frames_device(coded_model, gop, int(coder_group), stream_chunk)
-        return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found)
+        return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found, launched)
     # Pipeline: the GPU forward + D2H of frame i+1 runs while host workers range-code earlier frames (the coder's C call
     # releases the GIL).  A frame has 8 x scales independent streams, but the 8 streams of its finest scale carry 73 % of the
     # symbols, so one frame keeps only ~8 threads busy: TWO frames are coded concurrently, each on half of the threads
@@ -314,21 +400,26 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
         while pending:
             hand_over(pending.pop(0), coder)
         frames_bytes = [j.result() for j in jobs]
-    return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found)
+    return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found, launched)
 
 
-def decode_one_frame(model, frame_enc_bytes, xyz_low, chunk=0, n_threads=1, device_decoder=False):
+def decode_one_frame(model, frame_enc_bytes, xyz_low, chunk=0, n_threads=1, device_decoder=False, digests=None, origin=None, frame=0):
     """decoder.decode_one_frame (decoder.py:153-176): coarse to fine, 8 AC-decoded stages per scale.  A scale is ONE call into the
     library (model.decode_scale -> linr_decode_scale: kernel map, the 7-neighbour occupancy read off it instead of
     qscTensor.set_offset_tensor's searches, the 8 stage forwards with their host round trips, upper_layer), so the Python side of a
     frame is seven buffer allocations.  chunk = S > 0: the stage streams are chunked (side_info's stream_chunk) and a stage's chunks are
     decoded on n_threads host threads.  device_decoder=True: the range decoders run on the GPU (model.decode_scale(device_decoder=True)
-    -> linr_decode_opts.device), no host round trip per stage; n_threads is ignored."""
+    -> linr_decode_opts.device), no host round trip per stage; n_threads is ignored.
+    digests = the frame's stored values (stream_digests.unpack: one per scale; None: no check): every scale's children are checked
+    (verify_levels) before the next scale is started, scale 0 with `origin` (the frame's coord_data_min) added; a level that differs
+    raises _lib.LinrDigestError naming `frame` and the scale."""
     lowx = unique_sorted(xyz_low)          # (hidden_channel_conv 16 / 32: the same loop, model.decode_scale -> linr_decode_scale_wide)
     bits = max(1, int(xyz_low.max()).bit_length()) if xyz_low.numel() else 1       # coordinates of the coarsest level
     for s_idx in range(len(frame_enc_bytes) - 1, -1, -1):
         bits = min(bits + 1, 21)
         lowx = model.decode_scale(lowx, s_idx, frame_enc_bytes[s_idx], bits, chunk, n_threads, device_decoder)
+        if digests is not None:
+            verify_levels([lowx], [digests[s_idx]], [frame], s_idx, [origin] if s_idx == 0 and origin is not None else None)
     return {'dec_coord': lowx}
 
 
@@ -347,24 +438,36 @@ LOCKSTEP_MAX_FRAMES = 64                  # LINR_DECODE_MAX_FRAMES of include/li
 LOCKSTEP_MAX_ROWS = (1 << 26) - 64        # rows of one lock-step call: the compressed kernel map's 32-bit bound (linr_cmap_fits32)
 
 
-def _lockstep_scale(model, lows, s_idx, encs, n_threads, chunk=0, device_decoder=False):
-    """One scale of a lock-step group; a group whose levels together pass the row bound of one call is halved."""
+def _lockstep_scale(model, lows, s_idx, encs, n_threads, chunk=0, device_decoder=False, check=None):
+    """One scale of a lock-step group; a group whose levels together pass the row bound of one call is halved.  check = (the frames'
+    stored digests of this scale, their frame ids, their origins or None): the call's children - back to back, the frames as
+    segments - are verified (verify_levels) behind it."""
     if len(lows) > 1 and sum(int(c.shape[0]) for c in lows) > LOCKSTEP_MAX_ROWS:
         h = len(lows) // 2
-        return (_lockstep_scale(model, lows[:h], s_idx, encs[:h], n_threads, chunk, device_decoder) +
-                _lockstep_scale(model, lows[h:], s_idx, encs[h:], n_threads, chunk, device_decoder))
-    return model.decode_scale_batch(lows, s_idx, encs, n_threads, chunk, device_decoder)
+        halves = [None, None] if check is None else [tuple(None if c is None else c[:h] for c in check),
+                                                     tuple(None if c is None else c[h:] for c in check)]
+        return (_lockstep_scale(model, lows[:h], s_idx, encs[:h], n_threads, chunk, device_decoder, halves[0]) +
+                _lockstep_scale(model, lows[h:], s_idx, encs[h:], n_threads, chunk, device_decoder, halves[1]))
+    out = model.decode_scale_batch(lows, s_idx, encs, n_threads, chunk, device_decoder)
+    if check is not None:
+        verify_levels(out, check[0], check[1], s_idx, check[2])
+    return out
 
 
-def decode_frames_lockstep(model, frames_enc_bytes, xyz_lows, n_threads=8, chunk=0, device_decoder=False):
+def decode_frames_lockstep(model, frames_enc_bytes, xyz_lows, n_threads=8, chunk=0, device_decoder=False, digests=None, origins=None,
+                           frame_ids=None):
     """decode_one_frame for a group of frames with the same number of scales, in lock step: coarse to fine, every scale of the whole
     group is ONE call into the library (model.decode_scale_batch -> linr_decode_scale_batch; with device_decoder
-    linr_decode_opts.device, the group's range decoders on the GPU).  Returns the frames' coordinates."""
+    linr_decode_opts.device, the group's range decoders on the GPU).  Returns the frames' coordinates.
+    digests = per frame its stored values (stream_digests.unpack; None: no check): every scale of the group is verified before the next
+    is started, scale 0 with the frames' `origins` added; frame_ids (default 0, 1, ...) name the frames in a LinrDigestError."""
     if device_decoder and getattr(model, '_wide', None) is not None:
         raise ValueError('the device decoder needs hidden_channel_conv 8')
     lows = [unique_sorted(x) for x in xyz_lows]
+    ids = list(range(len(lows))) if frame_ids is None else list(frame_ids)
     for s_idx in range(len(frames_enc_bytes[0]) - 1, -1, -1):
-        lows = _lockstep_scale(model, lows, s_idx, [f[s_idx] for f in frames_enc_bytes], n_threads, chunk, device_decoder)
+        check = None if digests is None else ([d[s_idx] for d in digests], ids, list(origins) if s_idx == 0 and origins is not None else None)
+        lows = _lockstep_scale(model, lows, s_idx, [f[s_idx] for f in frames_enc_bytes], n_threads, chunk, device_decoder, check)
     return lows
 
 
@@ -379,7 +482,8 @@ def lockstep_groups(todo, n_scales, lockstep):
     return groups
 
 
-def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=None, lockstep=0, n_threads=None, device_decoder=False):
+def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=None, lockstep=0, n_threads=None, device_decoder=False,
+               verify=True):
     """decoder.decode_one_gop: rebuild the model from model.bin, then every frame from its streams alone.
     lockstep=B > 0 (opt-in; 0 = the per-frame path below, untouched): the requested frames are decoded in groups of up to B
     consecutive entries, the scales of a group from coarsest to finest in lock step (decode_frames_lockstep), the group's range
@@ -397,6 +501,13 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
     linr_decode_scale / linr_decode_scale_batch): no host coder threads (n_threads is ignored) and one synchronisation per scale instead of one
     per stage.  It reads the same streams and side_info.json and decodes the same geometry; it composes with workers, lockstep and
     stream_chunk.
+    verify=True (the default; it does nothing for a GOP without digests, i.e. without side_info's 'digests'; with the field but without
+    enc['digests_bin'] - a deleted file - it is LinrError):
+    every decoded scale of every requested frame is digested on the GPU and compared with the stream's value before the next scale is
+    started (verify_levels: one library call and one small read per scale; in lock step the group's frames as segments), on every
+    path above.  The first level that differs raises _lib.LinrDigestError (frame, scale, want, got) - before garbage is expanded
+    further.  A digests.bin whose length does not fit the GOP's stream files, or a format version of a newer build, is LinrError
+    before any launch.  verify=False: nothing of this runs.
     Frames are independent once the model is known; with workers > 1 they are decoded by a host thread pool, each
     thread on its own HIP stream (a frame's own chain - 56 stage forwards with a serial range decode in between - cannot
     be parallelised, but the range decoding of one frame overlaps the stage forwards and copies of the others; the
@@ -410,6 +521,18 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
         raise LinrError('this stream was coded with network arithmetic version %d; this build decodes version %d (the fp32 '
                         'accumulation order of the convolutions is part of the stream format: decode with the build that '
                         'encoded it)' % (coded_with, ARITH_VERSION))
+    stored = None
+    if verify and side.get('digests'):
+        from ._lib import LinrError
+        stream_digests.check_version(side)
+        if enc.get('digests_bin') is None:
+            raise LinrError('side_info.json says that the GOP carries digests, but there is no bins/digests.bin (decode with verify=False '
+                            'to do without)')
+        try:
+            stored = stream_digests.unpack(enc['digests_bin'], [len(f) for f in enc['frames']])
+        except ValueError as e:
+            raise LinrError(str(e)) from None
+    side.pop('digests', None)
     want = {k: side[k] for k in ('scale_num', 'block_layers', 'hidden_channel_conv') if k in side}
     have = model_shape(model_ori)
     if any(int(v) != have[k] for k, v in want.items()):
@@ -434,12 +557,13 @@ def decode_gop(model_ori, enc, device='cuda', frames=None, workers=1, timing=Non
 
     def one(i):
         xyz_low = torch.tensor(lows[i].astype(np.int32), device=device)
-        dec = decode_one_frame(model, list(enc['frames'][i]), xyz_low, chunk, per_frame, device_decoder)['dec_coord']
+        dec = decode_one_frame(model, list(enc['frames'][i]), xyz_low, chunk, per_frame, device_decoder,
+                               None if stored is None else stored[i], mins[i].tolist(), i)['dec_coord']
         return dec + torch.tensor(mins[i], device=device, dtype=torch.int32)
 
     if lockstep and lockstep > 0 and todo:
         out = _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, min(int(lockstep), LOCKSTEP_MAX_FRAMES), n_threads, chunk,
-                                   device_decoder)
+                                   device_decoder, stored)
         if timing is not None:
             timing['lockstep_ws_bytes'] = int(getattr(model, '_lockstep_ws_peak', 0))          # the largest workspace of a call
         return out
@@ -469,7 +593,7 @@ def _map_on_streams(fn, items, workers):
         return list(pool.map(job, items))
 
 
-def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads, chunk=0, device_decoder=False):
+def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep, n_threads, chunk=0, device_decoder=False, stored=None):
     n_threads = _coder_threads(n_threads)
     groups = lockstep_groups(todo, {i: len(enc['frames'][i]) for i in set(todo)}, lockstep)
     workers = max(1, min(int(workers), len(groups)))
@@ -477,7 +601,8 @@ def _decode_gop_lockstep(model, enc, lows, mins, todo, device, workers, lockstep
 
     def one(group):
         xyz_lows = [torch.tensor(lows[i].astype(np.int32), device=device) for i in group]
-        dec = decode_frames_lockstep(model, [list(enc['frames'][i]) for i in group], xyz_lows, per_group, chunk, device_decoder)
+        dec = decode_frames_lockstep(model, [list(enc['frames'][i]) for i in group], xyz_lows, per_group, chunk, device_decoder,
+                                     None if stored is None else [stored[i] for i in group], [mins[i].tolist() for i in group], group)
         return [d + torch.tensor(mins[i], device=device, dtype=torch.int32) for i, d in zip(group, dec)]
 
     return [x for out in _map_on_streams(one, groups, workers) for x in out]
@@ -494,6 +619,9 @@ def write_gop(enc, result_dir):
         f.write(enc['model_bin'])
     with open(os.path.join(bins, 'low_enc_bytes.bin'), 'wb') as f:
         f.write(enc['low_enc_bytes'])
+    if enc.get('digests_bin') is not None:
+        with open(os.path.join(bins, 'digests.bin'), 'wb') as f:
+            f.write(enc['digests_bin'])
     with open(os.path.join(result_dir, 'side_info.json'), 'w') as f:
         json.dump(enc['side_info'], f, indent=4)
 
@@ -517,4 +645,8 @@ def read_gop(result_dir):
         low = f.read()
     with open(os.path.join(result_dir, 'side_info.json')) as f:
         side = json.load(f)
-    return {'frames': frames, 'model_bin': model_bin, 'low_enc_bytes': low, 'side_info': side}
+    digests_bin = None
+    if os.path.exists(os.path.join(bins, 'digests.bin')):
+        with open(os.path.join(bins, 'digests.bin'), 'rb') as f:
+            digests_bin = f.read()
+    return {'frames': frames, 'model_bin': model_bin, 'low_enc_bytes': low, 'side_info': side, 'digests_bin': digests_bin}

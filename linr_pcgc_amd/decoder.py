@@ -16,14 +16,16 @@ from .encoder import gop_bounds
 def decode(inargs):
     """decoder.py:16-48.  inargs: 'gop_names', 'result_enc_dir', 'result_dec_dir', 'Gen_Model', 'dataset' (a MytestDataset: the
     sorted voxel list of every frame), 'write_flag'; optional 'device_decoder' (True: the range decoders run on the GPU,
-    codec.decode_gop device_decoder=)."""
+    codec.decode_gop device_decoder=), 'verify' (default True: a GOP that carries digests is checked scale by scale,
+    codec.decode_gop verify=; _lib.LinrDigestError names the frame and scale that differ)."""
     os.makedirs(inargs['result_dec_dir'], exist_ok=True)
     for gop_name in inargs['gop_names']:
         first, last = gop_bounds(gop_name)
         decode_one_gop({'gop_bound': [first, last], 'frame_num': last - first + 1, 'result_enc_dir': inargs['result_enc_dir'],
                         'result_dec_dir': inargs['result_dec_dir'], 'Gen_Model': inargs['Gen_Model'], 'gop_name': gop_name,
                         'reading_data': Read_Data_with_cache(inargs['dataset'], list(range(first, last + 1))),
-                        'write_flag': inargs['write_flag'], 'device_decoder': bool(inargs.get('device_decoder', False))})
+                        'write_flag': inargs['write_flag'], 'device_decoder': bool(inargs.get('device_decoder', False)),
+                        'verify': bool(inargs.get('verify', True))})
 
 
 def decode_one_gop(inargs):
@@ -32,6 +34,8 @@ def decode_one_gop(inargs):
     enc = codec.read_gop(os.path.join(inargs['result_enc_dir'], inargs['gop_name']))
     dev = 'cuda' if torch.cuda.is_available() else 'cpu'
     extra = {'device_decoder': True} if inargs.get('device_decoder', False) else {}
+    if not inargs.get('verify', True):
+        extra['verify'] = False
     decoded = codec.decode_gop(inargs['Gen_Model'](), enc, dev, frames=list(range(inargs['frame_num'])), workers=1, **extra)
     with PlyWriter() as writer:          # formatted on the GPU, written by the writer's thread; closed before this returns or raises
         for frame_idx, dec in enumerate(decoded):
@@ -61,16 +65,22 @@ def parser():
                          'hidden_channel_conv 8 only); the files read are the same')
     ap.add_argument('--ply-parse', '--ply_parse', dest='ply_parse', default='host', choices=['host', 'device'],
                     help='with --ori-dir: the original PLY frames are parsed by the host parser (default) or on the GPU (ply.read_points_device)')
+    ap.add_argument('--no-verify', '--no_verify', dest='verify', action='store_false',
+                    help='do not check the decoded octree levels against the digests a GOP carries (codec.decode_gop verify=False); without '
+                         'this flag a GOP encoded with --digests is checked scale by scale and the first level that differs ends the run')
     return ap
 
 
 def main(argv=None):
     """python -m linr_pcgc_amd.decoder --enc-dir OUT/result_enc --dec-dir OUT/dec [--ori-dir frames --ori-type ply --ply-parse device] [--lockstep B]
-    [--device-decoder]
+    [--device-decoder] [--no-verify]
     The decoder as its own program (decoder.py:179-200): every GOP under --enc-dir from its files alone, frames written as
     frameXXXX.ply; with --ori-dir each one is also compared with the input.  The model's shape travels in side_info.json (the
     reference hard-codes it, decoder.py:189); for streams without it the scale count is read off the stream files and width /
-    block_layers are flags."""
+    block_layers are flags.  A GOP that carries digests (run.py --digests; stream_digests.py) is verified against them while it is
+    decoded - no originals needed -; the first level that differs ends the program with a non-zero status and a message that names
+    the GOP, frame and scale.  The closing line says so when every GOP had them."""
+    from ._lib import LinrDigestError
     from .model_core import LINR_PCGC_Model
     args = parser().parse_args(argv)
     names = sorted((n for n in os.listdir(args.enc_dir) if n.startswith('gop_')), key=lambda n: gop_bounds(n)[0])
@@ -83,7 +93,9 @@ def main(argv=None):
         truth = MytestDataset(args.ori_dir, ori_type=args.ori_type, device_parse=args.ply_parse == 'device')
     dev = 'cuda' if torch.cuda.is_available() else 'cpu'
     extra = {'device_decoder': True} if args.device_decoder else {}
-    frames = 0
+    if not args.verify:
+        extra['verify'] = False
+    frames, verified = 0, 0
     with PlyWriter() as writer:          # closed - every file complete - before main returns or raises
         for name in names:
             first, last = gop_bounds(name)
@@ -93,10 +105,14 @@ def main(argv=None):
                      'hidden_channel_conv': int(side.get('hidden_channel_conv', args.hidden_channel_conv)),
                      'block_layers': int(side.get('block_layers', args.block_layers)), 'outstage': 8, 'instage': 1}
             gen = lambda: LINR_PCGC_Model(shape).to(dev)
-            if args.lockstep > 0:
-                decoded = codec.decode_gop(gen(), enc, dev, lockstep=args.lockstep, **extra)
-            else:
-                decoded = codec.decode_gop(gen(), enc, dev, workers=1 if shape['hidden_channel_conv'] != 8 else 4, **extra)
+            try:
+                if args.lockstep > 0:
+                    decoded = codec.decode_gop(gen(), enc, dev, lockstep=args.lockstep, **extra)
+                else:
+                    decoded = codec.decode_gop(gen(), enc, dev, workers=1 if shape['hidden_channel_conv'] != 8 else 4, **extra)
+            except LinrDigestError as e:
+                raise SystemExit('%s: %s' % (name, e))
+            verified += bool(args.verify and side.get('digests') and enc.get('digests_bin') is not None)
             if len(decoded) != last - first + 1:
                 raise ValueError('%s holds %d frames, its name says %d' % (name, len(decoded), last - first + 1))
             for i, dec in enumerate(decoded):
@@ -106,7 +122,8 @@ def main(argv=None):
                         raise AssertionError('frame %d does not decode to the input' % (first + i))
                 writer.submit(os.path.join(args.dec_dir, 'frame%s.ply' % str(first + i).zfill(4)), dec)
                 frames += 1
-    print('decoded %d frames of %d GOPs into %s%s' % (frames, len(names), args.dec_dir, '' if truth is None else ' (all equal to the input)'))
+    notes = ([] if truth is None else ['all equal to the input']) + (["verified against the stream's digests"] if verified == len(names) else [])
+    print('decoded %d frames of %d GOPs into %s%s' % (frames, len(names), args.dec_dir, ' (%s)' % ', '.join(notes) if notes else ''))
 
 
 if __name__ == '__main__':

@@ -14,7 +14,7 @@ import torch
 from .custom_dataset import Read_Data_with_cache
 from .model_codec import Model_Estimate
 from .test_utils import enc_all_frame_low_xyz, write_bin_file
-from . import codec
+from . import codec, stream_digests
 from .stream_chunks import SIDE_BITS, check_chunk
 
 
@@ -26,7 +26,8 @@ def gop_bounds(gop_name):
 def encode(enc_args):
     """encoder.py:20-54.  enc_args: 'outputdir' (holds <gop>/model.pth), 'gop_names', 'Gen_Model', 'dataset', 'encode_dir'; optional
     'qrange_search' (default off), 'qrange_trims', 'qrange_frames': the rate-checked quantiser range of codec.encode_gop; optional
-    'stream_chunk' (default 0 = off): its chunked stage streams."""
+    'stream_chunk' (default 0 = off): its chunked stage streams; optional 'digests' (default off): its per-scale geometry digests
+    (bins/digests.bin, stream_digests.py)."""
     os.makedirs(enc_args['encode_dir'], exist_ok=True)
     for gop_name in enc_args['gop_names']:
         first, last = gop_bounds(gop_name)
@@ -35,7 +36,7 @@ def encode(enc_args):
                         'model_path': os.path.join(enc_args['outputdir'], gop_name, 'model.pth'),
                         'result_dir': os.path.join(enc_args['encode_dir'], gop_name), 'reading_data': reading,
                         'low_enc_bytes': enc_all_frame_low_xyz(reading, last - first + 1),
-                        **{k: enc_args[k] for k in ('qrange_search', 'qrange_trims', 'qrange_frames', 'stream_chunk') if k in enc_args}})
+                        **{k: enc_args[k] for k in ('qrange_search', 'qrange_trims', 'qrange_frames', 'stream_chunk', 'digests') if k in enc_args}})
 
 
 def encode_one_frame(model, all_inargs, ori=None, stream_chunk=0):
@@ -56,7 +57,9 @@ def encode_one_frame(model, all_inargs, ori=None, stream_chunk=0):
 def encode_one_gop(inargs):
     """encoder.py:57-156.  Returns {'bpp_all', 'point_bpp', 'model_bpp', 'xyzlow_bpp'} (test_utils.py:146-157's accounting; the
     two extra side-info fields of this codec counted with the model).  inargs['stream_chunk'] = S > 0: the chunked stage streams of
-    codec.encode_gop (side_info's 'stream_chunk', 32 bits more with the model; hidden_channel_conv 8 only)."""
+    codec.encode_gop (side_info's 'stream_chunk', 32 bits more with the model; hidden_channel_conv 8 only).  inargs['digests'] true:
+    its per-scale geometry digests (codec.gop_digests_launch on the reading data: bins/digests.bin and side_info's 'digests',
+    8 * len(digests.bin) + 8 bits more with the model, returned as 'digest_bits' too)."""
     low = inargs.get('low_enc_bytes')
     if low is None:
         raise ValueError('low_enc_bytes is None')
@@ -97,6 +100,12 @@ def encode_one_gop(inargs):
     side_info.update(codec.model_shape(trained))
     if stream_chunk:
         side_info['stream_chunk'] = stream_chunk
+    digests_bin = None
+    if inargs.get('digests', False):
+        side_info['digests'] = stream_digests.VERSION
+        digests_bin = codec.gop_digests_bin(codec.gop_digests_launch([inargs['reading_data'][i] for i in range(inargs['frame_num'])]))
+        with open(os.path.join(bins_dir, 'digests.bin'), 'wb') as f:
+            f.write(digests_bin)
     if found is not None and len(found['trims']) > 1:
         side_info['qrange_trim'] = int(found['trims'][found['chosen']])
         side_info['qrange_candidates'] = len(found['trims'])
@@ -110,6 +119,7 @@ def encode_one_gop(inargs):
         write_bin_file(frame_idx, out['all_bytes'], bins_dir)
         bits += out['all_bit']
         points += frame['point_num']
-    model_bits = packed['bit_real'] + codec.EXTRA_SIDE_BITS + (SIDE_BITS if stream_chunk else 0)
-    return {'point_bpp': bits / points, 'model_bpp': model_bits / points, 'xyzlow_bpp': len(low) * 8 / points,
+    model_bits = packed['bit_real'] + codec.EXTRA_SIDE_BITS + (SIDE_BITS if stream_chunk else 0) + stream_digests.bits(digests_bin)
+    return {**({} if digests_bin is None else {'digest_bits': stream_digests.bits(digests_bin)}),
+            'point_bpp': bits / points, 'model_bpp': model_bits / points, 'xyzlow_bpp': len(low) * 8 / points,
             'bpp_all': (bits + model_bits + len(low) * 8) / points}

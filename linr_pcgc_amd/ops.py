@@ -490,6 +490,33 @@ def octree_occupancy(child, parent):
     return occ
 
 
+def coords_digest(coords, seg_off=None, origins=None, out=None):
+    """The geometry digests (include/linr_hip.h "geometry digests"; stream_digests.py) of row segments of coords (int32 [N,3] on the
+    GPU) in one library call (linr_coords_digest_segments: two launches on the current stream, no synchronisation).  seg_off: n_seg + 1
+    host offsets, segment j = rows [seg_off[j], seg_off[j + 1]) (None: one segment, all rows); origins: host int32 [n_seg][3] added to
+    the rows first (None: zeros).  Returns a device int64 [n_seg] tensor holding the 64-bit patterns of the uint64 digests
+    (.cpu().numpy().view(numpy.uint64)); out: a contiguous device int64 [n_seg] view to write them into instead."""
+    import numpy as np
+    _dev(coords, torch.int32, 'coords')
+    L = _lib.lib()
+    n = int(coords.shape[0])
+    seg = np.ascontiguousarray([0, n] if seg_off is None else seg_off, dtype=np.int64).reshape(-1)
+    n_seg = seg.size - 1
+    if n_seg >= 1 and (int(seg.max()) > n):
+        raise ValueError('seg_off reaches past the %d rows of coords' % n)
+    org = None if origins is None else np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
+    if org is not None and org.size != 3 * n_seg:
+        raise ValueError('origins must be [n_seg][3]')
+    if out is None:
+        out = torch.empty(max(n_seg, 0), dtype=torch.int64, device=coords.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != n_seg or out.device != coords.device:
+        raise ValueError('out must be a contiguous device int64 [n_seg] tensor')
+    ws, base, nbytes = _aligned_ws(L.linr_coords_digest_ws_bytes(n_seg), coords.device)
+    check(L.linr_coords_digest_segments(coords.data_ptr() if n else None, seg.ctypes.data, n_seg, None if org is None else org.ctypes.data,
+                                        out.data_ptr(), base, nbytes, _stream()), 'linr_coords_digest_segments')
+    return out
+
+
 # ---- bf16 / uint8-weight executor of the wide network (csrc/wide_bf16.hip; WideNet.forward_bf16) ----------------------------------
 def wide_bf16_prep(codes, qrange, conv_tab, n_conv, n_img, pf, img):
     """linr_wide_bf16_prep: pf = the de-quantised fp32 parameters, img = the bf16 A-operand images of the n_conv convolutions of conv_tab

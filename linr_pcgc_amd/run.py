@@ -70,6 +70,12 @@ def parse(argv=None):
                          'and -decoded independently, on the coder threads or a wave each (codec.encode_gop stream_chunk=): a few bytes per '
                          'chunk; travels as stream_chunk in side_info.json, which builds before this option cannot read; '
                          '--hidden-channel-conv 8 only')
+    ap.add_argument('--digests', action='store_true',
+                    help='make every GOP self-checking (codec.encode_gop digests=; stream_digests.py): a 32-bit digest of every octree level '
+                         'of every frame, computed on the GPU, goes into bins/digests.bin (4 bytes per frame and scale, counted in model_bpp / '
+                         'bpp_all with 8 bits for the digests field of side_info.json).  A decoder of this build checks each level as it '
+                         'decodes it and names the first frame and scale that differ; earlier builds ignore field and file.  Every other '
+                         'file is byte for byte what the run without this flag writes')
     ap.add_argument('--ply-parse', '--ply_parse', dest='ply_parse', default='host', choices=['host', 'device'],
                     help='with --input-glob / --ori_dir: PLY frames are parsed by the host parser on a thread pool (default) or on the GPU '
                          '(ply.read_many_device, on the staging stream); the encoded files are byte for byte the same')
@@ -354,6 +360,7 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                                    device_codes=getattr(args, 'device_codes', False),
                                    device_coder=getattr(args, 'device_coder', False), coder_group=getattr(args, 'coder_group', 8),
                                    **({'stream_chunk': args.stream_chunk} if getattr(args, 'stream_chunk', 0) else {}),
+                                   **({'digests': True} if getattr(args, 'digests', False) else {}),
                                    **({'qrange_search': True, 'qrange_trims': getattr(args, 'qrange_trims', None),
                                        'qrange_frames': getattr(args, 'qrange_frames', 4)} if getattr(args, 'qrange_search', False) else {}))
             res_dir = os.path.join(args.out, 'result_enc', gop_parallel.gop_name(group))
@@ -382,6 +389,8 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                 result['qat_from'] = info['qat_from']
             if 'qrange' in enc:
                 result['qrange'] = enc['qrange']
+            if 'digest_bits' in enc:
+                result['digest_bits'] = enc['digest_bits']
             if getattr(args, 'mid_test', False):
                 result['mid_test'] = half['mid']
             return result
