@@ -45,7 +45,10 @@ def _padded(t, dev):
 
 
 def _empty_padded(n, c, dev):
-    buf = torch.zeros((n + 1, c), device=dev)
+    """An output the entry writes (not accumulates): NaN rows, so that a row or channel that is never written fails instead of reading as a
+    plausible number, behind the zero row that the entry's own later launches gather (H, gM, gH)."""
+    buf = torch.full((n + 1, c), float('nan'), device=dev)
+    buf[0] = 0.0
     return buf, buf[1:]
 
 
@@ -124,7 +127,7 @@ def test_inception_layer_forward_backward(env):
     env['lib'].check(L.linr_inception_bwd_data(*args, env['lib'].LINR_RELU_MASK | env['lib'].LINR_ACCUM, _stream()), 'bwd masked')
     _close(gX, (xo.grad + old) * (x_h > 0), 1e-4, 1e-4, 'masked accumulated input gradient')
     # weight gradients of the two 4->4 convolutions (one pass) and of the rest through the plain entries
-    slab = torch.empty((512, 872), device=dev)
+    slab = torch.full((512, 872), float('nan'), device=dev)
     env['lib'].check(L.linr_spconv_wgrad_dual44(H.data_ptr(), gI.data_ptr(), 8, gM.data_ptr(), 4, env['nbr'].data_ptr(), None,
                                                 env['ld'], n, slab.data_ptr(), _stream()), 'linr_spconv_wgrad_dual44')
     tot = slab.double().sum(0).cpu()
@@ -138,7 +141,7 @@ def test_inception_layer_forward_backward(env):
     nbr4 = torch.full((27, ld4), -1, dtype=torch.int32, device=dev)
     nbr4[:, :n] = env['nbr']
     t8t = ops.kmap_tile8t(nbr4, n)
-    slab4 = torch.empty_like(slab)
+    slab4 = torch.full_like(slab, float('nan'))
     env['lib'].check(L.linr_spconv_wgrad_dual44(H.data_ptr(), gI.data_ptr(), 8, gM.data_ptr(), 4, nbr4.data_ptr(), t8t.data_ptr(),
                                                 ld4, n, slab4.data_ptr(), _stream()), 'wgrad_dual44 transposing')
     assert torch.equal(slab, slab4), 'the transposing kernel must give the same partials'
@@ -160,8 +163,8 @@ def test_head_forward_backward(env):
     d = lambda t: t.to(dev).contiguous()
     _, prior = _padded(prior_h, dev)
     occ = d(occ_h)
-    c_out = torch.empty((n, 8), device=dev)
-    p_out = torch.empty(n, device=dev)
+    c_out = torch.full((n, 8), float('nan'), device=dev)
+    p_out = torch.full((n,), float('nan'), device=dev)
     bits = torch.zeros(1, dtype=torch.float64, device=dev)
     ws = torch.empty(L.linr_head_workspace_bytes(n), dtype=torch.uint8, device=dev)
     Wd, bd, w1d, b1d, w2d, b2d = d(Wp), d(bp), d(w1), d(b1), d(w2), d(b2)
@@ -180,15 +183,15 @@ def test_head_forward_backward(env):
     _close(p_out, p_ref.view(-1), 1e-4, 1e-6, 'p')
     assert abs(float(bits) - float(bits_ref)) <= 1e-5 * float(bits_ref)
     # decoder form: no target, no bits - same probabilities, bit for bit
-    p2 = torch.empty_like(p_out)
+    p2 = torch.full_like(p_out, float('nan'))
     env['lib'].check(L.linr_head_fwd(prior.data_ptr(), env['lo'].data_ptr(), env['mask'].data_ptr(), env['ld'], n, Wd.data_ptr(),
                                      bd.data_ptr(), w1d.data_ptr(), b1d.data_ptr(), w2d.data_ptr(), b2d.data_ptr(), None, 0,
                                      c_out.data_ptr(), p2.data_ptr(), None, None, 0, _stream()), 'linr_head_fwd (decoder)')
     assert torch.equal(p_out, p2)
     gscale = 1.0 / 12345.0
     (bits_ref * gscale).backward()
-    gc = torch.empty((n, 8), device=dev)
-    ghead = torch.empty(241, device=dev)
+    gc = torch.full((n, 8), float('nan'), device=dev)
+    ghead = torch.full((241,), float('nan'), device=dev)
     env['lib'].check(L.linr_head_bwd(c_out.data_ptr(), p_out.data_ptr(), occ.data_ptr() + 4 * k, 8, w1d.data_ptr(), b1d.data_ptr(),
                                      w2d.data_ptr(), gscale, gc.data_ptr(), n, ghead.data_ptr(), ws.data_ptr(), ws.numel(),
                                      _stream()), 'linr_head_bwd')
@@ -198,7 +201,7 @@ def test_head_forward_backward(env):
     _rel_own_max(gh[192:216], b1o.grad, 'gb1')
     _rel_own_max(gh[216:240].view(1, 24), w2o.grad, 'gw2')
     _rel_own_max(gh[240:241], b2o.grad, 'gb2')
-    g2 = torch.empty_like(ghead)
+    g2 = torch.full_like(ghead, float('nan'))
     env['lib'].check(L.linr_head_bwd(c_out.data_ptr(), p_out.data_ptr(), occ.data_ptr() + 4 * k, 8, w1d.data_ptr(), b1d.data_ptr(),
                                      w2d.data_ptr(), gscale, gc.data_ptr(), n, g2.data_ptr(), ws.data_ptr(), ws.numel(),
                                      _stream()), 'linr_head_bwd again')
@@ -220,7 +223,7 @@ def test_occ_conv7_matches_seven_oracle_convs(env):
         w_off.append(cur); chunks.append(w.reshape(-1)); cur += w.numel()
         b_off.append(cur); chunks.append(b); cur += 8
     params = torch.cat(chunks).to(dev)
-    out = torch.zeros((7, n + 1, 8), device=dev)
+    out = torch.full((7, n + 1, 8), float('nan'), device=dev)
     o_off = [g * (n + 1) * 8 for g in range(7)]
     arr = lambda v: (ctypes.c_int64 * 7)(*v)
     env['lib'].check(L.linr_occ_conv7(occ.data_ptr(), env['lo'].data_ptr(), env['mask'].data_ptr(), env['ld'], n, params.data_ptr(),
@@ -247,12 +250,12 @@ def test_scale_context_forward_backward(env, golden_dir):
     off_feat = torch.cat(offs).to(dev).contiguous()
     fr = env['lib'].LinrFrame(rows=R, n_scales=3, model_scale_num=5, block_layers=2, flags=0, row_off_h=row_off.ctypes.data,
                               scale_idx_h=sidx.ctypes.data, nbr=0, nbr_ld=R, nbr_lo=0, nbr_mask=0, offset_feat=off_feat.data_ptr(), occ=0, nbr8t=0)
-    mix, hid, x0 = (torch.empty((R, c), device=dev) for c in (16, 16, 8))
+    mix, hid, x0 = (torch.full((R, c), float('nan'), device=dev) for c in (16, 16, 8))
     env['lib'].check(L.linr_sce_fwd(model.flat_parameters().data_ptr(), ctypes.byref(fr), mix.data_ptr(), hid.data_ptr(), x0.data_ptr(),
                                     _stream()), 'linr_sce_fwd')
     gx0_h = torch.randn(R, 8, generator=torch.Generator().manual_seed(2))
     gx0 = gx0_h.to(dev)
-    ghid = torch.empty((R, 16), device=dev)
+    ghid = torch.full((R, 16), float('nan'), device=dev)
     env['lib'].check(L.linr_sce_bwd(model.flat_parameters().data_ptr(), ctypes.byref(fr), gx0.data_ptr(), hid.data_ptr(), ghid.data_ptr(),
                                     _stream()), 'linr_sce_bwd')
     for j, (s, si) in enumerate(use):
@@ -267,7 +270,7 @@ def test_scale_context_forward_backward(env, golden_dir):
         assert torch.equal(mix[a:b, 8:15].cpu(), offs[j]) and bool((mix[a:b, 15] == 0).all())
     # the complete backward (linr_sce_bwd_params): gradients of scale_emb and the three scales' MLPs against autograd, zeros for the
     # scales the frame does not contain; mix is optional in the forward
-    hid2, x02 = torch.empty_like(hid), torch.empty_like(x0)
+    hid2, x02 = torch.full_like(hid, float('nan')), torch.full_like(x0, float('nan'))
     env['lib'].check(L.linr_sce_fwd(model.flat_parameters().data_ptr(), ctypes.byref(fr), None, hid2.data_ptr(), x02.data_ptr(), _stream()),
                      'linr_sce_fwd')
     assert torch.equal(hid2, hid) and torch.equal(x02, x0)

@@ -1,5 +1,8 @@
 """GPU parity of the single operators through the C-ABI against the CPU oracle: kernel map, octree occupancy, conv3 forward /
 backward (gather and compressed-map MFMA forms), pointwise layers, BCE bits, Adam.  Tolerances: tests/gpu_common.py.
+Outputs that an entry writes (not accumulates) start as NaN, so that a row or channel that is never written fails.
+linr_slab_reduce (the fixed-order sum of the weight-gradient entries' per-block partials) runs here inside ops.spconv_wgrad_cmap; its own
+test against float64 - odd and 512 slab rows, either destination NULL, LINR_ACCUM - is tests/test_gpu_conv8_ops.py::_check_reduce.
 """
 import math
 import os
@@ -111,11 +114,12 @@ def test_spconv_fwd_bwd(pkg, shell, cin, cout, pad):
         return buf[1:]
     xd = padded(x) if pad else x.to(dev)
     god = padded(go) if pad else go.to(dev)
-    out = ops.spconv_fwd(xd, nbr, w.to(dev), b.to(dev), res=res.to(dev), relu=True, pad_row=pad)
+    nan = lambda c: torch.full((n, c), float('nan'), device=dev)          # written, not accumulated: a row never written fails
+    out = ops.spconv_fwd(xd, nbr, w.to(dev), b.to(dev), res=res.to(dev), relu=True, pad_row=pad, out=nan(cout))
     _close(out, ref, 1e-4, 1e-4, 'fwd')
-    out2 = ops.spconv_fwd(xd, nbr, w.to(dev), b.to(dev), pad_row=pad)
-    assert torch.equal(out2, ops.spconv_fwd(xd, nbr, w.to(dev), b.to(dev), pad_row=pad)), 'fwd must be bit-reproducible'
-    gin = ops.spconv_bwd_data(god, nbr, w.to(dev), pad_row=pad)
+    out2 = ops.spconv_fwd(xd, nbr, w.to(dev), b.to(dev), pad_row=pad, out=nan(cout))
+    assert torch.equal(out2, ops.spconv_fwd(xd, nbr, w.to(dev), b.to(dev), pad_row=pad, out=nan(cout))), 'fwd must be bit-reproducible'
+    gin = ops.spconv_bwd_data(god, nbr, w.to(dev), pad_row=pad, out=nan(cin))
     _close(gin, xo.grad, 1e-4, 1e-4, 'bwd_data')
     gw, gb = ops.spconv_bwd_weight(xd, god, nbr, cin, cout, pad_row=pad)
     scale = float(wo.grad.abs().max())
@@ -137,7 +141,8 @@ def test_spconv_pad_equals_branch_bitwise(pkg, shell):
     nbr = ops.kmap_build(torch.from_numpy(sc['coord']).to(dev))
     buf = torch.zeros((n + 1, 8), device=dev)
     buf[1:] = x.to(dev)
-    assert torch.equal(ops.spconv_fwd(buf[1:], nbr, w, b, pad_row=True), ops.spconv_fwd(x.to(dev), nbr, w, b))
+    nan = lambda: torch.full((n, 8), float('nan'), device=dev)
+    assert torch.equal(ops.spconv_fwd(buf[1:], nbr, w, b, pad_row=True, out=nan()), ops.spconv_fwd(x.to(dev), nbr, w, b, out=nan()))
 
 
 def test_spconv_channel_slices(pkg, shell):
@@ -228,26 +233,22 @@ def test_cmap_mfma_conv_bit_identical_to_gather_kernel(pkg, shell, cin, cout):
     nbr = ops.kmap_build(torch.from_numpy(sc['coord']).to(dev))
     lo, mask = ops.kmap_compress(nbr)
     # the compressed map must decode to the same table
-    dec = torch.full_like(nbr, -1)
-    for q in range(9):
-        b0, b1, b2 = (mask >> (3 * q)) & 1, (mask >> (3 * q + 1)) & 1, (mask >> (3 * q + 2)) & 1
-        dec[q] = torch.where(b0 == 1, lo[q], dec[q])
-        dec[q + 9] = torch.where(b1 == 1, lo[q] + b0, dec[q + 9])
-        dec[q + 18] = torch.where(b2 == 1, lo[q] + b0 + b1, dec[q + 18])
-    assert torch.equal(dec, nbr)
+    from conv8_ref import decode_cmap
+    assert torch.equal(decode_cmap(lo, mask), nbr)
     ld_in = 8
     xb = torch.zeros((n + 1, ld_in), device=dev)
     xb[1:, :cin] = torch.randn(n, cin, generator=g).to(dev)
     w = (torch.randn(27, cin, cout, generator=g) * 0.2).to(dev)
     b = torch.randn(cout, generator=g).to(dev)
-    ref = ops.spconv_fwd(xb[1:], nbr, w, b.view(1, -1), relu=True, pad_row=True)
-    got = ops.spconv_cmap(xb[1:], lo, mask, n, w, b, relu=True)
+    nan = lambda c: torch.full((n, c), float('nan'), device=dev)          # torch.equal is False on a NaN: every entry must be written
+    ref = ops.spconv_fwd(xb[1:], nbr, w, b.view(1, -1), relu=True, pad_row=True, out=nan(cout))
+    got = ops.spconv_cmap(xb[1:], lo, mask, n, w, b, relu=True, out=nan(cout))
     assert torch.equal(ref, got)
     if cin in (4, 8):                       # backward-data: gathered width cout, produced width cin
         gb = torch.zeros((n + 1, 8), device=dev)
         gb[1:, :cout] = torch.randn(n, cout, generator=g).to(dev)
-        ref_b = ops.spconv_bwd_data(gb[1:], nbr, w, pad_row=True)
-        got_b = ops.spconv_cmap(gb[1:], lo, mask, n, w, None, bwd=True)
+        ref_b = ops.spconv_bwd_data(gb[1:], nbr, w, pad_row=True, out=nan(cin))
+        got_b = ops.spconv_cmap(gb[1:], lo, mask, n, w, None, bwd=True, out=nan(cin))
         assert torch.equal(ref_b, got_b)
 
 
