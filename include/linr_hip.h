@@ -701,6 +701,38 @@ LINR_API int linr_overfit_plan(const linr_frame* const* frames_h, int32_t n_fram
 LINR_API size_t linr_overfit_ws_bytes(int64_t n_params, int32_t n_frames, int32_t epochs);
 LINR_API int linr_overfit_gop(const linr_overfit_frame* frames, const linr_overfit_args* args, linr_overfit_result* result, void* stream);
 
+/* ---- averaged weights (opt-in; csrc/params_avg.hip, csrc/params_avg_host.cpp) ----------------------------------------------------
+ * What is coded after an overfit is the LAST iterate of an optimiser that still takes steps about one quantiser step wide.  These
+ * entries keep K exponential averages of the iterates beside the training, so that the encoder may code one of them instead - where a
+ * measured rate says so (codec.search_average); a decoder de-quantises whatever vector model.bin holds.
+ *
+ * linr_params_average: one update of all K averages,  avg[k][i] = fma(w_k, params[i] - avg[k][i], avg[k][i])  for i < n: the
+ *   difference rounded to fp32 on its own, then one fused multiply-add - an exponential average with decay d_k = 1 - (double)w_k.
+ *   Started from zero and updated T times, avg[k] * (1 / (1 - d_k^T)) is the debiased average (formed by the caller: one multiply per
+ *   element, not hot).  params: device [n] floats, 16-byte aligned, read ONCE for all rows; weights_h: HOST [K] floats, each in
+ *   (0, 1], K in 1..4, they travel as a kernel argument; avg: device [K][stride] floats, 16-byte aligned, stride >= n and a multiple
+ *   of 4 (the elements behind n are not touched).  ONE launch, 16-byte accesses and a scalar tail, no atomics, no host
+ *   synchronisation, no state in the library; profiler / poison class 12.  NaN and inf in params propagate into every row.
+ *   n == 0 launches nothing.  Refused before the launch: n < 0, K, a NULL weights_h, a weight outside (0, 1] or NaN, stride, a NULL
+ *   params / avg (LINR_EINVAL, in this order), then alignment (LINR_EALIGN).
+ * linr_params_average_host: the same as a plain loop over HOST pointers (std::fmaf; no GPU needed, no alignment asked) - the
+ *   definition of the arithmetic.
+ * linr_overfit_gop_avg: linr_overfit_gop with the averaging launch queued behind EVERY training step (all executors: it reads
+ *   args->params, the fp32 master).  avg->avg: device [n_avg][stride]; the first n_params floats of every row are zeroed by the
+ *   call, so after it row k holds the average of all epochs * n_frames iterates (whatever epoch is kept).  avg is checked as
+ *   linr_params_average checks its arguments, behind every check of linr_overfit_gop and in front of the first launch.  Training is
+ *   untouched: parameters, moments, losses and `result` are those of linr_overfit_gop.  avg == NULL: linr_overfit_gop to the letter. */
+typedef struct linr_overfit_avg {
+    int32_t n_avg;                  /* 1..4 */
+    float weight[4];                /* w_k = 1 - decay_k, each in (0, 1]; the first n_avg are read */
+    float* avg;                     /* device [n_avg][stride], 16-byte aligned */
+    int64_t stride;                 /* >= n_params, a multiple of 4 */
+} linr_overfit_avg;
+LINR_API int linr_params_average(const float* params, int64_t n, const float* weights_h, int32_t K, int64_t stride, float* avg, void* stream);
+LINR_API int linr_params_average_host(const float* params_h, int64_t n, const float* weights_h, int32_t K, int64_t stride, float* avg_h);
+LINR_API int linr_overfit_gop_avg(const linr_overfit_frame* frames, const linr_overfit_args* args, const linr_overfit_avg* avg,
+                                  linr_overfit_result* result, void* stream);
+
 /* Staged DECODE of one frame object (decoder.decode_one_frame, decoder.py:153-176 + CNP.decode, models/upsample.py:249-295) as
  * ONE call: for stage k = 0..7 { linr_net_forward[_bf16](k, k+1); probabilities of the stage -> pinned host buffer; the range
  * decoder on every scale's stream k (linr_ac_decode_binary, host); decoded symbols -> column k of f->occ } - the loop the

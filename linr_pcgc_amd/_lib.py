@@ -86,7 +86,13 @@ class LinrOverfitResult(ctypes.Structure):
                 ('scale_steps_h', c_ptr)]
 
 
+class LinrOverfitAvg(ctypes.Structure):
+    """struct linr_overfit_avg (include/linr_hip.h): the averages linr_overfit_gop_avg keeps beside the training."""
+    _fields_ = [('n_avg', c_i32), ('weight', c_f32 * 4), ('avg', c_ptr), ('stride', c_i64)]
+
+
 LINR_OVERFIT_F32, LINR_OVERFIT_BF16, LINR_OVERFIT_WIDE = 0, 1, 2
+LINR_AVG_MAX = 4            # rows of linr_params_average / linr_overfit_avg
 
 _PROTOS = {
     'linr_abi_version': (ctypes.c_int, []),
@@ -264,6 +270,10 @@ _PROTOS = {
     'linr_overfit_ws_bytes': (c_size, [c_i64, c_i32, c_i32]),
     'linr_overfit_gop': (ctypes.c_int, [ctypes.POINTER(LinrOverfitFrame), ctypes.POINTER(LinrOverfitArgs), ctypes.POINTER(LinrOverfitResult),
                                         c_ptr]),
+    'linr_params_average': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr, c_ptr]),
+    'linr_params_average_host': (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr]),
+    'linr_overfit_gop_avg': (ctypes.c_int, [ctypes.POINTER(LinrOverfitFrame), ctypes.POINTER(LinrOverfitArgs), ctypes.POINTER(LinrOverfitAvg),
+                                            ctypes.POINTER(LinrOverfitResult), c_ptr]),
     'linr_coords_digest_ws_bytes': (c_size, [c_i32]),
     'linr_coords_digest_segments': (ctypes.c_int, [c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     'linr_coords_digest_host': (ctypes.c_uint64, [c_ptr, c_i64, c_ptr]),
@@ -314,7 +324,7 @@ class _Poisoned:
     CUs freshly filled with a NaN pattern (linr_debug_poison_now in front of it, linr_debug_poison(all classes) for the launches
     inside the executors).  The test suite must pass unchanged under it: no kernel may read on-chip state it did not write."""
     _HOST = ('linr_ac_', 'linr_stream_', 'linr_prof_', 'linr_debug_', 'linr_abi_version', 'linr_params_fake_quant_host',
-             'linr_params_fake_quant_ranges_host', 'linr_overfit_plan', 'linr_coords_digest_host')
+             'linr_params_fake_quant_ranges_host', 'linr_overfit_plan', 'linr_coords_digest_host', 'linr_params_average_host')
 
     def __init__(self, handle):
         self._h = handle

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .function_utils import pack_bitstream, unpack_bitstream
-from .model_codec import Model_Estimate, candidate_ranges, laplace_bits_est
+from .model_codec import Model_Estimate, candidate_ranges, compress_params, laplace_bits_est
 from .model_core import DeviceCoderSet, codes_word_off, encode_streams, encode_streams_codes
 from .module_utils import octree_level_obj, qscTensor, unique_sorted  # noqa: F401
 from . import stream_digests
@@ -182,7 +182,7 @@ def gop_digests_bin(launched):
     return stream_digests.pack([[next(it) for _ in range(n)] for n in n_scales])
 
 
-def _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found=None, digests=None):
+def _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found=None, digests=None, averaged=None):
     bits_est = float(torch.stack(bits_dev).sum())
     low = enc_all_frame_low_xyz(gop)
     points = sum(gop.point_nums)
@@ -191,6 +191,8 @@ def _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found=None, digest
     side_bits = EXTRA_SIDE_BITS + (STREAM_CHUNK_SIDE_BITS if side_info.get('stream_chunk') else 0)
     extra = {} if found is None else {'qrange': {'trims': found['trims'], 'objective_bits': found['objective_bits'],
                                                  'chosen': found['trims'][found['chosen']], 'search_s': found['search_s']}}
+    if averaged is not None:
+        extra['average'] = averaged
     if digests is not None:
         # ... and the digests, when the GOP has them: their file and the one-byte field (stream_digests.bits)
         digests_bin = gop_digests_bin(digests)
@@ -223,7 +225,76 @@ def qrange_eval_frames(n_frames, want):
     return [(2 * i + 1) * n_frames // (2 * want) for i in range(want)]
 
 
-def search_qrange(model, model_ori, gop, bitdepth=8, precision='f32', trims=None, eval_frames=4, frame_bits=None):
+def _quantise_own_range(vec, lo, hi, bitdepth, with_codes):
+    """One vector under the given range through linr_params_fake_quant_ranges (a device vector) or its host twin (a CPU vector: the
+    search on stub frames, no GPU needed) -> (de-quantised [n], codes as a host array or None, sum |q - mu|)."""
+    from . import _lib, engine
+    n = vec.numel()
+    if vec.is_cuda:
+        q, codes, stats = engine.params_fake_quant_ranges(vec, [(lo, hi)], bitdepth, codes=with_codes)
+        return q[0, :n], codes.cpu().numpy()[0, :n] if with_codes else None, stats
+    p = np.ascontiguousarray(vec.detach().numpy(), dtype=np.float32)
+    stride = (n + 3) & ~3
+    r = np.asarray([lo, hi], dtype=np.float32)
+    q, c, st = np.empty((1, stride), np.float32), np.empty((1, stride), np.uint16), np.empty((1, 4), np.int64)
+    _lib.check(_lib.lib().linr_params_fake_quant_ranges_host(p.ctypes.data, n, int(bitdepth), r.ctypes.data, 1, stride, q.ctypes.data,
+                                                             c.ctypes.data, st.ctypes.data), 'linr_params_fake_quant_ranges_host')
+    return torch.from_numpy(q[0, :n].copy()), c[0, :n] if with_codes else None, torch.from_numpy(st)
+
+
+def search_average(model, model_ori, gop, candidates, decays, bitdepth=8, precision='f32', eval_frames=4, frame_bits=None):
+    """The encoder's rate-checked choice between the model's own parameters and averages of the overfit's iterates (encode_gop avg=).
+    Adam's steps stay about one quantiser step wide to the end of an overfit, so the last iterate is a noisy one; an average of the
+    iterates (overfit_gop avg_decays=) may code cheaper - or not, so it is measured, like the quantiser range (search_qrange).
+    Candidate 0 is model.flat_parameters() (today's call), candidates 1..K the rows of `candidates` ([K][n], on the model's device)
+    with the decays `decays`.  Each is quantised under its OWN (min, max) - one small host read of the K + 1 pairs, then
+    linr_params_fake_quant_ranges per vector, whose integer stats give model_codec.laplace_bits_est -, filled into `model_ori` through
+    Model_Estimate._fill and asked for its bits on the evaluated frames (qrange_eval_frames) by the codec's own forward.  Objective:
+        model_bits_est_j + (frames / evaluated frames) * sum of the evaluated frames' bits
+    The smallest wins, a tie goes to the smaller index, so on the frames it evaluates the choice is never worse than the plain model.
+    A candidate with a non-finite element is never evaluated and never wins (its objective is None).  On the caller's stream, no draw
+    from torch's generator.  gop / frame_bits: as in search_qrange.  Returns {'decays' (K), 'objective_bits' (K + 1, plain first),
+    'chosen' (an index into the candidates: 0 = plain, j = decays[j - 1]), 'frames', 'search_s'}; `model_ori` is left filled with the
+    last evaluated candidate."""
+    import time
+    t0 = time.time()
+    flat = model.flat_parameters().detach()
+    n = flat.numel()
+    decays = [float(d) for d in decays]
+    cands = torch.as_tensor(candidates).detach()
+    if cands.dim() != 2 or cands.shape[0] != len(decays) or cands.shape[1] != n or cands.dtype != torch.float32 or cands.device != flat.device:
+        raise ValueError('search_average: %d decays need float32 candidates [%d][%d] on %s, got %s %s on %s'
+                         % (len(decays), len(decays), n, flat.device, cands.dtype, tuple(cands.shape), cands.device))
+    vecs = [flat] + [cands[k].contiguous() for k in range(len(decays))]
+    pairs = torch.stack([torch.stack([v.min(), v.max()]) for v in vecs]).cpu().tolist()          # NaN and inf show here
+    with_codes = bitdepth == 8
+    frames = gop.frames if frame_bits is None else gop
+    if frame_bits is None:
+        frame_bits = lambda cand, i: cand.frame_probs(frames[i])[1]
+    todo = qrange_eval_frames(len(frames), eval_frames)
+    bits, stats, evaluated = [], [], []
+    for j, (v, (lo, hi)) in enumerate(zip(vecs, pairs)):
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            continue
+        q, codes_h, st = _quantise_own_range(v, lo, hi, bitdepth, with_codes)
+        cand = Model_Estimate._fill(model_ori, q, codes_h, lo, hi, bitdepth)
+        cand.inference_precision = precision
+        bits.append(torch.stack([frame_bits(cand, i) for i in todo]).sum())
+        stats.append(st)
+        evaluated.append(j)
+    objective = [None] * len(vecs)
+    if evaluated:
+        bits = torch.stack(bits).cpu().tolist()
+        stats = torch.cat(stats).cpu().tolist()
+        up = len(frames) / len(todo)
+        for j, st, b in zip(evaluated, stats, bits):
+            objective[j] = laplace_bits_est(n, st[3], bitdepth) + up * b
+    finite = [j for j in evaluated if np.isfinite(objective[j])]
+    chosen = min(finite, key=lambda j: (objective[j], j)) if finite else 0
+    return {'decays': decays, 'objective_bits': objective, 'chosen': chosen, 'frames': todo, 'search_s': time.time() - t0}
+
+
+def search_qrange(model, model_ori, gop, bitdepth=8, precision='f32', trims=None, eval_frames=4, frame_bits=None, flat=None):
     """The encoder's rate-checked quantiser range (encode_gop qrange_search=True).  The model codec quantises with ONE step for the
     whole parameter vector, (max - min) / (2^bitdepth - 1), so a single outlier weight widens it for every other weight.  A decoder
     reads the range from side_info.json (min_param / max_param) and never checks that it is the vector's own, so the encoder may
@@ -238,11 +309,12 @@ def search_qrange(model, model_ori, gop, bitdepth=8, precision='f32', trims=None
     gop: an overfit.Gop, or - with frame_bits(candidate model, i) -> device float64[1], the bits of frame i - any sequence of frames
     (encoder.encode_one_gop's per-scale inputs).  Returns
     {'trims', 'ranges', 'objective_bits', 'chosen' (an index into trims), 'frames', 'search_s'}; `model_ori` is left filled with
-    the last candidate."""
+    the last candidate.  flat (None: model.flat_parameters()): the vector to search the range of instead - the average that
+    search_average chose."""
     import time
     from . import engine
     t0 = time.time()
-    flat = model.flat_parameters().detach()
+    flat = (model.flat_parameters() if flat is None else flat).detach()
     kept, ranges = candidate_ranges(flat.to('cpu', torch.float32), trims)
     with_codes = bitdepth == 8                               # what _fill hands to the executors that run from codes
     q, codes, stats = engine.params_fake_quant_ranges(flat, ranges, bitdepth, codes=with_codes)
@@ -266,7 +338,7 @@ def search_qrange(model, model_ori, gop, bitdepth=8, precision='f32', trims=None
 
 
 def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32', device_codes=False, device_coder=False,
-               coder_group=8, qrange_search=False, qrange_trims=None, qrange_frames=4, stream_chunk=0, digests=False):
+               coder_group=8, qrange_search=False, qrange_trims=None, qrange_frames=4, stream_chunk=0, digests=False, avg=None, avg_frames=4):
     """encoder.encode_one_gop: quantise the model, then per frame ONE forward over all scales and 8 x scales
     independent arithmetic-coded streams (thread pool).  precision='bf16': the forward runs on the bf16 / uint8-weight
     executor (BASELINE config[4]); the choice is recorded in side_info so that the decoder reproduces it.
@@ -290,17 +362,34 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     frame is computed on the GPU where the staged levels are (gop_digests_launch: two library calls per frame on the caller's stream,
     ONE host read per GOP, no draw from torch's generator) and returned as 'digests_bin' (write_gop: bins/digests.bin); side_info gets
     'digests' = 1, and 8 * len(digests_bin) + 8 bits are counted in model_bpp / bpp_all and reported as 'digest_bits'.  Every stream
-    and every other file is what digests=False writes; decode_gop checks each level as it decodes it."""
+    and every other file is what digests=False writes; decode_gop checks each level as it decodes it.
+    avg = overfit_gop's info['averages'] (opt-in; {'decays', 'steps', 'params' [K][n]}): search_average chooses by measured rate, on
+    avg_frames evaluated frames (0: all), between the model's own parameters and the K averages of the overfit's iterates.  A chosen
+    average goes through compress_params / _fill into `model_ori` - the training model, its optimiser and hence the checkpoint and the
+    next GOP's warm start are only read - and with qrange_search the range search then runs on it.  When the model's own parameters
+    win, every file but side_info.json's informational fields is byte for byte the plain run's.  side_info gains 'avg_decay' (the
+    chosen decay, null: the model's own) and 'avg_candidates' (not counted, ignored by the decoders), the result
+    'average' = {'decays', 'objective_bits', 'chosen', 'frames', 'search_s'}."""
     if device_coder and not 1 <= int(coder_group) <= 64:
         raise ValueError('coder_group must be in 1..64, got %r' % (coder_group,))
     stream_chunk = check_chunk(stream_chunk)
     if stream_chunk and getattr(model, '_wide', None) is not None:
         raise ValueError('stream_chunk needs hidden_channel_conv 8: the widths 16 and 32 decode stage-wise in Python, without chunks')
     n_threads = _coder_threads(n_threads)
-    found = search_qrange(model, model_ori, gop, bitdepth, precision, qrange_trims, qrange_frames) if qrange_search else None
+    averaged, avg_vec = None, None
+    if avg is not None and len(avg['decays']):
+        averaged = search_average(model, model_ori, gop, avg['params'], avg['decays'], bitdepth, precision, avg_frames)
+        if averaged['chosen']:                           # (0: the model's own parameters - everything below is today's call)
+            avg_vec = avg['params'][averaged['chosen'] - 1].detach().contiguous()
+    found = search_qrange(model, model_ori, gop, bitdepth, precision, qrange_trims, qrange_frames, flat=avg_vec) if qrange_search else None
     # trim 0 is the vector's own (min, max): today's call, to the letter
     qrange = found['ranges'][found['chosen']] if found is not None and found['chosen'] else None
-    comp = Model_Estimate().compress_model(model, bitdepth, True, model_ori, **({} if qrange is None else {'qrange': qrange}))
+    if avg_vec is None:
+        comp = Model_Estimate().compress_model(model, bitdepth, True, model_ori, **({} if qrange is None else {'qrange': qrange}))
+    else:
+        # the chosen average through the same model codec into the shell; the training model is only read
+        comp = compress_params(avg_vec, bitdepth, qrange)
+        comp['new_model'] = Model_Estimate._fill(model_ori, comp['recon_ret'], comp['symbols'], comp['min_param'], comp['max_param'], bitdepth)
     coded_model = comp['new_model']                      # the de-quantised model is what codes the geometry
     coded_model.inference_precision = precision
     side_info = {'mu': comp['mu'], 'b': comp['b'], 'min_param': comp['min_param'], 'max_param': comp['max_param'],
@@ -326,9 +415,14 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
     if found is not None and len(found['trims']) > 1:
         side_info['qrange_trim'] = int(found['trims'][found['chosen']])
         side_info['qrange_candidates'] = len(found['trims'])
+    # ... and which average of the iterates was coded (null: the model's own parameters) among how many candidates: not counted,
+    # ignored by the decoders (model.bin holds the vector)
+    if averaged is not None:
+        side_info['avg_decay'] = averaged['decays'][averaged['chosen'] - 1] if averaged['chosen'] else None
+        side_info['avg_candidates'] = len(averaged['decays']) + 1
     if device_coder:
         frames_bytes, bits_dev = _code_frames_device(coded_model, gop, int(coder_group), stream_chunk)
-        return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found, launched)
+        return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found, launched, averaged)
     # Pipeline: the GPU forward + D2H of frame i+1 runs while host workers range-code earlier frames (the coder's C call
     # releases the GIL).  A frame has 8 x scales independent streams, but the 8 streams of its finest scale carry 73 % of the
     # symbols, so one frame keeps only ~8 threads busy: TWO frames are coded concurrently, each on half of the threads
@@ -400,7 +494,7 @@ def encode_gop(model, model_ori, gop, bitdepth=8, n_threads=None, precision='f32
         while pending:
             hand_over(pending.pop(0), coder)
         frames_bytes = [j.result() for j in jobs]
-    return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found, launched)
+    return _gop_result(gop, comp, side_info, frames_bytes, bits_dev, found, launched, averaged)
 
 
 def decode_one_frame(model, frame_enc_bytes, xyz_low, chunk=0, n_threads=1, device_decoder=False, digests=None, origin=None, frame=0):

@@ -6,8 +6,8 @@ OUT=../liblinr_hip.so
 mkdir -p _obj
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -fvisibility=hidden -Wall"
 # the ONE list of sources: compiled below, linked in this order
-HIP="kmap spconv linear loss_optim prof bwd_tail net fused wgrad fused_bwd occ_wgrad net_bf16 train_bf16 decode octree wide wide_mul wide_bf16 wide_fwd wide_train ac_codes ac_device ac_device_dec ply_format ply_parse fake_quant overfit digest"
-CPP="ac ply digest_host"
+HIP="kmap spconv linear loss_optim prof bwd_tail net fused wgrad fused_bwd occ_wgrad net_bf16 train_bf16 decode octree wide wide_mul wide_bf16 wide_fwd wide_train ac_codes ac_device ac_device_dec ply_format ply_parse fake_quant params_avg overfit digest"
+CPP="ac ply digest_host params_avg_host"
 # stale <name> <dependencies>: the object is missing or older than one of them
 stale() {
   [ ! -f _obj/$1.o ] && return 0

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "layout.h"
 #include "bwd_tail.h"
+#include "params_avg.h"
 #include "prof.h"
 #include <math.h>
 #include <string.h>
@@ -198,7 +199,9 @@ extern "C" size_t linr_overfit_ws_bytes(int64_t n_params, int32_t n_frames, int3
     return make_ws(n_params, n_frames, epochs).total;
 }
 
-extern "C" int linr_overfit_gop(const linr_overfit_frame* frames, const linr_overfit_args* args, linr_overfit_result* result, void* stream) {
+// linr_overfit_gop (avg == NULL: to the letter) and linr_overfit_gop_avg (the averaging launch behind every step)
+static int overfit_core(const linr_overfit_frame* frames, const linr_overfit_args* args, const linr_overfit_avg* avg,
+                        linr_overfit_result* result, void* stream) {
     // ---- every check in front of the first launch ----
     if (!frames || !args || !result) return LINR_EINVAL;
     const linr_overfit_args& a = *args;
@@ -238,6 +241,10 @@ extern "C" int linr_overfit_gop(const linr_overfit_frame* frames, const linr_ove
     if (!linr_aligned16(a.params) || !linr_aligned16(a.exp_avg) || !linr_aligned16(a.exp_avg_sq) || !linr_aligned16(a.ws)) return LINR_EALIGN;
     const OvWs w = make_ws(n_params, a.n_frames, a.epochs);
     if (a.ws_bytes < w.total) return LINR_ENOSPC;
+    if (avg) {
+        int rc = linr_params_average_check(a.params, n_params, avg->weight, avg->n_avg, avg->stride, avg->avg);
+        if (rc < 0) return rc;
+    }
 
     // the schedule
     const int64_t n_steps = (int64_t)a.epochs * a.n_frames;
@@ -283,11 +290,16 @@ extern "C" int linr_overfit_gop(const linr_overfit_frame* frames, const linr_ove
         overfit_init_k<<<1, 64, 0, s>>>(bits, pn, base, count, p, base == 0 ? st : nullptr);
     }
     TRY(linr_launch_rc());
+    if (avg)          // the averages start from zero; what lies behind n_params in a row is left alone
+        for (int k = 0; k < avg->n_avg; ++k) TRY(linr_hip_rc(hipMemsetAsync(avg->avg + k * avg->stride, 0, 4 * (size_t)n_params, s)));
     const OvCopy save = {{a.params, a.exp_avg, a.exp_avg_sq}, {snap, snap + w.np4, snap + 2 * w.np4}};
     const OvCopy restore = {{snap, snap + w.np4, snap + 2 * w.np4}, {a.params, a.exp_avg, a.exp_avg_sq}};
     const bool qat = a.qat_from < a.epochs;
     for (int e = 0; e < a.epochs; ++e) {
-        for (int j = 0; j < a.n_frames; ++j) TRY(run_step(a, frames[j], step_args(e, j), stream, false));
+        for (int j = 0; j < a.n_frames; ++j) {
+            TRY(run_step(a, frames[j], step_args(e, j), stream, false));
+            if (avg) TRY(linr_params_average_launch(a.params, n_params, avg->weight, avg->n_avg, avg->stride, avg->avg, s));
+        }
         {
             ProfScope ps(s, PK_MISC, 0);
             params_finite_k<<<flat_grid(n_params), LINR_BLOCK, 0, s>>>(a.params, n_params, &st->finite);
@@ -325,4 +337,13 @@ extern "C" int linr_overfit_gop(const linr_overfit_frame* frames, const linr_ove
         if (result->scale_steps_h) for (int k = 0; k < S; ++k) result->scale_steps_h[k] = last.scale[k];
     }
     return 0;
+}
+
+extern "C" int linr_overfit_gop(const linr_overfit_frame* frames, const linr_overfit_args* args, linr_overfit_result* result, void* stream) {
+    return overfit_core(frames, args, nullptr, result, stream);
+}
+
+extern "C" int linr_overfit_gop_avg(const linr_overfit_frame* frames, const linr_overfit_args* args, const linr_overfit_avg* avg,
+                                    linr_overfit_result* result, void* stream) {
+    return overfit_core(frames, args, avg, result, stream);
 }

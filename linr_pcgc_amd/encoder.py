@@ -27,7 +27,8 @@ def encode(enc_args):
     """encoder.py:20-54.  enc_args: 'outputdir' (holds <gop>/model.pth), 'gop_names', 'Gen_Model', 'dataset', 'encode_dir'; optional
     'qrange_search' (default off), 'qrange_trims', 'qrange_frames': the rate-checked quantiser range of codec.encode_gop; optional
     'stream_chunk' (default 0 = off): its chunked stage streams; optional 'digests' (default off): its per-scale geometry digests
-    (bins/digests.bin, stream_digests.py)."""
+    (bins/digests.bin, stream_digests.py).  The averaged weights of codec.encode_gop(avg=) are not offered here: a checkpoint carries
+    the kept epoch's parameters and no averages of the iterates, so this road always codes the model's own parameters."""
     os.makedirs(enc_args['encode_dir'], exist_ok=True)
     for gop_name in enc_args['gop_names']:
         first, last = gop_bounds(gop_name)

@@ -258,6 +258,33 @@ def params_fake_quant_ranges(flat, ranges, bitdepth=8, codes=True):
     return q, c, st
 
 
+def params_average(flat, weights, avg):
+    """linr_params_average: one update of the K exponential averages `avg` (device float32 [K, stride], stride >= n and a multiple of
+    4, updated in place) with the flat parameter vector `flat` (device float32 [n]):  avg[k] = fma(w_k, flat - avg[k], avg[k])  with
+    weights [K] in (0, 1], K <= 4.  One launch on the current stream, nothing synchronises with the host."""
+    if not flat.is_cuda or not avg.is_cuda:
+        raise _lib.LinrError('params_average: the parameters and the averages must be on the GPU')
+    if avg.dtype != torch.float32 or flat.dtype != torch.float32 or avg.dim() != 2 or not avg.is_contiguous() or not flat.is_contiguous():
+        raise ValueError('params_average: flat float32 [n] and avg float32 [K, stride], both contiguous')
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if w.size != avg.shape[0]:
+        raise ValueError('params_average: %d weights for %d rows' % (w.size, avg.shape[0]))
+    check(_lib.lib().linr_params_average(flat.data_ptr(), flat.numel(), w.ctypes.data, int(w.size), int(avg.shape[1]), avg.data_ptr(),
+                                         _stream()), 'linr_params_average')
+
+
+def params_average_host(flat, weights, avg):
+    """linr_params_average_host: the same update on HOST arrays (flat float32 [n], avg float32 [K, stride] C-contiguous, updated in
+    place); no GPU needed."""
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if flat.dtype != np.float32 or avg.dtype != np.float32 or avg.ndim != 2 or not avg.flags.c_contiguous or not flat.flags.c_contiguous:
+        raise ValueError('params_average_host: flat float32 [n] and avg float32 [K, stride], both C-contiguous')
+    if w.size != avg.shape[0]:
+        raise ValueError('params_average_host: %d weights for %d rows' % (w.size, avg.shape[0]))
+    check(_lib.lib().linr_params_average_host(flat.ctypes.data, flat.size, w.ctypes.data, int(w.size), int(avg.shape[1]), avg.ctypes.data),
+          'linr_params_average_host')
+
+
 def _step_args(exp_avg, exp_avg_sq, gscale, step, lr, beta1, beta2, eps, weight_decay, bits, scale_steps, qparams, bitdepth):
     """The linr_step_args of one training step, by field name."""
     return _lib.LinrStepArgs(gscale=float(gscale), exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), lr=float(lr),
@@ -348,10 +375,12 @@ def overfit_plan(frames, epochs, model_scale_num, step=0, sched_steps=0, lr=0.01
 
 def overfit_gop(frames, point_nums, executor, flat_params, exp_avg, exp_avg_sq, arena, arena_bytes, epochs, lr, min_lr, gamma, step_size,
                 step, sched_steps, scale_steps, beta1, beta2, eps, weight_decay, keep_best=True, qat_from=None, bitdepth=8, qparams=None,
-                hidden=8, flags=0, occ_bf16=None):
+                hidden=8, flags=0, occ_bf16=None, avg=None):
     """linr_overfit_gop: the whole overfit of a GOP - every epoch, every frame's training step, the epoch's mean loss and the choice of
     the best epoch - queued by ONE call that synchronises the current stream once, at its end; ctypes releases the GIL for its duration.
     frames: engine.Frame list; arena: the executor's arena address for the largest frame; occ_bf16: per-frame addresses (bf16 executor).
+    avg = (weights [K] in (0, 1], device float32 [K, stride]) (opt-in; None: linr_overfit_gop, today's call): linr_overfit_gop_avg - the
+    rows are zeroed by the call and receive one linr_params_average update behind every step.
     Returns (losses float64 [epochs], best_epoch, best_loss, step, sched_steps, lr, scale_steps) - the optimiser state that belongs to
     what the call left in flat_params (include/linr_hip.h: linr_overfit_result)."""
     L = _lib.lib()
@@ -373,5 +402,14 @@ def overfit_gop(frames, point_nums, executor, flat_params, exp_avg, exp_avg_sq, 
                                 qparams=None if qparams is None else qparams.data_ptr(), arena=arena, arena_bytes=int(arena_bytes),
                                 ws=base, ws_bytes=ws.numel() - (base - ws.data_ptr()))
     res = _lib.LinrOverfitResult(losses_h=losses.ctypes.data, scale_steps_h=out_ss.ctypes.data)
-    check(L.linr_overfit_gop(fr, ctypes.byref(args), ctypes.byref(res), _stream()), 'linr_overfit_gop')
+    if avg is None:
+        check(L.linr_overfit_gop(fr, ctypes.byref(args), ctypes.byref(res), _stream()), 'linr_overfit_gop')
+    else:
+        w, rows = np.ascontiguousarray(avg[0], dtype=np.float32).reshape(-1), avg[1]
+        if not 1 <= w.size <= _lib.LINR_AVG_MAX or rows.dim() != 2 or rows.shape[0] != w.size or rows.dtype != torch.float32 or \
+                not rows.is_contiguous() or not rows.is_cuda:
+            raise ValueError('overfit_gop(avg=): 1..%d weights and a contiguous device float32 [K, stride] tensor' % _lib.LINR_AVG_MAX)
+        ca = _lib.LinrOverfitAvg(n_avg=int(w.size), weight=(ctypes.c_float * 4)(*([float(x) for x in w] + [0.0] * (4 - w.size))),
+                                 avg=rows.data_ptr(), stride=int(rows.shape[1]))
+        check(L.linr_overfit_gop_avg(fr, ctypes.byref(args), ctypes.byref(ca), ctypes.byref(res), _stream()), 'linr_overfit_gop_avg')
     return losses[:E].copy(), int(res.best_epoch), float(res.best_loss), int(res.step), int(res.sched_steps), float(res.lr), out_ss

@@ -153,11 +153,46 @@ def qat_first_epoch(epochs, qat_epochs):
     return max(0, int(epochs) - int(qat_epochs))
 
 
+AVG_MAX_DECAYS = 4            # LINR_AVG_MAX of csrc/params_avg.h: the rows of one linr_params_average call
+
+
+def avg_weights(decays):
+    """The update weights of the averaged iterates (overfit_gop avg_decays=): for every decay d in [0, 1) the fp32 weight
+    w = (float)(1 - d) of  avg += w * (params - avg);  at most AVG_MAX_DECAYS of them.  Returns a float32 array; the decay that is
+    really applied is 1 - (double)w (avg_debias_scales uses that one).  None or no decay: an empty array."""
+    import numpy as np
+    d = [] if decays is None else [float(x) for x in decays]
+    if len(d) > AVG_MAX_DECAYS:
+        raise ValueError('at most %d averaging decays, got %d' % (AVG_MAX_DECAYS, len(d)))
+    w = np.asarray([1.0 - x for x in d], dtype=np.float32)
+    for x, wk in zip(d, w):
+        if not (0.0 <= x < 1.0) or not (0.0 < float(wk) <= 1.0):
+            raise ValueError('an averaging decay must be in [0, 1) (and 1 - decay a positive float32), got %r' % (x,))
+    return w
+
+
+def avg_debias_scales(weights, steps):
+    """The scales that turn exponential averages accumulated from zero over `steps` updates into averages whose weights sum to one:
+    (float)(1 / (1 - d^steps)) with d = 1 - (double)w, formed in double, applied as ONE fp32 multiply per element."""
+    import numpy as np
+    if steps < 1:
+        raise ValueError('a debiased average needs one update or more, got %d' % steps)
+    return np.asarray([1.0 / (1.0 - (1.0 - float(w)) ** int(steps)) for w in weights], dtype=np.float32)
+
+
+def _averages_info(decays, weights, rows, n, steps):
+    """info['averages'] of overfit_gop: the debiased averages as a device [K][n] tensor (torch's elementwise multiply is one IEEE fp32
+    multiply per element); no update at all (0 epochs): the zero rows."""
+    import numpy as np
+    scales = torch.from_numpy(avg_debias_scales(weights, steps) if steps > 0 else np.ones(len(weights), np.float32)).to(rows.device)
+    return {'decays': [float(d) for d in decays], 'steps': int(steps), 'params': rows[:, :n] * scales[:, None]}
+
+
 # opt-in (LINR_C_OVERFIT=1, or overfit_gop(c_loop=True)): the whole overfit of a GOP as ONE C call (csrc/overfit.hip: linr_overfit_gop)
 C_OVERFIT = os.environ.get('LINR_C_OVERFIT', '0') == '1'
 
 
-def _overfit_gop_c(model, opt, gop, epochs, min_lr, keep, info, qat_epochs, qat_from, qat_bitdepth):
+def _overfit_gop_c(model, opt, gop, epochs, min_lr, keep, info, qat_epochs, qat_from, qat_bitdepth, avg=None):
     """overfit_gop's loop as one call of linr_overfit_gop: the same launches and the same host doubles, one synchronisation."""
     import math
     from . import _lib, engine
@@ -189,6 +224,8 @@ def _overfit_gop_c(model, opt, gop, epochs, min_lr, keep, info, qat_epochs, qat_
         extra = {'occ_bf16': [f.occ_bf16() for f in gop.frames]}
     if qat_epochs:
         extra.update(qparams=model.qat_parameters(), qat_from=qat_from, bitdepth=int(qat_bitdepth))
+    if avg is not None:          # (weights, rows): linr_overfit_gop_avg zeroes the rows and updates them behind every step
+        extra['avg'] = avg
     losses, best_epoch, best_loss, t, sched, lr, t_scale = engine.overfit_gop(
         gop.frames, gop.point_nums, executor, model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq, base, nbytes, epochs, opt.lr, min_lr,
         opt.gamma, opt.step_size, opt.t, opt.sched_steps, opt.t_scale, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay,
@@ -209,7 +246,8 @@ def _overfit_gop_c(model, opt, gop, epochs, min_lr, keep, info, qat_epochs, qat_
     return losses
 
 
-def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best', info=None, qat_epochs=0, qat_bitdepth=8, c_loop=None):
+def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best', info=None, qat_epochs=0, qat_bitdepth=8, c_loop=None,
+                avg_decays=None):
     """main.py:297-437: frames in fixed order, one optimiser + StepLR step per frame, lr clamp after each epoch.
     keep='best' (the reference's policy, main.py:413-426,440-451): model and optimiser are left in the state at the end of the epoch
     with the lowest mean loss; keep='last': in the state after the last epoch.  Returns the per-epoch mean loss (bits per point),
@@ -221,7 +259,13 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
     c_loop (opt-in; None: LINR_C_OVERFIT=1, read once): the loop below as ONE C call (linr_overfit_gop) that queues every step of
     every epoch and synchronises once - the same launches and the same host doubles, so parameters, moments and counters are those of
     the loop; the returned losses are summed in frame order instead of torch's reduction order (a few ulp).  Wide models then run
-    their one-call step whatever WideNet.c_step says.  Epochs cannot be observed from outside the call: on_epoch is refused."""
+    their one-call step whatever WideNet.c_step says.  Epochs cannot be observed from outside the call: on_epoch is refused.
+    avg_decays (opt-in; None or empty: today's launches and no others): up to 4 decays d in [0, 1).  For each an exponential average of
+    the iterates is kept on the device - a zeroed [K][stride] buffer when the overfit starts, ONE linr_params_average launch queued
+    behind every train_step, on model.flat_parameters() (the fp32 master of every executor) - and `info` receives
+    'averages' = {'decays', 'steps' (the updates made), 'params' (device [K][n]: the debiased averages at the end of the last epoch,
+    whatever epoch is kept)}: candidates for codec.encode_gop(avg=).  Training is untouched, bit for bit; c_loop=True runs
+    linr_overfit_gop_avg and returns the same averages."""
     if c_loop is None:
         c_loop = C_OVERFIT
     if c_loop and on_epoch is not None:
@@ -233,8 +277,17 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
         raise ValueError('qat_bitdepth must be in 2..16, got %r' % (qat_bitdepth,))
     if getattr(model, 'train_precision', 'f32') in ('bf16', 'bf16-deep'):
         gop.share_train_bf16_arena(deep=model.train_precision == 'bf16-deep')
+    avg_w = avg_weights(avg_decays)
+    avg_rows, n_params = None, model.flat_parameters().numel()
+    if len(avg_w):
+        avg_rows = torch.zeros((len(avg_w), (n_params + 3) & ~3), dtype=torch.float32, device=model.flat_parameters().device)
     if c_loop:
-        return _overfit_gop_c(model, opt, gop, epochs, min_lr, keep, info, qat_epochs, qat_from, qat_bitdepth)
+        losses = _overfit_gop_c(model, opt, gop, epochs, min_lr, keep, info, qat_epochs, qat_from, qat_bitdepth,
+                                None if avg_rows is None else (avg_w, avg_rows))
+        if avg_rows is not None and info is not None:
+            info['averages'] = _averages_info(avg_decays, avg_w, avg_rows, n_params, epochs * len(gop))
+        return losses
+    from . import engine
     losses = []
     dev = gop.frames[0].device
     bits = torch.zeros(len(gop), dtype=torch.float64, device=dev)         # one slot per frame: no per-step torch kernels
@@ -247,6 +300,8 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
                 train_step(model, opt, f, pn, out=bits[j:j + 1], qat_bitdepth=qat_bitdepth)
             else:
                 train_step(model, opt, f, pn, out=bits[j:j + 1])
+            if avg_rows is not None:
+                engine.params_average(model.flat_parameters(), avg_w, avg_rows)
         # the only host sync of the epoch.  Non-finite parameters make the epoch count as diverged (loss = inf): the loss itself
         # would not show them - BCELoss's clamp at -100 (models/model_core.py:76-81) turns a NaN probability into 100 nats
         val = (bits / pns).sum() / len(gop)
@@ -268,6 +323,8 @@ def overfit_gop(model, opt, gop, epochs, min_lr=4e-4, on_epoch=None, keep='best'
         info['coded_loss'] = best.loss if best is not None else (losses[-1] if losses else None)
         if qat_epochs:
             info['qat_from'] = qat_from
+        if avg_rows is not None:
+            info['averages'] = _averages_info(avg_decays, avg_w, avg_rows, n_params, epochs * len(gop))
     return losses
 
 

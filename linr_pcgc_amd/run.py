@@ -95,6 +95,13 @@ def parse(argv=None):
                     help='with --qrange-search: comma-separated trims, e.g. 0,1,2,4 (default 0,1,2,4,8,16,32,64; 0 is always tried)')
     ap.add_argument('--qrange-frames', '--qrange_frames', dest='qrange_frames', type=int, default=4,
                     help='with --qrange-search: frames of a GOP, evenly spaced, on which every candidate is measured (0: all)')
+    ap.add_argument('--avg-decays', '--avg_decays', dest='avg_decays', default=None,
+                    help='comma-separated decays in [0, 1), at most 4, e.g. 0.9,0.97,0.99: every overfit keeps an exponential average of '
+                         'its iterates per decay (one small launch behind every training step; training itself is untouched), and the encoder '
+                         'codes whichever of the model and its averages measures smallest on --avg-frames frames, model size included '
+                         '(codec.search_average); the plain model is always a candidate.  Checkpoints, warm starts and decoders are as ever')
+    ap.add_argument('--avg-frames', '--avg_frames', dest='avg_frames', type=int, default=4,
+                    help='with --avg-decays: frames of a GOP, evenly spaced, on which every candidate is measured (0: all)')
     ap.add_argument('--decode', action='store_true', help='decode every GOP again and check it is lossless')
     ap.add_argument('--decode-lockstep', '--decode_lockstep', dest='decode_lockstep', type=int, default=0,
                     help='with --decode: decode the frames of a GOP in groups of up to this many, all scales in lock step '
@@ -141,6 +148,14 @@ def parse(argv=None):
             ap.error('--qrange-trims must be >= 0')
     if args.qrange_frames < 0:
         ap.error('--qrange-frames must be >= 0')
+    if args.avg_decays is not None:
+        try:
+            args.avg_decays = tuple(float(d) for d in args.avg_decays.split(','))
+            overfit.avg_weights(args.avg_decays)
+        except ValueError as e:
+            ap.error('--avg-decays: comma-separated decays in [0, 1), at most %d (%s)' % (overfit.AVG_MAX_DECAYS, e))
+    if args.avg_frames < 0:
+        ap.error('--avg-frames must be >= 0')
     if args.stream_chunk and (args.stream_chunk % 64 or not 64 <= args.stream_chunk <= 1 << 24):
         ap.error('--stream-chunk must be 0 or a multiple of 64 in 64..2^24')
     if args.stream_chunk and args.hidden_channel_conv != 8:
@@ -313,6 +328,10 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
             log.close()
             raise ValueError('the one-call overfit (--c-overfit, LINR_C_OVERFIT=1) runs all epochs of a GOP in one call: the mid-test '
                              'cannot measure between them')
+        # --avg-decays (read with getattr, like every later option): the averages of the iterates ride along; info['averages'] holds
+        # them for finish_gop - a tensor of its own (the debiased read-out), complete at the synchronisation below like the model
+        if getattr(args, 'avg_decays', None):
+            loop['avg_decays'] = tuple(args.avg_decays)
         try:
             qat_epochs = int(getattr(args, 'qat_epochs', 0) or 0)
             if qat_epochs:
@@ -361,6 +380,7 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                                    device_coder=getattr(args, 'device_coder', False), coder_group=getattr(args, 'coder_group', 8),
                                    **({'stream_chunk': args.stream_chunk} if getattr(args, 'stream_chunk', 0) else {}),
                                    **({'digests': True} if getattr(args, 'digests', False) else {}),
+                                   **({'avg': info['averages'], 'avg_frames': getattr(args, 'avg_frames', 4)} if 'averages' in info else {}),
                                    **({'qrange_search': True, 'qrange_trims': getattr(args, 'qrange_trims', None),
                                        'qrange_frames': getattr(args, 'qrange_frames', 4)} if getattr(args, 'qrange_search', False) else {}))
             res_dir = os.path.join(args.out, 'result_enc', gop_parallel.gop_name(group))
@@ -389,6 +409,8 @@ def run_sequence_job(args, rank=0, world=1, dist=None, stage_all=False, files=No
                 result['qat_from'] = info['qat_from']
             if 'qrange' in enc:
                 result['qrange'] = enc['qrange']
+            if 'average' in enc:
+                result['average'] = enc['average']
             if 'digest_bits' in enc:
                 result['digest_bits'] = enc['digest_bits']
             if getattr(args, 'mid_test', False):
